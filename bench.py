@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: end-to-end depth-frames/s (480x640 f16 frames -> 3D joints) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K-step region `--reps` times and prints the headline line (`value`, `ms_per_step`).
+`--full` adds everything else the bench measures or checks: the hand-over regions from pinned host memory, the power /
+sustained-MFMA probe, the per-kernel roofline pass, the multi-person and precision-mode legs, the CPU baseline, the
+parity-mode / YoloPoseNet / RCCL child legs and the training step.  `--dump-outputs DIR` writes what the last timed step
+returned to its caller (the pose records of its 32 frames; with `--workload train` the loss terms, parameters and gradient)
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1 from a bare shell: bench.py starts N fresh ranks itself (torch.distributed.run, one process per GPU, RCCL over
 xGMI) BEFORE anything touches the GPU and relays rank 0's JSON line; started under torch.distributed.run it is a rank.
@@ -262,11 +269,12 @@ def train_step_cpu(batch, threads=32):
     return {"ms_per_step": round(dt * 1e3, 1), "frames_per_s": round(len(cpu[0]) / dt, 2), "cores": threads, "kind": "port"}
 
 
-def train_step_leg(dev, steps=8, warmup=2, world=1, group=None, lr=0.05, cpu=False, precision="fp32", batch_in=None):
+def train_step_leg(dev, steps=8, warmup=2, world=1, group=None, lr=0.05, cpu=False, precision="fp32", batch_in=None, extras=True, last=None):
     """BASELINE configs[4]: one training step of rtpose_light3d (train-mode forward, rtpose_light3d_loss_fgweight, backward,
     Nesterov SGD; popnet_amd.train.TrainEngine, every kernel hand-written HIP) on BATCH frames of 224 x 224 per rank from the
     reference's initial state, targets built on the GPU; with world > 1 the flat 22 MB gradient is all-reduced every step.
-    precision "fp32" = the parity mode (exact fp32 FMA chains), "bf16x3" = split-bf16; both on the round-6 planes engine (csrc/trainx.hip)."""
+    precision "fp32" = the parity mode (exact fp32 FMA chains), "bf16x3" = split-bf16; both on the round-6 planes engine (csrc/trainx.hip).
+    extras=False skips the bf16x3 leg next to the fp32 one; a dict `last` receives the engine and the loss terms of the last timed step."""
     from popnet_amd import synth
     from popnet_amd.train import TrainEngine
     batch, t_targets = batch_in if batch_in is not None else synth_training_batch(dev, BATCH)
@@ -284,9 +292,11 @@ def train_step_leg(dev, steps=8, warmup=2, world=1, group=None, lr=0.05, cpu=Fal
         t = eng.step(*batch)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if last is not None:
+        last.update(engine=eng, terms=t)
     flops = 3 * 13.343e9 * BATCH                                     # forward + data gradient + weight gradient, SURVEY 8d's per-frame figure
     extra = {"cpu_baseline": train_step_cpu(batch)} if cpu else {}
-    if precision == "fp32" and batch_in is None and world == 1:      # the opt-in fast mode on the same batch, next to the parity mode
+    if extras and precision == "fp32" and batch_in is None and world == 1:      # the opt-in fast mode on the same batch, next to the parity mode
         fast = train_step_leg(dev, steps, warmup, world, group, lr, False, "bf16x3", (batch, t_targets))
         extra["bf16x3"] = {k: fast[k] for k in ("ms_per_step", "frames_per_s_per_gpu", "tflops", "loss_first_step", "loss_last_step", "launch_mode")}
         extra["bf16x3"]["physical_bf16_tflops"] = round(3 * fast["tflops"], 1)
@@ -306,16 +316,32 @@ def train_step_leg(dev, steps=8, warmup=2, world=1, group=None, lr=0.05, cpu=Fal
 
 def train_workload(args, dev, world, rank, dist):
     """`--workload train`: the training step as the timed workload (weak scaling: BATCH frames per rank per step)."""
-    leg = train_step_leg(dev, steps=args.steps if args.steps < 200 else 20, warmup=max(2, min(args.warmup, 5)), world=world, group=None)
+    last = {}
+    leg = train_step_leg(dev, steps=args.steps, warmup=max(2, min(args.warmup, 5)), world=world, group=None, extras=args.full, last=last)
     ms = torch.tensor([leg["ms_per_step"]], device=dev)
     if world > 1:
         dist.all_reduce(ms, op=dist.ReduceOp.MAX)
+    if rank == 0 and args.dump_outputs:
+        eng = last["engine"]
+        dump_outputs(args.dump_outputs, {"loss_terms": last["terms"], "parameters": eng.flat_p, "gradient": eng.flat_g})
     if rank == 0:
         m = float(ms)
         print(json.dumps({"metric": "training frames/sec (rtpose_light3d_kdh3d_mpaug step, 224x224)", "value": round(world * BATCH / (m / 1e3), 1), "unit": "frames/s",
-                          "n_gpus": world, "steps": args.steps if args.steps < 200 else 20, "warmup": max(2, min(args.warmup, 5)), "ms_per_step": round(m, 3),
+                          "n_gpus": world, "steps": args.steps, "warmup": max(2, min(args.warmup, 5)), "ms_per_step": round(m, 3),
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                           "config": {"workload": "BASELINE configs[4]: training step, batch %d per GPU, data parallel" % BATCH}, "train_step": leg}))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy -- floating fields in their own precision (float32 / float64), integer fields
+    as float64 (exact for these widths).  Structured record arrays are written one field per file (<name>_<field>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        parts = {"%s_%s" % (name, f): a[f] for f in a.dtype.names} if a.dtype.names else {name: a}
+        for n, v in parts.items():
+            v = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+            np.save(os.path.join(path, n + ".npy"), np.ascontiguousarray(v))
 
 
 def bench_env():
@@ -461,8 +487,9 @@ def dist_check(dev, world, rank, dist):
 
 def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_active):
     """The timed regions of one (network, precision): `--reps` repetitions of the K-step region with the inputs resident in HBM
-    (-> value) and, with want_h2d, handed over from pinned host memory (-> h2d_inclusive), then the eager roofline pass with HIP
-    events around every conv launch.  Returns {"out": the JSON fields (rank 0; None elsewhere), "engine", "depth_host", "se"}."""
+    (-> value) and, with --full, the power / sustained-MFMA probe, the regions handed over from pinned host memory (want_h2d ->
+    h2d_inclusive) and the eager roofline pass with HIP events around every conv launch.  Returns {"out": the JSON fields (rank 0; None
+    elsewhere), "engine", "depth_host", "se", "last_records" / "last_seed": the last timed step's records and the seed of its input batch}."""
     from popnet_amd import _lib, synth
     from popnet_amd.pipeline import PoseEngine, StreamingEngine, YoloEngine
     Engine = PoseEngine if net == "rtpose" else YoloEngine
@@ -574,7 +601,7 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
     # power / clock of the SAME resident region, sampled through one extra UNTIMED repetition long enough for the firmware's moving
     # average (>= 0.9 s), and the box's sustained matrix-core ceiling (pn_mfma_sustained: nothing but MFMAs on random bf16, 1.5 s)
     power, sustained = None, None
-    if rank == 0 and world == 1 and not args.no_power:
+    if args.full and rank == 0 and world == 1 and not args.no_power:
         per_step = float(np.median(runs["resident"])) / K
         nlong = max(K, int(0.9 / max(per_step, 1e-6)) + 1)
         keep_records["on"] = False
@@ -629,6 +656,33 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
         torch.cuda.synchronize()
     med = {m: float(np.median(v)) for m, v in runs.items()}
     elapsed = med["resident"]
+    # what the last step of the last timed resident region handed to its caller: that step's records
+    last_records = keep_res[(K - 1) % K].numpy().view(WIRE).reshape(BATCH)
+    last_seed = 1234 + 1000 * rank + batch_res[(K - 1) % K]        # its input batch: synth.synth_depth(BATCH, 640, 480, seed=last_seed)
+
+    def rate(sec):
+        return round(world * K * BATCH / sec, 2)
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "depth-frames/sec end-to-end (480x640)", "value": rate(elapsed),
+            "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W, "warmup_steps_run": WARM,
+            "ms_per_step": round(elapsed / K * 1e3, 4),
+            "value_stat": {"what": "median of %d repetitions of the %d-step timed region" % (REPS, K), "min": rate(max(runs["resident"])), "max": rate(min(runs["resident"])),
+                           "runs": [rate(v) for v in runs["resident"]]},
+            "launch_mode": ("eager" if args.no_graph else "hipGraph replay (one graph per step)") + ", %d batches in flight on separate HIP streams" % PIPE, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": precision,
+            "data": "synthetic, %d distinct batches (%.0f MB) resident in HBM, a different batch every step" % (NIN, NIN * BATCH * 640 * 480 * 2 / 1e6),
+            "config": {"workload": "BASELINE configs[1]: batch=32 synthetic 480x640 f16 depth frames per GPU per step, "
+                                   "resize->224^2, " + ("rtpose_light3d forward + PAF pose parsing" if net == "rtpose" else
+                                                        "YoloPoseNet forward + box decode / NMS / skeleton read-out (secondary network of the path)") + ", records D2H",
+                       "frames_per_step_per_gpu": BATCH, "input": "480x640 f16", "network_input": "224x224",
+                       "weights": "seeded random, " + ("heat head calibrated (pipeline.calibrate_heads)" if net == "rtpose" else "confidence filters calibrated (pipeline.calibrate_yolo_conf)"),
+                       "records": "pn_pose_wire (%d B per frame) to pinned host memory every step" % witem if se.wire else "pn_yolo_frame to pinned host memory every step",
+                       "parallelism": "frames sharded x%d, one all-gather of records" % world},
+        }
+    if not args.full:
+        return {"out": out, "engine": engine, "depth_host": depth_host, "se": se, "last_records": last_records, "last_seed": last_seed}
 
     # ---- roofline pass: K steps again, eager, every conv launch bracketed by HIP events on the launch stream (event
     # records inside the throughput pass would perturb it) ----
@@ -678,7 +732,6 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
                         "flops_per_launch": round(kfl.value / max(kn.value, 1), 1)})
     frames_full = torch.stack([se.records(s) for s in range(PIPE)]).cpu()
 
-    out = None
     if rank == 0:
         first = {}                                               # the same input batch must give the same records, whatever step / slot / input mode ran it
 
@@ -696,7 +749,6 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
                 same = same and bt in first and np.array_equal(first[bt], rec.numpy().reshape(-1)[:first[bt].size])
         wire = keep_res.numpy().view(WIRE).reshape(K, BATCH)
         recs = frames_full.numpy().view(REC).reshape(PIPE, BATCH)
-        total_frames = world * K * BATCH
         achieved = conv_flops.value / (conv_ms.value * 1e-3) / 1e12 if conv_ms.value > 0 else 0.0
         peak = PEAK_TFLOPS[precision]
         # network outputs read + records written per frame
@@ -717,24 +769,7 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
             except Exception:
                 traffic = None
 
-        def rate(sec):
-            return round(total_frames / sec, 2)
-        out = {
-            "metric": "depth-frames/sec end-to-end (480x640)", "value": rate(elapsed),
-            "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W, "warmup_steps_run": WARM,
-            "ms_per_step": round(elapsed / K * 1e3, 4),
-            "value_stat": {"what": "median of %d repetitions of the %d-step timed region" % (REPS, K), "min": rate(max(runs["resident"])), "max": rate(min(runs["resident"])),
-                           "runs": [rate(v) for v in runs["resident"]]},
-            "launch_mode": ("eager" if args.no_graph else "hipGraph replay (one graph per step)") + ", %d batches in flight on separate HIP streams" % PIPE, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": precision,
-            "data": "synthetic, %d distinct batches (%.0f MB) resident in HBM, a different batch every step" % (NIN, NIN * BATCH * 640 * 480 * 2 / 1e6),
-            "config": {"workload": "BASELINE configs[1]: batch=32 synthetic 480x640 f16 depth frames per GPU per step, "
-                                   "resize->224^2, " + ("rtpose_light3d forward + PAF pose parsing" if net == "rtpose" else
-                                                        "YoloPoseNet forward + box decode / NMS / skeleton read-out (secondary network of the path)") + ", records D2H",
-                       "frames_per_step_per_gpu": BATCH, "input": "480x640 f16", "network_input": "224x224",
-                       "weights": "seeded random, " + ("heat head calibrated (pipeline.calibrate_heads)" if net == "rtpose" else "confidence filters calibrated (pipeline.calibrate_yolo_conf)"),
-                       "records": "pn_pose_wire (%d B per frame) to pinned host memory every step" % witem if se.wire else "pn_yolo_frame to pinned host memory every step",
-                       "parallelism": "frames sharded x%d, one all-gather of records" % world},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": dom["kernel"] + " (dominant convolution instantiation: %.0f of %.0f conv us/step)" % (dom["us_per_step"], conv_ms.value * 1e3 / K),
                          "achieved": dom["tflops"], "peak": peak, "unit": "TFLOP/s", "frac": round(dom["tflops"] / peak, 4),
                          "traffic": traffic, "traffic_source": traffic_source, "avg_launch_us": dom["avg_launch_us"], "flops_per_launch": dom["flops_per_launch"],
@@ -763,7 +798,7 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
                             "mean_persons": round(float(wire['n_persons' if net == "rtpose" else 'n_det'].mean()), 3),
                             "overflow_frames": int((wire['status'] != 0).sum()),
                             "same_batch_same_records_across_steps_slots_and_input_modes": same},
-        }
+        })
         if "h2d" in runs:
             out["h2d_inclusive"] = {"value": rate(med["h2d"]), "unit": "frames/s", "ms_per_step": round(med["h2d"] / K * 1e3, 4),
                                     "min": rate(max(runs["h2d"])), "max": rate(min(runs["h2d"])), "runs": [rate(v) for v in runs["h2d"]],
@@ -772,8 +807,7 @@ def pipelined_leg(args, dev, world, rank, dist, net, precision, want_h2d, dist_a
                                     "what": "same region, every batch handed over from pinned host memory (StreamingEngine.post_host / submit_posted: %.1f MB per step over PCIe on the copy stream into the slot's next input buffer). "
                                             "Streaming form: a batch's transfer is posted %d steps ahead of its step, so the first %d transfers leave before the region opens and the region posts the %d that follow its last step "
                                             "-- K transfers posted and K steps run inside the window, which closes when the last step's records are in pinned host memory; median of %d" % (BATCH * 640 * 480 * 2 / 1e6, AHEAD, AHEAD, AHEAD, REPS)}
-    se_engine, host0 = engine, depth_host
-    return {"out": out, "engine": se_engine, "depth_host": host0, "se": se}
+    return {"out": out, "engine": engine, "depth_host": depth_host, "se": se, "last_records": last_records, "last_seed": last_seed}
 
 
 def main():
@@ -795,6 +829,9 @@ def main():
     ap.add_argument("--launcher-dry-run", action="store_true", help="CPU check of the --gpus N self-launch (gloo, no GPU work)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group and run every exchange even at world_size 1 (in a fresh child rank started before any GPU call)")
     ap.add_argument("--workload", default="infer", choices=["infer", "train"], help="infer = the headline path (BASELINE configs[1]); train = the training step (configs[4])")
+    ap.add_argument("--full", action="store_true", help="besides the headline region, run every secondary measurement and check: hand-over regions, power / "
+                    "sustained-MFMA probe, roofline pass, multi-person and precision-mode legs, CPU baseline, child legs, training step, collective check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     env_seen = bench_env()                                          # refuses ablation switches before anything else runs
@@ -829,13 +866,19 @@ def main():
         return
     leg_s = {}
     _t = time.perf_counter()
-    legs = pipelined_leg(args, dev, world, rank, dist, args.net, args.precision, want_h2d=not args.no_h2d, dist_active=dist_active)
+    legs = pipelined_leg(args, dev, world, rank, dist, args.net, args.precision, want_h2d=args.full and not args.no_h2d, dist_active=dist_active)
     leg_s["timed_regions_and_roofline_pass"] = round(time.perf_counter() - _t, 1)
     # collectives: EVERY rank takes part (rank 0 alone would wait for the others forever)
-    dist_res = dist_check(dev, world, rank, dist) if dist_active else None
+    dist_res = dist_check(dev, world, rank, dist) if dist_active and args.full else None
     plan = plan_legs(world, rank, args.net, args.precision, args.no_extras, args.no_cpu_baseline)
+    if not args.full:                                               # a plain run: the headline region and nothing else
+        plan = dict.fromkeys(plan, False)
     if rank == 0:
         out = legs["out"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"records": legs["last_records"]})
+            out["dump_outputs"] = {"dir": args.dump_outputs, "input_seed": legs["last_seed"],
+                                   "what": "records_<field>.npy: the %s records of the last timed step's %d frames" % ("pn_pose_wire" if args.net == "rtpose" else "pn_yolo_frame", BATCH)}
         engine = legs["engine"]
         out["process_group"] = {"initialised": bool(dist_active), "note": "a plain `python bench.py --gpus 1` (how the driver runs N = 1) initialises no process group: same code "
                                 "path and value as the default line; under torch.distributed.run (N > 1, or --force-dist) the all-gather of the records closes every region"}
@@ -876,7 +919,7 @@ def main():
             import subprocess
             # a freshly started child's first region ran on clocks that had not settled (r05: runs[0] 9 % under the median): >= 30 untimed steps first
             cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(max(args.warmup, 30)), "--reps", str(args.reps),
-                   "--pipeline", str(args.pipeline), "--pool", str(args.pool), "--no-extras", "--no-cpu-baseline", "--no-power"] + extra
+                   "--pipeline", str(args.pipeline), "--pool", str(args.pool), "--no-extras", "--no-cpu-baseline", "--no-power", "--full"] + extra
             try:
                 p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
             except OSError as e:
@@ -939,7 +982,8 @@ def main():
             out["train_step"] = train_step_leg(dev, cpu=not args.no_cpu_baseline)
             leg_s["train_step"] = round(time.perf_counter() - _t, 1)
     if rank == 0:
-        surface_in_parsed(out)
+        if args.full:
+            surface_in_parsed(out)
         out["leg_seconds"] = leg_s
         out["env"] = dict(env_seen, library="popnet_amd/" + os.path.basename(_pl.LIB_PATH), lab_build=bool(lab_build),
                           GPU_MAX_HW_QUEUES=os.environ.get("GPU_MAX_HW_QUEUES"))

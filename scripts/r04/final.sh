@@ -2,8 +2,8 @@
 # round-4 final evidence: the driver's command, the default line, the whole GPU suite, smoke
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$1; mkdir -p $O
-S=$(date +%s); timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "driver-cmd bench wall $(( $(date +%s) - S )) s"
-S=$(date +%s); timeout 1500 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench wall $(( $(date +%s) - S )) s"
+S=$(date +%s); timeout 1500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "driver-cmd bench wall $(( $(date +%s) - S )) s"
+S=$(date +%s); timeout 1500 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench wall $(( $(date +%s) - S )) s"
 for f in bench_driver_cmd bench_default; do python - "$O/$f.json" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

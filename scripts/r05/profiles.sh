@@ -6,10 +6,10 @@ tag=$1; export POPNET_COMMIT=$2
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$tag; mkdir -p $O
 E="--no-cpu-baseline --no-extras --no-h2d --reps 1 --no-graph --pipeline 1 --steps 20 --warmup 5"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o runc -- python3 bench.py --no-cpu-baseline --no-extras > $O/stats.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_eager1 -o runc -- python3 bench.py $E > $O/stats_eager1.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_x3_eager1 -o runc -- python3 bench.py $E --precision bf16x3 > $O/stats_x3_eager1.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_yolo_eager1 -o runc -- python3 bench.py $E --net yolo > $O/stats_yolo_eager1.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o runc -- python3 bench.py --full --no-cpu-baseline --no-extras > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_eager1 -o runc -- python3 bench.py --full $E > $O/stats_eager1.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_x3_eager1 -o runc -- python3 bench.py --full $E --precision bf16x3 > $O/stats_x3_eager1.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_yolo_eager1 -o runc -- python3 bench.py --full $E --net yolo > $O/stats_yolo_eager1.log 2>&1
 for p in fp32 bf16x3; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_train_$p -o runc -- python3 scripts/train_bench.py 32 6 $p > $O/stats_train_$p.log 2>&1
 done
@@ -21,7 +21,7 @@ for mode in bf16 bf16x3; do
   i=0
   for set in "GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_MFMA" "TA_TA_BUSY_sum TA_BUSY_avr GRBM_TA_BUSY" "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
     i=$((i+1))
-    mkdir -p $O/pmc_$mode; rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$mode/pass$i -o runc -- python3 bench.py --steps 20 --warmup 4 --reps 1 --no-h2d --no-extras --no-cpu-baseline --no-graph --pipeline 1 --precision $mode > $O/pmc_$mode/pass$i.log 2>&1
+    mkdir -p $O/pmc_$mode; rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$mode/pass$i -o runc -- python3 bench.py --full --steps 20 --warmup 4 --reps 1 --no-h2d --no-extras --no-cpu-baseline --no-graph --pipeline 1 --precision $mode > $O/pmc_$mode/pass$i.log 2>&1
   done
   python3 scripts/pmc_kernel_table.py $O/pmc_$mode | tee $O/pmc_table_$mode.txt
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # h2d_inclusive fraction under runtime copy-path settings (same box, back to back).  usage: h2d_env.sh <tag>
 O=gpurun_out/$1; mkdir -p $O
-run() { name=$1; shift; env "$@" python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-power > $O/$name.json 2> $O/$name.err
+run() { name=$1; shift; env "$@" python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-power > $O/$name.json 2> $O/$name.err
   python - "$O/$name.json" "$name" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

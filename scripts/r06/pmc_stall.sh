@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; what=$2; O=gpurun_out/$tag; mkdir -p $O
 if [ "$what" = train ]; then CMD="python3 scripts/train_bench.py 32 4 bf16x3 nograph"; export POPNET_TRAINX_STREAMS=1
-else CMD="python3 bench.py --steps 10 --warmup 3 --reps 1 --no-h2d --no-extras --no-cpu-baseline --no-power --no-graph --pipeline 1 ${3:-}"; fi
+else CMD="python3 bench.py --full --steps 10 --warmup 3 --reps 1 --no-h2d --no-extras --no-cpu-baseline --no-power --no-graph --pipeline 1 ${3:-}"; fi
 mkdir -p $O/pmc_$what; i=0
 for set in "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY" \
            "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM SQ_VALU_MFMA_BUSY_CYCLES" \

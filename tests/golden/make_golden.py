@@ -856,6 +856,40 @@ def golden_train():
     print("train_step.npz: loss", out["s0_loss"], "->", out["s1_loss"])
 
 
+# ---- F12: the reference's pair-based Human class (common_coco.py:27-60) ----------------------
+COCO_PAIRS = [[1, 0, [0.5, 0.25], 2, 3, [0.4, 0.3], 0.9], [2, 3, [0.4, 0.3], 3, 1, [0.35, 0.45], 0.7],
+              [1, 1, [0.8, 0.2], 5, 0, [0.9, 0.3], 0.6], [5, 0, [0.9, 0.3], 6, 2, [0.95, 0.5], 0.8], [3, 1, [0.35, 0.45], 4, 4, [0.3, 0.6], 0.5]]
+
+
+def human_state(h):
+    """What tests/test_common_coco.py compares: uidx list, body parts, pair count, score (JSON-shaped)."""
+    return [sorted(h.uidx_list), [[k, v.uidx, v.part_idx, v.x, v.y, v.score] for k, v in sorted(h.body_parts.items())], len(h.pairs), h.score]
+
+
+def golden_common_coco():
+    """For every split of COCO_PAIRS: the reference Human built from each side, is_connected, and the merged human."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_ref_common_coco", os.path.join(TPM, "lib", "utils", "common_coco.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)                      # draws with cv2 only: the cv2 shim is enough
+
+    class Pair:
+        def __init__(self, p1, i1, c1, p2, i2, c2, score):
+            self.part_idx1, self.idx1, self.coord1 = p1, i1, tuple(c1)
+            self.part_idx2, self.idx2, self.coord2 = p2, i2, tuple(c2)
+            self.score = score
+    pairs = [Pair(*p) for p in COCO_PAIRS]
+    splits = []
+    for split in range(len(pairs) + 1):
+        a, b = ref.Human(pairs[:split]), ref.Human(pairs[split:])
+        rec = {"split": split, "first": human_state(a), "second": human_state(b), "connected": bool(a.is_connected(b))}
+        a.merge(b)
+        rec.update(merged=human_state(a), merged_part_count=a.part_count(), merged_max_score=a.get_max_score() if a.body_parts else None)
+        splits.append(rec)
+    json.dump({"pairs": COCO_PAIRS, "splits": splits}, open(os.path.join(OUT, "common_coco.json"), "w"))
+    print("common_coco.json: %d splits" % len(splits))
+
+
 def _same(a, b):
     """Exact comparison of two golden payloads (NaN == NaN); returns a list of differing paths."""
     bad = []
@@ -916,11 +950,12 @@ if __name__ == "__main__":
     args = [a for a in args if a != "--check"]
     if check:
         OUT = tempfile.mkdtemp(prefix="popnet_golden_check_")
-    which = args or ["keys", "forward", "parse", "yolo", "pafprocess", "cpp", "script", "script_yolo", "metrics", "script_metrics", "script_metrics_yolo", "targets", "train"]
+    which = args or ["keys", "forward", "parse", "yolo", "pafprocess", "cpp", "script", "script_yolo", "metrics", "script_metrics", "script_metrics_yolo", "targets", "train", "common_coco"]
     fns = {"keys": golden_state_dicts, "forward": golden_forward, "parse": golden_parse, "yolo": golden_yolo,
            "pafprocess": golden_pafprocess, "cpp": golden_paf_to_pose_cpp, "script": golden_script,
            "script_yolo": golden_script_yolo, "metrics": golden_metrics, "script_metrics": golden_script_metrics,
-           "script_metrics_yolo": lambda: golden_script_metrics("yolo"), "targets": golden_targets, "train": golden_train}
+           "script_metrics_yolo": lambda: golden_script_metrics("yolo"), "targets": golden_targets, "train": golden_train,
+           "common_coco": golden_common_coco}
     for w in which:
         fns[w]()
     if check:

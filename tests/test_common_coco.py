@@ -1,9 +1,7 @@
 """popnet_amd.utils.common_coco.Human: the pair-based assembly surface of tpm/lib/utils/common_coco.py:27-60 (CPU; data only)."""
+import json
 import os
 import sys
-import types
-
-import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from popnet_amd.utils.common_coco import BodyPart, Human  # noqa: E402
@@ -41,29 +39,23 @@ def test_pair_constructor_and_methods():
     assert e.get_max_score() == 0.3
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/third_party_methods"), reason="the reference tree is not on this box")
+def _json_state(h):
+    """_state in the JSON shape tests/golden/make_golden.py stores (golden_common_coco)."""
+    return [sorted(h.uidx_list), [[k, v.uidx, v.part_idx, v.x, v.y, v.score] for k, v in sorted(h.body_parts.items())], len(h.pairs), h.score]
+
+
 def test_same_states_as_the_reference_class():
-    """Every constructor / add_pair / merge / is_connected outcome against the reference's own class (imported with a stub cv2: the module
-    only draws with it)."""
-    saved = sys.modules.get("cv2")
-    sys.modules["cv2"] = types.ModuleType("cv2")
-    try:
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("_ref_common_coco", "/root/reference/third_party_methods/lib/utils/common_coco.py")
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-    finally:
-        if saved is None:
-            del sys.modules["cv2"]
-        else:
-            sys.modules["cv2"] = saved
-    for split in range(len(PAIRS) + 1):
-        mine, theirs = Human(PAIRS[:split]), ref.Human(PAIRS[:split])
-        assert _state(mine) == _state(theirs)
-        m2, t2 = Human(PAIRS[split:]), ref.Human(PAIRS[split:])
-        assert mine.is_connected(m2) == theirs.is_connected(t2)
+    """Every constructor / merge / is_connected outcome against the reference's own class, on the same pairs: its outcomes for every
+    split of PAIRS are stored in tests/golden/common_coco.json (make_golden.py step common_coco)."""
+    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "common_coco.json")))
+    assert g["pairs"] == [[p.part_idx1, p.idx1, list(p.coord1), p.part_idx2, p.idx2, list(p.coord2), p.score] for p in PAIRS]
+    assert [r["split"] for r in g["splits"]] == list(range(len(PAIRS) + 1))
+    for r in g["splits"]:
+        split = r["split"]
+        mine, m2 = Human(PAIRS[:split]), Human(PAIRS[split:])
+        assert _json_state(mine) == r["first"] and _json_state(m2) == r["second"]
+        assert mine.is_connected(m2) == r["connected"]
         mine.merge(m2)
-        theirs.merge(t2)
-        assert _state(mine) == _state(theirs) and mine.part_count() == theirs.part_count()
+        assert _json_state(mine) == r["merged"] and mine.part_count() == r["merged_part_count"]
         if mine.body_parts:
-            assert mine.get_max_score() == theirs.get_max_score()
+            assert mine.get_max_score() == r["merged_max_score"]

@@ -25,7 +25,7 @@ def test_rccl_process_group_gather_and_allreduce_on_the_gpu(gpu):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "6", "--warmup", "2", "--reps", "1",
-                        "--pool", "2", "--no-extras", "--no-cpu-baseline", "--no-h2d"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
+                        "--pool", "2", "--no-extras", "--no-cpu-baseline", "--no-h2d", "--full"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
