@@ -131,6 +131,19 @@ int pn_net_read_activation(pn_net *net, const char *name, int B, float *host_out
  * how the Python module materialises forward()'s `saved_for_loss` stage-1 entries
  * (tpm/lib/network/rtpose_light3d.py:340-342).                                                   */
 int pn_net_copy_activation(pn_net *net, const char *name, int B, float *dev_out, void *hip_stream);
+/* Test/diagnostic (per-layer checks).  Every activation buffer is also readable by number through
+ * pn_net_read_activation / pn_net_copy_activation as "buf<i>" (all channels, f32 NCHW; a bf16x3 buffer
+ * reads as hi + lo) and, in a bf16x3 net, "buf<i>.hi" / "buf<i>.lo" (one stored plane).
+ * pn_net_forward_partial runs steps [0, nsteps) of the compiled step list and stops: the same forward,
+ * descriptors, lock and batch rules as pn_*_forward.  It needs one full pn_*_forward first, at the same
+ * batch size, whose output buffers stay valid (a head step writes them).
+ * pn_net_num_steps: the number of steps.  pn_net_step_info writes a JSON description of step k into out
+ * (type stem / pool / conv / bblock, the kernel label, and per convolution its weight / BN prefixes, ks,
+ * stride, act, buffers with channel offsets, input-channel map, fused tail or pool); k = -1 describes the
+ * net (precision, input size, buffers as [H, W, C]).  PN_ERR_INVALID when cap is too small.             */
+int pn_net_forward_partial(pn_net *net, const float *x_dev, int B, int nsteps, void *hip_stream);
+int pn_net_num_steps(pn_net *net);
+int pn_net_step_info(pn_net *net, int k, char *out, size_t cap);
 /* Algorithmic FLOPs (2*MAC, convolutions only) of one frame through the finalized net. */
 double pn_net_flops_per_frame(pn_net *net);
 /* Freezes the launch descriptors at the batch size / output pointers of the last forward: afterwards a forward with

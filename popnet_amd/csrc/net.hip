@@ -118,6 +118,7 @@ struct pn_net {
     bool tickets_suspect = false;    // a forward of this net failed part-way: bb64_kernel's tile tickets may be non-zero -- re-zeroed before the next launch
     float *last_nchw[4] = {nullptr, nullptr, nullptr, nullptr};
     std::map<std::string, std::pair<int, std::pair<int, int>>> named;   // name -> (buf, (coff, C))
+    std::map<std::string, int> named_plane;   // bf16x3 "buf<i>.hi" / "buf<i>.lo": read that one plane (0 / 1) instead of hi + lo
     double flops_per_frame = 0;
     int out_h = 0, out_w = 0;
     // optional per-launch HIP-event timing (bench.py's live roofline measurement)
@@ -958,7 +959,35 @@ int refresh_problems(pn_net *n, int B, hipStream_t stream) {
     return PN_OK;
 }
 
-int run_forward(pn_net *n, const float *x, int B, hipStream_t stream) {
+// Kernel label of a step: the profiler's per-instantiation key (pn_net_profile_kernel) and pn_net_step_info's "kernel".
+std::string step_label(const pn_net *n, const Step &st) {
+    char lb[96];
+    if (st.type == Step::STEM) {
+        if (st.stem_pool_buf >= 0) return "stem7x7_pool_kernel";
+        if (st.stem_cin > 1) return "conv2d_forward+nchw_relu_to_nhwc_kernel";
+        if (n->prec == PN_PREC_F32) return "stem7x7_kernel";
+        return n->x3 ? "stem7x7_mfma_kernel<x3>" : "stem7x7_mfma_kernel";
+    }
+    if (st.type == Step::POOL) {
+        snprintf(lb, sizeof lb, "pool_kernel<%d%s>", st.mode, n->x3 ? ", split" : "");
+        return lb;
+    }
+    if (st.type == Step::BBLOCK) return n->x3 ? "bb64x3_kernel" : "bb64_kernel";
+    const ConvSpec &c0 = n->convs[st.conv_ids[0]];
+    bool mix = false;
+    for (int id : st.conv_ids) {
+        const ConvSpec &cs = n->convs[id];
+        if (cs.ks != c0.ks || (cs.tail_conv >= 0) != (c0.tail_conv >= 0)) mix = true;
+    }
+    if (c0.kern == 4) snprintf(lb, sizeof lb, "conv4_kernel");
+    else if (c0.kern == 3 && mix) snprintf(lb, sizeof lb, "conv3_mix_kernel");
+    else if (c0.kern == 3) snprintf(lb, sizeof lb, "conv3_kernel<%d, %d, %d, %d, %d, %d>", c0.ks, c0.wc, c0.wp, c0.nbuf, c0.pt, c0.rpg);
+    else snprintf(lb, sizeof lb, "conv_mfma_kernel<%d, %d, %d, %d, %d>", n->prec, c0.ks, c0.stride, c0.pitch, c0.cfg);
+    return lb;
+}
+
+// nsteps < 0: the whole step list; otherwise steps [0, nsteps) only (pn_net_forward_partial)
+int run_forward(pn_net *n, const float *x, int B, hipStream_t stream, int nsteps = -1) {
     pn_ctx *ctx = n->ctx;
     if (!n->finalized) return pn_set_error(ctx, PN_ERR_STATE, "pn_net_finalize has not been called");
     if (B < 1 || B > n->max_batch) return pn_set_error(ctx, PN_ERR_INVALID, "batch %d outside [1, %d]", B, n->max_batch);
@@ -977,7 +1006,9 @@ int run_forward(pn_net *n, const float *x, int B, hipStream_t stream) {
             if (st.type == Step::BBLOCK && st.bb_tickets) PN_HIP_CHECK(ctx, hipMemsetAsync(st.bb_tickets, 0, 256, stream));
         n->tickets_suspect = false;
     }
-    for (auto &st : n->steps) {
+    for (size_t si = 0; si < n->steps.size(); ++si) {
+        if ((int)si == nsteps) break;
+        Step &st = n->steps[si];
         int rc = PN_OK;
         pn_net::ProfRec *pr = nullptr;
         if (n->profiling) {
@@ -993,18 +1024,12 @@ int run_forward(pn_net *n, const float *x, int B, hipStream_t stream) {
             pr->label.clear();
             if (st.type == Step::CONV) {
                 for (int id : st.conv_ids) pr->flops += n->convs[id].flops * B;
-                char lb[96];
-                const ConvLaunch &cl = st.launch;
-                if (cl.kern == 4) snprintf(lb, sizeof lb, "conv4_kernel");
-                else if (cl.kern == 3 && cl.mix) snprintf(lb, sizeof lb, "conv3_mix_kernel");
-                else if (cl.kern == 3) snprintf(lb, sizeof lb, "conv3_kernel<%d, %d, %d, %d, %d, %d>", cl.ks, cl.wc, cl.wp, cl.nbuf, cl.pt, cl.rpg);
-                else snprintf(lb, sizeof lb, "conv_mfma_kernel<%d, %d, %d, %d, %d>", cl.prec, cl.ks, cl.stride, cl.pitch, cl.cfg);
-                pr->label = lb;
+                pr->label = step_label(n, st);
             }
             if (st.type == Step::BBLOCK) {       // counted with the convolutions: both convs' algorithmic FLOPs
                 pr->kind = (int)Step::CONV;
                 pr->flops = (n->convs[st.bb_a].flops + n->convs[st.bb_b].flops) * B;
-                pr->label = n->x3 ? "bb64x3_kernel" : "bb64_kernel";
+                pr->label = step_label(n, st);
             }
             PN_HIP_CHECK(ctx, hipEventRecord(pr->a, stream));
         }
@@ -1119,6 +1144,14 @@ int pn_net_finalize(pn_net *n, int precision, int max_batch, int in_h, int in_w)
     for (auto &st : n->steps)
         if (st.type == Step::CONV)
             if (int r = dev_alloc(n, (void **)&st.dev_probs, st.conv_ids.size() * sizeof(ConvProblem), true)) return r;
+    for (size_t i = 0; i < n->bufs.size(); ++i) {     // every buffer by number (pn_net_step_info's buffer indices), for per-layer checks
+        const std::string nm = "buf" + std::to_string(i);
+        n->named[nm] = {(int)i, {0, n->bufs[i].plane}};
+        if (n->x3) {
+            n->named[nm + ".hi"] = {(int)i, {0, n->bufs[i].plane}}; n->named_plane[nm + ".hi"] = 0;
+            n->named[nm + ".lo"] = {(int)i, {0, n->bufs[i].plane}}; n->named_plane[nm + ".lo"] = 1;
+        }
+    }
     n->tensors.clear();
     PN_HIP_CHECK(ctx, hipDeviceSynchronize());      // the zero fills above ran on the null stream: a forward on a non-blocking stream must not overtake them
     n->finalized = true;
@@ -1189,6 +1222,10 @@ int pn_net_copy_activation(pn_net *n, const char *name, int B, float *dev_out, v
     auto it = n->named.find(name);
     if (it == n->named.end()) return pn_set_error(ctx, PN_ERR_INVALID, "unknown activation '%s'", name);
     const Buf &b = n->bufs[it->second.first];
+    auto pl = n->named_plane.find(name);
+    if (pl != n->named_plane.end())        // one plane of a bf16x3 buffer, as stored
+        return pn_launch_nhwc_to_nchw(ctx, n->prec, b.p, dev_out, B, b.H, b.W, it->second.second.second, b.C,
+                                      it->second.second.first + pl->second * b.plane, 0, (hipStream_t)hip_stream);
     return pn_launch_nhwc_to_nchw(ctx, n->prec, b.p, dev_out, B, b.H, b.W, it->second.second.second, b.C,
                                   it->second.second.first, n->x3 ? b.plane : 0, (hipStream_t)hip_stream);
 }
@@ -1212,6 +1249,79 @@ int pn_net_read_activation(pn_net *n, const char *name, int B, float *host_out, 
     }
     (void)hipFree(tmp);
     return rc;
+}
+
+int pn_net_forward_partial(pn_net *n, const float *x_dev, int B, int nsteps, void *hip_stream) {
+    if (!n) return PN_ERR_INVALID;
+    if (!x_dev) return pn_set_error(n->ctx, PN_ERR_INVALID, "null device pointer");
+    if (n->last_B < 0) return pn_set_error(n->ctx, PN_ERR_STATE, "pn_net_forward_partial: run one full forward first");
+    if (nsteps < 0 || nsteps > (int)n->steps.size()) return pn_set_error(n->ctx, PN_ERR_INVALID, "nsteps %d outside [0, %zu]", nsteps, n->steps.size());
+    return run_forward(n, x_dev, B, (hipStream_t)hip_stream, nsteps);
+}
+
+int pn_net_num_steps(pn_net *n) {
+    if (!n) return PN_ERR_INVALID;
+    if (!n->finalized) return pn_set_error(n->ctx, PN_ERR_STATE, "net not finalized");
+    return (int)n->steps.size();
+}
+
+int pn_net_step_info(pn_net *n, int k, char *out, size_t cap) {
+    if (!n || !out || !cap) return PN_ERR_INVALID;
+    pn_ctx *ctx = n->ctx;
+    if (!n->finalized) return pn_set_error(ctx, PN_ERR_STATE, "net not finalized");
+    if (k < -1 || k >= (int)n->steps.size()) return pn_set_error(ctx, PN_ERR_INVALID, "step %d outside [-1, %zu)", k, n->steps.size());
+    std::string js;
+    char t[256];
+    auto add = [&](const char *fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(t, sizeof t, fmt, ap);
+        va_end(ap);
+        js += t;
+    };
+    auto conv = [&](int id) {
+        const ConvSpec &c = n->convs[id];
+        add("{\"w\": \"%s\", \"bn\": \"%s\", \"ks\": %d, \"stride\": %d, \"act\": %d, \"cout\": %d, \"embed3\": %d, ",
+            c.w.c_str(), c.bn.c_str(), c.embed3 ? 1 : c.ks, c.stride, c.act, c.cout, c.embed3 ? 1 : 0);
+        add("\"in_buf\": %d, \"in_coff\": %d, \"res_buf\": %d, \"res_coff\": %d, \"out_buf\": %d, \"out_coff\": %d, \"nchw_slot\": %d, \"cin_map\": [",
+            c.in_buf, c.in_coff, c.res_buf, c.res_coff, c.out_buf, c.out_coff, c.nchw_slot);
+        for (size_t i = 0; i < c.cin_map.size(); ++i) add(i ? ", %d" : "%d", c.cin_map[i]);
+        js += "], \"tail\": ";
+        if (c.tail_conv >= 0) {
+            const ConvSpec &b = n->convs[c.tail_conv];
+            add("{\"w\": \"%s\", \"act\": %d, \"cout\": %d, \"out_buf\": %d, \"out_coff\": %d, \"nchw_slot\": %d}",
+                b.w.c_str(), b.act, b.cout, b.out_buf, b.out_coff, b.nchw_slot);
+        } else js += "null";
+        js += ", \"pool\": ";
+        if (c.pool_tail) add("{\"mode\": 0, \"out_buf\": %d, \"out_coff\": %d}", c.pool_out_buf, c.pool_out_coff);
+        else js += "null";
+        js += "}";
+    };
+    if (k == -1) {
+        add("{\"prec\": \"%s\", \"in_h\": %d, \"in_w\": %d, \"input_dim\": %d, \"max_batch\": %d, \"steps\": %zu, \"bufs\": [",
+            n->x3 ? "bf16x3" : n->prec == PN_PREC_BF16 ? "bf16" : "fp32", n->in_h, n->in_w, n->input_dim, n->max_batch, n->steps.size());
+        for (size_t i = 0; i < n->bufs.size(); ++i) add(i ? ", [%d, %d, %d]" : "[%d, %d, %d]", n->bufs[i].H, n->bufs[i].W, n->bufs[i].plane);
+        js += "]}";
+    } else {
+        const Step &st = n->steps[k];
+        static const char *types[] = {"stem", "pool", "conv", "bblock"};
+        add("{\"type\": \"%s\", \"kernel\": \"%s\"", types[(int)st.type], step_label(n, st).c_str());
+        if (st.type == Step::STEM) add(", \"cin\": %d, \"out_buf\": %d, \"pool_buf\": %d", st.stem_cin, st.out_buf, st.stem_pool_buf);
+        else if (st.type == Step::POOL) add(", \"mode\": %d, \"in_buf\": %d, \"out_buf\": %d, \"C\": %d, \"out_coff\": %d", st.mode, st.in_buf, st.out_buf, st.C, st.out_coff);
+        else {
+            js += ", \"convs\": [";
+            const std::vector<int> ids = st.type == Step::BBLOCK ? std::vector<int>{st.bb_a, st.bb_b} : st.conv_ids;
+            for (size_t i = 0; i < ids.size(); ++i) {
+                if (i) js += ", ";
+                conv(ids[i]);
+            }
+            js += "]";
+        }
+        js += "}";
+    }
+    if (js.size() + 1 > cap) return pn_set_error(ctx, PN_ERR_INVALID, "pn_net_step_info: %zu bytes needed", js.size() + 1);
+    memcpy(out, js.c_str(), js.size() + 1);
+    return PN_OK;
 }
 
 double pn_net_flops_per_frame(pn_net *n) { return n ? n->flops_per_frame : 0.0; }
