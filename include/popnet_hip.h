@@ -363,6 +363,51 @@ int pn_slice_copy(pn_ctx *ctx, const float *src_dev, int src_ld, float *dst_dev,
 int pn_sgd_nesterov(pn_ctx *ctx, float *param_dev, const float *grad_dev, float *momentum_buf_dev, size_t n, float lr,
                     float momentum, float weight_decay, int first_step, float grad_scale, void *hip_stream);
 
+/* ---- YoloPoseNet training primitives (csrc/train_yolo.hip) ------------------------------------------------------------------
+ * What YoloPoseNet's train-mode forward / loss / backward needs beyond the rtpose primitives above; fp32 NCHW, asynchronous on the
+ * stream, fixed summation orders (a repeated call gives the same bits), no float atomics.
+ *   pn_conv2d_dgrad_strided  input gradient of nn.Conv2d at any stride (ks 1 or 3; layer2.0.conv1 / layer2.0.downsample.0 of
+ *                       tpm/lib/network/resnet.py run at stride 2): dx [N,Cin,H,W] (+)= the gather over the taps that hit each input
+ *                       pixel of dy [N,Cout,Ho,Wo] * w [Cout,Cin,ks,ks] -- one fmaf chain per pixel, output channel outer, taps row-major
+ *   pn_maxpool_forward  nn.MaxPool2d(k, stride, pad) (tpm/lib/network/yolo_posenet.py:36,114), planes = N * C; idx = int32 flat index
+ *                       of the maximum inside its plane; ties and NaN as PyTorch's CPU max_pool2d_with_indices (first maximum of the
+ *                       row-major window, the last NaN of a window)
+ *   pn_maxpool_backward dx [planes,H,W] = per pixel, the sum in output row-major order of the dy whose idx is that pixel
+ *   pn_yolo_loss        the per-slice casts of YoloPoseNet.forward (yolo_posenet.py:146-156) applied to the last convolution's raw
+ *                       output v [N, A(5+3J), h, w] (channel a(5+3J) + k) -> out (the module's output), terms [4] = loss_prior,
+ *                       loss_bbox, loss_obj, loss_selfpose of yolo_loss_fgweight_poseweight (weight_map [N,A,h,w] given) or
+ *                       yolo_loss_fgweight (weight_map NULL) (tpm/lib/network/losses.py:397-466), and dv = d loss_prior / d v;
+ *                       prior_map as out, mask_conf / mask_coord [N,A,h,w]
+ *   pn_build_prior_targets  build_prior_targets + bbox_ious (tpm/lib/datasets/datasets_kdh3d_mpaug.py:353-417,505-533, CR) for a
+ *                       batch: boxes [B,Pmax,4] f64 (x0, y0, x1, y1 network-input pixels, as Resize leaves ann['bbox']), kp2d
+ *                       [B,Pmax,J,2] f32, kp_z [B,Pmax,J] f64 metres, pose_weight [B,Pmax] f64, n_persons [B] -> prior_map
+ *                       [B,A(5+3J),h,w], mask_conf / mask_coord / weight_map [B,A,h,w] f32, h = int(input_y / stride_prior).
+ *                       float64 arithmetic in the reference's order, stored as float32; where persons share a cell the last one
+ *                       in list order writes it.  boxes / kp2d / kp_z / pose_weight may be NULL when Pmax = 0. */
+#define PN_YOLO_MAX_ANCHORS 8
+typedef struct pn_yolo_target_cfg {
+    int input_x, input_y;      /* network input size (224) */
+    int stride_prior;          /* 16  datasets_kdh3d_mpaug.py:229-230 */
+    int num_joints;            /* 15 */
+    int num_anchors;           /* 2 */
+    double anchors[PN_YOLO_MAX_ANCHORS][2];   /* (w, h) in prior cells: (6, 3), (12, 6)  train_yolo_posenet_kdh3d_mpaug.py:45 */
+    double noobject_scale, object_scale;      /* 0.1, 1.0 */
+    double depth_mean, depth_std;             /* 3, 2 */
+} pn_yolo_target_cfg;
+void pn_yolo_target_cfg_default(pn_yolo_target_cfg *cfg);
+int pn_conv2d_dgrad_strided(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int H, int W, int Cout,
+                            int ks, int stride, int pad, int accumulate, void *hip_stream);
+int pn_maxpool_forward(pn_ctx *ctx, const float *x_dev, float *y_dev, int *idx_dev, int planes, int H, int W, int k, int stride, int pad,
+                       void *hip_stream);
+int pn_maxpool_backward(pn_ctx *ctx, const float *dy_dev, const int *idx_dev, float *dx_dev, int planes, int H, int W, int k, int stride,
+                        int pad, void *hip_stream);
+int pn_yolo_loss(pn_ctx *ctx, const float *v_dev, const float *prior_map_dev, const float *mask_conf_dev, const float *mask_coord_dev,
+                 const float *weight_map_dev, int N, int A, int J, int h, int w, float *out_dev, float *terms_dev, float *dv_dev,
+                 void *hip_stream);
+int pn_build_prior_targets(pn_ctx *ctx, const double *boxes_dev, const float *kp2d_dev, const double *kp_z_dev, const double *pose_weight_dev,
+                           const int *n_persons_dev, int B, int Pmax, const pn_yolo_target_cfg *cfg, float *prior_map_dev,
+                           float *mask_conf_dev, float *mask_coord_dev, float *weight_map_dev, void *hip_stream);
+
 /* ---- training step on NHWC [hi | lo] bf16 planes (round 6; csrc/trainx.hip) -------------------------------------------------
  * One object runs forward + loss + backward of rtpose_light3d(15, 14, 2, input_dim = 1) in train mode for ONE batch shape:
  * the per-batch body of tpm/train_rtpose_light3d_kdh3d_mpaug.py:160-180 (CR) up to (not including) optimizer.step(), i.e.

@@ -36,6 +36,16 @@ class TargetCfg(C.Structure):
                 ("sigma", C.c_double), ("depth_max", C.c_double), ("depth_mean", C.c_double), ("depth_std", C.c_double)]
 
 
+PN_YOLO_MAX_ANCHORS = 8
+
+
+class YoloTargetCfg(C.Structure):
+    """pn_yolo_target_cfg"""
+    _fields_ = [("input_x", C.c_int), ("input_y", C.c_int), ("stride_prior", C.c_int), ("num_joints", C.c_int), ("num_anchors", C.c_int),
+                ("anchors", (C.c_double * 2) * PN_YOLO_MAX_ANCHORS), ("noobject_scale", C.c_double), ("object_scale", C.c_double),
+                ("depth_mean", C.c_double), ("depth_std", C.c_double)]
+
+
 class ParseCfg(C.Structure):
     """pn_parse_cfg"""
     _fields_ = [("thresh_heatmap", C.c_float), ("thresh_paf", C.c_float),
@@ -127,6 +137,12 @@ _SIGNATURES = {
     "pn_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "pn_slice_copy": (_i, [_vp, _vp, _i, _vp] + [_i] * 5 + [_vp]),
     "pn_sgd_nesterov": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, _f, _f, _f, _i, _f, _vp]),
+    "pn_conv2d_dgrad_strided": (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
+    "pn_maxpool_forward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
+    "pn_maxpool_backward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
+    "pn_yolo_loss": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 4),
+    "pn_yolo_target_cfg_default": (None, [C.POINTER(YoloTargetCfg)]),
+    "pn_build_prior_targets": (_i, [_vp] * 6 + [_i, _i, C.POINTER(YoloTargetCfg)] + [_vp] * 5),
     "pn_trainer_create": (_vp, [_vp]),
     "pn_trainer_destroy": (None, [_vp]),
     "pn_trainer_set_precision": (_i, [_vp, _i]),

@@ -36,6 +36,7 @@ struct pn_ctx {
 
 int pn_set_error(pn_ctx *ctx, int code, const char *fmt, ...);
 void pn_parse_big_free(pn_ctx *ctx);     // parse_paf.hip
+int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)
 
 #define PN_HIP_CHECK(ctx, expr)                                                              \
     do {                                                                                     \

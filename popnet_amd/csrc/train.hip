@@ -2293,6 +2293,8 @@ static int t_ws(pn_ctx *ctx, size_t bytes, void **out) {
     return PN_OK;
 }
 
+int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out) { return t_ws(ctx, bytes, out); }
+
 static int t_slices(long total, int C) {       // slices per channel so that the reduction fills the chip
     long s = (1024 + C - 1) / C;
     const long cap = (total + 4095) / 4096;

@@ -8,6 +8,8 @@ ORDERS the calls; every convolution, BatchNorm and pooling, forward and backward
     pn_conv2d_forward / pn_conv2d_dgrad / pn_conv2d_wgrad        nn.Conv2d
     pn_bn_train_forward / pn_bn_train_backward                   nn.BatchNorm2d in train mode (+ residual add + ReLU / LeakyReLU)
     pn_avgpool3s2_forward / pn_avgpool3s2_backward               nn.AvgPool2d(3, 2, 1)
+    pn_maxpool_forward / pn_maxpool_backward                     nn.MaxPool2d (YoloPoseNet)
+    pn_conv2d_dgrad_strided                                      the data gradient of a strided nn.Conv2d (YoloPoseNet's layer2.0)
 
 (the same kernels popnet_amd.train.TrainEngine drives without autograd; the engine stays the fast path: flat buffers, fused
 head + loss kernels, one hipGraph per step).  No PyTorch convolution / normalisation kernel is ever run; there is no CPU fallback.
@@ -61,11 +63,12 @@ class Conv2dFn(torch.autograd.Function):
         c.check(_lib.lib().pn_conv2d_wgrad(c.handle, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, Cin, H, W, Cout, ks, stride, pad, s), "pn_conv2d_wgrad")
         dx = None
         if ctx.needs_input_grad[0]:
-            if stride != 1:
-                raise _lib.PopnetError("popnet_amd: the data gradient of a strided convolution is not built (rtpose_light3d's only strided "
-                                       "convolution is the first layer, whose input needs no gradient)")
             dx = torch.empty_like(x)
-            c.check(_lib.lib().pn_conv2d_dgrad(c.handle, _ptr(dy), _ptr(w), _ptr(dx), N, Cin, H, W, Cout, ks, pad, 0, s), "pn_conv2d_dgrad")
+            if stride != 1:                    # YoloPoseNet's layer2.0.conv1 / downsample.0 (csrc/train_yolo.hip)
+                c.check(_lib.lib().pn_conv2d_dgrad_strided(c.handle, _ptr(dy), _ptr(w), _ptr(dx), N, Cin, H, W, Cout, ks, stride, pad, 0, s),
+                        "pn_conv2d_dgrad_strided")
+            else:
+                c.check(_lib.lib().pn_conv2d_dgrad(c.handle, _ptr(dy), _ptr(w), _ptr(dx), N, Cin, H, W, Cout, ks, pad, 0, s), "pn_conv2d_dgrad")
         return dx, dw, db, None, None
 
 
@@ -123,6 +126,44 @@ class AvgPool3s2Fn(torch.autograd.Function):
         dx = torch.empty(ctx.shape, device=dy.device, dtype=torch.float32)
         c.check(_lib.lib().pn_avgpool3s2_backward(c.handle, _ptr(dy), _ptr(dx), N * Cc, H, W, s), "pn_avgpool3s2_backward")
         return dx
+
+
+class MaxPoolFn(torch.autograd.Function):
+    """nn.MaxPool2d(k, stride, padding) (YoloPoseNet: (3, 2, 1) after the stem, (2, 2) in model2_1); the argmax indices of the forward
+    route the gradient (pn_maxpool_forward / pn_maxpool_backward)."""
+
+    @staticmethod
+    def forward(ctx, x, k, stride, pad):
+        x = x.contiguous()
+        c, s = _ctx(x)
+        N, Cc, H, W = x.shape
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        y = torch.empty((N, Cc, Ho, Wo), device=x.device, dtype=torch.float32)
+        idx = torch.empty((N, Cc, Ho, Wo), device=x.device, dtype=torch.int32)
+        c.check(_lib.lib().pn_maxpool_forward(c.handle, _ptr(x), _ptr(y), _ptr(idx), N * Cc, H, W, k, stride, pad, s), "pn_maxpool_forward")
+        ctx.save_for_backward(idx)
+        ctx.geom = (tuple(x.shape), k, stride, pad)
+        ctx.mark_non_differentiable(idx)
+        return y, idx
+
+    @staticmethod
+    def backward(ctx, dy, _didx):
+        idx, = ctx.saved_tensors
+        shape, k, stride, pad = ctx.geom
+        dy = dy.contiguous()
+        c, s = _ctx(dy)
+        N, Cc, H, W = shape
+        dx = torch.empty(shape, device=dy.device, dtype=torch.float32)
+        c.check(_lib.lib().pn_maxpool_backward(c.handle, _ptr(dy), _ptr(idx), _ptr(dx), N * Cc, H, W, k, stride, pad, s), "pn_maxpool_backward")
+        return dx, None, None, None
+
+
+def maxpool(x, m):
+    """nn.MaxPool2d parameter-free holder `m` applied through MaxPoolFn (square kernel / stride / padding, no dilation, floor mode)."""
+    k, st, pd = [(v, v) if isinstance(v, int) else tuple(v) for v in (m.kernel_size, m.stride, m.padding)]
+    if k[0] != k[1] or st[0] != st[1] or pd[0] != pd[1] or m.dilation not in (1, (1, 1)) or m.ceil_mode or m.return_indices:
+        raise _lib.PopnetError("popnet_amd: MaxPool2d(dilation=%s, ceil_mode=%s) is outside what pn_maxpool_forward computes" % (m.dilation, m.ceil_mode))
+    return MaxPoolFn.apply(x, k[0], st[0], pd[0])[0]
 
 
 def conv(x, m):

@@ -64,7 +64,45 @@ class YoloPoseNet(HipNetModule):
     def _net_args(self):
         return self._kind, self.num_parts, len(self.anchors), self.input_dim
 
+    # ---- train mode: the reference's forward (yolo_posenet.py:42-54,137-158, resnet.py BasicBlock) on the autograd-wrapped HIP primitives ----
+    def _forward_train(self, x):
+        from . import _autograd as ag
+        x = self._check_input(x)
+        if x.shape[2] % 16 or x.shape[3] % 16:
+            raise _lib.PopnetError("input size must be a multiple of 16")
+        for p in self.parameters():
+            if p.device != x.device:
+                raise _lib.PopnetError("popnet_amd: module parameters are on %s, the input on %s -- call model.cuda() (the HIP path has no CPU fallback)" % (p.device, x.device))
+
+        def block(u, a):                       # BasicBlock: conv1 carries the stride, downsample = 1x1 conv (same stride) + BN
+            y = ag.bn_act(ag.conv(a, u.conv1), u.bn1, ag.ACT_RELU)
+            y = ag.conv(y, u.conv2)
+            idn = a if u.downsample is None else ag.bn_act(ag.conv(a, u.downsample[0]), u.downsample[1], ag.ACT_NONE)
+            return ag.bn_act(y, u.bn2, ag.ACT_RELU, res=idn)
+
+        m0 = self.model0
+        a = ag.maxpool(ag.bn_act(ag.conv(x, m0.conv1), m0.bn1, ag.ACT_RELU), m0.maxpool)
+        for u in m0.layer1:
+            a = block(u, a)
+        for u in m0.layer2:                    # layer3 is built but never run by the reference (yolo_posenet.py:54)
+            a = block(u, a)
+        for i in (0, 3, 6, 9):                 # model1: make_stages, conv BN LeakyReLU(0.1) x 4 + a bare conv
+            a = ag.bn_act(ag.conv(a, self.model1[i]), self.model1[i + 1], ag.ACT_LEAKY)
+        a = ag.conv(a, self.model1[12])
+        a = ag.maxpool(ag.bn_act(ag.conv(a, self.model2_1[0]), self.model2_1[1], ag.ACT_LEAKY), self.model2_1[3])
+        for seq in (self.model2_2, self.model2_3):
+            a = ag.bn_act(ag.conv(a, seq[0]), seq[1], ag.ACT_LEAKY)
+        v = ag.conv(a, self.model2_4[0])
+        # the per-slice range casts of :146-156 are element-wise glue: left to torch (autograd orders them)
+        B, _, h, w = v.shape
+        s = v.view(B, len(self.anchors), 5 + 3 * self.num_parts, h, w).sigmoid()
+        out = torch.cat([(s[:, :, 0:2] - 0.5) * 2, s[:, :, 2:4] * 2, s[:, :, 4:5], (s[:, :, 5:] - 0.5) * 4], 2).view(v.shape)
+        self.invalidate()                      # the weights are about to change: the eval-mode net is re-folded on its next use
+        return out
+
     def forward(self, x):
+        if self.training:
+            return self._forward_train(x)
         x = self._check_input(x)
         B, _, H, W = x.shape
         dev = x.device

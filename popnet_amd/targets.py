@@ -82,6 +82,50 @@ def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, strid
     return heat, paf, z, fg
 
 
+def yolo_target_cfg(input_size=224, stride_prior=16, anchors=((6., 3.), (12., 6.)), num_joints=NUM_JOINTS, noobject_scale=0.1, object_scale=1.0):
+    cfg = _lib.YoloTargetCfg()
+    _lib.lib().pn_yolo_target_cfg_default(C.byref(cfg))
+    if not 1 <= len(anchors) <= _lib.PN_YOLO_MAX_ANCHORS:
+        raise _lib.PopnetError("prior_targets: 1 to %d anchors" % _lib.PN_YOLO_MAX_ANCHORS)
+    cfg.input_x = cfg.input_y = int(input_size)
+    cfg.stride_prior, cfg.num_joints, cfg.num_anchors = int(stride_prior), int(num_joints), len(anchors)
+    for a, (aw, ah) in enumerate(anchors):
+        cfg.anchors[a][0], cfg.anchors[a][1] = float(aw), float(ah)
+    cfg.noobject_scale, cfg.object_scale = float(noobject_scale), float(object_scale)
+    cfg.depth_mean, cfg.depth_std = float(DEPTH_MEAN), float(DEPTH_STD)
+    return cfg
+
+
+def prior_targets(boxes, kp2d, kp_z, pose_weight, n_persons, input_size=224, stride_prior=16, anchors=((6., 3.), (12., 6.)), noobject_scale=0.1,
+                  object_scale=1.0):
+    """The YOLO training targets of a batch: build_prior_targets + bbox_ious (tpm/lib/datasets/datasets_kdh3d_mpaug.py:353-417,505-533, CR),
+    fed like get_ground_truth feeds it (:556-585).  boxes [B,P,4] float64 (x0, y0, x1, y1 in network-input pixels, as Resize leaves
+    ann['bbox']), kp2d [B,P,J,2] float32 (network-input pixels), kp_z [B,P,J] float64 (metres), pose_weight [B,P] float64, n_persons [B]
+    int32 -> (prior_map [B,A(5+3J),g,g], prior_mask_conf, prior_mask_coord, prior_weight_map [B,A,g,g]) float32, g = int(input / stride_prior)."""
+    for t, n in ((boxes, "boxes"), (kp2d, "kp2d"), (kp_z, "kp_z"), (pose_weight, "pose_weight"), (n_persons, "n_persons")):
+        _lib.require_cuda_tensor(t, n)
+    if (boxes.dtype != torch.float64 or kp2d.dtype != torch.float32 or kp_z.dtype != torch.float64 or pose_weight.dtype != torch.float64
+            or n_persons.dtype != torch.int32):
+        raise _lib.PopnetError("prior_targets: boxes float64, kp2d float32, kp_z float64, pose_weight float64, n_persons int32")
+    B, P = kp2d.shape[0], kp2d.shape[1]
+    J = kp2d.shape[2] if kp2d.dim() == 4 else -1
+    if (kp2d.dim() != 4 or kp2d.shape[3] != 2 or boxes.shape != (B, P, 4) or kp_z.shape != (B, P, J) or pose_weight.shape != (B, P)
+            or n_persons.shape != (B,) or B < 1):
+        raise _lib.PopnetError("prior_targets: shape mismatch")
+    dev = kp2d.device
+    cfg = yolo_target_cfg(input_size, stride_prior, anchors, J, noobject_scale, object_scale)
+    A = len(anchors)
+    g = int(input_size / stride_prior)
+    boxes, kp2d, kp_z, pose_weight, n_persons = (t.contiguous() for t in (boxes, kp2d, kp_z, pose_weight, n_persons))
+    prior = torch.empty((B, A * (5 + 3 * J), g, g), dtype=torch.float32, device=dev)
+    conf, coord, weight = (torch.empty((B, A, g, g), dtype=torch.float32, device=dev) for _ in range(3))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None      # noqa: E731
+    ctx = _ctx(dev)
+    ctx.check(_lib.lib().pn_build_prior_targets(ctx.handle, ptr(boxes), ptr(kp2d), ptr(kp_z), ptr(pose_weight), ptr(n_persons), B, P, C.byref(cfg),
+                                                ptr(prior), ptr(conf), ptr(coord), ptr(weight), _lib.current_stream_ptr(dev)), "pn_build_prior_targets")
+    return prior, conf, coord, weight
+
+
 def _resize(frames, S, depth_max):
     """cv2.resize(INTER_LINEAR) to S x S + the [0, depth_max] clamp, un-normalised (pn_preprocess with mean 0, std 1)."""
     B, H, W = frames.shape
@@ -108,6 +152,23 @@ def mpaug_batch(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, input_s
     heat, paf, z, fg = rasterize_targets(kp, kp3d[..., 2].to(torch.float64).contiguous(), n_persons, depth_resize, input_size, stride, z_radius)
     x = ((img224 - float(DEPTH_MEAN)) / float(DEPTH_STD)).unsqueeze(1)
     return x, heat, paf, z, fg
+
+
+def mpaug_batch_yolo(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, boxes, pose_weight, input_size=224):
+    """mpaug_batch for the YoloPoseNet trainer (datasets_kdh3d_mpaug.py:245-340 (CR), evaluation transform): the same composed, resized and
+    normalised image, and the prior targets of its persons.  boxes [B,P,4] float64 already scaled to input_size (MPAugTrainSet.batch(...,
+    with_boxes=True)).  Returns image [B,1,S,S], prior_map, prior_mask_conf, prior_mask_coord, prior_weight_map."""
+    _lib.require_cuda_tensor(kp2d_org, "kp2d_org")
+    _lib.require_cuda_tensor(kp3d, "kp3d")
+    image = compose_depth(fg_depth, fg_mask, n_src, bg)
+    H, W = image.shape[1:]
+    img = _resize(image, input_size, DEPTH_MAX)
+    kp = kp2d_org.to(torch.float32).clone()
+    kp[..., 0] *= float(input_size) / W
+    kp[..., 1] *= float(input_size) / H
+    prior = prior_targets(boxes, kp, kp3d[..., 2].to(torch.float64).contiguous(), pose_weight, n_persons, input_size)
+    x = ((img - float(DEPTH_MEAN)) / float(DEPTH_STD)).unsqueeze(1)
+    return (x,) + prior
 
 
 AUG_MODS = [[0, 3], [1, 2], [0, 1], [2, 3], [4]]    # datasets_kdh3d_rtpose_mpaug.py:51 -- which annotation sets may share a frame
@@ -175,7 +236,9 @@ class MPAugTrainSet:
     def __len__(self):
         return max(len(i) for i in self.ids)              # dataset_len (:181)
 
-    def batch(self, indices):
+    def batch(self, indices, with_boxes=False, input_size=224):
+        """with_boxes: also return boxes [B,P,4] float64 (ann['bbox'] scaled by Resize to input_size, in float64 like
+        data_augmentation_2d3d.py:497-522) and pose_weight [B,P] float64 (ann['pose_weight']) -- the YoloPoseNet trainer's extra inputs."""
         import os
         src, n_src, bg_id = self.sampler.batch(indices)
         B, S = len(indices), self.max_sources
@@ -209,4 +272,19 @@ class MPAugTrainSet:
                 k3[b, p] = np.asarray(ann["3d_joints"], dtype=np.float64)
         dev = self.device
         t = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)      # noqa: E731
-        return t(fd), t(fm), t(n_src), t(np.stack(bgs).astype(dt)), t(k2), t(k3), t(npers)
+        out = (t(fd), t(fm), t(n_src), t(np.stack(bgs).astype(dt)), t(k2), t(k3), t(npers))
+        if not with_boxes:
+            return out
+        boxes = np.zeros((B, P, 4), dtype=np.float64)
+        pw = np.zeros((B, P), dtype=np.float64)
+        for b in range(B):
+            for p, ann in enumerate(persons[b]):
+                missing = [k for k in ("bbox", "pose_weight") if k not in ann]
+                if missing:
+                    raise KeyError("MPAugTrainSet.batch(with_boxes=True): an annotation lacks %s -- the YoloPoseNet trainer needs "
+                                   "'bbox' ([x0, y0, x1, y1], original pixels) and 'pose_weight' on every person" % " and ".join(repr(k) for k in missing))
+                bb = np.asarray(ann["bbox"], dtype=np.float64)
+                boxes[b, p, 0:4:2] = bb[0:4:2] * (float(input_size) / W)       # Resize: x by the width ratio, y by the height ratio (float64)
+                boxes[b, p, 1:4:2] = bb[1:4:2] * (float(input_size) / H)
+                pw[b, p] = float(ann["pose_weight"])
+        return out + (t(boxes), t(pw))

@@ -159,10 +159,12 @@ class TrainEngine:
                                            stride, pad, self._s()), "pn_conv2d_wgrad")
         if not need_dx:
             return None
-        if stride != 1:
-            raise _lib.PopnetError("popnet_amd.train: data gradient of a strided convolution is not needed by rtpose_light3d and not built")
         if dx is None:
             dx = self._buf("dx:" + name, x.shape)
+        if stride != 1:               # not needed by rtpose_light3d (its only strided convolution is the first); YoloPoseNet's layer2.0
+            self._check(self.L.pn_conv2d_dgrad_strided(self.ctx.handle, self._ptr(dy), self._ptr(w), self._ptr(dx), N, Cin, H, W, Cout, ks, stride, pad,
+                                                       1 if accumulate else 0, self._s()), "pn_conv2d_dgrad_strided")
+            return dx
         self._check(self.L.pn_conv2d_dgrad(self.ctx.handle, self._ptr(dy), self._ptr(w), self._ptr(dx), N, Cin, H, W, Cout, ks, pad, 1 if accumulate else 0, self._s()),
                     "pn_conv2d_dgrad")
         return dx
