@@ -56,9 +56,8 @@ typedef struct pn_net pn_net;
 /* ---- context -------------------------------------------------------------------------------
  * One context per GPU / stream owner.  Not thread-safe per context; independent contexts are. */
 int pn_abi_version(void);
-/* 1 when the library was built with -DPN_EXPERIMENTS (lab builds: the timing-only ablation and mixed-precision environment
- * switches POPNET_ABLATE_SKIP / POPNET_X3_BF16_CONVS are compiled in and can change results), 0 for the shipped library, which
- * honours no result-changing environment variable.  bench.py refuses to time a lab build. */
+/* Always 0: the library has no lab-build variant and honours no result-changing environment variable.  Kept for ABI
+ * compatibility (earlier lab builds returned 1; bench.py refuses to time a library that does). */
 int pn_build_experiments(void);
 /* Measurement aid (bench.py `roofline.peak_sustained_tflops`; no reference counterpart -- the reference has no device code): runs a loop of
  * nothing but v_mfma_f32_16x16x32_bf16 on random bf16 operands (`waves_per_simd` waves on every SIMD of every CU, no memory traffic)

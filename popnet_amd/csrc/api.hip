@@ -12,6 +12,7 @@
 #pragma clang fp contract(off)
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include "pn_internal.h"
 #include "preproc_pixel.h"
@@ -31,16 +32,42 @@ __global__ void preprocess_kernel(const TIN *__restrict__ depth, float *__restri
     out[gid] = pn_preproc_pixel(depth + (size_t)b * H * W, H, W, dy, dx, scale_x, scale_y, dmax, mean, stdv);
 }
 
+PnSwitches pn_read_switches() {
+    auto set = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+    auto is = [](const char *name, const char *value) { const char *e = getenv(name); return e && !strcmp(e, value); };
+    PnSwitches s;
+    s.no_conv3 = set("POPNET_NO_CONV3");
+    s.conv3_rpg8 = set("POPNET_CONV3_RPG8");
+    s.conv3_pt14 = num("POPNET_CONV3_PT14", 0);
+    s.conv3_nbuf2 = set("POPNET_CONV3_NBUF2");
+    s.generic_c64_off = num("POPNET_GENERIC_C64", 1) == 0;
+    if (set("POPNET_CONV4")) s.conv4 = num("POPNET_CONV4", 0) == 0 ? 0 : 1;
+    s.no_mix = set("POPNET_NO_MIX");
+    s.no_bblock = set("POPNET_NO_BBLOCK");
+    s.bblock_x3 = num("POPNET_BBLOCK_X3", 0) != 0;
+    s.bb64_static = set("POPNET_BB64_STATIC");
+    s.bb64_halves = num("POPNET_BB64_HALVES", 1) == 2 ? 2 : 1;
+    s.no_tailfuse = set("POPNET_NO_TAILFUSE");
+    s.no_poolfuse = set("POPNET_NO_POOLFUSE");
+    s.no_stempool = set("POPNET_NO_STEMPOOL");
+    s.no_embed3 = set("POPNET_NO_EMBED3");
+    s.train_x3_wide = set("POPNET_TRAIN_X3_WIDE");
+    s.train_wgrad_novec = set("POPNET_TRAIN_WGRAD_NOVEC");
+    s.trainx_one_stream = num("POPNET_TRAINX_STREAMS", 0) == 1;
+    s.trainx_stem_handover = set("POPNET_TRAINX_STEM_HANDOVER");
+    s.trainx_stem_gather = is("POPNET_TRAINX_STEM_FWD", "gather");
+    s.trainx_stem_bn_separate = is("POPNET_TRAINX_STEM_BN", "separate");
+    s.trainx_stem_depth = num("POPNET_TRAINX_STEM_DEPTH", 2);
+    s.trainx_pack_gather = is("POPNET_TRAINX_PACK", "gather");
+    s.trainx_legacy_wgrad = is("POPNET_TRAINX_WGRAD", "legacy");
+    return s;
+}
+
 extern "C" {
 
 int pn_abi_version(void) { return PN_ABI_VERSION; }
-int pn_build_experiments(void) {
-#ifdef PN_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
+int pn_build_experiments(void) { return 0; }     // kept in the ABI: the library has no lab-build variant any more
 
 pn_ctx *pn_create(int device_id) {
     pn_ctx *ctx = new pn_ctx();

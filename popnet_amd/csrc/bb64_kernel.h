@@ -22,7 +22,7 @@
 //     weights (W1 | W2 as one periodic 36-step stream, L2-resident: one 4 KB k-step each per phase, landed one phase later),
 //     waves 6, 7 the next tile's input image (HBM / Infinity Cache latency) and wait for it only at the end of the tile.
 //     vmcnt retires in issue order, so with both streams on one wave (round 2) every phase of conv1 waited for an image
-//     piece issued one phase earlier: 530 cycles per 320-cycle phase against 355 per 256 in conv2 (scripts/bblab.hip);
+//     piece issued one phase earlier: 530 cycles per 320-cycle phase against 355 per 256 in conv2 (lab timeline);
 //   * one barrier per TWO k-steps (a bare s_barrier for the compute waves: their fragment reads stay in flight across it):
 //     20 barriers per tile instead of 38; 160 KB of LDS, one workgroup per CU.
 //   * round 5: the tiles are handed out by TICKET (one atomic per tile, fetched a tile ahead by an image-loader wave and published through sixteen spare
@@ -60,7 +60,7 @@ __device__ __forceinline__ unsigned bb_relu_pk(unsigned w) {
 
 // HV = 1 (default): four compute waves of 64 couts.  HV = 2 (round 5, POPNET_BB64_HALVES=2): EIGHT compute waves -- the four pixel groups times two
 // cout halves, two per SIMD, so that one wave's fragment reads and barrier waits hide behind the other's MFMAs.  Same LDS images, same weight ring,
-// same k order per output: bit-identical.  Measured (scripts/bblab.hip, 32 x 112 x 112): the third tile takes 17 877 shader cycles instead of 19 595
+// same k order per output: bit-identical.  Measured (lab timeline, 32 x 112 x 112): the third tile takes 17 877 shader cycles instead of 19 595
 // (the intermediate write 1 944 instead of 3 057), the whole kernel 126 k instead of 136 k -- and 73.2-74.2 us instead of 71.8-72.1: the in-kernel
 // clock read 1.56 GHz against 1.71.  The package draws 1 370 W of its 1 400 W limit under this kernel (rocm-smi, profiles/r05_power.txt): twelve
 // waves and 55 % more LDS bytes per k-step (both halves read every B fragment) cost the clock what they save in cycles.  Kept as a switch.
@@ -114,13 +114,9 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
                 const int tnx = next_tile_raw(t, k);
 #pragma clang loop unroll(full)
                 for (int p = 0; p < 18; ++p) {                   // phase p = k-steps 2p, 2p + 1 of the tile's 36
-#ifndef BB_FAKE_NODMA_A
                     dma_a((2 * p + 4) % 36);
                     dma_a((2 * p + 5) % 36);
                     asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-#else
-                    asm volatile("s_barrier" ::: "memory");
-#endif
                     if (p == 8) asm volatile("s_barrier" ::: "memory");          // the compute waves publish the intermediate image
                 }
                 asm volatile("s_barrier" ::: "memory");                             // end of tile
@@ -171,9 +167,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             }
 #pragma clang loop unroll(full)
             for (int p = 0; p < 18; ++p) {
-#ifndef BB_FAKE_NODMA_IN
                 if (p < 12) { dma_in(tn, cur ^ 1, n0 + 2 * p); dma_in(tn, cur ^ 1, n0 + 2 * p + 1); }
-#endif
                 asm volatile("s_barrier" ::: "memory");
                 if (p == 8) asm volatile("s_barrier" ::: "memory");
             }
@@ -207,12 +201,10 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
     for (int ct = 0; ct < CT; ++ct) aq[0][ct] = *reinterpret_cast<const bf16x8 *>(smem + aaddr + ct * 1024);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     int cur = 0;
-    PN_STAMP_AT(0);
     for (int it = 0; t < P.ntiles; ++it) {
         const int tnx = next_tile_raw(t, it);
         int b, oy0, ox0, R, Wc;
         tile_geom(t, b, oy0, ox0, R, Wc);
-        if (it == 2) PN_STAMP_AT(1);                     // third tile: steady state
         const int MC = Wc + 2, nmid = (R + 2) * MC, nout = R * Wc;
         const float inv_mc = 1.0f / (float)MC, inv_wc = 1.0f / (float)Wc;
         const int inb = cur * BB_IN;
@@ -262,7 +254,6 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             // images are stable)
             if (ph & 1) asm volatile("s_barrier" ::: "memory");
         }
-        if (it == 2) PN_STAMP_AT(2);
         // ---------------- intermediate: bias + ReLU -> bf16 -> LDS image (zero outside the map) ----------------
 #pragma clang loop unroll(full)
         for (int pt = 0; pt < PT1; ++pt) {
@@ -294,7 +285,6 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (it == 2) PN_STAMP_AT(3);
         // ---------------- conv2: 18 k-steps on the intermediate image ----------------
 #define BB_OFF2(j) ((((j) / PT2) / KK) * 2 * BB_MIDQ + BB_TAPOFF(((j) / PT2) % KK))
 #pragma unroll
@@ -323,7 +313,6 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             __builtin_amdgcn_sched_barrier(0);
             if (ph & 1) asm volatile("s_barrier" ::: "memory");
         }
-        if (it == 2) PN_STAMP_AT(4);
         // ---------------- output: bias + residual (centre of the input image) + ReLU, 2 x 16-B stores per pixel ----------------
         {
             const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -355,11 +344,9 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // the loader may now refill this image's buffer
-        if (it == 2) PN_STAMP_AT(5);
         cur ^= 1;
         t = __builtin_amdgcn_readfirstlane(tnx);
     }
-    PN_STAMP_AT(12);
 #undef BB_OFF1
 #undef BB_OFF2
 #undef BB_TAPOFF
@@ -369,11 +356,6 @@ static int bb64_launch(pn_ctx *ctx, const BBProblem &P, int num_cus, hipStream_t
     static PnLdsAttr attr[2];
     const int halves = P.halves == 2 ? 2 : 1;        // 2 (POPNET_BB64_HALVES=2 when the net was compiled): the eight-compute-wave form -- 7 % fewer cycles, 2-3 % MORE time
     if (int rc = pn_lds_attr(ctx, attr[halves - 1], halves == 2 ? reinterpret_cast<const void *>(bb64_kernel<2>) : reinterpret_cast<const void *>(bb64_kernel<1>), BB_LDS)) return rc;
-    // experiment switch: POPNET_BB64_CUS = workgroups of the persistent launch (default: one per CU).  Fewer leave whole CUs to the
-    // kernels of other streams while this one runs (a bb64 workgroup owns its CU's LDS).
-    static int cap = -1;
-    if (cap < 0) { const char *e = getenv("POPNET_BB64_CUS"); cap = e ? atoi(e) : 0; }
-    if (cap > 0 && cap < num_cus) num_cus = cap;
     const int grid = P.ntiles < num_cus ? P.ntiles : num_cus;
     if (halves == 2) hipLaunchKernelGGL(bb64_kernel<2>, dim3(grid), dim3(768), BB_LDS, stream, P);
     else hipLaunchKernelGGL(bb64_kernel<1>, dim3(grid), dim3(512), BB_LDS, stream, P);

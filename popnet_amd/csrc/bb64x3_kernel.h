@@ -38,13 +38,7 @@
 #define BX_ASLOT 4096
 #define BX_LDS (BX_OFF_A + BX_NSLOT * BX_ASLOT)   // 163840 B = all of a CU's LDS
 #define BX_KS 54                              // k-steps per convolution: 3 plane pairs x 2 halves x 9 taps
-#ifdef BX_FAKE_NOBAR                          // timing-only ablation (scripts/bbx3lab.hip): no per-k-step barrier
-#define BX_KBAR do {} while (0)
-#elif defined(BX_LAGA)                        // the slot of step g is refilled during step g: its fragment reads (issued in the first MFMA groups of step g - 1) are drained first
-#define BX_KBAR asm volatile("s_waitcnt lgkmcnt(2)\n\ts_barrier" ::: "memory")
-#else
 #define BX_KBAR asm volatile("s_barrier" ::: "memory")
-#endif
 
 __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
     typedef __bf16 T;
@@ -86,28 +80,13 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
                 sn = sn == BX_NSLOT - 1 ? 0 : sn + 1;
             };
             dma_next(); dma_next(); dma_next(); dma_next();     // k-steps 0..3
-#ifdef BX_LAGA
-            dma_next();                                          // ... and 4: the loop issues step g + 5 into the slot of step g (three steps of slack)
-            asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");
-#else
             asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");        // 0 and 1 have landed
-#endif
             asm volatile("s_barrier" ::: "memory");              // (the compute waves have read k-step 0's fragments)
             for (; t < P.ntiles; t += gridDim.x) {
 #pragma clang loop unroll(disable)
                 for (int g = 0; g < 2 * BX_KS; ++g) {
-#ifndef BX_FAKE_NODMA_A
                     dma_next();                                  // step g + 4 into the slot of step g - 1
-#endif
-#ifdef BX_FAKE_NOWAIT
-                    BX_KBAR;
-#elif defined(BX_FAKE_NOBAR)
-                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#elif defined(BX_LAGA)
-                    asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");  // g + 2 has landed; g + 3 .. g + 5 in flight
-#else
                     asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");  // g + 2 has landed
-#endif
                     if (g == BX_KS - 1) asm volatile("s_barrier" ::: "memory");    // the compute waves publish the intermediate image
                 }
                 asm volatile("s_barrier" ::: "memory");          // end of tile
@@ -142,9 +121,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
             if (more) set_tile(t + (int)gridDim.x);
 #pragma clang loop unroll(disable)
             for (int g = 0; g < 2 * BX_KS; ++g) {
-#ifndef BX_FAKE_NODMA_IN
                 if (more && g >= BX_KS && g < BX_KS + 40) dma_in(g - BX_KS);     // under conv2: the input image is free
-#endif
                 BX_KBAR;
                 if (g == BX_KS - 1) asm volatile("s_barrier" ::: "memory");
             }
@@ -167,11 +144,9 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     int slot = 1;                                        // ring slot of the NEXT k-step's fragments
     const int out_ps = P.out_split * 2;                 // plane distance of the output tensor in bytes
-    PN_STAMP_AT(0);
     for (int it = 0; t < P.ntiles; t += gridDim.x, ++it) {
         int b, oy0, ox0, R, Wc;
         tile_geom(t, b, oy0, ox0, R, Wc);
-        if (it == 2) PN_STAMP_AT(1);                     // third tile: steady state
         const int MC = Wc + 2, nmid = (R + 2) * MC, nout = R * Wc;
         const float inv_mc = 1.0f / (float)MC, inv_wc = 1.0f / (float)Wc;
         int ba1[PT1], ba2[PT2];
@@ -208,41 +183,23 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
             for (int pt = 0; pt < PT1; ++pt) {
                 const int j = ph * PT1 + pt, jr = j + BQ - 1;
                 // the next step's four A fragments in the first two MFMA groups: the last one is >= 10 MFMAs old when its first MFMA issues
-#ifndef BX_FAKE_NOA
-#ifdef BX_A_G0
-                if (pt == 0) {
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) aq[(ph + 1) & 1][ct] = *reinterpret_cast<const bf16x8 *>(smem + an + ct * 1024);
-                }
-#else
                 if (pt < 2) {
                     aq[(ph + 1) & 1][2 * pt] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt) * 1024);
                     aq[(ph + 1) & 1][2 * pt + 1] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt + 1) * 1024);
                 }
-#endif
-#endif
-#ifndef BX_FAKE_NOB
                 if (jr < BX_KS * PT1) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba1[jr % PT1] + BX_OFF1(jr));
-#endif
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
                     acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
-#ifdef BX_A_G0
-                if (pt == 0 && jr < BX_KS * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-                else if (pt == 0) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                else if (jr < BX_KS * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#else
                 if (pt < 2 && jr < BX_KS * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 else if (pt < 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                 else if (jr < BX_KS * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#endif
                 __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             slot = slot == BX_NSLOT - 1 ? 0 : slot + 1;
             BX_KBAR;     // bare: the fragment reads of the next step stay in flight across it
         }
-        if (it == 2) PN_STAMP_AT(2);
         // ---------------- residual: the centre of the input image, both planes, into registers (the image is refilled under conv2) ----------------
         u32x4 rres[PT2][4];
 #pragma clang loop unroll(full)
@@ -282,7 +239,6 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // intermediate image published; the input image is free
-        if (it == 2) PN_STAMP_AT(3);
         // ---------------- conv2: 54 k-steps on the intermediate image ----------------
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -297,41 +253,23 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
 #pragma clang loop unroll(full)
             for (int pt = 0; pt < PT2; ++pt) {
                 const int j = ph * PT2 + pt, jr = j + BQ - 1;
-#ifndef BX_FAKE_NOA
-#ifdef BX_A_G0
-                if (pt == 0) {
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) aq[(ph + 1) & 1][ct] = *reinterpret_cast<const bf16x8 *>(smem + an + ct * 1024);
-                }
-#else
                 if (pt < 2) {
                     aq[(ph + 1) & 1][2 * pt] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt) * 1024);
                     aq[(ph + 1) & 1][2 * pt + 1] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt + 1) * 1024);
                 }
-#endif
-#endif
-#ifndef BX_FAKE_NOB
                 if (jr < BX_KS * PT2) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba2[jr % PT2] + BX_OFF2(jr));
-#endif
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
                     acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
-#ifdef BX_A_G0
-                if (pt == 0 && jr < BX_KS * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-                else if (pt == 0) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                else if (jr < BX_KS * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#else
                 if (pt < 2 && jr < BX_KS * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 else if (pt < 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                 else if (jr < BX_KS * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#endif
                 __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             slot = slot == BX_NSLOT - 1 ? 0 : slot + 1;
             BX_KBAR;
         }
-        if (it == 2) PN_STAMP_AT(4);
         // ---------------- output: (acc + b2) + x_hi + x_lo, ReLU, hi / lo split, two planes of 2 x 16-B stores per pixel ----------------
         {
             const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -366,9 +304,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
             }
         }
         asm volatile("s_barrier" ::: "memory");         // end of tile: the next input image has landed (the image loaders waited for it)
-        if (it == 2) PN_STAMP_AT(5);
     }
-    PN_STAMP_AT(12);
 #undef BX_KOFF
 #undef BX_TAP1
 #undef BX_TAP2

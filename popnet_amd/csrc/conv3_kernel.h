@@ -24,19 +24,10 @@
 #pragma once
 #include "conv_mfma_kernel.h"
 
-#ifndef PN_CONV3_OCC
-#define PN_CONV3_OCC 4
-#endif
-// -DPN_CONV3_NT_STORE: output tiles leave with the nt hint (experiment v21: faster alone, slower in the network, where the next layer re-reads them)
-#ifndef PN_CONV3_FAST_EPILOGUE
-#define PN_CONV3_FAST_EPILOGUE 2  // wave-uniform fast epilogue: 0 never, 1 every instantiation, 2 the 128-cout blocks only (profiles/README.md v23)
-#endif
-#if !defined(PN_CONV3_PIECEMAJOR) && !defined(PN_CONV3_QUARTERMAJOR)
-#define PN_CONV3_HALFMAJOR 1      // LDS halo layout, see the header comment; -DPN_CONV3_PIECEMAJOR selects the first layout (experiments)
-#endif
-// -DPN_CONV3_QUARTERMAJOR (round 5): conv4_kernel's image, [4 planes of 16 channels][halo row][32 px][32 B] -- the 16 lanes of a
-// ds_read_b128 phase cover one whole 256-byte bank row (no conflict; the half-major image: 2-way), one DMA instruction = one 32-pixel halo row of a plane
-// (32 segments of 32 B instead of 16 of 64 B).  Measured: profiles/r05_notes.txt.
+constexpr int PN_CONV3_OCC = 4;             // waves per SIMD of the 4-row kernels
+// (output tiles with the nt store hint, experiment v21: faster alone, slower in the network, where the next layer re-reads them; removed)
+constexpr int PN_CONV3_FAST_EPILOGUE = 2;   // wave-uniform fast epilogue: 0 never, 1 every instantiation, 2 the 128-cout blocks only (profiles/README.md v23)
+// (the piece-major and quarter-major LDS halo layouts of earlier rounds were measured and removed: profiles/README.md v16, profiles/r05_notes.txt)
 
 // LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS [lds_dst, lds_dst + 1024).
 // M0 is written in the same statement that uses it (the compiler does not preserve it around asm).
@@ -44,12 +35,6 @@ __device__ __forceinline__ void pn_glds16(gcptr src, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-}
-
-// 16-byte write-through store (sc1): the line is written to memory at once and dropped from the XCD's L2 (no dirty line is
-// left for the end-of-kernel write-back).  Inline asm: hipcc keeps no vmcnt bookkeeping for it -- stores need none.
-__device__ __forceinline__ void pn_store16_wt(PN_GLOBAL void *p, u32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(p), "v"(v) : "memory");
 }
 
 // LDS-DMA, scalar base + 32-bit lane offset: no 64-bit address registers, the per-step pointer bump is scalar.
@@ -82,23 +67,11 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
     constexpr int NG = 8 * (HR / 2);                   // DMA instructions per chunk, spread over the waves
     constexpr int FRAGB = 1024;
     constexpr int NSTEP = KK * 2;
-#ifndef PN_CONV3_NA2
-#define PN_CONV3_NA2 6
-#endif
-#ifndef PN_CONV3_NA14
-#define PN_CONV3_NA14 3
-#endif
-#ifndef PN_CONV3_DB14
-#define PN_CONV3_DB14 6
-#endif
-    constexpr int NA = KS == 1 ? 2 : (NBUF == 2 ? PN_CONV3_NA2 : (PT == 14 ? PN_CONV3_NA14 : 3));   // NSTEP % NA == 0: the queue slot of a k-step must not depend on the chunk
+    constexpr int NA = KS == 1 ? 2 : (NBUF == 2 ? 6 : 3);   // NSTEP % NA == 0: the queue slot of a k-step must not depend on the chunk
     static_assert(NSTEP % NA == 0, "weight queue depth must divide the k-steps of a chunk");
     constexpr int IMG = 8 * PS;                        // bytes of one halo image
     constexpr int NITEM = NSTEP * PT;
-#ifndef PN_CONV3_DB
-#define PN_CONV3_DB 3
-#endif
-    constexpr int DB = PT == 14 ? PN_CONV3_DB14 : PN_CONV3_DB;
+    constexpr int DB = PT == 14 ? 6 : 3;               // B fragments in flight
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     if ((int)blockIdx.x >= P.nblocks) return;
@@ -109,7 +82,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         bx = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
     }
     const int tid = threadIdx.x;
-    PN_STAMP_AT(0);
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wc = wave / WP, wp = wave % WP;
@@ -160,9 +132,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
     gcptr img = (gcptr)P.in + ((size_t)b * P.H * P.W * P.in_cs + P.in_coff) * 2;
     const unsigned zero_rel = P.in_zero_off - (unsigned)(((size_t)b * P.H * P.W * P.in_cs + P.in_coff) * 2);   // zero page relative to img
     const int row_b = P.W * P.in_cs * 2, col_b = P.in_cs * 2;
-    const int hcol = lane & 31, hrow = lane >> 5;
-    const bool col_ok = hcol < HC && (unsigned)(ix0 + hcol) < (unsigned)P.W;
-    const unsigned coloff = (unsigned)((ix0 + hcol) * col_b);
     const int Hin = P.H;
     // Branch-free on purpose (a branch inside the unrolled K loop splits it into basic blocks and the
     // compiler then drains the weight queue at every block boundary): an instruction that has nothing
@@ -170,15 +139,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
     auto stage_one = [&](int chunk, int j, int bufoff, bool live) {   // j-th DMA instruction of this wave for `chunk`
         const int n = wave * NGW + j;                    // wave-uniform
         const bool on = live && n < NG;
-#if defined(PN_CONV3_QUARTERMAJOR)
-        const int pln = n / HR, rr = n - pln * HR;          // plane of 16 channels, halo row
-        const int px = lane >> 1;
-        const int iy = iy0 + rr;
-        const bool inb = (int)on & (int)(px < HC) & (int)((unsigned)(ix0 + px) < (unsigned)P.W) & (int)((unsigned)iy < (unsigned)Hin);
-        unsigned off = (unsigned)(iy * row_b + (ix0 + px) * col_b + pln * 32 + (lane & 1) * 16);
-        const int pc = 0, i = 0;
-        const int dst_hm = pln * (IMG / 4) + rr * (PITCH * 32);
-#elif defined(PN_CONV3_HALFMAJOR)
         // half-major image [2 halves][halo row][32 px][4 pieces x 16 B]: one instruction = 16 pixels x 64 contiguous bytes
         // (4 adjacent lanes = one 64-B segment of a pixel line) instead of 64 pixels x 16 B
         const int hh = n / (2 * HR), rr = (n - hh * 2 * HR) >> 1, gg = n & 1;
@@ -186,29 +146,12 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         const int iy = iy0 + rr;
         const bool inb = (int)on & (int)(px < HC) & (int)((unsigned)(ix0 + px) < (unsigned)P.W) & (int)((unsigned)iy < (unsigned)Hin);
         unsigned off = (unsigned)(iy * row_b + (ix0 + px) * col_b + hh * 64 + (lane & 3) * 16);
-        const int pc = 0, i = 0;
         const int dst_hm = hh * (IMG / 2) + (rr * PITCH + gg * 16) * 64;
-#else
-        const int pc = n / (HR / 2), i = n - pc * (HR / 2);
-        const int iy = iy0 + 2 * i + hrow;
-        const bool inb = (int)on & (int)col_ok & (int)((unsigned)iy < (unsigned)Hin);
-        unsigned off = (unsigned)(iy * row_b + pc * 16) + coloff;
-        const int dst_hm = 0;
-#endif
-#ifdef PN_CONV3_FAKE_LINDMA   // timing experiment (wrong results): each DMA instruction reads 1 KB of consecutive bytes
-        off = (unsigned)(min(max(iy0 + 2 * i, 0), Hin - 2) * row_b + max(ix0, 0) * col_b) + lane * 16;
-#endif
         asm volatile("" : "+v"(off));                    // materialise: the select below must stay a v_cndmask, not a branch
         const int csrc = chunk >= in_wrap ? chunk - in_wrap : chunk;      // bf16x3: the third plane pair reads the hi plane again
         const unsigned zrel = zero_rel - (unsigned)(csrc * 128);
-#ifndef PN_CONV3_FAKE_NODMA                               // timing experiment (wrong results): no halo fetch at all
         pn_glds16(img + csrc * 128 + (inb ? off : zrel),
-#if defined(PN_CONV3_HALFMAJOR) || defined(PN_CONV3_QUARTERMAJOR)
                   (unsigned)__builtin_amdgcn_readfirstlane(on ? bufoff + dst_hm : (NBUF >= 3 ? nchunks : NBUF) * IMG));
-#else
-                  (unsigned)__builtin_amdgcn_readfirstlane(on ? bufoff + pc * PS + i * (2 * PITCH * 16) + dst_hm : (NBUF >= 3 ? nchunks : NBUF) * IMG));
-#endif
-#endif
     };
     auto stage = [&](int chunk, int bufoff) {
 #pragma unroll
@@ -226,16 +169,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         int s = slot < npix ? slot : 0;
         int ry = (int)(((float)s + 0.5f) * inv_wc);
         int rx = s - ry * Wc;
-#if defined(PN_CONV3_QUARTERMAJOR)
-        baddr[pt] = (q >> 1) * (IMG / 4) + (q & 1) * 16 + (ry * PITCH + rx) * 32;
-#elif defined(PN_CONV3_HALFMAJOR)
         baddr[pt] = q * 16 + (ry * PITCH + rx) * 64;
-#else
-        baddr[pt] = q * PS + (ry * PITCH + rx) * 16;
-#endif
-#ifdef PN_CONV3_FAKE_NOWRAP   // timing experiment only (wrong results): every pixel tile reads 16 consecutive entries
-        baddr[pt] = q * PS + (pt * 16 + c) * 16;
-#endif
     }
     f32x4 acc[CT][PT];
 #pragma unroll
@@ -243,10 +177,8 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    PN_STAMP_AT(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    PN_STAMP_AT(2);
 
     static_assert(NBUF != 2 || NGW <= NSTEP, "the next chunk's DMA is spread one instruction per k-step");
     // a wave whose 32 couts lie beyond the layer's cout (a 64-cout conv sharing the launch of a 128-cout
@@ -261,13 +193,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             if (NBUF == 2 && more) stage(chunk + 1, nxt);
         } else {
         // item j = (k-step s = half * KK + tap, pixel tile pt)
-#if defined(PN_CONV3_QUARTERMAJOR)
-#define PN3_OFF(j) ((((j) / PT) / KK) * (IMG / 2) + (((((j) / PT) % KK) / KS) * PITCH + ((((j) / PT) % KK) % KS)) * 32)
-#elif defined(PN_CONV3_HALFMAJOR)
 #define PN3_OFF(j) ((((j) / PT) / KK) * (IMG / 2) + (((((j) / PT) % KK) / KS) * PITCH + ((((j) / PT) % KK) % KS)) * 64)
-#else
-#define PN3_OFF(j) ((((j) / PT) / KK) * 4 * PS + (((((j) / PT) % KK) / KS) * PITCH + ((((j) / PT) % KK) % KS)) * 16)
-#endif
         Frag bq[DB];
 #pragma unroll
         for (int j = 0; j < DB - 1; ++j) bq[j] = read_b_frag<PN_PREC_BF16>(sm + PN3_OFF(j), baddr[j % PT]);
@@ -280,12 +206,8 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             if (pt == 0) {
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {        // wpack ends with NA-1 spare fragments
-#ifndef PN_CONV3_FAKE_NOA                                // timing experiments only (wrong results)
                     aq[(s + NA - 1) % NA][ct] = load_w(wbase[ct]);
-#endif
-#ifndef PN_CONV3_FAKE_SAMEA                              // timing experiment: every weight load hits the same (L1-resident) KB
                     wbase[ct] += FRAGB;
-#endif
                 }
                 // double-buffered: the next chunk's image is fetched by ONE DMA instruction per k-step (the
                 // compiler does not count asm memory ops, so each one shortens the effective depth of the
@@ -293,9 +215,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
                 if (NBUF == 2 && s < NGW) stage_one(chunk + 1, s, nxt, more);
             }
             const int jr = j + DB - 1;
-#ifndef PN_CONV3_FAKE_NOB
             if (jr < NITEM) bq[jr % DB] = read_b_frag<PN_PREC_BF16>(sm + PN3_OFF(jr), baddr[jr % PT]);
-#endif
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) acc[ct][pt] = mma(aq[s % NA][ct], bq[j % DB], acc[ct][pt]);
             if (pt == 0) __builtin_amdgcn_sched_group_barrier(0x020, CT, 0);
@@ -305,7 +225,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         }
 #undef PN3_OFF
         }
-        PN_STAMP_AT(3 + 2 * (chunk & 3));
         if (more && NBUF < 3) {
             if (NBUF == 2) {
                 // every DMA is older than the 2*(NA-1) weight loads in flight: wait for exactly those
@@ -319,7 +238,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
                 __syncthreads();
             }
         }
-        PN_STAMP_AT(4 + 2 * (chunk & 3));
     }
 
     // ---- fused 1x1 tail (ConvProblem::tail_w, net.hip::fuse_1x1_tails): this block's 128-channel tile is the whole input of
@@ -413,7 +331,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             *reinterpret_cast<PN_GLOBAL u32x4 *>(op) = *reinterpret_cast<u32x4 *>(o8);
             if (tsplit) *reinterpret_cast<PN_GLOBAL u32x4 *>(op + tsplit) = *reinterpret_cast<u32x4 *>(l8);
         }
-        PN_STAMP_AT(12);
         return;
     }
     if constexpr (TAIL == 1) {
@@ -452,9 +369,6 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             else if (act == PN_ACT_LEAKY) park(std::integral_constant<int, PN_ACT_LEAKY>{});
             else park(std::integral_constant<int, PN_ACT_NONE>{});           // net.hip::fuse_1x1_tails admits these three only
             __syncthreads();
-#ifdef PN_TAIL_FAKE_NOMMA
-            return;
-#endif
             const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(P.tail_w), 0, 2 * 4 * 1024, 0x00020000);
             unsigned tlane = (unsigned)lane * 16u;
             asm volatile("" : "+v"(tlane));              // keep the eight fragment loads BEHIND the barrier: hoisted above it they are live beside the 56 accumulators
@@ -492,16 +406,13 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
                         for (int i = 0; i < 4; ++i) {
                             const int ch = 8 * q + 4 * t + i;
                             float v = c2[t][i] + tb[ch < tcout ? ch : 0];
-#ifndef PN_TAIL_FAKE_NOACT
                             // the two sigmoid casts of the heads (rtpose_light3d.py:335-337) or none: same expressions as pn_activate
                             if (tact == PN_ACT_SIG_PM2) v = (pn_sigmoid(v) - 0.5f) * 4.f;
                             else if (tact == PN_ACT_SIG) v = pn_sigmoid(v);
-#endif
                             v8[4 * t + i] = ch < tcout ? v : 0.f;
                             o8[4 * t + i] = (T)v8[4 * t + i];
                         }
                     const int nvalid = tcout - 8 * q;
-#ifndef PN_TAIL_FAKE_NOSTORE
                     if (tout && nvalid > 0) {
                         PN_GLOBAL T *op = tout + opix * (size_t)P.tail_out_cs + 8 * q;
                         if (nvalid >= 8) *reinterpret_cast<PN_GLOBAL u32x4 *>(op) = *reinterpret_cast<u32x4 *>(o8);
@@ -513,18 +424,13 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k)
                             if (8 * q + k < tcout) tnchw[((size_t)b * tcout + 8 * q + k) * hw + (size_t)(oy0 + ry) * Wo + (ox0 + rx)] = v8[k];
-#else
-                    if (v8[0] == 123.456f && nvalid > 0 && tnchw) tnchw[0] = v8[1] + v8[2] + v8[3] + v8[4] + v8[5] + v8[6] + v8[7];
-#endif
                 }
             }
-            PN_STAMP_AT(12);
             return;
         }
     }
 
     // ---- epilogue: identical contract to conv_mfma_kernel.h (permuted cout rows, direct stores) ----
-    PN_STAMP_AT(11);
     constexpr int LC = CT * 4;
     const int cw = (cb * WC + wc) * (CT * 16) + LC * q;
     const int cout = P.cout, act = P.act;
@@ -585,11 +491,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
                         ov[k] = pl == 1 ? (T)(v[k] - (float)hi) : hi;
                     }
                     if (full) {
-#ifdef PN_CONV3_NT_STORE
-                        __builtin_nontemporal_store(*reinterpret_cast<u32x4 *>(ov), reinterpret_cast<PN_GLOBAL u32x4 *>(op));
-#else
                         *reinterpret_cast<PN_GLOBAL u32x4 *>(op) = *reinterpret_cast<u32x4 *>(ov);
-#endif
                     } else {
                         for (int k = 0; k < LC; ++k)
                             if (cw + k < cout) op[k] = ov[k];
@@ -604,12 +506,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             }
         }
     };
-#if defined(PN_CONV3_HALFMAJOR) || defined(PN_CONV3_QUARTERMAJOR)
-#if defined(PN_CONV3_QUARTERMAJOR)
-#define PN3_PIXOF(ba) (((unsigned)(ba) - (unsigned)((q >> 1) * (IMG / 4))) >> 5)
-#else
 #define PN3_PIXOF(ba) ((unsigned)(ba) >> 6)
-#endif
     // Fast path, chosen per WAVE (every condition is wave-uniform, so no exec-mask branching): all 32 couts of the wave
     // exist, NHWC output only, a compile-time activation.  The pixel of a slot is recovered from its LDS read address
     // (baddr = q*16 + (ry*32 + rx)*64) instead of being divided out again; same arithmetic on the values as `finish`,
@@ -672,15 +569,12 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             else if (act == PN_ACT_LEAKY) finish_fast(std::integral_constant<int, PN_ACT_LEAKY>{}, std::false_type{});
             else finish_fast(std::integral_constant<int, PN_ACT_NONE>{}, std::false_type{});
         }
-        PN_STAMP_AT(12);
         return;
     }
-#endif
     if (act == PN_ACT_RELU) finish(std::integral_constant<int, PN_ACT_RELU>{});
     else if (act == PN_ACT_LEAKY) finish(std::integral_constant<int, PN_ACT_LEAKY>{});
     else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{});
     else finish(std::integral_constant<int, -1>{});
-    PN_STAMP_AT(12);
 }
 
 template <int KS, int WC, int WP, int NBUF, int PT, int RPG = PT * 4 / 7, int TAIL = 0>

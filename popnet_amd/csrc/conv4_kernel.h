@@ -28,26 +28,18 @@
 #include "conv3_kernel.h"
 
 #define PN4_ASLOT 8192                  // one k-step of weight fragments: 8 cout tiles x 1 KB
-#ifndef PN4_RING
-#define PN4_RING 3                      // weight ring slots (3: slot = immediate; 4: runtime slot, no LDS-read drain at the barrier)
-#endif
-#ifndef PN4_PITCH
-#define PN4_PITCH 32                    // halo pixels per LDS row (36: a 16-pixel tile that wraps a 28-pixel row stays conflict-free)
-#endif
-#ifndef PN4_LGKM
-#define PN4_LGKM 0                      // LDS reads left in flight at the k-step barrier (3 = the three B reads issued last)
-#endif
+constexpr int PN4_RING = 3;             // weight ring slots: the slot of a k-step is an immediate offset
+constexpr int PN4_PITCH = 32;           // halo pixels per LDS row
 #define PN4_ARING (PN4_RING * PN4_ASLOT)
 #define PN4_BQUART (5 * PN4_PITCH * 32 + 1024)   // one 16-channel quarter plane of a strip image: 6 halo rows x PITCH px x 32 B (the last row: the 1 KiB a DMA writes)
 #define PN4_BSTRIP (2 * PN4_BQUART)     // one 32-channel half image of one strip
 #define PN4_BBUF (2 * PN4_BSTRIP)       // both strips
 #define PN4_LDS (PN4_ARING + 2 * PN4_BBUF)
 
-// One block of problem P; block_x = the block's index within the problem's launch (blockIdx.x of conv4_kernel; the persistent
-// experiment of scripts/stagelab.hip walks several (problem, block_x) pairs per workgroup).
+// One block of problem P; block_x = the block's index within the problem's launch (blockIdx.x of conv4_kernel).
 __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block_x) {
     typedef __bf16 T;
-    constexpr int KS = 3, KK = 9, PT = 7, CT = 4, PITCH = PN4_PITCH, RING = PN4_RING;
+    constexpr int KS = 3, KK = 9, PT = 7, CT = 4, PITCH = PN4_PITCH;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     if (block_x >= P.nblocks) return;
@@ -58,7 +50,6 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
         bx = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
     }
     const int tid = threadIdx.x;
-    PN_STAMP_AT(0);
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wp = wave >> 1, wc = wave & 1;            // strip, cout half
@@ -134,7 +125,6 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
         baddr[pt] = PN4_ARING + wp * PN4_BSTRIP + (q >> 1) * PN4_BQUART + (q & 1) * 16 + (ry * PITCH + rx) * 32;
     }
     const int aaddr = wc * 4096 + lane * 16;
-    static_assert(RING == 3 || RING == 4, "weight ring: 3 slots (immediate slot offsets) or 4 (runtime slot)");
     f32x4 acc[CT][PT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
@@ -145,18 +135,13 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
     // takes part in the DMA and the barriers
     const bool active = (cb * 2 + wc) * 64 < P.cout;
 
-    PN_STAMP_AT(1);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    PN_STAMP_AT(2);
 
     // item j = (phase ph, pixel tile pt): B fragment of tap ph % 9 from image (ph / 9) & 1
 #define PN4_BOFF(j) (((((j) / PT) / KK) & 1) * PN4_BBUF + (((((j) / PT) % KK) / KS) * PITCH + ((((j) / PT) % KK) % KS)) * 32)
     // B fragments are read BQ - 1 items (4 MFMAs each) ahead of their use: with 2 ahead a lone wave on its SIMD spent
     // 147 of 717 cycles per k-step waiting for LDS (profiles/README.md, conv4 ablations)
-#ifndef PN4_BQ
-#define PN4_BQ 6
-#endif
-    constexpr int BQ = PN4_BQ;
+    constexpr int BQ = 6;
     static_assert((2 * KK * PT) % BQ == 0, "queue slot of an item must not depend on the chunk");
     bf16x8 aq[2][CT], bq[BQ];
     if (active) {
@@ -176,38 +161,19 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
             for (int ph = 0; ph < 2 * KK; ++ph) {            // k-step s = chunk * 18 + ph
                 const int tap = ph % KK, half = ph / KK;
                 const int hh = chunk * 2 + half;
-                // RING == 4: k-step s lives in slot s & 3 (wave-uniform, computed on the scalar unit + one v_add per step)
-                const int sstep = chunk * (2 * KK) + ph;
-                const int anext = RING == 3 ? aaddr + ((ph + 1) % 3) * PN4_ASLOT : aaddr + (int)__builtin_amdgcn_readfirstlane(((sstep + 1) & 3) * PN4_ASLOT);
+                const int anext = aaddr + ((ph + 1) % 3) * PN4_ASLOT;
                 // (1) staging for later steps: one halo piece of the NEXT half (taps 0..5), the weight fragments of step s + 3
-                // (-DPN4_DMA_MID: issued between the 3rd and the 4th pixel tile's MFMAs instead of in front of the step's first MFMA)
-                auto stage = [&]() {
-#ifndef PN4_FAKE_NODMA_B                        // -DPN4_FAKE_*: timing-only ablations (wrong results), scripts/conv4lab.hip
-                    if (tap < 6) dma_b(tap, (half + 1) & 1, hh + 1);
-#endif
-#ifndef PN4_FAKE_NODMA_A
-                    dma_a(RING == 3 ? ph % 3 : (int)__builtin_amdgcn_readfirstlane((sstep + 3) & 3));
-#endif
-                };
-#ifndef PN4_DMA_MID
-                stage();
-#else
-                if (!MATH) stage();
-#endif
+                if (tap < 6) dma_b(tap, (half + 1) & 1, hh + 1);
+                dma_a(ph % 3);
                 // (2) this step's 28 MFMAs; fragment reads for the next step / the next items between them
                 if (MATH) {
                     __builtin_amdgcn_sched_barrier(0);
 #pragma clang loop unroll(full)
                     for (int pt = 0; pt < PT; ++pt) {
                         const int j = ph * PT + pt, jr = j + BQ - 1;
-#ifdef PN4_DMA_MID
-                        if (pt == 3) { __builtin_amdgcn_sched_barrier(0); stage(); __builtin_amdgcn_sched_barrier(0); }
-#endif
-#ifndef PN4_FAKE_NOLDS
                         if (pt < CT)
                             aq[(ph + 1) & 1][pt] = *reinterpret_cast<const bf16x8 *>(smem + anext + pt * 1024);
                         bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + baddr[jr % PT] + PN4_BOFF(jr % (2 * KK * PT)));
-#endif
 #pragma unroll
                         for (int ct = 0; ct < CT; ++ct)
                             acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
@@ -219,28 +185,9 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
                 }
                 // (3) everything older than the newest weight step (and this phase's halo piece) has landed; every fragment
                 // read issued so far has returned (the slot / image it came from may be overwritten after the barrier)
-#if defined(PN4_FAKE_NOBAR)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#elif defined(PN4_FAKE_NODMA_A) || defined(PN4_FAKE_NODMA_B)
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-#if PN4_RING == 4
-                // 4 slots: the slot refilled in step s + 1 was last read in step s - 1 and the image refilled during a half was
-                // last read before the previous half's final MFMAs -- no LDS read has to drain here
-                if (tap < 6) asm volatile("s_waitcnt vmcnt(3)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-#elif PN4_LGKM == 3
-                // the three LDS reads issued last in a step are B fragments of later items (checked in the ISA): only the A reads
-                // (the slot refilled right after this barrier) have to be back
-                if (tap < 6) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(3)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(3)\n\ts_barrier" ::: "memory");
-#else
                 if (tap < 6) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-#endif
             }
-            PN_STAMP_AT(3 + 2 * (chunk & 3));
         }
     };
     if (active) kloop(std::true_type{});
@@ -252,7 +199,6 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
     // ---- epilogue: a lane holds 16 CONSECUTIVE couts of each of its pixels (net.hip packs the rows with
     // pn_conv_row_channel(tile, row, 4)): bias + residual + activation + two 16-B NHWC stores per pixel tile; the four
     // lane quarters cover one whole 128-B line of the pixel ----
-    PN_STAMP_AT(11);
     constexpr int LC = CT * 4;
     const int wave_c0 = (cb * 2 + wc) * 64;
     const int cw = wave_c0 + LC * q;
@@ -309,19 +255,8 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
                     }
                     if (slot < npix) {
                         PN_GLOBAL u32x4 *op = reinterpret_cast<PN_GLOBAL u32x4 *>(ob + (opix * (unsigned)out_cs + (unsigned)(pl * split)));
-#ifdef PN4_WT_STORE
-                        // write-through (sc1): the tile leaves the XCD's L2 now, while other blocks still compute, instead of in
-                        // the end-of-kernel write-back of ~23 MB of dirty lines that the next launch has to wait for
-                        pn_store16_wt(op, reinterpret_cast<u32x4 *>(ov)[0]);
-                        pn_store16_wt(op + 1, reinterpret_cast<u32x4 *>(ov)[1]);
-#elif defined(PN4_NT_STORE)
-                        // experiment: non-temporal stores (conv3's v21, profiles/README.md: faster alone, slower in the network)
-                        __builtin_nontemporal_store(reinterpret_cast<u32x4 *>(ov)[0], op);
-                        __builtin_nontemporal_store(reinterpret_cast<u32x4 *>(ov)[1], op + 1);
-#else
                         op[0] = reinterpret_cast<u32x4 *>(ov)[0];
                         op[1] = reinterpret_cast<u32x4 *>(ov)[1];
-#endif
                     }
                 }
             }
@@ -337,7 +272,6 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
             else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{}, std::false_type{});
             else finish(std::integral_constant<int, -1>{}, std::false_type{});
         }
-        PN_STAMP_AT(12);
         return;
     }
     // general path (ragged cout, NCHW f32 export): element-wise, same arithmetic
@@ -373,7 +307,6 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
                 }
         }
     }
-    PN_STAMP_AT(12);
 }
 
 __global__ __launch_bounds__(256, 2) void conv4_kernel(const ConvProblem *__restrict__ probs) {
@@ -381,9 +314,7 @@ __global__ __launch_bounds__(256, 2) void conv4_kernel(const ConvProblem *__rest
 }
 
 static int conv4_launch(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream) {
-    // POPNET_CONV4_LDS=<bytes> (experiment): ask for more LDS than the kernel uses, e.g. 90000 = one block per CU, which leaves half of the
-    // CU's registers and 70 KB of its LDS to the small launches of the other batches in flight
-    static const size_t lds = getenv("POPNET_CONV4_LDS") ? std::max<size_t>(PN4_LDS, (size_t)atol(getenv("POPNET_CONV4_LDS"))) : PN4_LDS;
+    const size_t lds = PN4_LDS;
     static PnLdsAttr attr;
     if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(conv4_kernel), lds)) return rc;
     hipLaunchKernelGGL(conv4_kernel, dim3(L.max_blocks, L.nprob), dim3(256), lds, stream, L.probs_dev);

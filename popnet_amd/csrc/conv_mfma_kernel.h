@@ -26,9 +26,6 @@
 #pragma once
 #include <type_traits>
 #include "pn_internal.h"
-#ifndef PN_STAMP_AT
-#define PN_STAMP_AT(i) do {} while (0)     // scripts/convlab.hip: in-kernel s_memtime timeline
-#endif
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -194,7 +191,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     }
 
     const int tid = threadIdx.x;
-    PN_STAMP_AT(0);
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wc = wave / WP, wp = wave % WP;
@@ -342,9 +338,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     for (int ct = 0; ct < CT; ++ct) wbase[ct] += (NA - 1) * FRAGB;
     if (MAXST > 0) { stage_load(0); stage_store(buf0); }
     else stage_direct(0, buf0);
-    PN_STAMP_AT(1);
     __syncthreads();
-    PN_STAMP_AT(2);
 
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const char *sm = (chunk & 1) ? buf1 : buf0;
@@ -395,14 +389,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
         }
 #undef PN_BADDRX
 #undef PN_BADDR
-        PN_STAMP_AT(3 + 2 * (chunk & 3));
         if (more) {
             if (!P.lds_two) __syncthreads();             // single LDS image: wait for every wave's reads
             if (MAXST > 0) stage_store(nbuf);
             else stage_direct(chunk + 1, nbuf);
             __syncthreads();
         }
-        PN_STAMP_AT(4 + 2 * (chunk & 3));
     }
 
     // ---- epilogue ------------------------------------------------------------------------------
@@ -412,7 +404,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     // lane adds the folded bias, the residual (one 16-B load), applies the activation and writes
     // one 16-B (bf16, CT = 2) NHWC piece per pixel tile straight from registers -- no LDS transpose,
     // no barrier; the four lane quarters of a wave cover 64 contiguous bytes of a pixel's line.
-    PN_STAMP_AT(11);
     constexpr int BC = WC * CT * 16;
     constexpr int LC = CT * 4;
     const int cw = (cb * WC + wc) * (CT * 16) + LC * q;          // first output channel of this lane
@@ -510,7 +501,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     else if (act == PN_ACT_LEAKY) finish(std::integral_constant<int, PN_ACT_LEAKY>{});
     else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{});
     else finish(std::integral_constant<int, -1>{});
-    PN_STAMP_AT(12);
 }
 
 

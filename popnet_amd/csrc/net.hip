@@ -73,8 +73,8 @@ struct Step {
     void *bb_wpack = nullptr;
     float *bb_bias1 = nullptr, *bb_bias2 = nullptr;
     int *bb_tickets = nullptr;       // two zeroed ints: bb64_kernel's tile tickets (BBProblem::tickets)
-    bool bb_static = false;          // POPNET_BB64_STATIC=1 when the net was compiled: tiles by position
-    int bb_halves = 1;               // POPNET_BB64_HALVES=2 when the net was compiled: bb64_kernel<2>
+    bool bb_static = false;          // PnSwitches::bb64_static: tiles by position
+    int bb_halves = 1;               // PnSwitches::bb64_halves: bb64_kernel<2>
     // STEM
     int out_buf = -1;
     int stem_pool_buf = -1;          // >= 0: the MaxPool2d(3, 2, 1) that follows runs inside the stem launch and writes this buffer (build_yolo)
@@ -107,6 +107,7 @@ struct pn_net {
     std::map<std::string, HostTensor> tensors;
     bool finalized = false;
     int prec = PN_PREC_F32, max_batch = 0, in_h = 0, in_w = 0;
+    PnSwitches sw;                   // read when the net is compiled (pn_net_finalize)
     std::vector<Buf> bufs;
     std::vector<ConvSpec> convs;
     std::vector<Step> steps;
@@ -185,31 +186,7 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
         if (m >= cin_ref)
             return pn_set_error(ctx, PN_ERR_INVALID, "%s: input-channel map exceeds Cin=%d", cs.w.c_str(), cin_ref);
     std::vector<int> wsel;                        // bf16x3: which half of the split weight multiplies this input channel (0 = hi, 1 = lo)
-    // experiment switch (per-layer mixed precision inside a bf16x3 net): POPNET_X3_BF16_CONVS = comma-separated
-    // substrings of conv names that run as PLAIN bf16 -- they read only the hi plane of their input (one MFMA pass instead of
-    // three) and still write all three planes, so every other layer is unchanged
-    bool x3_low = false;
-#ifdef PN_EXPERIMENTS      // lab builds only (POPNET_EXTRA_HIPCC_FLAGS=-DPN_EXPERIMENTS): the shipped library has no result-changing environment switch
-    if (n->x3)
-        if (const char *e = getenv("POPNET_X3_BF16_CONVS")) {
-            std::string pats(e);
-            size_t pos = 0;
-            while (pos <= pats.size()) {
-                size_t c = pats.find(',', pos);
-                if (c == std::string::npos) c = pats.size();
-                const std::string pat = pats.substr(pos, c - pos);
-                if (!pat.empty() && cs.w.find(pat) != std::string::npos) x3_low = true;
-                pos = c + 1;
-            }
-        }
-#endif
-    if (n->x3 && x3_low) {
-        const int pc = n->bufs[cs.in_buf].plane;
-        if (cs.in_coff != 0 || (int)map.size() > pc)
-            return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: bf16x3 convolutions read whole buffers", cs.w.c_str());
-        map.resize(pc, -1);
-        wsel.assign(pc, 0);
-    } else if (n->x3) {
+    if (n->x3) {
         // the input is the WHOLE buffer, three planes of `plane` channels: [x_hi | x_lo | x_hi] against [W_hi | W_hi | W_lo]
         // = x_hi W_hi + x_lo W_hi + x_hi W_lo (the dropped x_lo W_lo term is 2^-16 of the product)
         const int pc = n->bufs[cs.in_buf].plane;
@@ -260,7 +237,7 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
     geo.pt = cs.pt; geo.rpg = cs.rpg;
     {
         const Buf &ib0 = n->bufs[cs.in_buf];
-        pn_plan_conv_kernel(n->prec, n->max_batch, n->ctx->num_cus, ib0.H, ib0.W, cout, ks, cs.stride, cs.cin_chunks, cs.wc_min, cs.nbuf_min, cs.k4_level, geo);
+        pn_plan_conv_kernel(n->prec, n->max_batch, n->ctx->num_cus, ib0.H, ib0.W, cout, ks, cs.stride, cs.cin_chunks, cs.wc_min, cs.nbuf_min, cs.k4_level, n->sw, geo);
     }
     cs.cfg = geo.cfg; cs.kern = geo.kern; cs.wc = geo.wc; cs.wp = geo.wp; cs.nbuf = geo.nbuf; cs.pt = geo.pt; cs.rpg = geo.rpg; cs.Wt = geo.Wt; cs.R = geo.R;
     const int BC = cs.kern == 4 ? 128 : (cs.kern == 3 ? cs.wc * 32 : pn_cfg_couts(cs.cfg));
@@ -359,8 +336,7 @@ void harmonize_level(pn_net *n, const std::vector<int> &ids) {
             const long strips = (long)n->max_batch * ((ib.H + 3) / 4) * ((ib.W + 29) / 30);
             blocks += ((strips + 1) / 2) * ((w->shape[0] + 127) / 128);
         }
-        const char *e = getenv("POPNET_CONV4");
-        if (e ? atoi(e) == 0 : blocks < 448) k4 = false;
+        if (n->sw.conv4 < 0 ? blocks < 448 : n->sw.conv4 == 0) k4 = false;
         if (k4)
             for (int id : ids) n->convs[id].k4_level = 1;
     }
@@ -393,7 +369,6 @@ void add_conv_level(pn_net *n, const std::vector<int> &ids) {
         st.type = Step::CONV;
         const ConvSpec &a = n->convs[ids[i]];
         // conv3_mix_kernel: the 128-cout 3x3 blocks and the fused-tail 1x1 blocks of a level share one launch
-        static const bool no_mix = getenv("POPNET_NO_MIX") != nullptr;
         auto mixable = [](const ConvSpec &c) {
             return c.kern == 3 && c.stride == 1 && c.wc == 4 && c.wp == 1 && c.nbuf == 1 && c.pt == 7 && c.rpg == 4 && !c.pool_tail && (c.ks == 3 ? c.tail_conv < 0 : c.ks == 1);
         };
@@ -402,7 +377,7 @@ void add_conv_level(pn_net *n, const std::vector<int> &ids) {
             if (used[j]) continue;
             const bool same = (b.tail_conv >= 0) == (a.tail_conv >= 0) && b.pool_tail == a.pool_tail && b.ks == a.ks && b.stride == a.stride && b.pitch == a.pitch && b.R == a.R && b.Wt == a.Wt && b.kern == a.kern &&
                 (a.kern == 4 || (a.kern == 3 ? (b.wc == a.wc && b.wp == a.wp && b.nbuf == a.nbuf && b.pt == a.pt && b.rpg == a.rpg) : b.cfg == a.cfg));
-            const bool mixed = !no_mix && mixable(a) && mixable(b) && b.R == a.R && b.Wt == a.Wt && (a.ks == 3 || b.ks == 3 || (a.tail_conv >= 0) == (b.tail_conv >= 0));
+            const bool mixed = !n->sw.no_mix && mixable(a) && mixable(b) && b.R == a.R && b.Wt == a.Wt && (a.ks == 3 || b.ks == 3 || (a.tail_conv >= 0) == (b.tail_conv >= 0));
             if (same || mixed) {
                 st.conv_ids.push_back(ids[j]);
                 used[j] = true;
@@ -514,15 +489,12 @@ int fold_bn(pn_net *n, const ConvSpec &cs, int cout, std::vector<double> &scale,
 // BasicBlock(64) pairs (conv a: 3x3 64->64 + ReLU into a scratch buffer; conv b: 3x3 64->64 on it + residual = a's input +
 // ReLU) become ONE level {-2, a, b} run by bb64_kernel (bf16) or bb64x3_kernel (bf16x3: two-plane LDS images, 6-row tiles).
 void fuse_basic_blocks(pn_net *n, std::vector<std::vector<int>> &levels) {
-    if (n->prec != PN_PREC_BF16 || getenv("POPNET_NO_BBLOCK") || getenv("POPNET_NO_CONV3")) return;
+    if (n->prec != PN_PREC_BF16 || n->sw.no_bblock || n->sw.no_conv3) return;
     // bf16x3: the fused kernel is built, bit-identical and faster ALONE (2 x 227 us against 4 x 100 us of conv3_kernel<3, 2, 2, 1, 7, 4> per step
     // once tensors are stored as two planes), but a persistent 160-KB-of-LDS workgroup per CU shuts the other in-flight batches out of
     // every CU for its whole life: through the bench's pipelined region the two-launch plan wins (25.7 k against 24.0 k frames/s on the
     // same box, profiles/r04_bb64x3_ab.txt).  POPNET_BBLOCK_X3=1 selects the fused kernel (tests, one-stream latency runs).
-    if (n->x3 && !(getenv("POPNET_BBLOCK_X3") && atoi(getenv("POPNET_BBLOCK_X3")))) return;
-#ifdef PN_EXPERIMENTS
-    if (n->x3 && getenv("POPNET_X3_BF16_CONVS")) return;      // the mixed-precision experiment runs single-pass convs the fused kernel does not know
-#endif
+    if (n->x3 && !n->sw.bblock_x3) return;
     for (size_t i = 0; i + 1 < levels.size(); ++i) {
         if (levels[i].size() != 1 || levels[i + 1].size() != 1 || levels[i][0] < 0 || levels[i + 1][0] < 0) continue;
         const ConvSpec &a = n->convs[levels[i][0]], &b = n->convs[levels[i + 1][0]];
@@ -585,8 +557,8 @@ int add_bblock(pn_net *n, int ia, int ib) {
     PN_HIP_CHECK(ctx, hipMemcpy(st.bb_bias1, hb[0].data(), 64 * 4, hipMemcpyHostToDevice));
     PN_HIP_CHECK(ctx, hipMemcpy(st.bb_bias2, hb[1].data(), 64 * 4, hipMemcpyHostToDevice));
     if (int rc = dev_alloc(n, (void **)&st.bb_tickets, 256, true)) return rc;
-    st.bb_static = getenv("POPNET_BB64_STATIC") != nullptr;          // experiment switches, read when the net is compiled (A/B runs, bit-identity tests)
-    if (const char *e = getenv("POPNET_BB64_HALVES")) st.bb_halves = atoi(e) == 2 ? 2 : 1;
+    st.bb_static = n->sw.bb64_static;          // A/B runs, bit-identity tests
+    st.bb_halves = n->sw.bb64_halves;
     n->steps.push_back(st);
     return PN_OK;
 }
@@ -597,7 +569,7 @@ int add_bblock(pn_net *n, int ia, int ib) {
 // channels, next level) takes B as its tail: B disappears from its level, A's launch writes B's output.  bf16 only (the
 // three-plane bf16x3 form keeps the two-launch path); POPNET_NO_TAILFUSE=1 keeps the two launches (bit-identity tests).
 void fuse_1x1_tails(pn_net *n, std::vector<std::vector<int>> &levels) {
-    if (n->prec != PN_PREC_BF16 || n->x3 || getenv("POPNET_NO_TAILFUSE") || getenv("POPNET_NO_CONV3")) return;
+    if (n->prec != PN_PREC_BF16 || n->x3 || n->sw.no_tailfuse || n->sw.no_conv3) return;
     for (size_t li = 0; li + 1 < levels.size(); ++li) {
         if (levels[li].empty() || levels[li][0] < 0 || levels[li + 1].empty() || levels[li + 1][0] < 0) continue;
         for (int ia : levels[li]) {
@@ -649,7 +621,7 @@ void fuse_1x1_tails(pn_net *n, std::vector<std::vector<int>> &levels) {
 // disappear; blocks recompute one shared row and column (25 % more matrix work on a bandwidth-bound layer).  Same values, same
 // summation order as the two launches: bit-identical (POPNET_NO_POOLFUSE=1 keeps them).  bf16 and (round 5) bf16x3: the parked tile as two planes.
 void fuse_pool_tails(pn_net *n, std::vector<std::vector<int>> &levels) {
-    if (n->prec != PN_PREC_BF16 || getenv("POPNET_NO_POOLFUSE") || getenv("POPNET_NO_CONV3")) return;       // (bf16x3 since round 5: two parked planes)
+    if (n->prec != PN_PREC_BF16 || n->sw.no_poolfuse || n->sw.no_conv3) return;       // (bf16x3 since round 5: two parked planes)
     for (size_t li = 0; li + 1 < levels.size(); ++li) {
         if (levels[li].size() != 1 || levels[li][0] < 0) continue;
         const std::vector<int> &pl = levels[li + 1];
@@ -815,7 +787,7 @@ int build_yolo(pn_net *n) {
     auto level = [&](std::vector<int> ids) { levels.push_back(ids); };
     // conv1 - bn1 - relu - maxpool (yolo_posenet.py:101-108): one launch in bf16 (conv_misc.hip::stem7x7_pool_kernel; the 112 x 112 x 64
     // map is never stored); POPNET_NO_STEMPOOL=1, fp32 and bf16x3 keep the stem and the pool as two launches
-    if (n->prec == PN_PREC_BF16 && !n->x3 && n->input_dim == 1 && !getenv("POPNET_NO_STEMPOOL")) n->steps.back().stem_pool_buf = X0;
+    if (n->prec == PN_PREC_BF16 && !n->x3 && n->input_dim == 1 && !n->sw.no_stempool) n->steps.back().stem_pool_buf = X0;
     else levels.push_back({-1, 1, A1, X0, 64, 0});   // maxpool 3x3 s2
     int cur = X0, other = X1;
     for (int i = 0; i < 3; ++i) {
@@ -827,7 +799,7 @@ int build_yolo(pn_net *n) {
     {   // layer2.0: the 3x3 stride-2 conv and its 1x1 stride-2 shortcut (resnet.py:59-77) read the same map at the same stride.  bf16 / bf16x3: the
         // shortcut runs as the centre tap of a 3x3 problem in the SAME launch (one launch and 12 us of pure latency less per step; every added
         // product is an exact zero, so the sums are the 1x1 convolution's bit for bit: POPNET_NO_EMBED3=1 keeps the two launches, tested)
-        const bool embed = n->prec == PN_PREC_BF16 && !getenv("POPNET_NO_EMBED3");
+        const bool embed = n->prec == PN_PREC_BF16 && !n->sw.no_embed3;
         const int c1 = add_conv(n, "model0.layer2.0.conv1", "model0.layer2.0.bn1", 3, 2, cur, 0, YT, 0, PN_ACT_RELU);
         const int cd = add_conv(n, "model0.layer2.0.downsample.0", "model0.layer2.0.downsample.1", embed ? 3 : 1, 2, cur, 0, YD, 0, PN_ACT_NONE);
         n->convs[cd].embed3 = embed;
@@ -1033,17 +1005,6 @@ int run_forward(pn_net *n, const float *x, int B, hipStream_t stream, int nsteps
             }
             PN_HIP_CHECK(ctx, hipEventRecord(pr->a, stream));
         }
-        // timing-only ablation (wrong results): POPNET_ABLATE_SKIP = comma-separated classes of launches to skip --
-        // "pool", "head" (<= 32-cout generic launches), "c1x1" (conv3 1x1), "c3" (conv3 3x3), "stem"; what would the pipelined
-        // throughput be if these launches cost nothing?  (docs/lab-archive/tail_ablation.sh)
-#ifdef PN_EXPERIMENTS      // lab builds only: a timed region of the shipped library cannot be made to skip launches by the environment
-        static const char *skip = getenv("POPNET_ABLATE_SKIP");
-        if (skip) {
-            const char *cls = st.type == Step::POOL ? "pool" : st.type == Step::STEM ? "stem" : st.type == Step::BBLOCK ? "bb64" :
-                              (st.launch.kern == 4 ? "conv4" : st.launch.kern == 3 ? (st.launch.ks == 1 ? "c1x1" : "c3") : "head");
-            if (strstr(skip, cls)) { if (pr) PN_HIP_CHECK(ctx, hipEventRecord(pr->b, stream)); continue; }
-        }
-#endif
         if (st.type == Step::STEM && st.stem_pool_buf >= 0) {
             const Buf &ob = n->bufs[st.out_buf], &pb = n->bufs[st.stem_pool_buf];
             rc = pn_launch_stem_pool(ctx, x, st.stem_wfrag, st.stem_b, pb.p, B, n->in_h, n->in_w, ob.H, ob.W, pb.C, stream, n->frame_src.frames ? &n->frame_src : nullptr);
@@ -1133,6 +1094,7 @@ int pn_net_finalize(pn_net *n, int precision, int max_batch, int in_h, int in_w)
     PN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     n->x3 = precision == PN_PREC_BF16X3;                      // kernels and packing run as bf16; tensors carry three planes
     n->prec = n->x3 ? PN_PREC_BF16 : precision; n->max_batch = max_batch; n->in_h = in_h; n->in_w = in_w;
+    n->sw = pn_read_switches();
     int rc = n->kind == PN_NET_RTPOSE_LIGHT3D ? build_rtpose(n) : build_yolo(n);
     if (rc) return rc;
     for (auto &b : n->bufs) {

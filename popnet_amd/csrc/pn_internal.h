@@ -34,6 +34,40 @@ struct pn_ctx {
     unsigned train_pack_blocks = 0;
 };
 
+// Kernel-variant and scheduling switches: every form each one selects is tested against the default form (tests/test_gpu_*.py).
+// pn_read_switches (api.hip) is the library's only reader of the environment; each consumer takes one snapshot at a fixed moment:
+// a net when it is compiled (pn_net_finalize), a trainer in pn_trainer_finalize, the NCHW training primitives (pn_conv2d_*) at each call.
+struct PnSwitches {
+    // inference nets (net.hip, conv_plan.h)
+    bool no_conv3 = false;          // POPNET_NO_CONV3: no conv3 / conv4 / fused kernels, the generic kernel everywhere
+    bool conv3_rpg8 = false;        // POPNET_CONV3_RPG8: 8-row wave groups on narrow 3x3 maps
+    int conv3_pt14 = 0;             // POPNET_CONV3_PT14: 1 = 224-pixel wave tiles where the plan has WP = 2, 2 = on every 28-column 3x3 level as well
+    bool conv3_nbuf2 = false;       // POPNET_CONV3_NBUF2: the double-buffered conv3 variant where it applies
+    bool generic_c64_off = false;   // POPNET_GENERIC_C64=0: small maps keep the 128-cout generic blocks
+    int conv4 = -1;                 // POPNET_CONV4: unset -1 (by block count), 0 never, 1 whenever eligible
+    bool no_mix = false;            // POPNET_NO_MIX: no conv3_mix_kernel launches
+    bool no_bblock = false;         // POPNET_NO_BBLOCK: no fused BasicBlock kernel
+    bool bblock_x3 = false;         // POPNET_BBLOCK_X3=<nonzero>: the fused BasicBlock kernel in bf16x3 nets as well
+    bool bb64_static = false;       // POPNET_BB64_STATIC: bb64_kernel's static tile schedule
+    int bb64_halves = 1;            // POPNET_BB64_HALVES=2: bb64_kernel<2>
+    bool no_tailfuse = false;       // POPNET_NO_TAILFUSE: no fused 1x1 tails
+    bool no_poolfuse = false;       // POPNET_NO_POOLFUSE: no fused average pools
+    bool no_stempool = false;       // POPNET_NO_STEMPOOL: YoloPoseNet's stem and max pool as two launches
+    bool no_embed3 = false;         // POPNET_NO_EMBED3: YoloPoseNet's stride-2 shortcut as a launch of its own
+    // NCHW training primitives (train.hip)
+    bool train_x3_wide = false;     // POPNET_TRAIN_X3_WIDE: tconv3_tile_x3w_kernel on every shape it can hold
+    bool train_wgrad_novec = false; // POPNET_TRAIN_WGRAD_NOVEC: no tconv3_wgrad_x3v_kernel
+    // planes training engine (trainx.hip)
+    bool trainx_one_stream = false; // POPNET_TRAINX_STREAMS=1: the weight gradients on the step's own stream
+    bool trainx_stem_handover = false;  // POPNET_TRAINX_STEM_HANDOVER: the stem through NCHW f32 tensors
+    bool trainx_stem_gather = false;    // POPNET_TRAINX_STEM_FWD=gather: tconv_fwd_kernel<7, PL> for the stem forward
+    bool trainx_stem_bn_separate = false;   // POPNET_TRAINX_STEM_BN=separate: the stem's BatchNorm backward as a launch of its own
+    int trainx_stem_depth = 2;      // POPNET_TRAINX_STEM_DEPTH: 32-pixel chunks in flight per block of the stem weight gradient
+    bool trainx_pack_gather = false;    // POPNET_TRAINX_PACK=gather: tx::pack_kernel instead of tx::pack_rows_kernel
+    bool trainx_legacy_wgrad = false;   // POPNET_TRAINX_WGRAD=legacy: the NCHW f32 weight gradient of train.hip
+};
+PnSwitches pn_read_switches();
+
 int pn_set_error(pn_ctx *ctx, int code, const char *fmt, ...);
 void pn_parse_big_free(pn_ctx *ctx);     // parse_paf.hip
 int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)

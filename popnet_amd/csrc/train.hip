@@ -619,13 +619,6 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g
         for (int j = 0; j < 8; ++j) cmask |= (unsigned)(cbase + j < c.Cin) << j;
         // ---- halo tile of 32 channels (all loads first, then split + 16-byte stores) ----
         float hv[NH][8];
-#ifdef TX_FAKE_NOHALO                       // timing-only ablation (wrong results): no halo loads
-#pragma unroll
-        for (int i = 0; i < NH; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) hv[i][j] = 1.f;
-        if (0)
-#endif
 #pragma unroll
         for (int i = 0; i < NH; ++i) {
             const int okp = (int)(hoff[i] >= 0);
@@ -678,10 +671,8 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g
 #pragma unroll
                     for (int n = 0; n < 2; ++n) {
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
-#ifndef TX_FAKE_ONEPASS                     // timing-only ablation (wrong results): one MFMA pass instead of three
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
-#endif
                     }
                 }
             }
@@ -799,11 +790,7 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile 
                 const int okp = (int)(hoff[i] >= 0);
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-#ifdef TXW2_FAKE_NOHALO                      // timing-only ablations (wrong results): -DTXW2_FAKE_NOHALO / _NOMFMA, variant builds of scripts/r05
-                    hv[i - I0[half]][j] = 1.f + (float)okp;
-#else
                     hv[i - I0[half]][j] = xb[((cbase + j) * HW + hoff[i]) & -(okp & (int)((cmask >> j) & 1u))];
-#endif
             }
             if (half == 0) __syncthreads();       // the previous chunk's last kernel row has been consumed
 #pragma unroll
@@ -848,13 +835,9 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile 
                     const t_bf16x8 al = *reinterpret_cast<const t_bf16x8 *>(As_lo + ao);
 #pragma unroll
                     for (int n = 0; n < 4; ++n) {
-#ifndef TXW2_FAKE_NOMFMA
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
-#else
-                        acc[m][n][0] += (float)ah[0] * (float)bh[n][0] + (float)al[1] * (float)bl[n][1];
-#endif
                     }
                 }
             }
@@ -897,7 +880,7 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile 
     }
 }
 
-static bool t_tile_geometry_x3w(int Ho, int Wo, int N, int Cout, TTile *g) {     // 256-slot tiles; only when they still fill the chip
+static bool t_tile_geometry_x3w(int Ho, int Wo, int N, int Cout, bool every_shape, TTile *g) {     // 256-slot tiles; only when they still fill the chip
     g->tiles_x = (Wo + 63) / 64;
     g->TW = (Wo + g->tiles_x - 1) / g->tiles_x;
     g->R = 256 / g->TW;
@@ -910,7 +893,7 @@ static bool t_tile_geometry_x3w(int Ho, int Wo, int N, int Cout, TTile *g) {    
     g->CHP = 0;
     const long blocks = (long)N * g->tiles_x * g->tiles_y * ((Cout + 63) / 64);
     const long slots = (long)g->R * g->TW;
-    if (getenv("POPNET_TRAIN_X3_WIDE")) return g->HR * g->HC <= 400;      // tests: the wide kernel on every shape it can hold
+    if (every_shape) return g->HR * g->HC <= 400;      // PnSwitches::train_x3_wide (tests): the wide kernel on every shape it can hold
     return g->HR * g->HC <= 400 && blocks >= 448 && slots >= 192;
 }
 
@@ -1308,11 +1291,7 @@ __global__ __launch_bounds__(512, 1) void tconv3_wgrad_x3v_kernel(TConv c, TTile
     __syncthreads();
     for (int ph = 0; ph <= ntl; ++ph) {
       if ((ph & 1) == grp) {
-#ifdef TXV_FAKE_NOSTAGE
-        if (ph < 2) {
-#else
         if (ph < ntl) {
-#endif
             const int tile = tbeg + ph;
             const int tx = tile % g.tiles_x, ty = (tile / g.tiles_x) % g.tiles_y, img = tile / (g.tiles_x * g.tiles_y);
             const int y0 = ty * g.R, x0 = tx * g.TW;
@@ -1375,7 +1354,6 @@ __global__ __launch_bounds__(512, 1) void tconv3_wgrad_x3v_kernel(TConv c, TTile
             }
         }
       } else if (ph >= 1) {
-#ifndef TXV_FAKE_NOMFMA                          // timing-only ablations (wrong results): -DTXV_FAKE_NOMFMA / -DTXV_FAKE_NOSTAGE, variant builds of scripts/r05
         // 24 items (pixel group pg, channel tile n, kernel row ky), 9 MFMAs each.  Software-pipelined by hand: the six LDS reads of item
         // it + 1 are issued before the MFMAs of item it (the compiler's own schedule waited for every item's reads right before its
         // MFMAs and separated the dependent triple of an accumulator with s_nop: 45 % matrix-pipe use inside this section), and the three
@@ -1422,7 +1400,6 @@ __global__ __launch_bounds__(512, 1) void tconv3_wgrad_x3v_kernel(TConv c, TTile
             for (int kx = 0; kx < 3; ++kx) acc[n][ky * 3 + kx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[kx], acc[n][ky * 3 + kx], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-#endif
       }
       __syncthreads();
     }
@@ -2415,7 +2392,7 @@ int pn_conv2d_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, const
             if ((rc = t_pack_get(ctx, w_dev, Cout, Cin, 0, 1, 4 * wx, s, &ws, &fresh)) != PN_OK) return rc;
             if (!fresh) hipLaunchKernelGGL(wpack3_x3_kernel, dim3((unsigned)((wx + 255) / 256)), dim3(256), 0, s, w_dev, (__bf16 *)ws, Cout, Cin, 0);
             TTile gw2;
-            if (!getenv("POPNET_TRAIN_X3_NARROW") && t_tile_geometry_x3w(c.Ho, c.Wo, N, Cout, &gw2)) {
+            if (t_tile_geometry_x3w(c.Ho, c.Wo, N, Cout, pn_read_switches().train_x3_wide, &gw2)) {
                 const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * gw2.HR * gw2.HC * TXW2_PITCH;
                 hipLaunchKernelGGL(tconv3_tile_x3w_kernel, dim3((unsigned)(N * gw2.tiles_x * gw2.tiles_y), (unsigned)((Cout + 63) / 64)), dim3(256), ldsw2, s, c, gw2, (const __bf16 *)ws);
                 PN_HIP_CHECK(ctx, hipGetLastError());
@@ -2466,7 +2443,7 @@ int pn_conv2d_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float 
             if ((rc = t_pack_get(ctx, w_dev, Cin, Cout, 1, 1, 4 * wx, s, &ws, &fresh)) != PN_OK) return rc;
             if (!fresh) hipLaunchKernelGGL(wpack3_x3_kernel, dim3((unsigned)((wx + 255) / 256)), dim3(256), 0, s, w_dev, (__bf16 *)ws, Cin, Cout, 1);
             TTile gw2;
-            if (!getenv("POPNET_TRAIN_X3_NARROW") && t_tile_geometry_x3w(H, W, N, Cin, &gw2)) {
+            if (t_tile_geometry_x3w(H, W, N, Cin, pn_read_switches().train_x3_wide, &gw2)) {
                 const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * gw2.HR * gw2.HC * TXW2_PITCH;
                 hipLaunchKernelGGL(tconv3_tile_x3w_kernel, dim3((unsigned)(N * gw2.tiles_x * gw2.tiles_y), (unsigned)((Cin + 63) / 64)), dim3(256), ldsw2, s, c, gw2, (const __bf16 *)ws);
                 PN_HIP_CHECK(ctx, hipGetLastError());
@@ -2532,7 +2509,7 @@ int pn_conv2d_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float 
             setb = (size_t)2 * 64 * TXW_YP + (size_t)2 * TXW_CI * gw.CHB;
             S3 = (256 + groups2 - 1) / groups2;             // ping-pong variant: one 8-wave block per CU
             if (S3 > nt / 2) S3 = nt / 2;                   // at least two tiles per block, or the second wave group has nothing to do
-            pp = !getenv("POPNET_TRAIN_WGRAD_4WAVE") && S3 >= 1 && 2 * setb <= 158 * 1024 && 2 * setb >= 73728;
+            pp = S3 >= 1 && 2 * setb <= 158 * 1024 && 2 * setb >= 73728;
             if (pp) {
                 tps3 = (nt + S3 - 1) / S3;
                 S3 = (nt + tps3 - 1) / tps3;
@@ -2549,7 +2526,7 @@ int pn_conv2d_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float 
         if (x3) {
             TTileW gv;
             int ppi = 0, npieces = 0;
-            if (pp && !getenv("POPNET_TRAIN_WGRAD_NOVEC") && t_tile_geometry_wx3v(c, &gv, &ppi, &npieces) && gv.tiles_x == gw.tiles_x && gv.tiles_y == gw.tiles_y && gv.R == gw.R && gv.TW == gw.TW) {
+            if (pp && !pn_read_switches().train_wgrad_novec && t_tile_geometry_wx3v(c, &gv, &ppi, &npieces) && gv.tiles_x == gw.tiles_x && gv.tiles_y == gw.tiles_y && gv.R == gw.R && gv.TW == gw.TW) {
                 // the same tiles and slices as x3pp (bit-identical partial sums), one round trip of staging per tile
                 const size_t lds = std::max<size_t>((size_t)2 * 2 * TXW_CI * gv.CHB, (size_t)72 * 256 * 4);
                 hipLaunchKernelGGL(tconv3_wgrad_x3v_kernel, dim3((unsigned)((Cin + TXW_CI - 1) / TXW_CI), (unsigned)((Cout + 63) / 64), (unsigned)S3), dim3(512), lds, s, c, gv, (float *)ws, tps3, nt, ppi, npieces);
@@ -2634,9 +2611,8 @@ int pn_stem_forward_planes(pn_ctx *ctx, const float *x_dev, const float *w_dev, 
         const int tiles_x = (c.Wo + 15) / 16, tiles_y = (c.Ho + 7) / 8;
         const long ntiles = (long)N * tiles_x * tiles_y;
         // blocks per CU, one-stream traces of the step: 1: 49.1, 2: 41.5, 3: 42.8, 4: 45.0, 6: 48.3, 12: 62.2 us (three are resident at 148 registers; every block
-        // loads the 52 weight registers once) -- POPNET_STEM_FWD_BLOCKS overrides
-        const char *eb = getenv("POPNET_STEM_FWD_BLOCKS");
-        const unsigned blocks = (unsigned)std::min<long>(ntiles, (long)ctx->num_cus * (eb ? std::max(1, atoi(eb)) : 2));
+        // loads the 52 weight registers once)
+        const unsigned blocks = (unsigned)std::min<long>(ntiles, (long)ctx->num_cus * 2);
         if (f32) hipLaunchKernelGGL(tstem_fwd_kernel<1>, dim3(blocks), dim3(256), 0, s, c, tiles_x, tiles_y, (int)ntiles);
         else hipLaunchKernelGGL(tstem_fwd_kernel<0>, dim3(blocks), dim3(256), 0, s, c, tiles_x, tiles_y, (int)ntiles);
         PN_HIP_CHECK(ctx, hipGetLastError());

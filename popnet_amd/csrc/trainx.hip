@@ -76,6 +76,7 @@ struct pn_trainer {
     std::map<std::string, std::pair<size_t, size_t>> params;      // name -> (offset, numel) in the flat buffers
     std::map<std::string, float *> stats;                        // running_mean / running_var device pointers
     bool finalized = false;
+    PnSwitches sw;                   // read in pn_trainer_finalize
     bool legacy_wgrad = false;
     bool f32 = false;                // precision "fp32": one fp32 plane per tensor, the generic fp32 convolution kernel, K = 4 weight gradient
     std::vector<void *> allocs;
@@ -94,10 +95,9 @@ struct pn_trainer {
     int *cat_k_map = nullptr, *cat_ref_map = nullptr;           // [192] my channel -> reference channel ; [187] reference -> my channel
     double *partial = nullptr; size_t partial_doubles = 0;
     float *nchw_a = nullptr, *nchw_b = nullptr; size_t nchw_elems = 0;      // NCHW f32 scratch: the stem hand-over and the legacy weight gradient
-    float *wg_partial[4] = {nullptr, nullptr, nullptr, nullptr}; size_t wg_partial_floats = 0;      // one split-K scratch per side stream
+    float *wg_partial = nullptr; size_t wg_partial_floats = 0;      // split-K scratch of the weight gradients
     // the weight gradients run on a second stream beside the BatchNorm / data-gradient chain (matrix-core-bound next to bandwidth-bound launches)
-    hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};
-    int nside = 1, next_side = 0;            // POPNET_TRAINX_SIDES: weight gradients of different layers dealt round-robin to this many side streams
+    hipStream_t side = nullptr;
     bool two_streams = true;
     std::vector<hipEvent_t> events;
     size_t side_tail = (size_t)-1;            // ops.size() right after the last side-stream op: nothing new on the step's stream since = no new fork needed
@@ -243,7 +243,7 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
         pc.g = ConvGeom();
         const int wc_min = (wide[L.ks] && pc.rows > 32) ? 4 : 0;
         const int prec = t->f32 ? PN_PREC_F32 : PN_PREC_BF16;
-        pn_plan_conv_kernel(prec, t->B, ctx->num_cus, in.H, in.W, pc.rows, L.ks, 1, pc.cin_chunks, wc_min, 0, k4 ? 1 : 0, pc.g);
+        pn_plan_conv_kernel(prec, t->B, ctx->num_cus, in.H, in.W, pc.rows, L.ks, 1, pc.cin_chunks, wc_min, 0, k4 ? 1 : 0, t->sw, pc.g);
         const char *why = "";
         if (int rc = pn_plan_conv_tiles(prec, in.H, in.W, L.ks, 1, pc.g, &why)) return pn_set_error(ctx, rc, "pn_trainer: %s: %s", L.name.c_str(), why);
         if (pc.g.kern == 0 && L.ks == 1 && pc.g.pitch == 16) pc.g.pitch = 32;      // the generic 1x1 kernel is not instantiated for the 16-pixel pitch class (a wider LDS row is always valid)
@@ -538,38 +538,36 @@ void op_heads(pn_trainer *t, int stage, int dcat, const int dv[3]) {
 }
 
 // fork: the side stream may start once everything issued so far on the step's stream has finished; join: the other way round
-int op_fork(pn_trainer *t, int side = 0) {
-    if (!t->two_streams || (t->nside == 1 && t->ops.size() == t->side_tail)) return PN_OK;
+int op_fork(pn_trainer *t) {
+    if (!t->two_streams || t->ops.size() == t->side_tail) return PN_OK;
     hipEvent_t ev;
     PN_HIP_CHECK(t->ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     t->events.push_back(ev);
-    t->ops.push_back([t, ev, side](hipStream_t s) {
+    t->ops.push_back([t, ev](hipStream_t s) {
         PN_HIP_CHECK(t->ctx, hipEventRecord(ev, s));
-        PN_HIP_CHECK(t->ctx, hipStreamWaitEvent(t->side[side], ev, 0));
+        PN_HIP_CHECK(t->ctx, hipStreamWaitEvent(t->side, ev, 0));
         return (int)PN_OK;
     });
     return PN_OK;
 }
 int op_join(pn_trainer *t) {
     if (!t->two_streams) return PN_OK;
-    for (int k = 0; k < t->nside; ++k) {
-        hipEvent_t ev;
-        PN_HIP_CHECK(t->ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        t->events.push_back(ev);
-        t->ops.push_back([t, ev, k](hipStream_t s) {
-            PN_HIP_CHECK(t->ctx, hipEventRecord(ev, t->side[k]));
-            PN_HIP_CHECK(t->ctx, hipStreamWaitEvent(s, ev, 0));
-            return (int)PN_OK;
-        });
-    }
+    hipEvent_t ev;
+    PN_HIP_CHECK(t->ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    t->events.push_back(ev);
+    t->ops.push_back([t, ev](hipStream_t s) {
+        PN_HIP_CHECK(t->ctx, hipEventRecord(ev, t->side));
+        PN_HIP_CHECK(t->ctx, hipStreamWaitEvent(s, ev, 0));
+        return (int)PN_OK;
+    });
     return PN_OK;
 }
-// every op appended since `from` runs on side stream `side`
-void ops_to_side(pn_trainer *t, size_t from, int side = 0) {
+// every op appended since `from` runs on the side stream
+void ops_to_side(pn_trainer *t, size_t from) {
     if (!t->two_streams) return;
     for (size_t i = from; i < t->ops.size(); ++i) {
         auto f = t->ops[i];
-        t->ops[i] = [t, f, side](hipStream_t) { return f(t->side[side]); };
+        t->ops[i] = [t, f](hipStream_t) { return f(t->side); };
     }
     t->side_tail = t->ops.size();
 }
@@ -599,18 +597,16 @@ int op_wgrad(pn_trainer *t, int l, int dy) {
         return PN_OK;
     }
     if (L.b && !L.bn_follows) op_dbias(t, l, dy);      // (a bias in front of a BatchNorm: its gradient is identically zero and the flat gradient buffer already holds 0)
-    const int side = t->two_streams ? t->next_side : 0;
-    t->next_side = (t->next_side + 1) % t->nside;
-    if (int rc = op_fork(t, side)) return rc;
+    if (int rc = op_fork(t)) return rc;
     const size_t from = t->ops.size();
     if (t->f32) {
         if (int rc = tx::plan_wgrad_f32(t->ctx, t->B, X.H, X.W, (const float *)X.p, X.plane, (const float *)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw,
-                                        &t->wg_partial[side], &t->wg_partial_floats, t->ops))
+                                        &t->wg_partial, &t->wg_partial_floats, t->ops))
             return rc;
     } else if (int rc = tx::plan_wgrad(t->ctx, t->B, X.H, X.W, (const bf *)X.p, X.plane, (const bf *)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw,
-                                       &t->wg_partial[side], &t->wg_partial_floats, t->ops))
+                                       &t->wg_partial, &t->wg_partial_floats, t->ops))
         return rc;
-    ops_to_side(t, from, side);
+    ops_to_side(t, from);
     return PN_OK;
 }
 
@@ -656,9 +652,8 @@ int build(pn_trainer *t) {
     t->nchw_elems = std::max(t->nchw_elems, (size_t)B * 64 * H2 * W2);
     {
         const TxTensor c0 = t->T[C0];
-        const bool handover = getenv("POPNET_TRAINX_STEM_HANDOVER") != nullptr;      // the NCHW f32 hand-over of the round's first builds (bit-identical; A/B)
-        const char *esf = getenv("POPNET_TRAINX_STEM_FWD");
-        const int stem_gather = esf && !strcmp(esf, "gather");                        // A/B: tconv_fwd_kernel<7, PL> instead of tstem_fwd_kernel (bit-identical)
+        const bool handover = t->sw.trainx_stem_handover;                  // the NCHW f32 hand-over of the round's first builds (bit-identical; A/B)
+        const int stem_gather = t->sw.trainx_stem_gather;                  // A/B: tconv_fwd_kernel<7, PL> instead of tstem_fwd_kernel (bit-identical)
         t->ops.push_back([=](hipStream_t s) {
             if (!handover) return pn_stem_forward_planes(t->ctx, t->img, w_stem, c0.p, c0.cs(), c0.split(), t->f32, B, 1, H, W, 64, 7, 2, 3, stem_gather, s);
             if (int r = pn_conv2d_forward(t->ctx, t->img, w_stem, nullptr, t->nchw_a, B, 1, H, W, 64, 7, 2, 3, 0, (void *)s)) return r;
@@ -826,11 +821,9 @@ int build(pn_trainer *t) {
     TX(block_bwd(b20, dA6, H4, W4, 64, 128, &dP1, s56));
     // (own scratch per block: a weight gradient still running on the side stream reads dC2 / dC1 of its block)
     // the stem's BatchNorm backward is applied inside its weight-gradient kernel (train.hip::tstem_wgrad_kernel): dC0 never exists
-    const bool stem_handover = getenv("POPNET_TRAINX_STEM_HANDOVER") != nullptr;      // A/B: the NCHW f32 hand-over of the round's first builds (bit-identical)
-    const char *esb = getenv("POPNET_TRAINX_STEM_BN");
-    const bool stem_bn_separate = stem_handover || (esb && !strcmp(esb, "separate"));  // A/B: bn_bwd_apply_kernel writes dC0, the weight gradient reads it (bit-identical)
-    const char *esd = getenv("POPNET_TRAINX_STEM_DEPTH");
-    const int stem_depth = esd ? atoi(esd) : 2;                                         // A/B: chunks of 32 pixels in flight per block (1, 2, 4; bit-identical): 102-163 / 83-91 / 105 us over six traces
+    const bool stem_handover = t->sw.trainx_stem_handover;                             // A/B: the NCHW f32 hand-over of the round's first builds (bit-identical)
+    const bool stem_bn_separate = stem_handover || t->sw.trainx_stem_bn_separate;       // A/B: bn_bwd_apply_kernel writes dC0, the weight gradient reads it (bit-identical)
+    const int stem_depth = t->sw.trainx_stem_depth;                                     // A/B: chunks of 32 pixels in flight per block (1, 2, 4; bit-identical): 102-163 / 83-91 / 105 us over six traces
     int s112[6], s112b[6], dA4, dA2, dA0, dC0 = -1;
     for (int i = 0; i < 4; ++i) { TX(TT(H2, W2, 64, &s112[i])); TX(TT(H2, W2, 64, &s112b[i])); }
     s112[4] = s112[5] = s112b[4] = s112b[5] = -1;
@@ -866,8 +859,7 @@ int build(pn_trainer *t) {
     if ((rc = tx_alloc(t, (void **)&t->nchw_a, std::max<size_t>(t->nchw_elems, 1) * 4, true))) return rc;
     if ((rc = tx_alloc(t, (void **)&t->nchw_b, std::max<size_t>(t->nchw_elems, 1) * 4, true))) return rc;
     if (t->wg_partial_floats)
-        for (int k = 0; k < t->nside; ++k)
-            if ((rc = tx_alloc(t, (void **)&t->wg_partial[k], t->wg_partial_floats * 4, true))) return rc;
+        if ((rc = tx_alloc(t, (void **)&t->wg_partial, t->wg_partial_floats * 4, true))) return rc;
     if (!t->packs.empty()) {
         if ((rc = tx_alloc(t, (void **)&t->packs_dev, t->packs.size() * sizeof(tx::PackDesc), false))) return rc;
         PN_HIP_CHECK(ctx, hipMemcpy(t->packs_dev, t->packs.data(), t->packs.size() * sizeof(tx::PackDesc), hipMemcpyHostToDevice));
@@ -895,8 +887,7 @@ void pn_trainer_destroy(pn_trainer *t) {
     if (!t) return;
     for (void *p : t->allocs) (void)hipFree(p);
     for (hipEvent_t ev : t->events) (void)hipEventDestroy(ev);
-    for (int k = 0; k < 4; ++k)
-        if (t->side[k]) (void)hipStreamDestroy(t->side[k]);
+    if (t->side) (void)hipStreamDestroy(t->side);
     delete t;
 }
 
@@ -929,23 +920,15 @@ int pn_trainer_finalize(pn_trainer *t, float *flat_param_dev, float *flat_grad_d
     if (!flat_param_dev || !flat_grad_dev || B < 1 || H < 8 || W < 8) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_finalize: bad arguments");
     PN_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     t->flat_p = flat_param_dev; t->flat_g = flat_grad_dev; t->B = B; t->H = H; t->W = W; t->momentum = bn_momentum; t->eps = bn_eps;
-    const char *e = getenv("POPNET_TRAINX_WGRAD");
-    t->legacy_wgrad = e && !strcmp(e, "legacy");
-    const char *epk = getenv("POPNET_TRAINX_PACK");
-    t->pack_gather = epk && !strcmp(epk, "gather");
-    const char *e2 = getenv("POPNET_TRAINX_STREAMS");
-    t->two_streams = !(e2 && atoi(e2) == 1) && !t->legacy_wgrad;
-    if (const char *e3 = getenv("POPNET_TRAINX_SIDES")) t->nside = std::max(1, std::min(4, atoi(e3)));
-    if (!t->two_streams) t->nside = 1;
+    t->sw = pn_read_switches();
+    t->legacy_wgrad = t->sw.trainx_legacy_wgrad;
+    t->pack_gather = t->sw.trainx_pack_gather;
+    t->two_streams = !t->sw.trainx_one_stream && !t->legacy_wgrad;
     if (t->two_streams) {
         // LOWEST priority: the weight gradients fill what the step's own stream (the dependency chain that bounds the step) leaves idle, never the other way round
         int lo = 0, hi = 0;
         PN_HIP_CHECK(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        const char *ep = getenv("POPNET_TRAINX_SIDE_PRIORITY");       // experiments: "default" = no priority
-        for (int k = 0; k < t->nside; ++k) {
-            if (ep && !strcmp(ep, "default")) PN_HIP_CHECK(ctx, hipStreamCreateWithFlags(&t->side[k], hipStreamNonBlocking));
-            else PN_HIP_CHECK(ctx, hipStreamCreateWithPriority(&t->side[k], hipStreamNonBlocking, lo));
-        }
+        PN_HIP_CHECK(ctx, hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, lo));
     }
     if (int rc = build(t)) return rc;
     t->finalized = true;

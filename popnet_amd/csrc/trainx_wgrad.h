@@ -27,181 +27,18 @@ namespace tx {
 typedef __attribute__((ext_vector_type(4))) __bf16 bf4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
-struct WgArgs {
-    const bf *x; int x_cs, x_split; unsigned x_zero;        // input tensor, byte offset of its zero page
-    const bf *dy; int dy_cs, dy_split; unsigned dy_zero;    // output gradient
-    int B, H, W;
-    int Wt, tiles_x, strips_per_img, nstrips, strips_per_block;
-    int ncit;                                               // 64-channel tiles on the cin side (blockIdx.y = cot * ncit + cit)
-    int co_pad, ci_pad;
-    float *partial;                                         // [split][tap][co_pad][ci_pad]
-};
-
 __device__ __forceinline__ void glds16(const void *sbase, unsigned voff, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
 
-template <int KS, int R>
-__global__ __launch_bounds__(256, 2) void wgrad_kernel(WgArgs a) {
-    typedef __attribute__((address_space(3))) bf4 lds4;
-    constexpr int KK = KS * KS, PAD = KS / 2, HR = R + KS - 1;
-    constexpr int ROWB = 2 * 32 * 128;                    // bytes of one image row: 2 planes x 32 pixel slots x 64 channels
-    constexpr int XIMG = HR * ROWB;
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // [x halo image][dy image]
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 1, wn = wave & 1;              // cout half, cin half of the 64 x 64 block tile
-    const int cot = blockIdx.y / a.ncit, cit = blockIdx.y - cot * a.ncit;
-    const int co0 = cot * 64, ci0 = cit * 64;
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int pxl = 4 * g + q;
-
-    // transposed-read addresses (bytes): lane 4q + p of group g supplies row (= pixel) q, channels 4p .. 4p + 3 of the 16-channel window
-    int addrA[2], addrB[KS][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int win = wm * 2 + mt, swz = (pxl >> 1) & 3;
-        addrA[mt] = XIMG + pxl * 128 + ((((win ^ swz) << 1) | (p >> 1)) << 4) + ((p & 1) << 3);
-    }
-#pragma unroll
-    for (int kx = 0; kx < KS; ++kx)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int win = wn * 2 + nt, hp = pxl + kx, swz = (hp >> 1) & 3;
-            addrB[kx][nt] = hp * 128 + ((((win ^ swz) << 1) | (p >> 1)) << 4) + ((p & 1) << 3);
-        }
-
-    f4 acc[2][2][KK];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int tp = 0; tp < KK; ++tp) acc[mt][nt][tp] = f4{0.f, 0.f, 0.f, 0.f};
-
-    // DMA lane roles: one instruction = 8 pixels x 8 slots of 16 B (one plane); slot sp of pixel px holds logical slot ((sp >> 1) ^ ((px >> 1) & 3)) << 1 | (sp & 1)
-    const int dpx = lane >> 3, dsp = lane & 7;
-    const int dma_px = wave * 8 + dpx;
-    const int dma_slot = (((dsp >> 1) ^ ((dma_px >> 1) & 3)) << 1) | (dsp & 1);
-    const unsigned lane_x = (unsigned)(((dma_px - PAD) * a.x_cs + ci0 + dma_slot * 8) * 2);      // (two's complement: added to the strip base modulo 2^32)
-    const unsigned lane_y = (unsigned)((dma_px * a.dy_cs + co0 + dma_slot * 8) * 2);
-    const unsigned rowx = (unsigned)(a.W * a.x_cs * 2), rowy = (unsigned)(a.W * a.dy_cs * 2);
-    const unsigned planex = (unsigned)(a.x_split * 2), planey = (unsigned)(a.dy_split * 2);
-    const unsigned dma_lds = (unsigned)__builtin_amdgcn_readfirstlane(wave * 1024);
-    const int s0 = blockIdx.x * a.strips_per_block, s1 = min(s0 + a.strips_per_block, a.nstrips);
-    for (int sid = s0; sid < s1; ++sid) {
-        const int b = sid / a.strips_per_img, rem = sid - b * a.strips_per_img;
-        const int ty = rem / a.tiles_x, tx_ = rem - ty * a.tiles_x;
-        const int oy0 = ty * R, ox0 = tx_ * a.Wt;
-        const int Wc = min(a.Wt, a.W - ox0);
-        __syncthreads();                                   // every wave has finished reading the previous strip's images
-        // x halo image: HR rows x 2 planes, dy image: R rows x 2 planes; each (row, plane) is four 8-pixel pieces: wave w fetches piece w of every one.
-        // Addresses in 32-bit arithmetic (a tensor is < 4 GiB): strip base and row validity on the scalar unit, one lane constant, one select per piece
-        // (the first version spent 1.9 vector instructions per MFMA on 64-bit address arithmetic: 31 % matrix-pipe use from one wave per SIMD)
-        {
-            const unsigned bx0 = (unsigned)(((long)(b * a.H + oy0 - PAD) * a.W + ox0) * (long)a.x_cs * 2);
-            const unsigned by0 = (unsigned)(((long)(b * a.H + oy0) * a.W + ox0) * (long)a.dy_cs * 2);
-            const bool okx = dma_px < Wc + 2 * PAD && (unsigned)(ox0 - PAD + dma_px) < (unsigned)a.W;
-            const bool oky = dma_px < Wc;
-#pragma unroll
-            for (int i = 0; i < HR * 2; ++i) {
-                const int row = i >> 1, pl = i & 1;
-                const bool rowok = (unsigned)(oy0 - PAD + row) < (unsigned)a.H;            // wave-uniform
-                const unsigned off = (okx && rowok) ? bx0 + (unsigned)row * rowx + (unsigned)pl * planex + lane_x : a.x_zero;
-                glds16(a.x, off, (unsigned)(i * 4096) + dma_lds);
-            }
-#pragma unroll
-            for (int i = 0; i < R * 2; ++i) {
-                const int row = i >> 1, pl = i & 1;
-                const bool rowok = oy0 + row < a.H;
-                const unsigned off = (oky && rowok) ? by0 + (unsigned)row * rowy + (unsigned)pl * planey + lane_y : a.dy_zero;
-                glds16(a.dy, off, (unsigned)(XIMG + i * 4096) + dma_lds);
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // Software-pipelined over the R * KK (row, tap) items of the strip: the fragments of item i + 1 are requested BEFORE the twelve MFMAs of item i are issued
-        // (one wave per SIMD: nothing else hides an LDS round trip; the compiler's own schedule read two fragments, waited, issued four MFMAs -- 31 % matrix-pipe use).
-        // sched_group_barrier pins the interleave: two reads, three MFMAs, four times per item.
-        const int rows = min(R, a.H - oy0);                // wave-uniform: rows below the map hold dy = 0 and are skipped
-        auto load_a = [&](int r, bf8 (&A)[2][2]) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    const bf4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrA[mt] + r * ROWB + pl * 4096));
-                    const bf4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrA[mt] + r * ROWB + pl * 4096 + 2048));
-                    A[mt][pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-        };
-        auto load_b = [&](int r, int tp, bf8 (&Bf)[2][2]) {
-            const int ky = tp / KS, kx = tp - ky * KS;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    const bf4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrB[kx][nt] + (r + ky) * ROWB + pl * 4096));
-                    const bf4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrB[kx][nt] + (r + ky) * ROWB + pl * 4096 + 2048));
-                    Bf[nt][pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-        };
-        bf8 A[2][2][2], Bq[2][2][2];                       // [item parity]: current and next fragments
-        load_a(0, A[0]);
-        load_b(0, 0, Bq[0]);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (r >= rows) break;
-#pragma unroll
-            for (int tp = 0; tp < KK; ++tp) {
-                const int cur = (r * KK + tp) & 1, nxt = cur ^ 1, ac = r & 1;
-                const bool more = tp + 1 < KK || r + 1 < rows;
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) {
-                    if (tp + 1 < KK) load_b(r, tp + 1, Bq[nxt]);
-                    else { load_b(r + 1, 0, Bq[nxt]); load_a(r + 1, A[ac ^ 1]); }
-                }
-                // product-major: the three MFMAs into one accumulator tile sit four instructions apart (a dependent MFMA issued back to back waits out the first one's passes)
-#pragma unroll
-                for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc[mt][nt][tp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ac][mt][pr == 1 ? 1 : 0], Bq[cur][nt][pr == 2 ? 1 : 0], acc[mt][nt][tp], 0, 0, 0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // two LDS reads of the next item ...
-                    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);      // ... then three MFMAs of this one
-                }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // partial[split][tap][co][ci]: a lane's 16 neighbours write 64 contiguous bytes
-    float *part = a.partial + (size_t)blockIdx.x * KK * a.co_pad * a.ci_pad;
-#pragma unroll
-    for (int tp = 0; tp < KK; ++tp)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int co = co0 + wm * 32 + mt * 16 + 4 * g + i, ci = ci0 + wn * 32 + nt * 16 + (lane & 15);
-                    part[((size_t)tp * a.co_pad + co) * a.ci_pad + ci] = acc[mt][nt][tp][i];
-                }
-}
-
-// ---- row-streaming form -------------------------------------------------------------------------------------------------------------------------
-// Same tiles, same fragments, same products as wgrad_kernel; what differs is how the images reach LDS.  wgrad_kernel fetches a 3-row strip (5 halo rows
-// of x, 3 rows of dy: 64 KB), waits, computes, and -- alone on its CU since the split-K went to one block per CU -- exposes that round trip once per strip
-// (36 % of wave cycles waiting).  Here a block walks a COLUMN STRIP top-down: rings of KS + D x rows and 1 + D dy rows (D = 2: the same 64 KB), per row ONE
-// group of four LDS-DMA instructions per wave for the row D ahead, ONE barrier, a counted `s_waitcnt vmcnt` (the D - 1 newer groups stay in flight) --
-// and no halo row is ever fetched twice.  A block owns `rows_per_block` consecutive rows of the flattened (image, column strip, row) space; where its range
-// crosses into the next column strip the rings are re-primed.
+// ---- the kernel: a block walks a column strip row by row ---------------------------------------------------------------------------------------
+// A first form fetched a 3-row strip (5 halo rows of x, 3 rows of dy: 64 KB), waited, computed, and -- alone on its CU since the split-K went to one
+// block per CU -- exposed that round trip once per strip (36 % of wave cycles waiting).  Here a block walks a COLUMN STRIP top-down: rings of KS + D x rows
+// and 1 + D dy rows (D = 2: the same 64 KB), per row ONE group of four LDS-DMA instructions per wave for the row D ahead, ONE barrier, a counted
+// `s_waitcnt vmcnt` (the D - 1 newer groups stay in flight) -- and no halo row is ever fetched twice.  A block owns `rows_per_block` consecutive rows of
+// the flattened (image, column strip, row) space; where its range crosses into the next column strip the rings are re-primed.
 struct WgsArgs {
     const bf *x; int x_cs, x_split; unsigned x_zero;
     const bf *dy; int dy_cs, dy_split; unsigned dy_zero;
@@ -227,6 +64,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_kernel(WgsArgs a) {
     const int co0 = cot * 64, ci0 = cit * 64;
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
     const int pxl = 4 * g + q;
+    // transposed-read addresses (bytes): lane 4q + p of group g supplies row (= pixel) q, channels 4p .. 4p + 3 of the 16-channel window
     int addrA[2], addrB[KS][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
@@ -613,78 +451,42 @@ inline int plan_wgrad_f32(pn_ctx *ctx, int B, int H, int W, const float *x, int 
 inline int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const bf *x, int x_plane, const bf *dy, int dy_plane, int Cin, int Cout, int ks, const int *k_map, float *dw,
                       float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops) {
     if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "weight gradient on planes: kernel size %d not built", ks);
-    const int R = ks == 3 ? 3 : 4, KK = ks * ks, pad = ks / 2;
+    const int KK = ks * ks, pad = ks / 2;
     const int seg_max = 32 - 2 * pad;                      // a halo row holds 32 pixels
-    WgArgs a;
-    memset(&a, 0, sizeof a);
-    a.x = x; a.x_cs = 2 * x_plane; a.x_split = x_plane; a.x_zero = (unsigned)((size_t)B * H * W * 2 * x_plane * 2);
-    a.dy = dy; a.dy_cs = 2 * dy_plane; a.dy_split = dy_plane; a.dy_zero = (unsigned)((size_t)B * H * W * 2 * dy_plane * 2);
-    a.B = B; a.H = H; a.W = W;
-    a.tiles_x = (W + seg_max - 1) / seg_max;
-    a.Wt = (W + a.tiles_x - 1) / a.tiles_x;
-    a.strips_per_img = ((H + R - 1) / R) * a.tiles_x;
-    a.nstrips = B * a.strips_per_img;
+    WgsArgs w;
+    memset(&w, 0, sizeof w);
+    w.x = x; w.x_cs = 2 * x_plane; w.x_split = x_plane; w.x_zero = (unsigned)((size_t)B * H * W * 2 * x_plane * 2);
+    w.dy = dy; w.dy_cs = 2 * dy_plane; w.dy_split = dy_plane; w.dy_zero = (unsigned)((size_t)B * H * W * 2 * dy_plane * 2);
+    w.B = B; w.H = H; w.W = W;
+    w.tiles_x = (W + seg_max - 1) / seg_max;
+    w.Wt = (W + w.tiles_x - 1) / w.tiles_x;
     const int ci_my = k_map ? x_plane : Cin;               // channels of x that carry weights (the stage-2 input: the whole plane, re-ordered)
     const int ncot = (Cout + 63) / 64;
-    a.ncit = (ci_my + 63) / 64;
-    a.co_pad = ncot * 64; a.ci_pad = a.ncit * 64;
-    if (a.co_pad > dy_plane || a.ci_pad > x_plane) return pn_set_error(ctx, PN_ERR_INVALID, "weight gradient on planes: channel tiles exceed the planes");
-    const int pairs = ncot * a.ncit;
+    w.ncit = (ci_my + 63) / 64;
+    w.co_pad = ncot * 64; w.ci_pad = w.ncit * 64;
+    if (w.co_pad > dy_plane || w.ci_pad > x_plane) return pn_set_error(ctx, PN_ERR_INVALID, "weight gradient on planes: channel tiles exceed the planes");
+    const int pairs = ncot * w.ncit;
     // split-K slices: ONE block per CU.  Every slice costs a 147 KB partial tile written and read back, and a lone 64 KB block leaves the rest of the CU to
     // the BatchNorm / data-gradient launches of the step's own stream (same box, eager step: 1/2 block per CU 7.10 ms, 1: 6.49-6.68, 1.5: 6.93, 2: 7.03, 3: 7.39)
-    const int per_cu_x2 = getenv("POPNET_TRAINX_WG_BLOCKS") ? atoi(getenv("POPNET_TRAINX_WG_BLOCKS")) : 2;      // blocks per CU, in halves (experiments)
-    int S = std::max(1, std::min(a.nstrips, (per_cu_x2 * ctx->num_cus / 2 + pairs - 1) / pairs));
-    a.strips_per_block = (a.nstrips + S - 1) / S;
-    S = (a.nstrips + a.strips_per_block - 1) / a.strips_per_block;
-    *partial_floats = std::max(*partial_floats, (size_t)S * KK * a.co_pad * a.ci_pad);
-    const size_t lds = (size_t)((R + ks - 1) + R) * 8192;
-    const WgArgs a0 = a;
-    const bool stream_form = !(getenv("POPNET_TRAINX_WG_STREAM") && atoi(getenv("POPNET_TRAINX_WG_STREAM")) == 0);
-    if (stream_form) {
-        constexpr int D = 2;
-        WgsArgs w;
-        memset(&w, 0, sizeof w);
-        w.x = a.x; w.x_cs = a.x_cs; w.x_split = a.x_split; w.x_zero = a.x_zero;
-        w.dy = a.dy; w.dy_cs = a.dy_cs; w.dy_split = a.dy_split; w.dy_zero = a.dy_zero;
-        w.B = B; w.H = H; w.W = W; w.Wt = a.Wt; w.tiles_x = a.tiles_x;
-        w.rows_total = B * a.tiles_x * H;
-        int Sr = std::max(1, std::min(w.rows_total, (per_cu_x2 * ctx->num_cus / 2 + pairs - 1) / pairs));
-        w.rows_per_block = (w.rows_total + Sr - 1) / Sr;
-        Sr = (w.rows_total + w.rows_per_block - 1) / w.rows_per_block;
-        w.ncit = a.ncit; w.co_pad = a.co_pad; w.ci_pad = a.ci_pad;
-        *partial_floats = std::max(*partial_floats, (size_t)Sr * KK * a.co_pad * a.ci_pad);
-        const size_t ldss = (size_t)(5 + 5) * 8192;            // two rings of five rows
-        ops.push_back([=](hipStream_t s) {
-            WgsArgs ww = w;
-            ww.partial = *partial;
-            if (ks == 3) {
-                static PnLdsAttr attr;
-                if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_stream_kernel<3, 2>), ldss)) return rc;
-                hipLaunchKernelGGL((wgrad_stream_kernel<3, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
-            } else {
-                static PnLdsAttr attr;
-                if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_stream_kernel<1, 2>), ldss)) return rc;
-                hipLaunchKernelGGL((wgrad_stream_kernel<1, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
-            }
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((size_t)KK * ww.co_pad * ww.ci_pad + 15) / 16)), dim3(256), 0, s, (const float *)ww.partial, Sr, KK, ww.co_pad, ww.ci_pad, Cout, Cin, k_map, dw);
-            PN_HIP_CHECK(ctx, hipGetLastError());
-            return (int)PN_OK;
-        });
-        return PN_OK;
-    }
+    w.rows_total = B * w.tiles_x * H;
+    int Sr = std::max(1, std::min(w.rows_total, (ctx->num_cus + pairs - 1) / pairs));
+    w.rows_per_block = (w.rows_total + Sr - 1) / Sr;
+    Sr = (w.rows_total + w.rows_per_block - 1) / w.rows_per_block;
+    *partial_floats = std::max(*partial_floats, (size_t)Sr * KK * w.co_pad * w.ci_pad);
+    const size_t ldss = (size_t)(5 + 5) * 8192;            // two rings of five rows
     ops.push_back([=](hipStream_t s) {
-        WgArgs a = a0;
-        a.partial = *partial;                              // the host reads the pointer when the step launches (the buffer exists by then)
+        WgsArgs ww = w;
+        ww.partial = *partial;                             // the host reads the pointer when the step launches (the buffer exists by then)
         if (ks == 3) {
             static PnLdsAttr attr;
-            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_kernel<3, 3>), lds)) return rc;
-            hipLaunchKernelGGL((wgrad_kernel<3, 3>), dim3(S, pairs), dim3(256), lds, s, a);
+            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_stream_kernel<3, 2>), ldss)) return rc;
+            hipLaunchKernelGGL((wgrad_stream_kernel<3, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
         } else {
             static PnLdsAttr attr;
-            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_kernel<1, 4>), lds)) return rc;
-            hipLaunchKernelGGL((wgrad_kernel<1, 4>), dim3(S, pairs), dim3(256), lds, s, a);
+            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_stream_kernel<1, 2>), ldss)) return rc;
+            hipLaunchKernelGGL((wgrad_stream_kernel<1, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
         }
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((size_t)KK * a.co_pad * a.ci_pad + 15) / 16)), dim3(256), 0, s, (const float *)a.partial, S, KK, a.co_pad, a.ci_pad, Cout, Cin, k_map, dw);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((size_t)KK * ww.co_pad * ww.ci_pad + 15) / 16)), dim3(256), 0, s, (const float *)ww.partial, Sr, KK, ww.co_pad, ww.ci_pad, Cout, Cin, k_map, dw);
         PN_HIP_CHECK(ctx, hipGetLastError());
         return (int)PN_OK;
     });

@@ -23,10 +23,6 @@ from .network.rtpose_light3d import rtpose_light3d
 from .utils.paf_to_pose import make_parse_cfg
 
 
-import os as _os
-_NO_FRAMES_IN = bool(_os.environ.get("POPNET_NO_FRAMES_IN"))     # experiment switch: pn_preprocess + pn_*_forward as two calls in every precision
-
-
 class PoseEngine:
     def __init__(self, precision="bf16", state_dict=None, device=None, max_batch=32, input_size=224,
                  w_org=480, h_org=640, intrinsics=INTRINSICS, weight_seed=0, private_ctx=False, calib_gain=1.0):
@@ -141,7 +137,7 @@ class PoseEngine:
     def forward_frames(self, depth):
         """preprocess + forward as ONE call on the raw frames (pn_rtpose_forward_frames: the stem resizes / clamps / normalises its own
         input tile; bit-identical maps, the pre-processed tensor is never written).  The fp32 parity mode keeps the two calls."""
-        if _PREC.get(str(self.model.precision).lower()) == _lib.PN_PREC_F32 or _NO_FRAMES_IN:
+        if _PREC.get(str(self.model.precision).lower()) == _lib.PN_PREC_F32:
             B = self.preprocess(depth)
             self.forward(B)
             return B
@@ -247,7 +243,7 @@ class YoloEngine:
 
     def forward_frames(self, depth):
         """preprocess + forward as one call on the raw frames (pn_yolo_forward_frames); fp32 keeps the two calls."""
-        if _PREC.get(str(self.model.precision).lower()) == _lib.PN_PREC_F32 or _NO_FRAMES_IN:
+        if _PREC.get(str(self.model.precision).lower()) == _lib.PN_PREC_F32:
             B = self.preprocess(depth)
             self.forward(B)
             return B
