@@ -7,6 +7,10 @@ model2_2 / model2_3 = conv, BN, LeakyReLU; model2_4 = conv to A (5 + 3J) channel
 wh 2 s, conf s, joints (s - 0.5) 4 of s = sigmoid).  BatchNorm uses batch statistics and updates the running ones (momentum 0.1).
 The losses: coord / obj / selfpose mean squared errors with the masks as weights (plain) or multiplied into both sides and the
 pose weight map as weight (pose-weighted); x 4 for coord, x 3J for selfpose; loss_prior their sum.
+The mask-forced form (forward(..., forced=...)): every ReLU / LeakyReLU takes its branch from a given mask instead of the sign of its own
+pre-activation (where(m, z, slope z): derivative 1 where m is set, slope elsewhere) and every max pool takes its value and routes its gradient
+through a given flat index per window (gather) instead of its own argmax.  With the masks and indices of a GPU step it computes, in fp64, the
+step that GPU run took: what is left between the two is arithmetic, not which side of zero a pre-activation landed on.
 Also the seeded prior targets of the training goldens (tests/golden/make_golden_yolo.py imports them from here).
 """
 import numpy as np
@@ -42,8 +46,11 @@ def _params(sd, dtype, requires_grad=True):
     return out
 
 
-def forward(P, x, num_parts=NUM_JOINTS, anchors=ANCHORS):
-    """P: {name: tensor} (parameters with requires_grad, running statistics updated in place) -> cast output [B, A(5+3J), H/16, W/16]."""
+def forward(P, x, num_parts=NUM_JOINTS, anchors=ANCHORS, forced=None, record=None):
+    """P: {name: tensor} (parameters with requires_grad, running statistics updated in place) -> cast output [B, A(5+3J), H/16, W/16].
+    Masks and indices are keyed like YoloTrainEngine's: "bn:<BatchNorm name>" -> bool [B, C, H, W] (the activation after that BatchNorm
+    passes z, else takes slope z), "mp:stem" / "mp:model2_1" -> int [B, C, Ho, Wo] (flat index into the pool's input plane).
+    forced: the mask-forced form (module docstring) with these; record: a dict that receives this evaluation's own (z > 0, argmax)."""
     def conv(a, n, stride=1, pad=None):
         w = P[n + ".weight"]
         return F.conv2d(a, w, P.get(n + ".bias"), stride, w.shape[-1] // 2 if pad is None else pad)
@@ -51,22 +58,40 @@ def forward(P, x, num_parts=NUM_JOINTS, anchors=ANCHORS):
     def bn(a, n):
         return F.batch_norm(a, P[n + ".running_mean"], P[n + ".running_var"], P[n + ".weight"], P[n + ".bias"], True, 0.1, 1e-5)
 
+    def act(z, n, slope):
+        if record is not None:
+            record["bn:" + n] = (z > 0).detach()
+        if forced is None:
+            return F.relu(z) if slope == 0 else F.leaky_relu(z, slope)
+        return torch.where(forced["bn:" + n].to(torch.bool), z, z * slope)
+
+    def pool(a, n, k, stride, pad):
+        if forced is None and record is None:
+            return F.max_pool2d(a, k, stride, pad)
+        y, idx = F.max_pool2d(a, k, stride, pad, return_indices=True)
+        if record is not None:
+            record["mp:" + n] = idx
+        if forced is None:
+            return y
+        i = forced["mp:" + n].to(torch.long)
+        return a.flatten(2).gather(2, i.flatten(2)).view(i.shape)
+
     def block(a, p, stride):
-        y = F.relu(bn(conv(a, p + ".conv1", stride), p + ".bn1"))
+        y = act(bn(conv(a, p + ".conv1", stride), p + ".bn1"), p + ".bn1", 0)
         y = bn(conv(y, p + ".conv2"), p + ".bn2")
         idn = bn(conv(a, p + ".downsample.0", stride, 0), p + ".downsample.1") if (p + ".downsample.0.weight") in P else a
-        return F.relu(y + idn)
+        return act(y + idn, p + ".bn2", 0)
 
-    a = F.max_pool2d(F.relu(bn(conv(x, "model0.conv1", 2, 3), "model0.bn1")), 3, 2, 1)
+    a = pool(act(bn(conv(x, "model0.conv1", 2, 3), "model0.bn1"), "model0.bn1", 0), "stem", 3, 2, 1)
     for layer, n, first_stride in (("layer1", 3, 1), ("layer2", 4, 2)):
         for i in range(n):
             a = block(a, "model0.%s.%d" % (layer, i), first_stride if i == 0 else 1)
     for i in (0, 3, 6, 9):
-        a = F.leaky_relu(bn(conv(a, "model1.%d" % i), "model1.%d" % (i + 1)), 0.1)
+        a = act(bn(conv(a, "model1.%d" % i), "model1.%d" % (i + 1)), "model1.%d" % (i + 1), 0.1)
     a = conv(a, "model1.12")
-    a = F.max_pool2d(F.leaky_relu(bn(conv(a, "model2_1.0"), "model2_1.1"), 0.1), 2, 2)
+    a = pool(act(bn(conv(a, "model2_1.0"), "model2_1.1"), "model2_1.1", 0.1), "model2_1", 2, 2, 0)
     for m in ("model2_2", "model2_3"):
-        a = F.leaky_relu(bn(conv(a, m + ".0"), m + ".1"), 0.1)
+        a = act(bn(conv(a, m + ".0"), m + ".1"), m + ".1", 0.1)
     v = conv(a, "model2_4.0")
     B, _, h, w = v.shape
     s = v.view(B, len(anchors), 5 + 3 * num_parts, h, w).sigmoid()
@@ -91,12 +116,13 @@ def loss_terms(out, prior, conf, coord, weight=None, num_joints=NUM_JOINTS, num_
     return torch.stack([c + ob + sp, c, ob, sp])
 
 
-def train_step(sd, img, prior, conf, coord, weight=None, dtype=torch.float32):
-    """One forward + loss + backward on the CPU -> {"terms": ndarray [4], "grads": {name: tensor}, "out": tensor, "stats": {name: tensor}}."""
+def train_step(sd, img, prior, conf, coord, weight=None, dtype=torch.float32, forced=None, record=None):
+    """One forward + loss + backward on the CPU -> {"terms": ndarray [4], "grads": {name: tensor}, "out": tensor, "stats": {name: tensor}}.
+    forced / record: as in forward()."""
     P = _params(sd, dtype)
     x = torch.as_tensor(img).to(dtype)
     cast = [None if a is None else torch.as_tensor(a).to(dtype) for a in (prior, conf, coord, weight)]
-    out = forward(P, x)
+    out = forward(P, x, forced=forced, record=record)
     terms = loss_terms(out, *cast)
     terms[0].backward()
     grads = {k: v.grad.detach().clone() for k, v in P.items() if v.requires_grad}
