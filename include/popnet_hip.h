@@ -437,6 +437,26 @@ int pn_trainer_forward_backward(pn_trainer *t, const float *img_dev, const float
                                 const float *fg_mask_dev, float *loss_terms_dev, void *hip_stream);
 /* split-bf16 MFMA FLOPs (3 x 2 MAC) of the convolutions one step runs on the matrix cores (forward + data gradient; the weight gradient has the forward's count) */
 double pn_trainer_conv_flops(pn_trainer *t);
+/* Diagnostics of a finalized trainer (per-op checks; nothing here runs unless called).
+ * pn_trainer_num_ops: entries of the step's op list.  pn_trainer_op_info writes a JSON description of op k: "kind" (pack, stem_fwd, bn_fwd,
+ * conv, pool_fwd, heads, bn_bwd, dbias, wgrad, add, pool_bwd, stem_wgrad, fork, join), "stream" (step / side), "kernels" (labels; convolutions as
+ * pn_net_step_info labels them), and per problem the layer / BatchNorm name and every tensor read or written as {"t": id, "coff", "c"}; a
+ * weight gradient also has tiles_x, Wt, rows_per_block and the slice count Sr.  k = -1 describes the trainer: precision, B, H, W and the
+ * tensor table [H, W, plane] by id.  PN_ERR_INVALID when cap is too small.
+ * pn_trainer_run_ops runs ops [first, last) with the per-step pointers of pn_trainer_forward_backward, then waits for hip_stream AND the side
+ * stream (a range may end between a fork and its join).
+ * pn_trainer_read_tensor / pn_trainer_write_tensor move frames [frame0, frame0 + nframes) of tensor `id` as f32 NCHW [nframes][plane][H][W]
+ * (host memory; host_elems must be exactly that count).  which: 0 the value (hi + lo), 1 / 2 the stored hi / lo plane (bf16x3 trainers).
+ * Writing splits as the kernels' stores do: hi = bf16(v), lo = bf16(v - hi).  Both wait for the two streams first.
+ * pn_trainer_read_vector: "<BatchNorm name>.mean | invstd | scale | shift | k1 | k2 | k3" ([C]) or "head_out.<stage 0|1>.<0 paf|1 heat|2 z>"
+ * (f32 NCHW).  A bad id, range, name or element count is PN_ERR_INVALID. */
+int pn_trainer_num_ops(pn_trainer *t);
+int pn_trainer_op_info(pn_trainer *t, int k, char *out, size_t cap);
+int pn_trainer_run_ops(pn_trainer *t, const float *img_dev, const float *heat_gt_dev, const float *paf_gt_dev, const float *z_gt_dev,
+                       const float *fg_mask_dev, float *loss_terms_dev, int first, int last, void *hip_stream);
+int pn_trainer_read_tensor(pn_trainer *t, int id, int which, int frame0, int nframes, float *host_out, size_t host_elems, void *hip_stream);
+int pn_trainer_write_tensor(pn_trainer *t, int id, int frame0, int nframes, const float *host_in, size_t host_elems, void *hip_stream);
+int pn_trainer_read_vector(pn_trainer *t, const char *name, float *host_out, size_t host_elems, void *hip_stream);
 
 /* ---- Yolo-Pose+ decode ----------------------------------------------------------------------
  * Replaces parse_prior_pose (tpm/lib/utils/prior_pose_align.py:10-168, pred_vis=False), quirks

@@ -151,6 +151,12 @@ _SIGNATURES = {
     "pn_trainer_finalize": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f]),
     "pn_trainer_forward_backward": (_i, [_vp] * 8),
     "pn_trainer_conv_flops": (_d, [_vp]),
+    "pn_trainer_num_ops": (_i, [_vp]),
+    "pn_trainer_op_info": (_i, [_vp, _i, C.c_char_p, _sz]),
+    "pn_trainer_run_ops": (_i, [_vp] * 7 + [_i, _i, _vp]),
+    "pn_trainer_read_tensor": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "pn_trainer_write_tensor": (_i, [_vp, _i, _i, _i, _vp, _sz, _vp]),
+    "pn_trainer_read_vector": (_i, [_vp, C.c_char_p, _vp, _sz, _vp]),
     "pn_retrieve_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "pn_nms_peaks": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "pn_parse_yolo": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_float), _i, _i, _i, _i, _f, _f, _f, _f, _i, C.POINTER(ParseCfg), _vp, _vp]),

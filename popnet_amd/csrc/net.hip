@@ -933,17 +933,13 @@ int refresh_problems(pn_net *n, int B, hipStream_t stream) {
 
 // Kernel label of a step: the profiler's per-instantiation key (pn_net_profile_kernel) and pn_net_step_info's "kernel".
 std::string step_label(const pn_net *n, const Step &st) {
-    char lb[96];
     if (st.type == Step::STEM) {
         if (st.stem_pool_buf >= 0) return "stem7x7_pool_kernel";
         if (st.stem_cin > 1) return "conv2d_forward+nchw_relu_to_nhwc_kernel";
         if (n->prec == PN_PREC_F32) return "stem7x7_kernel";
         return n->x3 ? "stem7x7_mfma_kernel<x3>" : "stem7x7_mfma_kernel";
     }
-    if (st.type == Step::POOL) {
-        snprintf(lb, sizeof lb, "pool_kernel<%d%s>", st.mode, n->x3 ? ", split" : "");
-        return lb;
-    }
+    if (st.type == Step::POOL) return pn_pool_kernel_label(st.mode, n->x3);
     if (st.type == Step::BBLOCK) return n->x3 ? "bb64x3_kernel" : "bb64_kernel";
     const ConvSpec &c0 = n->convs[st.conv_ids[0]];
     bool mix = false;
@@ -951,11 +947,7 @@ std::string step_label(const pn_net *n, const Step &st) {
         const ConvSpec &cs = n->convs[id];
         if (cs.ks != c0.ks || (cs.tail_conv >= 0) != (c0.tail_conv >= 0)) mix = true;
     }
-    if (c0.kern == 4) snprintf(lb, sizeof lb, "conv4_kernel");
-    else if (c0.kern == 3 && mix) snprintf(lb, sizeof lb, "conv3_mix_kernel");
-    else if (c0.kern == 3) snprintf(lb, sizeof lb, "conv3_kernel<%d, %d, %d, %d, %d, %d>", c0.ks, c0.wc, c0.wp, c0.nbuf, c0.pt, c0.rpg);
-    else snprintf(lb, sizeof lb, "conv_mfma_kernel<%d, %d, %d, %d, %d>", n->prec, c0.ks, c0.stride, c0.pitch, c0.cfg);
-    return lb;
+    return pn_conv_kernel_label(n->prec, c0.kern, mix, c0.ks, c0.stride, c0.pitch, c0.cfg, c0.wc, c0.wp, c0.nbuf, c0.pt, c0.rpg);
 }
 
 // nsteps < 0: the whole step list; otherwise steps [0, nsteps) only (pn_net_forward_partial)

@@ -188,6 +188,20 @@ struct ConvLaunch {
     const ConvProblem *probs_dev;
 };
 int pn_launch_conv(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+// Kernel label of a convolution launch / a pool launch: the profiler's per-instantiation key, pn_net_step_info's and pn_trainer_op_info's "kernel"
+inline std::string pn_conv_kernel_label(int prec, int kern, bool mix, int ks, int stride, int pitch, int cfg, int wc, int wp, int nbuf, int pt, int rpg) {
+    char lb[96];
+    if (kern == 4) snprintf(lb, sizeof lb, "conv4_kernel");
+    else if (kern == 3 && mix) snprintf(lb, sizeof lb, "conv3_mix_kernel");
+    else if (kern == 3) snprintf(lb, sizeof lb, "conv3_kernel<%d, %d, %d, %d, %d, %d>", ks, wc, wp, nbuf, pt, rpg);
+    else snprintf(lb, sizeof lb, "conv_mfma_kernel<%d, %d, %d, %d, %d>", prec, ks, stride, pitch, cfg);
+    return lb;
+}
+inline std::string pn_pool_kernel_label(int mode, bool split) {
+    char lb[48];
+    snprintf(lb, sizeof lb, "pool_kernel<%d%s>", mode, split ? ", split" : "");
+    return lb;
+}
 int pn_launch_conv3(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);     // conv3_inst_*.hip
 int pn_launch_conv4(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);     // conv4_inst.hip
 

@@ -16,6 +16,7 @@
 // optimiser, the data-parallel all-reduce and the checkpoint format are untouched.  The 7x7 single-channel stem keeps train.hip's NCHW
 // kernels (Cin = 1: nothing for the matrix cores to contract over) behind two layout hand-overs.
 #include <algorithm>
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -60,6 +61,21 @@ struct TxLayer {                      // one nn.Conv2d
     float *bias_pad = nullptr;
 };
 
+struct OpDesc {                       // what ops[k] is, for pn_trainer_op_info: recorded beside the closure where it is pushed
+    std::string kind, body;           // body: the JSON members after "kind" and "stream"
+    bool side = false;
+};
+
+std::string jf(const char *fmt, ...) {
+    char t[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(t, sizeof t, fmt, ap);
+    va_end(ap);
+    return t;
+}
+std::string jref(int id, int coff, int c) { return id < 0 ? std::string("null") : jf("{\"t\": %d, \"coff\": %d, \"c\": %d}", id, coff, c); }
+
 struct ConvUse {                      // one convolution launch problem
     int layer; bool dgrad;
     int in, out, out_coff, res;       // tensors (-1 = none)
@@ -85,6 +101,7 @@ struct pn_trainer {
     std::vector<TxLayer> layers;
     std::vector<ConvLaunch> launches;
     std::vector<std::function<int(hipStream_t)>> ops;
+    std::vector<OpDesc> op_desc;     // one per op (diagnostics: pn_trainer_op_info)
     std::vector<tx::PackDesc> packs;
     std::vector<tx::BiasDesc> biases;
     tx::PackDesc *packs_dev = nullptr;
@@ -136,6 +153,13 @@ int new_tensor(pn_trainer *t, int H, int W, int plane, int *id) {
 }
 
 int pad64(int c) { return (c + 63) / 64 * 64; }
+
+// describes the op pushed last
+void describe(pn_trainer *t, const char *kind, const std::string &body) {
+    OpDesc d;
+    d.kind = kind; d.body = body;
+    t->op_desc.push_back(d);
+}
 
 int find_param(pn_trainer *t, const std::string &name, size_t numel, const float **p, float **g) {
     auto it = t->params.find(name);
@@ -324,6 +348,20 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
         t->launches.push_back(cl);
         const size_t li = t->launches.size() - 1;
         t->ops.push_back([t, li](hipStream_t s) { return pn_launch_conv(t->ctx, t->launches[li], s); });
+        std::string body = jf("\"kernels\": [\"%s\"], \"problems\": [", pn_conv_kernel_label(cl.prec, cl.kern, false, cl.ks, 1, cl.pitch, cl.cfg, cl.wc, cl.wp, cl.nbuf, cl.pt, cl.rpg).c_str());
+        for (size_t m = 0; m < members.size(); ++m) {
+            const PlannedConv &pc = pcs[members[m]];
+            const TxLayer &L = t->layers[pc.u.layer];
+            int hs = -1, hb = -1;
+            for (int st = 0; st < 2; ++st)
+                for (int b = 0; b < 3; ++b)
+                    if (pc.u.out_nchw && pc.u.out_nchw == t->head_out[st][b]) { hs = st; hb = b; }
+            body += jf("%s{\"layer\": \"%s\", \"dgrad\": %d, \"act\": %d, \"bias\": %d, \"ks\": %d, \"cin\": %d, \"cout\": %d, \"cat\": %d, \"rows\": %d, \"R\": %d, \"Wt\": %d, ",
+                       m ? ", " : "", L.name.c_str(), pc.u.dgrad ? 1 : 0, pc.u.act, (!pc.u.dgrad && L.b) ? 1 : 0, pc.ks, L.cin, L.cout, L.cat ? 1 : 0, pc.rows, pc.g.R, pc.g.Wt);
+            body += "\"in\": " + jref(pc.u.in, 0, t->T[pc.u.in].plane) + ", \"out\": " + jref(pc.u.out, pc.u.out_coff, pc.rows) + ", \"res\": " + jref(pc.u.res, 0, pc.rows);
+            body += hs >= 0 ? jf(", \"nchw\": \"head_out.%d.%d\"}", hs, hb) : std::string(", \"nchw\": null}");
+        }
+        describe(t, "conv", body + "]");
     }
     return PN_OK;
 }
@@ -384,6 +422,12 @@ void op_bn_fwd(pn_trainer *t, std::vector<BnUse> uses) {
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    std::string body = jf("\"kernels\": [\"reduce_kernel<0>\", \"bn_finish_kernel\", \"bn_apply_kernel\"], \"problems\": [");
+    for (int i = 0; i < n; ++i) {
+        body += jf("%s{\"bn\": \"%s\", \"act\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, ", i ? ", " : "", t->bns[uses[i].bn].name.c_str(), uses[i].act, g[i].C, g[i].ppb, g[i].nblk);
+        body += "\"x\": " + jref(uses[i].x, 0, g[i].C) + ", \"res\": " + jref(uses[i].res, 0, g[i].C) + ", \"y\": " + jref(uses[i].y, 0, g[i].C) + "}";
+    }
+    describe(t, "bn_fwd", body + "]");
 }
 void op_bn_fwd(pn_trainer *t, int bn, int x, int res, int y, int act) { op_bn_fwd(t, std::vector<BnUse>{{bn, x, res, y, act}}); }
 
@@ -438,6 +482,14 @@ void op_bn_bwd(pn_trainer *t, std::vector<BnBwdUse> uses) {
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    std::string body = uses[0].dx < 0 ? "\"kernels\": [\"reduce_kernel<1>\", \"bn_bwd_finish_kernel\"], \"problems\": ["
+                                      : "\"kernels\": [\"reduce_kernel<1>\", \"bn_bwd_finish_kernel\", \"bn_bwd_apply_kernel\"], \"problems\": [";
+    for (int i = 0; i < n; ++i) {
+        const BnBwdUse &u = uses[i];
+        body += jf("%s{\"bn\": \"%s\", \"act\": %d, \"has_res\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, ", i ? ", " : "", t->bns[u.bn].name.c_str(), u.act, u.has_res ? 1 : 0, g[i].C, g[i].ppb, g[i].nblk);
+        body += "\"x\": " + jref(u.x, 0, g[i].C) + ", \"dy\": " + jref(u.dy, 0, g[i].C) + ", \"y\": " + jref(u.y, 0, g[i].C) + ", \"dx\": " + jref(u.dx, 0, g[i].C) + ", \"dres\": " + jref(u.dres, 0, g[i].C) + "}";
+    }
+    describe(t, "bn_bwd", body + "]");
 }
 void op_bn_bwd(pn_trainer *t, int bn, int x, int dy, int y, int dx, int dres, int act, bool has_res) {
     op_bn_bwd(t, std::vector<BnBwdUse>{{bn, x, dy, y, dx, dres, act, has_res}});
@@ -463,6 +515,8 @@ void op_dbias(pn_trainer *t, int l, int dy) {
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    describe(t, "dbias", jf("\"kernels\": [\"reduce_kernel<2>\", \"sum_finish_kernel\"], \"layer\": \"%s\", \"cout\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, \"dy\": ",
+                            t->layers[l].name.c_str(), t->layers[l].cout, C, ppb, nblk) + jref(dy, 0, C));
 }
 
 void op_add(pn_trainer *t, std::vector<std::array<int, 2>> ins /* (tensor, channel offset) */, int C, int out) {
@@ -479,6 +533,9 @@ void op_add(pn_trainer *t, std::vector<std::array<int, 2>> ins /* (tensor, chann
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    std::string body = "\"kernels\": [\"add_kernel\"], \"ins\": [";
+    for (size_t i = 0; i < ins.size(); ++i) body += (i ? ", " : "") + jref(ins[i][0], ins[i][1], C);
+    describe(t, "add", body + "], \"out\": " + jref(out, 0, C));
 }
 
 void op_pool_fwd(pn_trainer *t, int x, int y, int out_coff) {
@@ -486,6 +543,7 @@ void op_pool_fwd(pn_trainer *t, int x, int y, int out_coff) {
     t->ops.push_back([=](hipStream_t s) {
         return pn_launch_pool(t->ctx, t->f32 ? PN_PREC_F32 : PN_PREC_BF16, 0, X.p, Y.p, t->B, X.H, X.W, X.plane, X.cs(), Y.cs(), out_coff, X.split(), Y.split(), s);
     });
+    describe(t, "pool_fwd", jf("\"kernels\": [\"%s\"], \"x\": ", pn_pool_kernel_label(0, !t->f32).c_str()) + jref(x, 0, X.plane) + ", \"y\": " + jref(y, out_coff, X.plane));
 }
 
 void op_pool_bwd(pn_trainer *t, int dy, int dx) {
@@ -499,6 +557,7 @@ void op_pool_bwd(pn_trainer *t, int dy, int dx) {
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    describe(t, "pool_bwd", "\"kernels\": [\"avgpool_bwd_kernel\"], \"dy\": " + jref(dy, 0, DX.plane) + ", \"dx\": " + jref(dx, 0, DX.plane));
 }
 
 // loss terms and head gradients of a stage's three heads (one launch); dcat = the stage-2 input gradient whose slices reach the stage-1 heads (or -1)
@@ -535,6 +594,12 @@ void op_heads(pn_trainer *t, int stage, int dcat, const int dv[3]) {
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    std::string body = jf("\"kernels\": [\"head_kernel\", \"loss_finish_kernel\"], \"stage\": %d, \"heads\": [", stage);
+    for (int b = 0; b < 3; ++b) {
+        body += jf("%s{\"out\": \"head_out.%d.%d\", \"kind\": %d, \"C\": %d, \"fg\": %d, \"loss\": %d, ", b ? ", " : "", stage, b, HEAD_KIND[b], HEAD_C[b], b == 2 ? 1 : 0, 3 * stage + b);
+        body += "\"dextra\": " + jref(dcat, dcat >= 0 ? CAT_OFF[b] : 0, HEAD_C[b]) + ", \"dv\": " + jref(dv[b], 0, DV[b].plane) + "}";
+    }
+    describe(t, "heads", body + "]");
 }
 
 // fork: the side stream may start once everything issued so far on the step's stream has finished; join: the other way round
@@ -548,6 +613,7 @@ int op_fork(pn_trainer *t) {
         PN_HIP_CHECK(t->ctx, hipStreamWaitEvent(t->side, ev, 0));
         return (int)PN_OK;
     });
+    describe(t, "fork", "\"kernels\": []");
     return PN_OK;
 }
 int op_join(pn_trainer *t) {
@@ -560,6 +626,7 @@ int op_join(pn_trainer *t) {
         PN_HIP_CHECK(t->ctx, hipStreamWaitEvent(s, ev, 0));
         return (int)PN_OK;
     });
+    describe(t, "join", "\"kernels\": []");
     return PN_OK;
 }
 // every op appended since `from` runs on the side stream
@@ -568,6 +635,7 @@ void ops_to_side(pn_trainer *t, size_t from) {
     for (size_t i = from; i < t->ops.size(); ++i) {
         auto f = t->ops[i];
         t->ops[i] = [t, f](hipStream_t) { return f(t->side); };
+        t->op_desc[i].side = true;
     }
     t->side_tail = t->ops.size();
 }
@@ -594,18 +662,24 @@ int op_wgrad(pn_trainer *t, int l, int dy) {
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return pn_conv2d_wgrad(t->ctx, t->nchw_a, t->nchw_b, LL.dw, LL.db, t->B, LL.cin, X.H, X.W, LL.cout, LL.ks, 1, LL.ks / 2, (void *)s);
         });
+        describe(t, "wgrad", jf("\"kernels\": [\"planes_to_nchw_kernel\", \"pn_conv2d_wgrad\"], \"layer\": \"%s\", \"ks\": %d, \"cin\": %d, \"cout\": %d, \"cat\": %d, \"bias\": %d, \"x\": ",
+                                L.name.c_str(), L.ks, L.cin, L.cout, L.cat ? 1 : 0, L.db ? 1 : 0) + jref(L.x, 0, X.plane) + ", \"dy\": " + jref(dy, 0, DY.plane));
         return PN_OK;
     }
     if (L.b && !L.bn_follows) op_dbias(t, l, dy);      // (a bias in front of a BatchNorm: its gradient is identically zero and the flat gradient buffer already holds 0)
     if (int rc = op_fork(t)) return rc;
     const size_t from = t->ops.size();
+    tx::WgPlan wp;
     if (t->f32) {
         if (int rc = tx::plan_wgrad_f32(t->ctx, t->B, X.H, X.W, (const float *)X.p, X.plane, (const float *)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw,
-                                        &t->wg_partial, &t->wg_partial_floats, t->ops))
+                                        &t->wg_partial, &t->wg_partial_floats, t->ops, &wp))
             return rc;
     } else if (int rc = tx::plan_wgrad(t->ctx, t->B, X.H, X.W, (const bf *)X.p, X.plane, (const bf *)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw,
-                                       &t->wg_partial, &t->wg_partial_floats, t->ops))
+                                       &t->wg_partial, &t->wg_partial_floats, t->ops, &wp))
         return rc;
+    describe(t, "wgrad", jf("\"kernels\": [\"%s<%d, 2>\", \"wgrad_reduce_kernel\"], \"layer\": \"%s\", \"ks\": %d, \"cin\": %d, \"cout\": %d, \"cat\": %d, \"tiles_x\": %d, \"Wt\": %d, "
+                            "\"rows_per_block\": %d, \"Sr\": %d, \"x\": ", t->f32 ? "wgrad_f32_kernel" : "wgrad_stream_kernel", L.ks, L.name.c_str(), L.ks, L.cin, L.cout, L.cat ? 1 : 0,
+                            wp.tiles_x, wp.Wt, wp.rows_per_block, wp.Sr) + jref(L.x, 0, X.plane) + ", \"dy\": " + jref(dy, 0, DY.plane));
     ops_to_side(t, from);
     return PN_OK;
 }
@@ -643,6 +717,7 @@ int build(pn_trainer *t) {
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
+    describe(t, "pack", jf("\"kernels\": [\"%s\", \"bias_kernel\"]", t->pack_gather ? "pack_kernel" : "pack_rows_kernel"));
     ops_to_side(t, pack_from);
     // stem: model0.conv1 7x7 / 2 on the NCHW f32 image (train.hip), handed over as planes
     int C0, A0;
@@ -663,6 +738,8 @@ int build(pn_trainer *t) {
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return (int)PN_OK;
         });
+        describe(t, "stem_fwd", jf("\"kernels\": [%s], \"layer\": \"model0.conv1\", \"out\": ",
+                                   handover ? "\"tconv_fwd_kernel\", \"nchw_to_planes_kernel\"" : (stem_gather ? "\"tconv_fwd_kernel<7>\"" : "\"tstem_fwd_kernel\"")) + jref(C0, 0, 64));
     }
     int bn_stem;
     TX(new_bn(t, "model0.bn1", 64, &bn_stem));
@@ -851,6 +928,9 @@ int build(pn_trainer *t) {
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return pn_conv2d_wgrad(t->ctx, t->img, t->nchw_b, dw_stem, nullptr, B, 1, H, W, 64, 7, 2, 3, (void *)s);
         });
+        describe(t, "stem_wgrad", jf("\"kernels\": [%s], \"layer\": \"model0.conv1\", \"bn\": %s, \"x\": ",
+                                     stem_handover ? "\"planes_to_nchw_kernel\", \"pn_conv2d_wgrad\"" : "\"tstem_wgrad_kernel\"", stem_bn_separate ? "null" : "\"model0.bn1\"") +
+                                      jref(C0, 0, 64) + ", \"dy\": " + jref(stem_bn_separate ? dC0 : dA0, 0, 64));
     }
     TX(op_join(t));                               // the step ends when the last weight gradient has landed
 #undef TX
@@ -869,6 +949,7 @@ int build(pn_trainer *t) {
         PN_HIP_CHECK(ctx, hipMemcpy(t->biases_dev, t->biases.data(), t->biases.size() * sizeof(tx::BiasDesc), hipMemcpyHostToDevice));
     }
     PN_HIP_CHECK(ctx, hipDeviceSynchronize());
+    if (t->op_desc.size() != t->ops.size()) return pn_set_error(ctx, PN_ERR_STATE, "pn_trainer: %zu ops, %zu descriptions", t->ops.size(), t->op_desc.size());
     return PN_OK;
 }
 
@@ -949,5 +1030,155 @@ int pn_trainer_forward_backward(pn_trainer *t, const float *img_dev, const float
 }
 
 double pn_trainer_conv_flops(pn_trainer *t) { return t ? t->flops_conv : 0.0; }
+
+// ---- diagnostics: the step as a list of described ops, runnable in ranges, with host access to every tensor (tests/test_gpu_train_layers.py) ----
+int pn_trainer_num_ops(pn_trainer *t) {
+    if (!t) return PN_ERR_INVALID;
+    if (!t->finalized) return pn_set_error(t->ctx, PN_ERR_STATE, "pn_trainer_num_ops: trainer not finalized");
+    return (int)t->ops.size();
+}
+
+int pn_trainer_op_info(pn_trainer *t, int k, char *out, size_t cap) {
+    if (!t || !out || !cap) return PN_ERR_INVALID;
+    pn_ctx *ctx = t->ctx;
+    if (!t->finalized) return pn_set_error(ctx, PN_ERR_STATE, "pn_trainer_op_info: trainer not finalized");
+    if (k < -1 || k >= (int)t->ops.size()) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_op_info: op %d outside [-1, %zu)", k, t->ops.size());
+    std::string js;
+    if (k == -1) {
+        js = jf("{\"prec\": \"%s\", \"B\": %d, \"H\": %d, \"W\": %d, \"ops\": %zu, \"momentum\": %.9g, \"eps\": %.9g, \"tensors\": [", t->f32 ? "fp32" : "bf16x3", t->B, t->H, t->W, t->ops.size(),
+                (double)t->momentum, (double)t->eps);
+        for (size_t i = 0; i < t->T.size(); ++i) js += jf(i ? ", [%d, %d, %d]" : "[%d, %d, %d]", t->T[i].H, t->T[i].W, t->T[i].plane);
+        js += "]}";
+    } else {
+        const OpDesc &d = t->op_desc[k];
+        js = jf("{\"kind\": \"%s\", \"stream\": \"%s\", ", d.kind.c_str(), d.side ? "side" : "step") + d.body + "}";
+    }
+    if (js.size() + 1 > cap) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_op_info: %zu bytes needed", js.size() + 1);
+    memcpy(out, js.c_str(), js.size() + 1);
+    return PN_OK;
+}
+
+static int tx_sync(pn_trainer *t, hipStream_t s) {
+    PN_HIP_CHECK(t->ctx, hipStreamSynchronize(s));
+    if (t->side) PN_HIP_CHECK(t->ctx, hipStreamSynchronize(t->side));
+    return PN_OK;
+}
+
+int pn_trainer_run_ops(pn_trainer *t, const float *img_dev, const float *heat_gt_dev, const float *paf_gt_dev, const float *z_gt_dev, const float *fg_mask_dev,
+                       float *loss_terms_dev, int first, int last, void *hip_stream) {
+    if (!t) return PN_ERR_INVALID;
+    pn_ctx *ctx = t->ctx;
+    if (!t->finalized) return pn_set_error(ctx, PN_ERR_STATE, "pn_trainer_run_ops: pn_trainer_finalize has not been called");
+    if (!img_dev || !heat_gt_dev || !paf_gt_dev || !z_gt_dev || !fg_mask_dev || !loss_terms_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_run_ops: null device pointer");
+    if (first < 0 || last < first || last > (int)t->ops.size()) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_run_ops: [%d, %d) outside [0, %zu]", first, last, t->ops.size());
+    t->img = img_dev; t->target[0] = paf_gt_dev; t->target[1] = heat_gt_dev; t->target[2] = z_gt_dev; t->fg = fg_mask_dev; t->loss = loss_terms_dev;
+    hipStream_t s = (hipStream_t)hip_stream;
+    for (int k = first; k < last; ++k)
+        if (int rc = t->ops[k](s)) return rc;
+    return tx_sync(t, s);          // both streams: a range may end between a fork and its join
+}
+
+static inline float tx_bf2f(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
+static inline uint16_t tx_f2bf(float f) {          // round to nearest even, as the device's float -> __bf16 conversion
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+static int tx_tensor_range(pn_trainer *t, const char *what, int id, int frame0, int nframes, size_t host_elems, size_t *frame_elems) {
+    pn_ctx *ctx = t->ctx;
+    if (!t->finalized) return pn_set_error(ctx, PN_ERR_STATE, "%s: trainer not finalized", what);
+    if (id < 0 || id >= (int)t->T.size()) return pn_set_error(ctx, PN_ERR_INVALID, "%s: tensor %d outside [0, %zu)", what, id, t->T.size());
+    if (frame0 < 0 || nframes < 1 || frame0 > t->B - nframes) return pn_set_error(ctx, PN_ERR_INVALID, "%s: frames [%d, %d + %d) outside [0, %d)", what, frame0, frame0, nframes, t->B);
+    const TxTensor &X = t->T[id];
+    *frame_elems = (size_t)X.H * X.W * X.plane;
+    if (host_elems != *frame_elems * nframes) return pn_set_error(ctx, PN_ERR_INVALID, "%s: %zu host elements, %zu expected", what, host_elems, *frame_elems * nframes);
+    return PN_OK;
+}
+
+int pn_trainer_read_tensor(pn_trainer *t, int id, int which, int frame0, int nframes, float *host_out, size_t host_elems, void *hip_stream) {
+    if (!t || !host_out) return PN_ERR_INVALID;
+    pn_ctx *ctx = t->ctx;
+    size_t fe = 0;
+    if (int rc = tx_tensor_range(t, "pn_trainer_read_tensor", id, frame0, nframes, host_elems, &fe)) return rc;
+    if (which < 0 || which > 2 || (t->f32 && which)) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_read_tensor: plane selector %d (0 value, 1 hi, 2 lo; planes exist in a bf16x3 trainer only)", which);
+    const TxTensor &X = t->T[id];
+    if (int rc = tx_sync(t, (hipStream_t)hip_stream)) return rc;
+    std::vector<uint32_t> raw(fe * nframes);              // 4 bytes per channel in both storage forms
+    PN_HIP_CHECK(ctx, hipMemcpy(raw.data(), X.p + (size_t)frame0 * fe * 4, raw.size() * 4, hipMemcpyDeviceToHost));
+    const size_t HW = (size_t)X.H * X.W;
+    for (int f = 0; f < nframes; ++f)
+        for (size_t p = 0; p < HW; ++p) {
+            const char *px = (const char *)raw.data() + ((size_t)f * HW + p) * X.plane * 4;
+            for (int c = 0; c < X.plane; ++c) {
+                float v;
+                if (t->f32) v = ((const float *)px)[c];
+                else {
+                    const uint16_t *h = (const uint16_t *)px;
+                    const float hi = tx_bf2f(h[c]), lo = tx_bf2f(h[X.plane + c]);
+                    v = which == 1 ? hi : which == 2 ? lo : hi + lo;
+                }
+                host_out[((size_t)f * X.plane + c) * HW + p] = v;
+            }
+        }
+    return PN_OK;
+}
+
+int pn_trainer_write_tensor(pn_trainer *t, int id, int frame0, int nframes, const float *host_in, size_t host_elems, void *hip_stream) {
+    if (!t || !host_in) return PN_ERR_INVALID;
+    pn_ctx *ctx = t->ctx;
+    size_t fe = 0;
+    if (int rc = tx_tensor_range(t, "pn_trainer_write_tensor", id, frame0, nframes, host_elems, &fe)) return rc;
+    const TxTensor &X = t->T[id];
+    std::vector<uint32_t> raw(fe * nframes);
+    const size_t HW = (size_t)X.H * X.W;
+    for (int f = 0; f < nframes; ++f)
+        for (size_t p = 0; p < HW; ++p) {
+            char *px = (char *)raw.data() + ((size_t)f * HW + p) * X.plane * 4;
+            for (int c = 0; c < X.plane; ++c) {
+                const float v = host_in[((size_t)f * X.plane + c) * HW + p];
+                if (t->f32) ((float *)px)[c] = v;
+                else {                                   // Lay<bf>::st1: hi = bf(v), lo = bf(v - hi)
+                    uint16_t *h = (uint16_t *)px;
+                    h[c] = tx_f2bf(v);
+                    h[X.plane + c] = tx_f2bf(v - tx_bf2f(h[c]));
+                }
+            }
+        }
+    if (int rc = tx_sync(t, (hipStream_t)hip_stream)) return rc;
+    PN_HIP_CHECK(ctx, hipMemcpy(X.p + (size_t)frame0 * fe * 4, raw.data(), raw.size() * 4, hipMemcpyHostToDevice));
+    return PN_OK;
+}
+
+int pn_trainer_read_vector(pn_trainer *t, const char *name, float *host_out, size_t host_elems, void *hip_stream) {
+    if (!t || !name || !host_out) return PN_ERR_INVALID;
+    pn_ctx *ctx = t->ctx;
+    if (!t->finalized) return pn_set_error(ctx, PN_ERR_STATE, "pn_trainer_read_vector: trainer not finalized");
+    const std::string nm = name;
+    const float *src = nullptr;
+    size_t n = 0;
+    int st = -1, b = -1;
+    if (sscanf(name, "head_out.%d.%d", &st, &b) == 2) {
+        if (st < 0 || st > 1 || b < 0 || b > 2 || nm != jf("head_out.%d.%d", st, b)) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_read_vector: unknown '%s'", name);
+        src = t->head_out[st][b]; n = (size_t)t->B * HEAD_C[b] * (t->H / 8) * (t->W / 8);
+    } else {
+        const size_t dot = nm.rfind('.');
+        if (dot != std::string::npos) {
+            const std::string bn = nm.substr(0, dot), what = nm.substr(dot + 1);
+            static const char *names[7] = {"mean", "invstd", "scale", "shift", "k1", "k2", "k3"};
+            for (const TxBn &x : t->bns)
+                if (x.name == bn)
+                    for (int i = 0; i < 7; ++i)
+                        if (what == names[i]) { src = x.mean + (size_t)i * x.C; n = (size_t)x.C; }
+        }
+    }
+    if (!src) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_read_vector: unknown '%s' (<BatchNorm>.mean|invstd|scale|shift|k1|k2|k3 or head_out.<stage>.<head>)", name);
+    if (host_elems != n) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_read_vector: %zu host elements, %zu expected", host_elems, n);
+    if (int rc = tx_sync(t, (hipStream_t)hip_stream)) return rc;
+    PN_HIP_CHECK(ctx, hipMemcpy(host_out, src, n * 4, hipMemcpyDeviceToHost));
+    return PN_OK;
+}
 
 }  // extern "C"

@@ -404,10 +404,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
     dw[((size_t)co * Cin + ref) * KK + tp] = t;
 }
 
+// What a plan decided (diagnostics: the length of the fp32 summation chains of one output element is rows_per_block rows of <= Wt pixels in a block, then Sr slices)
+struct WgPlan { int tiles_x = 0, Wt = 0, rows_per_block = 0, Sr = 0; };
+
 // Plans the weight gradient of one layer and appends its two launches to `ops`.  *partial_floats grows to what the layer needs; the
 // buffer itself (*partial) is allocated by the caller after every layer has been planned (the kernels read the pointer at launch time).
 inline int plan_wgrad_f32(pn_ctx *ctx, int B, int H, int W, const float *x, int x_plane, const float *dy, int dy_plane, int Cin, int Cout, int ks, const int *k_map, float *dw,
-                          float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops) {
+                          float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops, WgPlan *plan = nullptr) {
     if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "fp32 weight gradient: kernel size %d not built", ks);
     const int KK = ks * ks, pad = ks / 2, seg_max = 32 - 2 * pad;
     WgfArgs w;
@@ -428,6 +431,7 @@ inline int plan_wgrad_f32(pn_ctx *ctx, int B, int H, int W, const float *x, int 
     w.rows_per_block = (w.rows_total + Sr - 1) / Sr;
     Sr = (w.rows_total + w.rows_per_block - 1) / w.rows_per_block;
     *partial_floats = std::max(*partial_floats, (size_t)Sr * KK * w.co_pad * w.ci_pad);
+    if (plan) { plan->tiles_x = w.tiles_x; plan->Wt = w.Wt; plan->rows_per_block = w.rows_per_block; plan->Sr = Sr; }
     const size_t ldss = (size_t)10 * 8192;
     ops.push_back([=](hipStream_t s) {
         WgfArgs ww = w;
@@ -449,7 +453,7 @@ inline int plan_wgrad_f32(pn_ctx *ctx, int B, int H, int W, const float *x, int 
 }
 
 inline int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const bf *x, int x_plane, const bf *dy, int dy_plane, int Cin, int Cout, int ks, const int *k_map, float *dw,
-                      float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops) {
+                      float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops, WgPlan *plan = nullptr) {
     if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "weight gradient on planes: kernel size %d not built", ks);
     const int KK = ks * ks, pad = ks / 2;
     const int seg_max = 32 - 2 * pad;                      // a halo row holds 32 pixels
@@ -473,6 +477,7 @@ inline int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const bf *x, int x_plane
     w.rows_per_block = (w.rows_total + Sr - 1) / Sr;
     Sr = (w.rows_total + w.rows_per_block - 1) / w.rows_per_block;
     *partial_floats = std::max(*partial_floats, (size_t)Sr * KK * w.co_pad * w.ci_pad);
+    if (plan) { plan->tiles_x = w.tiles_x; plan->Wt = w.Wt; plan->rows_per_block = w.rows_per_block; plan->Sr = Sr; }
     const size_t ldss = (size_t)(5 + 5) * 8192;            // two rings of five rows
     ops.push_back([=](hipStream_t s) {
         WgsArgs ww = w;

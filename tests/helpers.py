@@ -23,6 +23,31 @@ def state_dict_from_keys(keys, seed):
     return {k: torch.from_numpy(v) for k, v in synth.fill_state_dict(template, seed=seed).items()}
 
 
+def init_like_state_dict(keys, seed):
+    """The state a training run starts from: every conv weight N(0, 0.01) (rtpose_light3d._initialize_weights_norm, :358-362),
+    conv biases U(+-1/sqrt(fan_in)) (nn.Conv2d default), BatchNorm weight 1 / bias 0 / mean 0 / var 1."""
+    g = torch.Generator().manual_seed(seed)
+    shapes = dict((k, tuple(s)) for k, s in keys)
+    sd = {}
+    for k, shp in shapes.items():
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            sd[k] = torch.zeros(shp)
+        elif k.endswith("running_var"):
+            sd[k] = torch.ones(shp)
+        elif len(shp) == 4:
+            sd[k] = torch.randn(shp, generator=g) * 0.01
+        elif k.endswith(".weight"):
+            sd[k] = torch.ones(shp)                                   # BatchNorm weight
+        elif k[:-len(".bias")] + ".running_mean" in shapes:
+            sd[k] = torch.zeros(shp)                                  # BatchNorm bias
+        else:
+            w = shapes[k[:-len(".bias")] + ".weight"]
+            sd[k] = (torch.rand(shp, generator=g) * 2 - 1) / np.sqrt(w[1] * w[2] * w[3])
+    return sd
+
+
 def parse_case_inputs(golden, name):
     if name in SPECIAL_CASES:
         return (golden.parse["in_%s_heat" % name], golden.parse["in_%s_paf" % name], golden.parse["in_%s_z" % name])
