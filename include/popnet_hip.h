@@ -298,6 +298,32 @@ int pn_rasterize_targets(pn_ctx *ctx, const float *kp2d_dev, const double *kp_z_
                          const float *depth_resize_dev, const pn_target_cfg *cfg, float *heat_dev, float *paf_dev,
                          float *z_dev, float *fg_dev, void *hip_stream);
 
+/* ---- random training augmentation ---------------------------------------------------------------------
+ * The image half of the reference's training transform Compose([Cvt2ndarray, Rotate(cx, cy), RenderDepth(cx, cy, max_ratio), Crop,
+ * Resize(S)]) (tpm/lib/datasets/data_augmentation_2d3d.py:411-448, 283-350, 94-128, 497-522) plus the clamp and normalisation of
+ * pn_preprocess, as ONE launch for the batch: composed [B,H,W] f32 (what pn_compose_depth writes) -> out [B,1,S,S] f32
+ *   out = (clamp(Resize(Crop(RenderDepth(Rotate(frame)))), 0, depth_max) - depth_mean) / depth_std
+ * bit for bit what OpenCV 4.2's scalar float32 paths of warpAffine(INTER_LINEAR, constant border 0) and resize(INTER_LINEAR) give.
+ * Each item has its own record.  The host decides every integer of the geometry (the int() truncations of RenderDepth and Crop,
+ * numpy's clamping of slice ends) and inverts the rotation matrix in double, in warpAffine's own operation order.
+ * items_host holds the B records; the call checks them, enqueues their upload into items_dev (room for B records, the caller's
+ * buffer: nothing is allocated) on the stream and launches the kernel behind it, so the kernel reads exactly what was checked.  It
+ * does not synchronise; items_host must stay untouched until the stream has passed the call (with pageable host memory the runtime
+ * stages the bytes before the call returns).  An item whose source is exactly 2S x 2S is PN_ERR_UNSUPPORTED like pn_preprocess
+ * (cv::resize runs INTER_AREA there); inconsistent geometry is PN_ERR_INVALID; nothing is copied or launched in either case.       */
+typedef struct pn_augment_item {
+    double m[6];                  /* Rotate: the INVERTED 2x3 matrix (destination pixel -> source), row major, as warpAffine holds it */
+    float scale;                  /* RenderDepth: float32(a), a recomputed from the truncated corner                                  */
+    int render_x, render_y;       /* where pixel (0,0) of the render image lies in the rotated frame: the slice start when a <= 1,
+                                     (-dx, -dy) of the paste into the zero image otherwise                                            */
+    int render_w, render_h;       /* size of the render image                                                                        */
+    int crop_x0, crop_y0, crop_x1, crop_y1;   /* Crop's slice of the render image, ends exclusive and already clamped to its size    */
+    int src_w, src_h;             /* the size Resize sees: crop_x1 - crop_x0, crop_y1 - crop_y0                                      */
+} pn_augment_item;
+size_t pn_sizeof_augment_item(void);
+int pn_augment_resize(pn_ctx *ctx, const float *composed_dev, const pn_augment_item *items_host, pn_augment_item *items_dev,
+                      int B, int H, int W, float *out_dev, int S, float depth_max, float depth_mean, float depth_std, void *hip_stream);
+
 /* ---- training step primitives (BASELINE configs[4]) ------------------------------
  * fp32, NCHW, contiguous -- the layout of the reference's own tensors, so every intermediate can be laid next to the
  * reference module's.  One entry per differentiable primitive of rtpose_light3d in train mode; popnet_amd/train.py

@@ -46,6 +46,13 @@ class YoloTargetCfg(C.Structure):
                 ("depth_mean", C.c_double), ("depth_std", C.c_double)]
 
 
+class AugmentItem(C.Structure):
+    """pn_augment_item"""
+    _fields_ = [("m", C.c_double * 6), ("scale", C.c_float), ("render_x", C.c_int), ("render_y", C.c_int), ("render_w", C.c_int),
+                ("render_h", C.c_int), ("crop_x0", C.c_int), ("crop_y0", C.c_int), ("crop_x1", C.c_int), ("crop_y1", C.c_int),
+                ("src_w", C.c_int), ("src_h", C.c_int)]
+
+
 class ParseCfg(C.Structure):
     """pn_parse_cfg"""
     _fields_ = [("thresh_heatmap", C.c_float), ("thresh_paf", C.c_float),
@@ -122,6 +129,8 @@ _SIGNATURES = {
     "pn_target_cfg_default": (None, [C.POINTER(TargetCfg)]),
     "pn_compose_depth": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "pn_rasterize_targets": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(TargetCfg), _vp, _vp, _vp, _vp, _vp]),
+    "pn_sizeof_augment_item": (_sz, []),
+    "pn_augment_resize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _f, _f, _vp]),
     "pn_train_set_precision": (_i, [_vp, _i]),
     "pn_train_ws_keep": (_i, [_vp, _i]),
     "pn_train_pack_cache": (_i, [_vp, _i]),
@@ -204,6 +213,8 @@ def lib():
         raise PopnetError("pn_pose_wire layout mismatch: C %d vs numpy %d" % (handle.pn_sizeof_pose_wire(), POSE_WIRE_DTYPE.itemsize))
     if handle.pn_sizeof_yolo_frame() != YOLO_FRAME_DTYPE.itemsize:
         raise PopnetError("pn_yolo_frame layout mismatch")
+    if handle.pn_sizeof_augment_item() != C.sizeof(AugmentItem):
+        raise PopnetError("pn_augment_item layout mismatch: C %d vs ctypes %d" % (handle.pn_sizeof_augment_item(), C.sizeof(AugmentItem)))
     _lib = handle
     return _lib
 

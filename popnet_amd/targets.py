@@ -4,10 +4,14 @@ Host-side mirror of the reference's training dataset item, batched and on the de
   KDH3D_Keypoints.__getitem__   third_party_methods/lib/datasets/datasets_kdh3d_rtpose_mpaug.py:223-286 (CR line endings)
   get_ground_truth              ...:318-401 (putGaussianMaps heatmap.py:20-36, putVecMaps paf.py:18-69, putJointZ posemap.py:83-106)
   Compose([Cvt2ndarray, Resize]) third_party_methods/lib/datasets/data_augmentation_2d3d.py:70-89,497-522
-The arithmetic lives in csrc/targets.hip (pn_compose_depth, pn_rasterize_targets) and csrc/api.hip (pn_preprocess); this
-module only owns tensors and the call order.  There is no CPU fallback: inputs must be device tensors.
+  Compose([Cvt2ndarray, Rotate, RenderDepth, Crop, Resize])   ...:411-448,283-350,94-128 -- the random training transform
+The arithmetic lives in csrc/targets.hip (pn_compose_depth, pn_rasterize_targets), csrc/augment.hip (pn_augment_resize) and
+csrc/api.hip (pn_preprocess); this module only owns tensors and the call order.  There is no CPU fallback: images must be device
+tensors.  The random transform's LABEL half (15 joints per person) and its integer geometry are host work, in numpy, mirroring the
+reference operation for operation so that every dtype rounds the same way.
 """
 import ctypes as C
+import math
 import random
 
 import numpy as np
@@ -136,10 +140,187 @@ def _resize(frames, S, depth_max):
     return out[:, 0]
 
 
-def mpaug_batch(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, input_size=224, stride=8, z_radius=2):
-    """A batch of training items as KDH3D_Keypoints.__getitem__ builds them for given source choices (evaluation transform
-    Compose([Cvt2ndarray, Resize])).  kp2d_org [B,P,15,2] float32 in ORIGINAL pixel coordinates, kp3d [B,P,15,3] float64 metres.
-    Returns image [B,1,S,S] (normalised), heat, paf, z, fg."""
+def augmentation(rot, a, crops, H, W, cx, cy, input_size=224):
+    """One item's random transform from explicit values: rot (degrees, Rotate), a (the ratio RenderDepth draws), crops = (left, right,
+    top, bottom) fractions (Crop), for H x W frames with the intrinsics' principal point (cx, cy).  -> dict with the values, the
+    forward rotation matrix (labels), the inverted one (image, for the kernel) and every integer the chain derives:
+      render_corner   (new_xmin, new_ymin, new_xmax, new_ymax) of RenderDepth, int() truncated;   render_a  a recomputed from them
+      render_x/_y/_w/_h   the render image in the rotated frame (slice with numpy's clamping for a <= 1, zero image with the frame
+                      pasted at (dy, dx) otherwise);   crop_bounds   (xmin, ymin, xmax, ymax) of Crop;   crop_x0.. the clamped slice
+      src_w, src_h    the size Resize sees.
+    Nothing here touches the GPU.  A geometry the reference itself cannot run (the paste does not fit, an empty image) raises."""
+    rot, a_drawn, crops = float(rot), float(a), tuple(float(c) for c in crops)
+    cx, cy, H, W = float(cx), float(cy), int(H), int(W)
+    # getRotationMatrix2D: the centre is a Point2f; alpha, beta in double.  This and the inversion below are the product's own copy of
+    # what tests/cv2_warp_reference.py restates; tests/test_augment_reference.py compares inv_mat with that restatement, and the
+    # exact-rational derivation of tests/test_cv2_warp_kat.py pins the restatement -- through that equality it guards this copy too.
+    fcx, fcy = float(np.float32(cx)), float(np.float32(cy))
+    ang = rot * (math.pi / 180)
+    alpha, beta = math.cos(ang) * 1.0, math.sin(ang) * 1.0
+    fwd = np.array([[alpha, beta, (1 - alpha) * fcx - beta * fcy], [-beta, alpha, beta * fcx + (1 - alpha) * fcy]], dtype=np.float64)
+    # warpAffine's inversion, in its operation order (imgwarp.cpp)
+    m = [float(v) for v in fwd.reshape(6)]
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0] = A11
+    m[1] *= -D
+    m[3] *= -D
+    m[4] = A22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    # RenderDepth (data_augmentation_2d3d.py:303-335)
+    xmin, ymin, xmax, ymax = float(0), float(0), float(W), float(H)
+    new_xmin, new_ymin = int(a_drawn * (xmin - cx) + cx), int(a_drawn * (ymin - cy) + cy)
+    new_xmax, new_ymax = int(a_drawn * (xmax - cx) + cx), int(a_drawn * (ymax - cy) + cy)
+    ax, ay = (new_xmin - cx) / (xmin - cx), (new_ymin - cy) / (ymin - cy)
+    a = (ax + ay) / 2
+    if a <= 1:
+        y0, y1, _ = slice(new_ymin, new_ymax).indices(H)
+        x0, x1, _ = slice(new_xmin, new_xmax).indices(W)
+        render_x, render_y, render_w, render_h = x0, y0, max(x1 - x0, 0), max(y1 - y0, 0)
+    else:
+        dx, dy = int(xmin - new_xmin), int(ymin - new_ymin)
+        render_w, render_h = new_xmax - new_xmin + 1, new_ymax - new_ymin + 1
+        fits = render_w > 0 and render_h > 0
+        if fits:
+            y0, y1, _ = slice(dy, dy + H).indices(render_h)
+            x0, x1, _ = slice(dx, dx + W).indices(render_w)
+            fits = (y0, y1 - y0, x0, x1 - x0) == (dy, H, dx, W)
+        if not fits:
+            raise _lib.PopnetError("augmentation: RenderDepth with a = %r cannot paste the %dx%d frame at (%d, %d) into its %dx%d image "
+                                   "(the reference raises here too)" % (a_drawn, W, H, dx, dy, render_w, render_h))
+        render_x, render_y = -dx, -dy
+    if render_w < 1 or render_h < 1:
+        raise _lib.PopnetError("augmentation: RenderDepth with a = %r leaves an empty image" % a_drawn)
+    # Crop (:102-118) on the render image
+    c_xmin, c_ymin = int(min(crops[0] * render_w, render_w)), int(min(crops[2] * render_h, render_h))
+    c_xmax, c_ymax = int(max(render_w - 1 - crops[1] * render_w, 0)), int(max(render_h - 1 - crops[3] * render_h, 0))
+    cy0, cy1, _ = slice(c_ymin, c_ymax).indices(render_h)
+    cx0, cx1, _ = slice(c_xmin, c_xmax).indices(render_w)
+    if cx1 - cx0 < 1 or cy1 - cy0 < 1:
+        raise _lib.PopnetError("augmentation: Crop %r leaves an empty image" % (crops,))
+    return dict(rot=rot, a=a_drawn, crops=crops, cx=cx, cy=cy, H=H, W=W, input_size=int(input_size), rot_mat=fwd, inv_mat=tuple(m),
+                render_corner=(new_xmin, new_ymin, new_xmax, new_ymax), render_a=a, render_x=render_x, render_y=render_y,
+                render_w=render_w, render_h=render_h, crop_bounds=(c_xmin, c_ymin, c_xmax, c_ymax), crop_x0=cx0, crop_y0=cy0,
+                crop_x1=cx1, crop_y1=cy1, src_w=cx1 - cx0, src_h=cy1 - cy0)
+
+
+def draw_augmentation(H, W, cx, cy, min_ratio=0.7, max_ratio=1.7, max_crop=0.1, input_size=224):
+    """Draws one item's transform from Python's `random` in the reference's order -- Rotate: uniform(-10, 10); RenderDepth:
+    uniform(min_ratio, max_ratio); Crop: four uniform(0, max_crop) for left, right, top, bottom -- and derives its geometry."""
+    rot = random.uniform(-10, 10)
+    a = random.uniform(min_ratio, max_ratio)
+    crops = tuple(random.uniform(0, max_crop) for _ in range(4))
+    return augmentation(rot, a, crops, H, W, cx, cy, input_size)
+
+
+class AugmentationBatch:
+    """The transforms of a batch's items (dicts of augmentation()): the pn_augment_item records for the image kernel and the host
+    transform of the labels."""
+
+    def __init__(self, items):
+        self.items = list(items)
+        if not self.items:
+            raise _lib.PopnetError("AugmentationBatch: no items")
+        self.H, self.W, self.input_size = self.items[0]["H"], self.items[0]["W"], self.items[0]["input_size"]
+        if any((it["H"], it["W"], it["input_size"]) != (self.H, self.W, self.input_size) for it in self.items):
+            raise _lib.PopnetError("AugmentationBatch: the items of a batch share the frame size and the input size")
+        self.records = (_lib.AugmentItem * len(self.items))()
+        for r, it in zip(self.records, self.items):
+            r.m[:] = it["inv_mat"]
+            r.scale = float(np.float32(it["render_a"]))
+            for k in ("render_x", "render_y", "render_w", "render_h", "crop_x0", "crop_y0", "crop_x1", "crop_y1", "src_w", "src_h"):
+                setattr(r, k, it[k])
+
+    def __len__(self):
+        return len(self.items)
+
+    def transform_labels(self, kp2d_org, kp3d, boxes=None):
+        """kp2d_org [B,P,15,2] float32 (original pixels), kp3d [B,P,15,3] float64, boxes [B,P,4] float64 (original pixels) or None, as
+        host arrays -> (kp2d [B,P,15,2] float32 in network-input pixels, kp_z [B,P,15] float64, boxes [B,P,4] float64 or None).
+        Rotate: homographic_transform of the float32 joints by the float64 3x3 (lib/utils/common.py:96-104), assigned back to float32;
+        boxes are NOT rotated, as in the reference.  RenderDepth: minus its corner, z times the recomputed a (float64).  Crop: minus its
+        corner.  Resize: times S / w, S / h of the item (float32 joints times a Python float; boxes in float64).  Padding slots are
+        transformed like persons; nobody reads them."""
+        kp = np.array(kp2d_org, dtype=np.float32)
+        kz = np.array(np.asarray(kp3d)[..., 2], dtype=np.float64)
+        bx = None if boxes is None else np.array(boxes, dtype=np.float64)
+        if kp.shape[0] != len(self.items):
+            raise _lib.PopnetError("AugmentationBatch: %d items for a batch of %d" % (len(self.items), kp.shape[0]))
+        for b, it in enumerate(self.items):
+            M = np.vstack([it["rot_mat"], [0, 0, 1]])
+            ox, oy = it["render_corner"][0], it["render_corner"][1]
+            qx, qy = it["crop_bounds"][0], it["crop_bounds"][1]
+            wr, hr = float(it["input_size"]) / it["src_w"], float(it["input_size"]) / it["src_h"]
+            for p in range(kp.shape[1]):
+                j = kp[b, p]
+                x, y = j[:, 0], j[:, 1]
+                trans = np.matmul(M, np.vstack([x, y, np.ones_like(y)]))
+                j[:, 0], j[:, 1] = trans[0, :] / trans[2, :], trans[1, :] / trans[2, :]
+                j[:, 0] -= ox
+                j[:, 1] -= oy
+                j[:, 0] -= qx
+                j[:, 1] -= qy
+                j[:, 0] *= wr
+                j[:, 1] *= hr
+            kz[b] *= it["render_a"]
+            if bx is not None:
+                bx[b, :, 0:4:2] -= ox
+                bx[b, :, 1:4:2] -= oy
+                bx[b, :, 0:4:2] -= qx
+                bx[b, :, 1:4:2] -= qy
+                bx[b, :, 0:4:2] = bx[b, :, 0:4:2] * wr
+                bx[b, :, 1:4:2] = bx[b, :, 1:4:2] * hr
+        return kp, kz, bx
+
+
+def augment_resize(frames, aug, input_size=224, depth_max=DEPTH_MAX, mean=0.0, std=1.0):
+    """Rotate -> RenderDepth -> Crop -> Resize -> clamp to [0, depth_max] -> (x - mean) / std of composed frames [B,H,W] float32 (device)
+    with the per-item transforms of `aug` (AugmentationBatch): ONE launch for the batch (pn_augment_resize).  -> [B,1,S,S] float32.
+    An item that Resize would decimate by exactly 2 in both axes is refused with a PopnetError naming it: cv2.resize(INTER_LINEAR)
+    switches to INTER_AREA there, which is not built (as in pn_preprocess).  With the MP-3DHP geometry (480 x 512 frames, S = 224,
+    a in [0.7, 1.7], crops up to 0.1) this cannot occur: a crop that is 448 wide needs a >= 0.93, which leaves at least 477 rows."""
+    _lib.require_cuda_tensor(frames, "frames")
+    if frames.dtype != torch.float32 or frames.dim() != 3:
+        raise _lib.PopnetError("augment_resize: frames must be [B,H,W] float32")
+    B, H, W = frames.shape
+    if len(aug) != B or (aug.H, aug.W) != (H, W) or aug.input_size != int(input_size):
+        raise _lib.PopnetError("augment_resize: the augmentation was drawn for %d items of %dx%d -> %d, the call has %d of %dx%d -> %d"
+                               % (len(aug), aug.W, aug.H, aug.input_size, B, W, H, int(input_size)))
+    frames = frames.contiguous()
+    items = torch.empty(C.sizeof(aug.records), dtype=torch.uint8, device=frames.device)      # the call uploads the records it has checked
+    out = torch.empty((B, 1, int(input_size), int(input_size)), dtype=torch.float32, device=frames.device)
+    ctx = _ctx(frames.device)
+    ctx.check(_lib.lib().pn_augment_resize(ctx.handle, C.c_void_p(frames.data_ptr()), C.cast(aug.records, C.c_void_p), C.c_void_p(items.data_ptr()),
+                                           B, H, W, C.c_void_p(out.data_ptr()), int(input_size), float(depth_max), float(mean), float(std),
+                                           _lib.current_stream_ptr(frames.device)), "pn_augment_resize")
+    return out
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def mpaug_batch(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, input_size=224, stride=8, z_radius=2, aug=None):
+    """A batch of training items as KDH3D_Keypoints.__getitem__ builds them for given source choices.  kp2d_org [B,P,15,2] float32 in
+    ORIGINAL pixel coordinates, kp3d [B,P,15,3] float64 metres.  Returns image [B,1,S,S] (normalised), heat, paf, z, fg.
+    aug=None: the evaluation transform Compose([Cvt2ndarray, Resize]); the labels are device tensors.
+    aug (AugmentationBatch): the random training transform Compose([Cvt2ndarray, Rotate, RenderDepth, Crop, Resize]) -- the image
+    through one pn_augment_resize launch, the labels through the host transform, the rest as without it.  Hand kp2d_org / kp3d over
+    as HOST arrays then (MPAugTrainSet.batch(augment=True) returns them so).  Device tensors are accepted, but reading them back is
+    a device synchronisation in the middle of the batch."""
+    if aug is not None:
+        image = compose_depth(fg_depth, fg_mask, n_src, bg)
+        img224 = augment_resize(image, aug, input_size, DEPTH_MAX)[:, 0]
+        depth_resize = _resize(img224, int(input_size / stride), 3.0e38)
+        kp, kz, _ = aug.transform_labels(_host(kp2d_org), _host(kp3d))
+        dev = image.device
+        heat, paf, z, fg = rasterize_targets(torch.from_numpy(kp).to(dev), torch.from_numpy(kz).to(dev), n_persons.to(dev), depth_resize,
+                                             input_size, stride, z_radius)
+        x = ((img224 - float(DEPTH_MEAN)) / float(DEPTH_STD)).unsqueeze(1)
+        return x, heat, paf, z, fg
     _lib.require_cuda_tensor(kp2d_org, "kp2d_org")
     _lib.require_cuda_tensor(kp3d, "kp3d")
     image = compose_depth(fg_depth, fg_mask, n_src, bg)
@@ -154,10 +335,22 @@ def mpaug_batch(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, input_s
     return x, heat, paf, z, fg
 
 
-def mpaug_batch_yolo(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, boxes, pose_weight, input_size=224):
+def mpaug_batch_yolo(fg_depth, fg_mask, n_src, bg, kp2d_org, kp3d, n_persons, boxes, pose_weight, input_size=224, aug=None):
     """mpaug_batch for the YoloPoseNet trainer (datasets_kdh3d_mpaug.py:245-340 (CR), evaluation transform): the same composed, resized and
     normalised image, and the prior targets of its persons.  boxes [B,P,4] float64 already scaled to input_size (MPAugTrainSet.batch(...,
-    with_boxes=True)).  Returns image [B,1,S,S], prior_map, prior_mask_conf, prior_mask_coord, prior_weight_map."""
+    with_boxes=True)).  Returns image [B,1,S,S], prior_map, prior_mask_conf, prior_mask_coord, prior_weight_map.
+    aug (AugmentationBatch): the random training transform, as in mpaug_batch (host arrays for the labels; device tensors force a
+    synchronisation); boxes are then in ORIGINAL pixels (float64, as MPAugTrainSet.batch(with_boxes=True, augment=True) returns
+    them) and take the offsets and scales of the joints, but not the rotation."""
+    if aug is not None:
+        image = compose_depth(fg_depth, fg_mask, n_src, bg)
+        img = augment_resize(image, aug, input_size, DEPTH_MAX)[:, 0]
+        kp, kz, bx = aug.transform_labels(_host(kp2d_org), _host(kp3d), _host(boxes))
+        dev = image.device
+        prior = prior_targets(torch.from_numpy(bx).to(dev), torch.from_numpy(kp).to(dev), torch.from_numpy(kz).to(dev), pose_weight.to(dev),
+                              n_persons.to(dev), input_size)
+        x = ((img - float(DEPTH_MEAN)) / float(DEPTH_STD)).unsqueeze(1)
+        return (x,) + prior
     _lib.require_cuda_tensor(kp2d_org, "kp2d_org")
     _lib.require_cuda_tensor(kp3d, "kp3d")
     image = compose_depth(fg_depth, fg_mask, n_src, bg)
@@ -180,7 +373,8 @@ class MPAugSampler:
     contribute, each joins with probability 0.8 (`uniform(0, 1) > 0.8: continue`), set ii contributes its frame
     index % len(ids[ii]); when nobody joined one random set is taken; the background is index % n_backgrounds.  Draws from
     Python's `random` in the reference's order (randint, then one uniform per candidate, then randint), so that a seeded run
-    picks the same sources as the reference does."""
+    picks the same sources as the reference does.  With augment=True each item's six augmentation draws (draw_augmentation) follow
+    that item's source draws, because the reference interleaves them inside __getitem__."""
 
     def __init__(self, set_sizes, n_backgrounds, aug_mods=AUG_MODS, p_join=0.8):
         self.set_sizes, self.n_backgrounds, self.aug_mods, self.p_join = list(set_sizes), int(n_backgrounds), [list(m) for m in aug_mods], p_join
@@ -199,9 +393,19 @@ class MPAugSampler:
             src.append((ii, index % self.set_sizes[ii]))
         return src, index % self.n_backgrounds
 
-    def batch(self, indices):
-        """-> (src [B,S,2] int64 (set, frame) padded with -1, n_src [B] int32, bg [B] int64) for the caller's gather."""
-        picks = [self.sources(i) for i in indices]
+    def batch(self, indices, augment=False, **aug_args):
+        """-> (src [B,S,2] int64 (set, frame) padded with -1, n_src [B] int32, bg [B] int64) for the caller's gather.
+        augment=True: aug_args are draw_augmentation's (H, W, cx, cy, ...), and the AugmentationBatch of the items comes fourth."""
+        picks, items = [], []
+        for i in indices:
+            picks.append(self.sources(i))
+            if augment:
+                items.append(draw_augmentation(**aug_args))
+        if augment:
+            return self._arrays(picks) + (AugmentationBatch(items),)
+        return self._arrays(picks)
+
+    def _arrays(self, picks):
         src = np.full((len(picks), self.max_sources, 2), -1, dtype=np.int64)
         for r, (s, _) in enumerate(picks):
             src[r, :len(s)] = s
@@ -232,15 +436,47 @@ class MPAugTrainSet:
             random.shuffle(self.bg)
         self.sampler = MPAugSampler([len(i) for i in self.ids], len(self.bg), aug_mods=[m for m in AUG_MODS if max(m) < len(self.ids)] or [[0]])
         self.max_sources = self.sampler.max_sources
+        self._hw = None
 
     def __len__(self):
         return max(len(i) for i in self.ids)              # dataset_len (:181)
 
-    def batch(self, indices, with_boxes=False, input_size=224):
+    def _principal_point(self):
+        """cx, cy of the annotation files' `intrinsics` (Rotate and RenderDepth turn and scale about it); every file must name the same."""
+        pts = set()
+        for a in self.annos:
+            intr = a.get("intrinsics")
+            if not intr or "cx" not in intr or "cy" not in intr:
+                raise KeyError("MPAugTrainSet.batch(augment=True): every annotation file needs 'intrinsics' with 'cx' and 'cy' (Rotate and RenderDepth turn and scale about the principal point)")
+            pts.add((float(intr["cx"]), float(intr["cy"])))
+        if len(pts) != 1:
+            raise _lib.PopnetError("MPAugTrainSet.batch(augment=True): the annotation files disagree on the principal point: %s" % sorted(pts))
+        return pts.pop()
+
+    def _frame_size(self):
+        """(H, W) of the dataset's frames, needed before an item's transform can be drawn: read once from the first background's header
+        and kept; batch() checks every batch against it."""
+        if self._hw is None:
+            import os
+            self._hw = tuple(np.load(os.path.join(self.bg_dir, self.bg[0]["file_name"]), mmap_mode="r").shape)
+        return self._hw
+
+    def batch(self, indices, with_boxes=False, input_size=224, augment=False, max_aug_ratio=1.7):
         """with_boxes: also return boxes [B,P,4] float64 (ann['bbox'] scaled by Resize to input_size, in float64 like
-        data_augmentation_2d3d.py:497-522) and pose_weight [B,P] float64 (ann['pose_weight']) -- the YoloPoseNet trainer's extra inputs."""
+        data_augmentation_2d3d.py:497-522) and pose_weight [B,P] float64 (ann['pose_weight']) -- the YoloPoseNet trainer's extra inputs.
+        augment: draw the random training transform of every item (Rotate / RenderDepth(max_ratio=max_aug_ratio) / Crop about the
+        `intrinsics` cx, cy of the first annotation file, interleaved with the source draws like the reference's __getitem__) and
+        append the batch's AugmentationBatch as the LAST element, for mpaug_batch(..., aug=) / mpaug_batch_yolo(..., aug=).  The
+        labels then stay on the host (kp2d_org, kp3d and boxes as numpy arrays: their transform is host work) and boxes stay in
+        ORIGINAL pixels, because the transform's offsets come before its scale."""
         import os
-        src, n_src, bg_id = self.sampler.batch(indices)
+        if augment:
+            cx, cy = self._principal_point()
+            H0, W0 = self._frame_size()
+            src, n_src, bg_id, aug = self.sampler.batch(indices, augment=True, H=H0, W=W0, cx=cx, cy=cy, max_ratio=float(max_aug_ratio),
+                                                        input_size=input_size)
+        else:
+            src, n_src, bg_id = self.sampler.batch(indices)
         B, S = len(indices), self.max_sources
         frames, masks, bgs, persons = [], [], [], []
         for b in range(B):
@@ -272,9 +508,11 @@ class MPAugTrainSet:
                 k3[b, p] = np.asarray(ann["3d_joints"], dtype=np.float64)
         dev = self.device
         t = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)      # noqa: E731
-        out = (t(fd), t(fm), t(n_src), t(np.stack(bgs).astype(dt)), t(k2), t(k3), t(npers))
+        if augment and (H, W) != (aug.H, aug.W):
+            raise _lib.PopnetError("MPAugTrainSet.batch: frames of %dx%d after a background of %dx%d" % (W, H, aug.W, aug.H))
+        out = (t(fd), t(fm), t(n_src), t(np.stack(bgs).astype(dt)), k2 if augment else t(k2), k3 if augment else t(k3), t(npers))
         if not with_boxes:
-            return out
+            return out + ((aug,) if augment else ())
         boxes = np.zeros((B, P, 4), dtype=np.float64)
         pw = np.zeros((B, P), dtype=np.float64)
         for b in range(B):
@@ -284,7 +522,10 @@ class MPAugTrainSet:
                     raise KeyError("MPAugTrainSet.batch(with_boxes=True): an annotation lacks %s -- the YoloPoseNet trainer needs "
                                    "'bbox' ([x0, y0, x1, y1], original pixels) and 'pose_weight' on every person" % " and ".join(repr(k) for k in missing))
                 bb = np.asarray(ann["bbox"], dtype=np.float64)
-                boxes[b, p, 0:4:2] = bb[0:4:2] * (float(input_size) / W)       # Resize: x by the width ratio, y by the height ratio (float64)
-                boxes[b, p, 1:4:2] = bb[1:4:2] * (float(input_size) / H)
+                if augment:
+                    boxes[b, p] = bb
+                else:
+                    boxes[b, p, 0:4:2] = bb[0:4:2] * (float(input_size) / W)   # Resize: x by the width ratio, y by the height ratio (float64)
+                    boxes[b, p, 1:4:2] = bb[1:4:2] * (float(input_size) / H)
                 pw[b, p] = float(ann["pose_weight"])
-        return out + (t(boxes), t(pw))
+        return out + ((boxes, t(pw), aug) if augment else (t(boxes), t(pw)))

@@ -9,8 +9,11 @@ expect (:300-340).  Data parallel over the GPUs of one node: `--gpus N` (per-rep
     python scripts/train_mpaug.py --train-annotations labels_train_*.json --val-annotations labels_test_*.json \
         --image-dir depth_maps --bg-file labels_bg.json --bg-dir bg_maps --seg-dir seg_maps --output-dir out [--epochs 200]
 
-Not reproduced: the random augmentation chain (Rotate / RenderDepth / Crop of data_augmentation_2d3d.py) -- items go through
-the evaluation transform (Cvt2ndarray + Resize), which is what popnet_amd.targets mirrors bit for bit.
+`--augment 1` trains with the reference's random augmentation chain Compose([Cvt2ndarray, Rotate(cx, cy), RenderDepth(cx, cy,
+max_ratio=--max-aug-ratio), Crop, Resize]) (data_augmentation_2d3d.py; :298-305 of the reference's trainer): the image half as one
+more launch per batch (pn_augment_resize), the label half on the host, cx / cy from the annotation file's `intrinsics`.  The default
+`--augment 0` sends the items through the evaluation transform (Cvt2ndarray + Resize) as before.  Training batches only: validation
+never augments.  popnet_amd.targets mirrors both transforms bit for bit.
 """
 import argparse
 import os
@@ -77,6 +80,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--weight", default=None, help="start from this checkpoint instead of the module's initial state")
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--augment", type=int, choices=(0, 1), default=0, help="1: random Rotate / RenderDepth / Crop on the training batches (the reference's training transform)")
+    ap.add_argument("--max-aug-ratio", type=float, default=1.7, help="RenderDepth's max_ratio (the reference's --max_aug_ratio)")
     args = ap.parse_args(argv)
 
     import popnet_amd  # noqa: F401
@@ -120,7 +125,11 @@ def main(argv=None):
         t0, run = time.time(), 0.0
         for i in range(n_batches):
             mine = order[i * args.batch_size + rank * per_rank: i * args.batch_size + (rank + 1) * per_rank]
-            batch = [t.contiguous() for t in targets.mpaug_batch(*train_set.batch(mine), input_size=args.square_edge, z_radius=args.z_radius)]
+            if args.augment:
+                *parts, aug = train_set.batch(mine, input_size=args.square_edge, augment=True, max_aug_ratio=args.max_aug_ratio)
+            else:
+                parts, aug = train_set.batch(mine), None
+            batch = [t.contiguous() for t in targets.mpaug_batch(*parts, input_size=args.square_edge, z_radius=args.z_radius, aug=aug)]
             if eng.steps >= 1 and captured_lr != eng.lr:          # the step as one hipGraph (re-captured when the plateau rule moved lr)
                 eng.capture(*batch, warmup_steps=0)
                 captured_lr = eng.lr

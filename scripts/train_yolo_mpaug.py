@@ -9,7 +9,10 @@ expect.  Built like scripts/train_mpaug.py (and reuses its Plateau).  The annota
     python scripts/train_yolo_mpaug.py --train-annotations labels_train_*.json --val-annotations labels_test_*.json \
         --image-dir depth_maps --bg-file labels_bg.json --bg-dir bg_maps --seg-dir seg_maps --output-dir out [--epochs 200]
 
-Not reproduced: the random augmentation chain (as in train_mpaug.py); hipGraph capture of the step; several GPUs.
+`--augment 1` / `--max-aug-ratio` as in train_mpaug.py: the reference's random Rotate / RenderDepth / Crop on the training batches
+(:290-297 of the reference's trainer), boxes shifted and scaled with the joints but not rotated; validation never augments.
+
+Not reproduced: hipGraph capture of the step; several GPUs.
 """
 import argparse
 import os
@@ -61,6 +64,8 @@ def main(argv=None):
     ap.add_argument("--print-freq", type=int, default=20)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--weight", default=None, help="start from this checkpoint instead of the module's initial state")
+    ap.add_argument("--augment", type=int, choices=(0, 1), default=0, help="1: random Rotate / RenderDepth / Crop on the training batches (the reference's training transform)")
+    ap.add_argument("--max-aug-ratio", type=float, default=1.7, help="RenderDepth's max_ratio (the reference's --max_aug_ratio)")
     args = ap.parse_args(argv)
 
     import popnet_amd  # noqa: F401
@@ -83,8 +88,12 @@ def main(argv=None):
     module.precision = "fp32"
     rw = bool(args.rarity_weight)
 
-    def make(ds, idx):
-        return [t.contiguous() for t in targets.mpaug_batch_yolo(*ds.batch(idx, with_boxes=True, input_size=args.square_edge), input_size=args.square_edge)]
+    def make(ds, idx, augment=False):
+        if augment:
+            *parts, aug = ds.batch(idx, with_boxes=True, input_size=args.square_edge, augment=True, max_aug_ratio=args.max_aug_ratio)
+        else:
+            parts, aug = ds.batch(idx, with_boxes=True, input_size=args.square_edge), None
+        return [t.contiguous() for t in targets.mpaug_batch_yolo(*parts, input_size=args.square_edge, aug=aug)]
 
     plateau, best = Plateau(), float("inf")
     os.makedirs(args.output_dir, exist_ok=True)
@@ -94,7 +103,7 @@ def main(argv=None):
         n_batches = len(order) // args.batch_size     # drop_last=True
         t0, run = time.time(), 0.0
         for i in range(n_batches):
-            img, prior, conf, coord, weight = make(train_set, order[i * args.batch_size:(i + 1) * args.batch_size])
+            img, prior, conf, coord, weight = make(train_set, order[i * args.batch_size:(i + 1) * args.batch_size], augment=bool(args.augment))
             terms = eng.step(img, prior, conf, coord, weight if rw else None)
             if i % args.print_freq == 0:
                 tl = terms.cpu().tolist()
