@@ -387,6 +387,17 @@ int pn_slice_copy(pn_ctx *ctx, const float *src_dev, int src_ld, float *dst_dev,
                   void *hip_stream);
 int pn_sgd_nesterov(pn_ctx *ctx, float *param_dev, const float *grad_dev, float *momentum_buf_dev, size_t n, float lr,
                     float momentum, float weight_decay, int first_step, float grad_scale, void *hip_stream);
+/* Diagnostics (tests): which kernel a convolution primitive would launch for a shape under the context's current precision
+ * (pn_train_set_precision) and kernel switches, as JSON: "kernel" (the label, e.g. tconv3_tile_x3w_kernel, tconv_wgrad_kernel<1>), "pack"
+ * (the weight pack kernel the call runs or reads from the cache), the tile geometry "TW", "R", "tiles_x", "tiles_y" (0 for the generic
+ * kernels), "grid"; for PN_PLAN_WGRAD also "slices", "per_slice" tiles or pixels ("per_slice_unit") and "t_slices", the slices of the
+ * bias-gradient reduction.  It calls the very functions the launches decide with and launches nothing: a context without a device will
+ * do (so does pn_train_set_precision).  PN_PLAN_DGRAD ignores stride.  PN_ERR_INVALID for arguments the entry itself refuses or when cap
+ * is too small.  pn_train_reduce_slices: the slices of pn_bn_train_forward / _backward's per-channel reductions (negative: bad arguments). */
+enum { PN_PLAN_FORWARD = 0, PN_PLAN_DGRAD = 1, PN_PLAN_DGRAD_STRIDED = 2, PN_PLAN_WGRAD = 3 };
+int pn_train_conv_plan_info(pn_ctx *ctx, int which, int N, int Cin, int H, int W, int Cout, int ks, int stride, int pad, char *out,
+                            size_t cap);
+int pn_train_reduce_slices(pn_ctx *ctx, int N, int C, int HW);
 
 /* ---- YoloPoseNet training primitives (csrc/train_yolo.hip) ------------------------------------------------------------------
  * What YoloPoseNet's train-mode forward / loss / backward needs beyond the rtpose primitives above; fp32 NCHW, asynchronous on the

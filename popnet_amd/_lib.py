@@ -23,6 +23,7 @@ PN_MAX_PEAKS_PER_JOINT = 32
 PN_MAX_PEAKS = PN_NUM_JOINTS * PN_MAX_PEAKS_PER_JOINT
 PN_MAX_PERSONS = 32
 PN_YOLO_MAX_DET = 64
+PN_PLAN_FORWARD, PN_PLAN_DGRAD, PN_PLAN_DGRAD_STRIDED, PN_PLAN_WGRAD = 0, 1, 2, 3
 PN_FRAME_OVERFLOW_PEAKS, PN_FRAME_OVERFLOW_PERSONS = 1, 2
 
 
@@ -146,6 +147,8 @@ _SIGNATURES = {
     "pn_head_backward": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp]),
     "pn_slice_copy": (_i, [_vp, _vp, _i, _vp] + [_i] * 5 + [_vp]),
     "pn_sgd_nesterov": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, _f, _f, _f, _i, _f, _vp]),
+    "pn_train_conv_plan_info": (_i, [_vp] + [_i] * 9 + [C.c_char_p, _sz]),
+    "pn_train_reduce_slices": (_i, [_vp, _i, _i, _i]),
     "pn_conv2d_dgrad_strided": (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "pn_maxpool_forward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "pn_maxpool_backward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),

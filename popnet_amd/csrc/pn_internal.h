@@ -71,6 +71,7 @@ PnSwitches pn_read_switches();
 int pn_set_error(pn_ctx *ctx, int code, const char *fmt, ...);
 void pn_parse_big_free(pn_ctx *ctx);     // parse_paf.hip
 int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)
+const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned *grid_x, unsigned *grid_y);     // train_yolo.hip: kernel label and grid of pn_conv2d_dgrad_strided
 
 #define PN_HIP_CHECK(ctx, expr)                                                              \
     do {                                                                                     \

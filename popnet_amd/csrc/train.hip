@@ -10,6 +10,7 @@
 // Roofline: the three GEMM-shaped kernels are MFMA-bound (fp32-input matrix peak 157 TFLOP/s), everything else HBM-bound.
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include "pn_internal.h"
 
 typedef float t_f32x4 __attribute__((ext_vector_type(4)));
@@ -2281,6 +2282,141 @@ static int t_slices(long total, int C) {       // slices per channel so that the
     return (int)s;
 }
 
+// ---- dispatch decisions ------------------------------------------------------------------------------------------------
+// ONE function per entry decides which kernel a shape runs on and with what geometry; the launch code below and
+// pn_train_conv_plan_info (diagnostics, tests) both call it, so the description cannot drift from the launch.
+enum { TK_GENERIC = 0, TK_TILE, TK_TILE_X3, TK_TILE_X3W };                      // forward / data gradient
+enum { TKW_GENERIC = 0, TKW_TILE, TKW_X3, TKW_X3PP, TKW_X3V };                  // weight gradient
+
+struct TTilePlan {
+    int kernel;     // TK_*
+    TTile g;        // geometry of the chosen tile kernel (unset for TK_GENERIC)
+};
+
+// a 3x3 stride-1 convolution of K input channels to M output channels on an Ho x Wo map (the data gradient calls it with K = Cout, M = Cin)
+static TTilePlan t_plan_tile3(const pn_ctx *ctx, int N, int K, int M, int Ho, int Wo) {
+    TTilePlan p = TTilePlan();
+    p.kernel = TK_GENERIC;
+    if (K < 16 || !t_tile_geometry(Ho, Wo, 16, &p.g)) return p;
+    p.kernel = TK_TILE;
+    TTile gx;
+    if (ctx->train_x3 && K >= 32 && t_tile_geometry_x3(Ho, Wo, &gx)) {
+        p.kernel = TK_TILE_X3;
+        p.g = gx;
+        TTile gw2;
+        if (t_tile_geometry_x3w(Ho, Wo, N, M, pn_read_switches().train_x3_wide, &gw2)) {
+            p.kernel = TK_TILE_X3W;
+            p.g = gw2;
+        }
+    }
+    return p;
+}
+
+static TTilePlan t_plan_forward(const pn_ctx *ctx, int N, int Cin, int Cout, int Ho, int Wo, int ks, int stride, int pad) {
+    if (ks == 3 && stride == 1 && pad <= 2) return t_plan_tile3(ctx, N, Cin, Cout, Ho, Wo);
+    TTilePlan p = TTilePlan();
+    p.kernel = TK_GENERIC;
+    return p;
+}
+
+static TTilePlan t_plan_dgrad(const pn_ctx *ctx, int N, int Cin, int H, int W, int Cout, int ks) {
+    if (ks == 3) return t_plan_tile3(ctx, N, Cout, Cin, H, W);
+    TTilePlan p = TTilePlan();
+    p.kernel = TK_GENERIC;      // rotated weights (wflip_kernel), then pn_conv2d_forward's own plan
+    return p;
+}
+
+struct TWgradPlan {
+    int kernel;                 // TKW_*
+    TTile g;                    // fp32 tile kernel
+    TTileW gw;                  // x3 / x3pp (x3v: the same tiles, its own row layout in gv)
+    TTileW gv;
+    int ntiles, S, tps;         // fp32 tile kernel: tiles, slices, tiles per slice (S also sizes the partial-sum buffer of the split variants)
+    int nt, S2, tps2, S3, tps3; // split-bf16 variants: their own tile count; x3: S2 / tps2; x3pp, x3v: S3 / tps3
+    size_t setb;
+    int ppi, npieces;           // x3v
+    long slices, pps;           // generic kernel: slices of pps pixels
+    int csl;                    // slices of the bias-gradient reduction (t_slices)
+    int launch_slices() const { return kernel == TKW_GENERIC ? (int)slices : kernel == TKW_TILE ? S : kernel == TKW_X3 ? S2 : S3; }
+    long per_slice() const { return kernel == TKW_GENERIC ? pps : kernel == TKW_TILE ? tps : kernel == TKW_X3 ? tps2 : tps3; }
+};
+
+// c: the convolution with Ho, Wo, Kdim, P filled in
+static TWgradPlan t_plan_wgrad(const pn_ctx *ctx, const TConv &c, int ks) {
+    TWgradPlan p = TWgradPlan();
+    const int N = c.N, Cin = c.Cin, Cout = c.Cout;
+    const long P = c.P;
+    p.csl = t_slices(P, Cout);
+    if (ks == 3 && c.stride == 1 && c.pad <= 2 && Cin >= 16 && t_tile_geometry(c.Ho, c.Wo, 4, &p.g)) {
+        p.kernel = TKW_TILE;
+        const int ntiles = N * p.g.tiles_x * p.g.tiles_y, groups = ((Cin + 15) / 16) * ((Cout + 63) / 64);
+        int S = (512 + groups - 1) / groups;             // two blocks per CU: 512 fill the chip
+        if (S > ntiles) S = ntiles;
+        if (S < 1) S = 1;
+        const int tps = (ntiles + S - 1) / S;
+        S = (ntiles + tps - 1) / tps;
+        p.ntiles = ntiles; p.S = S; p.tps = tps;
+        // slice counts of the split-bf16 variants (their own tile grid)
+        const bool x3 = ctx->train_x3 && t_tile_geometry_wx3(c.Ho, c.Wo, &p.gw);
+        if (x3) {
+            p.kernel = TKW_X3;
+            const int nt = N * p.gw.tiles_x * p.gw.tiles_y;
+            const int groups2 = ((Cin + TXW_CI - 1) / TXW_CI) * ((Cout + 63) / 64);
+            int S2 = (512 + groups2 - 1) / groups2;             // two blocks per CU: 512 fill the chip; fewer slices = less partial-sum traffic
+            if (S2 > nt) S2 = nt;
+            if (S2 < 1) S2 = 1;
+            const int tps2 = (nt + S2 - 1) / S2;
+            S2 = (nt + tps2 - 1) / tps2;
+            p.setb = (size_t)2 * 64 * TXW_YP + (size_t)2 * TXW_CI * p.gw.CHB;
+            int S3 = (256 + groups2 - 1) / groups2;             // ping-pong variant: one 8-wave block per CU
+            if (S3 > nt / 2) S3 = nt / 2;                       // at least two tiles per block, or the second wave group has nothing to do
+            const bool pp = S3 >= 1 && 2 * p.setb <= 158 * 1024 && 2 * p.setb >= 73728;
+            int tps3 = 0;
+            if (pp) {
+                tps3 = (nt + S3 - 1) / S3;
+                S3 = (nt + tps3 - 1) / tps3;
+                p.kernel = TKW_X3PP;
+                // the same tiles and slices as x3pp (bit-identical partial sums), one round trip of staging per tile
+                if (!pn_read_switches().train_wgrad_novec && t_tile_geometry_wx3v(c, &p.gv, &p.ppi, &p.npieces) && p.gv.tiles_x == p.gw.tiles_x &&
+                    p.gv.tiles_y == p.gw.tiles_y && p.gv.R == p.gw.R && p.gv.TW == p.gw.TW)
+                    p.kernel = TKW_X3V;
+            }
+            p.nt = nt; p.S2 = S2; p.tps2 = tps2; p.S3 = S3; p.tps3 = tps3;
+        }
+        return p;
+    }
+    p.kernel = TKW_GENERIC;
+    const int tiles = ((c.Kdim + 63) / 64) * ((Cout + 63) / 64);
+    long slices = (1024 + tiles - 1) / tiles;
+    const long cap = (P + 1023) / 1024;
+    if (slices > cap) slices = cap;
+    if (slices < 1) slices = 1;
+    long pps = (P + slices - 1) / slices;
+    pps = (pps + TW_RC - 1) / TW_RC * TW_RC;
+    slices = (P + pps - 1) / pps;
+    p.slices = slices; p.pps = pps;
+    return p;
+}
+
+static const char *t_fwd_label(int kernel, int ks) {
+    switch (kernel) {
+    case TK_TILE: return "tconv3_tile_kernel";
+    case TK_TILE_X3: return "tconv3_tile_x3_kernel";
+    case TK_TILE_X3W: return "tconv3_tile_x3w_kernel";
+    default: return ks == 1 ? "tconv_fwd_kernel<1>" : ks == 3 ? "tconv_fwd_kernel<3>" : "tconv_fwd_kernel<7>";
+    }
+}
+
+static const char *t_wgrad_label(int kernel, int ks) {
+    switch (kernel) {
+    case TKW_TILE: return "tconv3_wgrad_tile_kernel";
+    case TKW_X3: return "tconv3_wgrad_x3_kernel";
+    case TKW_X3PP: return "tconv3_wgrad_x3pp_kernel";
+    case TKW_X3V: return "tconv3_wgrad_x3v_kernel";
+    default: return ks == 1 ? "tconv_wgrad_kernel<1>" : ks == 3 ? "tconv_wgrad_kernel<3>" : "tconv_wgrad_kernel<7>";
+    }
+}
+
 #define T_CTX_CHECK(name)                                                                                   \
     if (!ctx) return PN_ERR_INVALID;                                                                        \
     if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
@@ -2355,7 +2491,7 @@ int pn_train_pack_refresh(pn_ctx *ctx, void *hip_stream) {
 }
 
 int pn_train_set_precision(pn_ctx *ctx, int precision) {
-    T_CTX_CHECK("pn_train_set_precision")
+    if (!ctx) return PN_ERR_INVALID;          // a host-side switch: a context without a device takes it too (pn_train_conv_plan_info on a CPU-only host)
     if (precision != PN_PREC_F32 && precision != PN_PREC_BF16X3)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_train_set_precision: PN_PREC_F32 or PN_PREC_BF16X3");
     ctx->train_x3 = precision == PN_PREC_BF16X3;
@@ -2378,35 +2514,35 @@ int pn_conv2d_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, const
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_forward: size out of range");
     c.P = (int)P;
     hipStream_t s = (hipStream_t)hip_stream;
-    TTile g;
-    if (ks == 3 && stride == 1 && pad <= 2 && Cin >= 16 && t_tile_geometry(c.Ho, c.Wo, 16, &g)) {
+    const TTilePlan plan = t_plan_forward(ctx, N, Cin, Cout, c.Ho, c.Wo, ks, stride, pad);
+    if (plan.kernel != TK_GENERIC) {
         // second-generation 3x3 kernel: weights to [tap][ci][cout] in the scratch, then halo tiles
+        const TTile &g = plan.g;
         const size_t wn = (size_t)Cout * Cin * 9;
         const size_t wx = (size_t)((Cin + 31) / 32) * 9 * Cout * 32;        // elements per plane of the split-bf16 pack
         void *ws = nullptr;
         bool fresh = false;
         int rc;
         if ((rc = t_tile_lds_ok(ctx)) != PN_OK) return rc;
-        TTile gx;
-        if (ctx->train_x3 && Cin >= 32 && t_tile_geometry_x3(c.Ho, c.Wo, &gx)) {
+        const dim3 grid((unsigned)(N * g.tiles_x * g.tiles_y), (unsigned)((Cout + 63) / 64));
+        if (plan.kernel != TK_TILE) {
             if ((rc = t_pack_get(ctx, w_dev, Cout, Cin, 0, 1, 4 * wx, s, &ws, &fresh)) != PN_OK) return rc;
             if (!fresh) hipLaunchKernelGGL(wpack3_x3_kernel, dim3((unsigned)((wx + 255) / 256)), dim3(256), 0, s, w_dev, (__bf16 *)ws, Cout, Cin, 0);
-            TTile gw2;
-            if (t_tile_geometry_x3w(c.Ho, c.Wo, N, Cout, pn_read_switches().train_x3_wide, &gw2)) {
-                const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * gw2.HR * gw2.HC * TXW2_PITCH;
-                hipLaunchKernelGGL(tconv3_tile_x3w_kernel, dim3((unsigned)(N * gw2.tiles_x * gw2.tiles_y), (unsigned)((Cout + 63) / 64)), dim3(256), ldsw2, s, c, gw2, (const __bf16 *)ws);
+            if (plan.kernel == TK_TILE_X3W) {
+                const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * g.HR * g.HC * TXW2_PITCH;
+                hipLaunchKernelGGL(tconv3_tile_x3w_kernel, grid, dim3(256), ldsw2, s, c, g, (const __bf16 *)ws);
                 PN_HIP_CHECK(ctx, hipGetLastError());
                 return PN_OK;
             }
-            const size_t ldsx = (size_t)2 * TX_A_BYTES + (size_t)2 * gx.HR * gx.HC * TX_PITCH;
-            hipLaunchKernelGGL(tconv3_tile_x3_kernel, dim3((unsigned)(N * gx.tiles_x * gx.tiles_y), (unsigned)((Cout + 63) / 64)), dim3(256), ldsx, s, c, gx, (const __bf16 *)ws);
+            const size_t ldsx = (size_t)2 * TX_A_BYTES + (size_t)2 * g.HR * g.HC * TX_PITCH;
+            hipLaunchKernelGGL(tconv3_tile_x3_kernel, grid, dim3(256), ldsx, s, c, g, (const __bf16 *)ws);
             PN_HIP_CHECK(ctx, hipGetLastError());
             return PN_OK;
         }
         if ((rc = t_pack_get(ctx, w_dev, Cout, Cin, 0, 0, wn * sizeof(float), s, &ws, &fresh)) != PN_OK) return rc;
         if (!fresh) hipLaunchKernelGGL(wpack3_kernel, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, s, w_dev, (float *)ws, Cout, Cin, 0);
         const size_t lds = (size_t)(144 * TT_AP + 16 * g.CHP) * sizeof(float);
-        hipLaunchKernelGGL(tconv3_tile_kernel, dim3((unsigned)(N * g.tiles_x * g.tiles_y), (unsigned)((Cout + 63) / 64)), dim3(256), lds, s, c, g, (const float *)ws);
+        hipLaunchKernelGGL(tconv3_tile_kernel, grid, dim3(256), lds, s, c, g, (const float *)ws);
         PN_HIP_CHECK(ctx, hipGetLastError());
         return PN_OK;
     }
@@ -2430,34 +2566,34 @@ int pn_conv2d_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float 
     bool fresh = false;
     int rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    TTile g;
-    if (ks == 3 && Cout >= 16 && t_tile_geometry(H, W, 16, &g)) {
+    const TTilePlan plan = t_plan_dgrad(ctx, N, Cin, H, W, Cout, ks);
+    if (plan.kernel != TK_GENERIC) {
         // dX = conv(dY, rotated transposed weights, padding 2 - pad) on the halo-tile kernel: the packing IS the rotation
+        const TTile &g = plan.g;
         TConv c;
         c.x = dy_dev; c.w = nullptr; c.bias = nullptr; c.y = dx_dev;
         c.N = N; c.Cin = Cout; c.H = Ho; c.W = Wo; c.Cout = Cin; c.stride = 1; c.pad = 2 - pad; c.accumulate = accumulate;
         c.Ho = H; c.Wo = W; c.Kdim = Cout * 9; c.P = N * H * W;
         if ((rc = t_tile_lds_ok(ctx)) != PN_OK) return rc;
-        TTile gx;
-        if (ctx->train_x3 && Cout >= 32 && t_tile_geometry_x3(H, W, &gx)) {
+        const dim3 grid((unsigned)(N * g.tiles_x * g.tiles_y), (unsigned)((Cin + 63) / 64));
+        if (plan.kernel != TK_TILE) {
             if ((rc = t_pack_get(ctx, w_dev, Cin, Cout, 1, 1, 4 * wx, s, &ws, &fresh)) != PN_OK) return rc;
             if (!fresh) hipLaunchKernelGGL(wpack3_x3_kernel, dim3((unsigned)((wx + 255) / 256)), dim3(256), 0, s, w_dev, (__bf16 *)ws, Cin, Cout, 1);
-            TTile gw2;
-            if (t_tile_geometry_x3w(H, W, N, Cin, pn_read_switches().train_x3_wide, &gw2)) {
-                const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * gw2.HR * gw2.HC * TXW2_PITCH;
-                hipLaunchKernelGGL(tconv3_tile_x3w_kernel, dim3((unsigned)(N * gw2.tiles_x * gw2.tiles_y), (unsigned)((Cin + 63) / 64)), dim3(256), ldsw2, s, c, gw2, (const __bf16 *)ws);
+            if (plan.kernel == TK_TILE_X3W) {
+                const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * g.HR * g.HC * TXW2_PITCH;
+                hipLaunchKernelGGL(tconv3_tile_x3w_kernel, grid, dim3(256), ldsw2, s, c, g, (const __bf16 *)ws);
                 PN_HIP_CHECK(ctx, hipGetLastError());
                 return PN_OK;
             }
-            const size_t ldsx = (size_t)2 * TX_A_BYTES + (size_t)2 * gx.HR * gx.HC * TX_PITCH;
-            hipLaunchKernelGGL(tconv3_tile_x3_kernel, dim3((unsigned)(N * gx.tiles_x * gx.tiles_y), (unsigned)((Cin + 63) / 64)), dim3(256), ldsx, s, c, gx, (const __bf16 *)ws);
+            const size_t ldsx = (size_t)2 * TX_A_BYTES + (size_t)2 * g.HR * g.HC * TX_PITCH;
+            hipLaunchKernelGGL(tconv3_tile_x3_kernel, grid, dim3(256), ldsx, s, c, g, (const __bf16 *)ws);
             PN_HIP_CHECK(ctx, hipGetLastError());
             return PN_OK;
         }
         if ((rc = t_pack_get(ctx, w_dev, Cin, Cout, 1, 0, wn * sizeof(float), s, &ws, &fresh)) != PN_OK) return rc;
         if (!fresh) hipLaunchKernelGGL(wpack3_kernel, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, s, w_dev, (float *)ws, Cin, Cout, 1);
         const size_t lds = (size_t)(144 * TT_AP + 16 * g.CHP) * sizeof(float);
-        hipLaunchKernelGGL(tconv3_tile_kernel, dim3((unsigned)(N * g.tiles_x * g.tiles_y), (unsigned)((Cin + 63) / 64)), dim3(256), lds, s, c, g, (const float *)ws);
+        hipLaunchKernelGGL(tconv3_tile_kernel, grid, dim3(256), lds, s, c, g, (const float *)ws);
         PN_HIP_CHECK(ctx, hipGetLastError());
         return PN_OK;
     }
@@ -2481,92 +2617,48 @@ int pn_conv2d_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float 
     const long P = (long)N * c.Ho * c.Wo;
     if (c.Ho < 1 || c.Wo < 1 || P > 0x7fffffffL) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_wgrad: size out of range");
     c.P = (int)P;
-    const int csl0 = t_slices(P, Cout);
-    TTile g;
-    if (ks == 3 && stride == 1 && pad <= 2 && Cin >= 16 && t_tile_geometry(c.Ho, c.Wo, 4, &g)) {
-        const int ntiles = N * g.tiles_x * g.tiles_y, groups = ((Cin + 15) / 16) * ((Cout + 63) / 64);
-        int S = (512 + groups - 1) / groups;             // two blocks per CU: 512 fill the chip
-        if (S > ntiles) S = ntiles;
-        if (S < 1) S = 1;
-        const int tps = (ntiles + S - 1) / S;
-        S = (ntiles + tps - 1) / tps;
-        const size_t wn = (size_t)Cout * c.Kdim;
-        // slice counts of the split-bf16 variants (their own tile grid): the partial-sum buffer is sized for the largest
-        // grid any of the three kernels may be launched with
-        TTileW gw;
-        const bool x3 = ctx->train_x3 && t_tile_geometry_wx3(c.Ho, c.Wo, &gw);
-        int S2 = 0, S3 = 0, tps2 = 0, tps3 = 0, nt = 0;
-        size_t setb = 0;
-        bool pp = false;
-        if (x3) {
-            nt = N * gw.tiles_x * gw.tiles_y;
-            const int groups2 = ((Cin + TXW_CI - 1) / TXW_CI) * ((Cout + 63) / 64);
-            S2 = (512 + groups2 - 1) / groups2;             // two blocks per CU: 512 fill the chip; fewer slices = less partial-sum traffic
-            if (S2 > nt) S2 = nt;
-            if (S2 < 1) S2 = 1;
-            tps2 = (nt + S2 - 1) / S2;
-            S2 = (nt + tps2 - 1) / tps2;
-            setb = (size_t)2 * 64 * TXW_YP + (size_t)2 * TXW_CI * gw.CHB;
-            S3 = (256 + groups2 - 1) / groups2;             // ping-pong variant: one 8-wave block per CU
-            if (S3 > nt / 2) S3 = nt / 2;                   // at least two tiles per block, or the second wave group has nothing to do
-            pp = S3 >= 1 && 2 * setb <= 158 * 1024 && 2 * setb >= 73728;
-            if (pp) {
-                tps3 = (nt + S3 - 1) / S3;
-                S3 = (nt + tps3 - 1) / tps3;
-            }
-        }
-        const int Smax = std::max(S, x3 ? (pp ? S3 : S2) : 0);
+    const TWgradPlan plan = t_plan_wgrad(ctx, c, ks);
+    const size_t wn = (size_t)Cout * c.Kdim;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (plan.kernel != TKW_GENERIC) {
+        const bool x3 = plan.kernel != TKW_TILE;
+        // the partial-sum buffer is sized for the largest grid any of the kernels may be launched with
+        const int Smax = std::max(plan.S, x3 ? (plan.kernel == TKW_X3 ? plan.S2 : plan.S3) : 0);
         const size_t part_off = (wn * (size_t)Smax * sizeof(float) + 15) & ~(size_t)15;
         void *ws = nullptr;
-        int rc = t_ws(ctx, part_off + 16 + (size_t)Cout * csl0 * 2 * sizeof(double), &ws);
+        int rc = t_ws(ctx, part_off + 16 + (size_t)Cout * plan.csl * 2 * sizeof(double), &ws);
         if (rc != PN_OK) return rc;
         if ((rc = t_tile_lds_ok(ctx)) != PN_OK) return rc;
-        hipStream_t s = (hipStream_t)hip_stream;
-        bool done = false;
-        if (x3) {
-            TTileW gv;
-            int ppi = 0, npieces = 0;
-            if (pp && !pn_read_switches().train_wgrad_novec && t_tile_geometry_wx3v(c, &gv, &ppi, &npieces) && gv.tiles_x == gw.tiles_x && gv.tiles_y == gw.tiles_y && gv.R == gw.R && gv.TW == gw.TW) {
-                // the same tiles and slices as x3pp (bit-identical partial sums), one round trip of staging per tile
-                const size_t lds = std::max<size_t>((size_t)2 * 2 * TXW_CI * gv.CHB, (size_t)72 * 256 * 4);
-                hipLaunchKernelGGL(tconv3_wgrad_x3v_kernel, dim3((unsigned)((Cin + TXW_CI - 1) / TXW_CI), (unsigned)((Cout + 63) / 64), (unsigned)S3), dim3(512), lds, s, c, gv, (float *)ws, tps3, nt, ppi, npieces);
-                t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, S3);
-            } else if (pp) {
-                hipLaunchKernelGGL(tconv3_wgrad_x3pp_kernel, dim3((unsigned)((Cin + TXW_CI - 1) / TXW_CI), (unsigned)((Cout + 63) / 64), (unsigned)S3), dim3(512), 2 * setb, s, c, gw, (float *)ws, tps3, nt);
-                t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, S3);
-            } else {
-                hipLaunchKernelGGL(tconv3_wgrad_x3_kernel, dim3((unsigned)((Cin + TXW_CI - 1) / TXW_CI), (unsigned)((Cout + 63) / 64), (unsigned)S2), dim3(256), setb, s, c, gw, (float *)ws, tps2, nt);
-                t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, (int)S2);
-            }
-            done = true;
-        }
-        if (!done) {
+        const dim3 gridx((unsigned)((Cin + TXW_CI - 1) / TXW_CI), (unsigned)((Cout + 63) / 64), (unsigned)plan.launch_slices());
+        if (plan.kernel == TKW_X3V) {
+            const size_t lds = std::max<size_t>((size_t)2 * 2 * TXW_CI * plan.gv.CHB, (size_t)72 * 256 * 4);
+            hipLaunchKernelGGL(tconv3_wgrad_x3v_kernel, gridx, dim3(512), lds, s, c, plan.gv, (float *)ws, plan.tps3, plan.nt, plan.ppi, plan.npieces);
+            t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, plan.S3);
+        } else if (plan.kernel == TKW_X3PP) {
+            hipLaunchKernelGGL(tconv3_wgrad_x3pp_kernel, gridx, dim3(512), 2 * plan.setb, s, c, plan.gw, (float *)ws, plan.tps3, plan.nt);
+            t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, plan.S3);
+        } else if (plan.kernel == TKW_X3) {
+            hipLaunchKernelGGL(tconv3_wgrad_x3_kernel, gridx, dim3(256), plan.setb, s, c, plan.gw, (float *)ws, plan.tps2, plan.nt);
+            t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, plan.S2);
+        } else {
+            const TTile &g = plan.g;
             const size_t lds = (size_t)(128 * TT_YP + g.HR * g.HC * TT_HP + 128) * sizeof(float);
-            hipLaunchKernelGGL(tconv3_wgrad_tile_kernel, dim3((unsigned)((Cin + 15) / 16), (unsigned)((Cout + 63) / 64), (unsigned)S), dim3(256), lds, s, c, g, (float *)ws, tps, ntiles);
-            t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, (int)S);
+            hipLaunchKernelGGL(tconv3_wgrad_tile_kernel, dim3((unsigned)((Cin + 15) / 16), (unsigned)((Cout + 63) / 64), (unsigned)plan.S), dim3(256), lds, s, c, g, (float *)ws, plan.tps, plan.ntiles);
+            t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, plan.S);
         }
         if (dbias_dev) {
             double *part = (double *)((char *)ws + part_off);
-            t_chan_reduce<2>(s, nullptr, dy_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, Cout, c.Ho * c.Wo, csl0, part);
-            hipLaunchKernelGGL(sums_finish_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(64), 0, s, (const double *)part, Cout, csl0, dbias_dev, nullptr, nullptr);
+            t_chan_reduce<2>(s, nullptr, dy_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, Cout, c.Ho * c.Wo, plan.csl, part);
+            hipLaunchKernelGGL(sums_finish_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(64), 0, s, (const double *)part, Cout, plan.csl, dbias_dev, nullptr, nullptr);
         }
         PN_HIP_CHECK(ctx, hipGetLastError());
         return PN_OK;
     }
-    const int tiles = ((c.Kdim + 63) / 64) * ((Cout + 63) / 64);
-    long slices = (1024 + tiles - 1) / tiles;
-    const long cap = (P + 1023) / 1024;
-    if (slices > cap) slices = cap;
-    if (slices < 1) slices = 1;
-    long pps = (P + slices - 1) / slices;
-    pps = (pps + TW_RC - 1) / TW_RC * TW_RC;
-    slices = (P + pps - 1) / pps;
-    const size_t wn = (size_t)Cout * c.Kdim;
-    const int csl = t_slices(P, Cout);
+    const long slices = plan.slices, pps = plan.pps;
+    const int csl = plan.csl;
     void *ws = nullptr;
     int rc = t_ws(ctx, wn * slices * sizeof(float) + 16 + (size_t)Cout * csl * 2 * sizeof(double), &ws);
     if (rc != PN_OK) return rc;
-    hipStream_t s = (hipStream_t)hip_stream;
     dim3 grid((unsigned)((c.Kdim + 63) / 64), (unsigned)((Cout + 63) / 64), (unsigned)slices), block(256);
     if (ks == 1) hipLaunchKernelGGL(tconv_wgrad_kernel<1>, grid, block, 0, s, c, (float *)ws, (int)pps);
     else if (ks == 3) hipLaunchKernelGGL(tconv_wgrad_kernel<3>, grid, block, 0, s, c, (float *)ws, (int)pps);
@@ -2678,6 +2770,7 @@ int pn_bn_train_forward(pn_ctx *ctx, const float *x_dev, const float *gamma_dev,
     T_CTX_CHECK("pn_bn_train_forward")
     if (!x_dev || !gamma_dev || !beta_dev || !y_dev || !save_mean_dev || !save_invstd_dev || N < 1 || C < 1 || HW < 1 || (long)N * HW < 2)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_forward: bad arguments");
+    if ((long)N * C > 65535) return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_forward: N * C out of range");        // (grid.y of the apply kernel) refused before anything is launched
     const long cnt = (long)N * HW;
     const int sl = t_slices(cnt, C);
     void *ws = nullptr;
@@ -2685,7 +2778,6 @@ int pn_bn_train_forward(pn_ctx *ctx, const float *x_dev, const float *gamma_dev,
     if (rc != PN_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     t_chan_reduce<0>(s, x_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, C, HW, sl, (double *)ws);
-    if ((long)N * C > 65535) return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_forward: N * C out of range");
     const bool v4 = (HW & 3) == 0 && ((((size_t)x_dev) | ((size_t)y_dev) | ((size_t)res_dev)) & 15) == 0;
     if (v4)
         hipLaunchKernelGGL(bn_apply_kernel<4>, dim3((unsigned)((HW / 4 + 255) / 256), (unsigned)(N * C)), dim3(256), 0, s, x_dev, gamma_dev, beta_dev, (const double *)ws, sl,
@@ -2703,6 +2795,8 @@ int pn_bn_train_backward(pn_ctx *ctx, const float *x_dev, const float *dy_dev, c
     T_CTX_CHECK("pn_bn_train_backward")
     if (!x_dev || !dy_dev || !gamma_dev || !save_mean_dev || !save_invstd_dev || !dx_dev || !dgamma_dev || !dbeta_dev || (act != PN_ACT_NONE && !out_dev && !beta_dev))
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_backward: bad arguments (an activation needs out, or beta to recompute its mask)");
+    if (N < 1 || C < 1 || HW < 1 || (long)N * C > 65535)        // (grid.y of the apply kernel) refused before anything is launched
+        return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_backward: N * C out of range");
     const long cnt = (long)N * HW;
     const int sl = t_slices(cnt, C);
     void *ws = nullptr;
@@ -2711,7 +2805,6 @@ int pn_bn_train_backward(pn_ctx *ctx, const float *x_dev, const float *dy_dev, c
     hipStream_t s = (hipStream_t)hip_stream;
     t_chan_reduce<1>(s, x_dev, dy_dev, out_dev, save_mean_dev, save_invstd_dev, gamma_dev, beta_dev, act, N, C, HW, sl, (double *)ws);
     // d beta = sum g, d gamma = sum g (x - mean) * invstd: finished inside the apply kernel
-    if ((long)N * C > 65535) return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_backward: N * C out of range");
     const bool v4 = (HW & 3) == 0 && ((((size_t)x_dev) | ((size_t)dy_dev) | ((size_t)out_dev) | ((size_t)dx_dev) | ((size_t)dres_dev)) & 15) == 0;
     if (v4)
         hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3((unsigned)((HW / 4 + 255) / 256), (unsigned)(N * C)), dim3(256), 0, s, x_dev, dy_dev, out_dev, gamma_dev, beta_dev,
@@ -2790,6 +2883,68 @@ int pn_sgd_nesterov(pn_ctx *ctx, float *param_dev, const float *grad_dev, float 
                        lr, momentum, weight_decay, first_step, grad_scale);
     PN_HIP_CHECK(ctx, hipGetLastError());
     return PN_OK;
+}
+
+int pn_train_conv_plan_info(pn_ctx *ctx, int which, int N, int Cin, int H, int W, int Cout, int ks, int stride, int pad, char *out, size_t cap) {
+    if (!ctx) return PN_ERR_INVALID;
+    if (!out || N < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || stride < 1 || pad < 0 || (ks != 1 && ks != 3 && ks != 7) || which < PN_PLAN_FORWARD || which > PN_PLAN_WGRAD)
+        return pn_set_error(ctx, PN_ERR_INVALID, "pn_train_conv_plan_info: bad arguments");
+    if (which == PN_PLAN_DGRAD) stride = 1;
+    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+    const long P = (long)N * Ho * Wo;
+    if (Ho < 1 || Wo < 1 || P > 0x7fffffffL) return pn_set_error(ctx, PN_ERR_INVALID, "pn_train_conv_plan_info: size out of range");
+    static const char *names[] = {"forward", "dgrad", "dgrad_strided", "wgrad"};
+    char buf[1024];
+    int n = snprintf(buf, sizeof buf, "{\"which\":\"%s\",\"x3\":%d,\"Ho\":%d,\"Wo\":%d", names[which], ctx->train_x3 ? 1 : 0, Ho, Wo);
+    auto tile = [&](const char *label, const char *pack, int TW, int R, int tx, int ty, unsigned g0, unsigned g1, unsigned g2) {
+        n += snprintf(buf + n, sizeof buf - n, ",\"kernel\":\"%s\",\"pack\":\"%s\",\"TW\":%d,\"R\":%d,\"tiles_x\":%d,\"tiles_y\":%d,\"grid\":[%u,%u,%u]", label, pack, TW, R, tx, ty, g0,
+                      g1, g2);
+    };
+    if (which == PN_PLAN_FORWARD || which == PN_PLAN_DGRAD) {
+        const bool dg = which == PN_PLAN_DGRAD;
+        if (dg && pad > ks - 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_train_conv_plan_info: pad out of range for a data gradient");
+        // the data gradient is a forward convolution of dy (Cout channels, Ho x Wo) to the H x W input map
+        TTilePlan p = dg ? t_plan_dgrad(ctx, N, Cin, H, W, Cout, ks) : t_plan_forward(ctx, N, Cin, Cout, Ho, Wo, ks, stride, pad);
+        const int M = dg ? Cin : Cout, oh = dg ? H : Ho, ow = dg ? W : Wo;
+        // pn_conv2d_dgrad's fall-back: wflip_kernel, then pn_conv2d_forward(N, Cout, Ho, Wo -> Cin, stride 1, pad ks - 1 - pad)
+        if (dg && p.kernel == TK_GENERIC) p = t_plan_forward(ctx, N, Cout, Cin, H, W, ks, 1, ks - 1 - pad);
+        if (p.kernel == TK_GENERIC)
+            tile(t_fwd_label(p.kernel, ks), dg ? "wflip_kernel" : "", 0, 0, 0, 0, (unsigned)(((long)N * oh * ow + 127) / 128), (unsigned)((M + 63) / 64), 1u);
+        else
+            tile(t_fwd_label(p.kernel, ks), p.kernel == TK_TILE ? "wpack3_kernel" : "wpack3_x3_kernel", p.g.TW, p.g.R, p.g.tiles_x, p.g.tiles_y,
+                 (unsigned)(N * p.g.tiles_x * p.g.tiles_y), (unsigned)((M + 63) / 64), 1u);
+    } else if (which == PN_PLAN_DGRAD_STRIDED) {
+        unsigned g0 = 0, g1 = 0;
+        const char *label = pn_dgrad_strided_plan(N, Cin, H, W, ks, &g0, &g1);
+        if (!label || pad > ks - 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_train_conv_plan_info: pn_conv2d_dgrad_strided takes kernel 1 or 3, pad < kernel");
+        tile(label, "", 0, 0, 0, 0, g0, g1, 1u);
+    } else {
+        TConv c;
+        c.N = N; c.Cin = Cin; c.H = H; c.W = W; c.Cout = Cout; c.stride = stride; c.pad = pad; c.accumulate = 0;
+        c.Ho = Ho; c.Wo = Wo; c.Kdim = Cin * ks * ks; c.P = (int)P;
+        const TWgradPlan p = t_plan_wgrad(ctx, c, ks);
+        const char *label = t_wgrad_label(p.kernel, ks);
+        if (p.kernel == TKW_GENERIC)
+            tile(label, "", 0, 0, 0, 0, (unsigned)((c.Kdim + 63) / 64), (unsigned)((Cout + 63) / 64), (unsigned)p.slices);
+        else if (p.kernel == TKW_TILE)
+            tile(label, "", p.g.TW, p.g.R, p.g.tiles_x, p.g.tiles_y, (unsigned)((Cin + 15) / 16), (unsigned)((Cout + 63) / 64), (unsigned)p.S);
+        else {
+            const TTileW &g = p.kernel == TKW_X3V ? p.gv : p.gw;
+            tile(label, "", g.TW, g.R, g.tiles_x, g.tiles_y, (unsigned)((Cin + TXW_CI - 1) / TXW_CI), (unsigned)((Cout + 63) / 64), (unsigned)p.launch_slices());
+        }
+        n += snprintf(buf + n, sizeof buf - n, ",\"slices\":%d,\"per_slice\":%ld,\"per_slice_unit\":\"%s\",\"t_slices\":%d", p.launch_slices(), p.per_slice(),
+                      p.kernel == TKW_GENERIC ? "pixels" : "tiles", p.csl);
+    }
+    n += snprintf(buf + n, sizeof buf - n, "}");
+    if ((size_t)n + 1 > cap) return pn_set_error(ctx, PN_ERR_INVALID, "pn_train_conv_plan_info: %d bytes needed", n + 1);
+    memcpy(out, buf, (size_t)n + 1);
+    return PN_OK;
+}
+
+// slices of the per-channel reductions (BatchNorm statistics and gradients, bias gradient) over N * HW elements of C channels
+int pn_train_reduce_slices(pn_ctx *ctx, int N, int C, int HW) {
+    if (!ctx || N < 1 || C < 1 || HW < 1) return PN_ERR_INVALID;
+    return t_slices((long)N * HW, C);
 }
 
 }  // extern "C"

@@ -267,6 +267,14 @@ __global__ void prior_build_kernel(const double *__restrict__ boxes, const float
     }
 }
 
+// pn_conv2d_dgrad_strided's dispatch: kernel label and grid (nullptr: a kernel size it does not take); shared with pn_train_conv_plan_info
+const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned *grid_x, unsigned *grid_y) {
+    if (ks != 1 && ks != 3) return nullptr;
+    *grid_x = (unsigned)((H * W + 255) / 256);
+    *grid_y = (unsigned)std::min(N * Cin, 65535);
+    return ks == 3 ? "dgrad_strided_kernel<3>" : "dgrad_strided_kernel<1>";
+}
+
 #define Y_CTX_CHECK                                                                                         \
     if (!ctx) return PN_ERR_INVALID;                                                                        \
     if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
@@ -280,7 +288,9 @@ int pn_conv2d_dgrad_strided(pn_ctx *ctx, const float *dy_dev, const float *w_dev
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_dgrad_strided: bad arguments (kernel 1 or 3, stride >= 1, 0 <= pad < kernel)");
     const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
     if (Ho < 1 || Wo < 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_dgrad_strided: empty output");
-    const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)std::min(N * Cin, 65535));
+    unsigned gx = 0, gy = 0;
+    (void)pn_dgrad_strided_plan(N, Cin, H, W, ks, &gx, &gy);
+    const dim3 grid(gx, gy);
     hipStream_t s = (hipStream_t)hip_stream;
     if (ks == 3)
         hipLaunchKernelGGL(dgrad_strided_kernel<3>, grid, dim3(256), 0, s, dy_dev, w_dev, dx_dev, N, Cin, H, W, Cout, Ho, Wo, stride, pad, accumulate);
