@@ -236,6 +236,16 @@ int pn_parse_paf_unbounded(pn_ctx *ctx, const float *heat_dev, const float *paf_
 int pn_parse_paf_unbounded_fetch(pn_ctx *ctx, float *peaks_xys, int *peak_type, int *person_joint, double *person_score,
                                  int *person_count, double *joints_2d, double *joints_3d, double *part_conf);
 
+/* Read-only views of the connection lists (find_connected_joints, tpm/lib/utils/paf_to_pose.py:156-264) a parse left in the context:
+ * per limb the count and, in matching order, the indices (i into the source joint type's peaks, j into the destination's) and the
+ * float64 limb score.  Host arrays; both calls block until the device is idle and touch nothing on the launch path.
+ * pn_parse_debug_connections: frame `frame` of the last pn_parse_paf / pn_parse_paf_wire batch; count [L], conn_i / conn_j / conn_s
+ * [L][PN_MAX_CONN_PER_LIMB].  PN_ERR_STATE when no parse has run on the context or frame is outside that batch.
+ * pn_parse_paf_unbounded_connections: the last pn_parse_paf_unbounded; arrays [L][cap], cap >= every limb's count (the n_peaks that
+ * call returned always suffices), else PN_ERR_INVALID.                                                                              */
+int pn_parse_debug_connections(pn_ctx *ctx, int frame, int *count, int *conn_i, int *conn_j, double *conn_s);
+int pn_parse_paf_unbounded_connections(pn_ctx *ctx, int cap, int *count, int *conn_i, int *conn_j, double *conn_s);
+
 /* NMS(heatmaps, upsampFactor, bool_refine_center=True, config) (tpm/lib/utils/paf_to_pose.py:75-153) alone, on n_maps maps
  * [n_maps, h, w] f32 of one frame (any topology: `paf_to_pose_cpp`, paf_to_pose.py:381-385, runs it on the 18 COCO parts before
  * `process_paf`).  No capacity: count_dev [n_maps] int32 receives every map's peak count, peak_x / peak_y / peak_score_dev

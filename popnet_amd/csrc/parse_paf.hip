@@ -653,6 +653,24 @@ extern "C" int pn_parse_paf_wire(pn_ctx *ctx, const float *heat_dev, const float
     hipLaunchKernelGGL(group_readout_kernel, dim3(B), dim3(256), 0, s, heat_dev, z_dev, h, w, J_ + 1, L_ + 1, *cfg,
                        (const ParseWs *)ws, frames_dev, wire_dev);
     PN_HIP_CHECK(ctx, hipGetLastError());
+    ctx->parse_last_b = B;
+    return PN_OK;
+}
+
+// Read-only view of the connection lists the last pn_parse_paf / pn_parse_paf_wire left in the context's scratch (tests compare them with
+// find_connected_joints).  Host side, blocking; nothing on the launch path knows about it.
+extern "C" int pn_parse_debug_connections(pn_ctx *ctx, int frame, int *count, int *conn_i, int *conn_j, double *conn_s) {
+    if (!ctx) return PN_ERR_INVALID;
+    if (!count || !conn_i || !conn_j || !conn_s) return pn_set_error(ctx, PN_ERR_INVALID, "pn_parse_debug_connections: bad arguments");
+    if (!ctx->parse_ws || ctx->parse_last_b < 1) return pn_set_error(ctx, PN_ERR_STATE, "pn_parse_debug_connections: no parse has run on this context");
+    if (frame < 0 || frame >= ctx->parse_last_b)
+        return pn_set_error(ctx, PN_ERR_STATE, "pn_parse_debug_connections: frame %d outside the last batch of %d", frame, ctx->parse_last_b);
+    PN_HIP_CHECK(ctx, hipDeviceSynchronize());
+    const ParseWs *W = (const ParseWs *)ctx->parse_ws + frame;
+    PN_HIP_CHECK(ctx, hipMemcpy(count, W->conn_count, sizeof W->conn_count, hipMemcpyDeviceToHost));
+    PN_HIP_CHECK(ctx, hipMemcpy(conn_i, W->conn_i, sizeof W->conn_i, hipMemcpyDeviceToHost));
+    PN_HIP_CHECK(ctx, hipMemcpy(conn_j, W->conn_j, sizeof W->conn_j, hipMemcpyDeviceToHost));
+    PN_HIP_CHECK(ctx, hipMemcpy(conn_s, W->conn_s, sizeof W->conn_s, hipMemcpyDeviceToHost));
     return PN_OK;
 }
 
@@ -1181,6 +1199,26 @@ extern "C" int pn_parse_paf_unbounded_fetch(pn_ctx *ctx, float *peaks_xys, int *
     if (P && joints_2d) PN_HIP_CHECK(ctx, hipMemcpy(joints_2d, B->w.o_j2d, P * J_ * 16, hipMemcpyDeviceToHost));
     if (P && joints_3d) PN_HIP_CHECK(ctx, hipMemcpy(joints_3d, B->w.o_j3d, P * J_ * 24, hipMemcpyDeviceToHost));
     if (P && part_conf) PN_HIP_CHECK(ctx, hipMemcpy(part_conf, B->w.o_conf, P * J_ * 8, hipMemcpyDeviceToHost));
+    return PN_OK;
+}
+
+// Read-only view of the connection lists of the last pn_parse_paf_unbounded on this context: limb l's count[l] connections at [l][0 .. count[l]) of
+// arrays [L][cap].  A limb connects distinct peaks of two joint types, so cap = the n_peaks that call returned always suffices.
+extern "C" int pn_parse_paf_unbounded_connections(pn_ctx *ctx, int cap, int *count, int *conn_i, int *conn_j, double *conn_s) {
+    if (!ctx) return PN_ERR_INVALID;
+    if (!count || !conn_i || !conn_j || !conn_s || cap < 0) return pn_set_error(ctx, PN_ERR_INVALID, "pn_parse_paf_unbounded_connections: bad arguments");
+    BigHost *B = (BigHost *)ctx->parse_big;
+    if (!B || !B->blk_b) return pn_set_error(ctx, PN_ERR_STATE, "pn_parse_paf_unbounded_connections: no result (call pn_parse_paf_unbounded first)");
+    PN_HIP_CHECK(ctx, hipDeviceSynchronize());
+    PN_HIP_CHECK(ctx, hipMemcpy(count, B->w.conn_count, L_ * sizeof(int), hipMemcpyDeviceToHost));
+    for (int l = 0; l < L_; ++l) {
+        const size_t n = (size_t)count[l];
+        if (n > (size_t)cap || n > (size_t)B->hw) return pn_set_error(ctx, PN_ERR_INVALID, "pn_parse_paf_unbounded_connections: limb %d has %d connections, cap is %d", l, count[l], cap);
+        if (!n) continue;
+        PN_HIP_CHECK(ctx, hipMemcpy(conn_i + (size_t)l * cap, B->w.conn_i + (size_t)l * B->hw, n * sizeof(int), hipMemcpyDeviceToHost));
+        PN_HIP_CHECK(ctx, hipMemcpy(conn_j + (size_t)l * cap, B->w.conn_j + (size_t)l * B->hw, n * sizeof(int), hipMemcpyDeviceToHost));
+        PN_HIP_CHECK(ctx, hipMemcpy(conn_s + (size_t)l * cap, B->w.conn_s + (size_t)l * B->hw, n * sizeof(double), hipMemcpyDeviceToHost));
+    }
     return PN_OK;
 }
 

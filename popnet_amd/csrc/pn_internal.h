@@ -14,6 +14,7 @@ struct pn_ctx {
     void *parse_ws = nullptr;
     size_t parse_ws_bytes = 0;
     bool parse_ws_fixed = false;     // pn_parse_reserve: the scratch never moves again
+    int parse_last_b = 0;            // batch size of the last pn_parse_paf / pn_parse_paf_wire on this context (0 = none; pn_parse_debug_connections)
     void *parse_big = nullptr;       // workspace of the unbounded second pass (parse_paf.hip::BigHost), freed by pn_parse_big_free
     // scratch of the training kernels (flipped weights, split-reduction partials; train.hip), stream-ordered reuse
     void *train_ws = nullptr;

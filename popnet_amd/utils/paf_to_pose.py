@@ -113,6 +113,31 @@ def parse_paf_unbounded(heat, paf, z, cfg):
             "person_joint": pj, "joints_2d": j2, "joints_3d": j3, "part_conf": cf}
 
 
+def parse_connections(frame, device):
+    """The connection lists frame `frame` of the last parse_paf_batch / PoseEngine parse on `device`'s shared context left in the
+    scratch (pn_parse_debug_connections): per limb an [n, 3] float64 array (i, j, score) in matching order."""
+    ctx = _lib.Context.for_device(torch.device(device).index)
+    return fetch_connections(ctx, frame)
+
+
+def fetch_connections(ctx, frame):
+    Lm, M = _lib.PN_NUM_LIMBS, _lib.PN_MAX_PEAKS_PER_JOINT
+    cnt, ci, cj, cs = np.zeros((Lm,), np.int32), np.zeros((Lm, M), np.int32), np.zeros((Lm, M), np.int32), np.zeros((Lm, M), np.float64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    ctx.check(_lib.lib().pn_parse_debug_connections(ctx.handle, int(frame), vp(cnt), vp(ci), vp(cj), vp(cs)), "pn_parse_debug_connections")
+    return [np.stack([ci[l, :cnt[l]], cj[l, :cnt[l]], cs[l, :cnt[l]]], axis=1) for l in range(Lm)]
+
+
+def unbounded_connections(n_peaks, device):
+    """The same for the last parse_paf_unbounded on `device` (pn_parse_paf_unbounded_connections); n_peaks: the rows of its joint_list."""
+    ctx = _lib.Context.for_device(torch.device(device).index)
+    Lm, cap = _lib.PN_NUM_LIMBS, max(int(n_peaks), 1)
+    cnt, ci, cj, cs = np.zeros((Lm,), np.int32), np.zeros((Lm, cap), np.int32), np.zeros((Lm, cap), np.int32), np.zeros((Lm, cap), np.float64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    ctx.check(_lib.lib().pn_parse_paf_unbounded_connections(ctx.handle, cap, vp(cnt), vp(ci), vp(cj), vp(cs)), "pn_parse_paf_unbounded_connections")
+    return [np.stack([ci[l, :cnt[l]], cj[l, :cnt[l]], cs[l, :cnt[l]]], axis=1) for l in range(Lm)]
+
+
 def check_status(fr):
     if int(fr['status']):
         raise _lib.PopnetError("pose parse overflow (status=%d): more than %d peaks per joint or %d persons in a frame"

@@ -1040,10 +1040,11 @@ def test_yolo_full_batch_permutation_equivariance(gpu):
 @pytest.mark.parametrize("shape,dtype", [((240, 320), np.float16), ((240, 320), np.float32), ((512, 480), np.float16)])
 def test_engine_other_frame_sizes_and_dtypes(gpu, shape, dtype):
     """ITOP-sized (240x320) and 512-row frames, f16 and f32 storage: pre-processing equals the oracle bit for bit and the
-    records equal the oracle parse of the maps (the rescale uses the engine's w_org / h_org)."""
+    records of all three frames equal the oracle parse of the maps (the rescale uses the engine's w_org / h_org); a frame that
+    overflows the fixed-size record is compared through the unbounded second pass instead."""
     from oracle import parse_paf as O, preproc as opre
     from popnet_amd.pipeline import PoseEngine, records_to_numpy
-    from popnet_amd.utils.paf_to_pose import frame_assoc
+    from popnet_amd.utils.paf_to_pose import frame_assoc, parse_paf_unbounded
     H, W = shape
     eng = PoseEngine(precision="fp32", device=gpu, max_batch=3, w_org=W, h_org=H)
     depth = synth.synth_depth(3, H, W, seed=31, dtype=dtype)
@@ -1053,16 +1054,20 @@ def test_engine_other_frame_sizes_and_dtypes(gpu, shape, dtype):
     hp, hh, hz = (t[:3].cpu().numpy().transpose(0, 2, 3, 1) for t in (eng.paf, eng.heat, eng.z))
     compared = 0
     for b in range(3):
-        if int(recs[b]["status"]):          # the head calibration is for 480x640 statistics: a crowded map may hit the
-            continue                        # compile-time person-row limit, which is flagged, never silent
-        compared += 1
         ref = O.frame_to_records(hh[b].copy(), hp[b].copy(), hz[b].copy(), w_org=W, h_org=H)
-        a = frame_assoc(recs[b])
-        assert a.shape[0] == len(ref["humans_3d"])
-        if a.shape[0]:
-            assert np.array_equal(recs[b]["joints_2d"][:a.shape[0]], np.array(ref["humans_2d"]).reshape(-1, 15, 2))
-            assert np.array_equal(recs[b]["joints_3d"][:a.shape[0]], np.array(ref["humans_3d"]).reshape(-1, 15, 3))
-    assert compared >= 1
+        n = len(ref["humans_3d"])
+        if int(recs[b]["status"]):          # the head calibration is for 480x640 statistics: a crowded map may hit a compile-time limit, which is
+            r = parse_paf_unbounded(eng.heat[b], eng.paf[b], eng.z[b], eng.cfg)     # flagged, never silent -- such a frame is compared through the second pass
+            j2, j3 = r["joints_2d"], r["joints_3d"]
+        else:
+            a = frame_assoc(recs[b])
+            assert a.shape[0] == n
+            j2, j3 = recs[b]["joints_2d"][:n], recs[b]["joints_3d"][:n]
+        assert j2.shape[0] == n and j3.shape[0] == n
+        assert np.array_equal(j2, np.array(ref["humans_2d"], dtype=np.float64).reshape(-1, 15, 2))
+        assert np.array_equal(j3, np.array(ref["humans_3d"], dtype=np.float64).reshape(-1, 15, 3))
+        compared += 1
+    assert compared == 3
 
 
 @pytest.mark.parametrize("prec", ["bf16", "bf16x3"])
