@@ -1,0 +1,875 @@
+// Convolution kernels of the NCHW training engine (train.hip): forward and, with flipped weights, the stride-1 data gradient.
+//   tconv_fwd_kernel<KS>           any kernel size / stride: implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains), gathered operand
+//   tconv3_tile_kernel             3x3 stride 1 on halo tiles, fp32 MFMA
+//   tconv3_tile_x3 / _x3w_kernel   the same tiles on split-bf16 MFMA ("bf16x3"): 128 / 256 pixel slots per block
+//   tstem_fwd_kernel               the planes engine's 7x7 / 2 single-channel stem (trainx.hip)
+//   wpack3 / wpack3_x3 / wpack_all / wflip   weight packs of the kernels above
+// The launches, the geometry functions and the planners are in train.hip.
+#pragma once
+#include "pn_internal.h"
+
+
+typedef float t_f32x4 __attribute__((ext_vector_type(4)));
+
+struct TConv {
+    const float *x;      // [N, Cin, H, W]
+    const float *w;      // [Cout, Cin * KS * KS]
+    const float *bias;   // [Cout] or nullptr
+    float *y;            // [N, Cout, Ho, Wo]
+    int N, Cin, H, W, Cout, Ho, Wo, stride, pad, accumulate;
+    int Kdim;            // Cin * KS * KS
+    int P;               // N * Ho * Wo
+    // round 6 (the planes training engine's stem, trainx.hip): y / dY as a channel-minor planes tensor [pixel][pl_cs] instead of NCHW f32 --
+    // PL = 1: two bf16 planes [hi | lo] `pl_split` elements apart (value = hi + lo), PL = 2: one f32 plane.  Same values, same MFMA order as the
+    // NCHW form followed / preceded by trainx_kernels.h's layout pass: bit-identical, one 103 MB round trip less each way.
+    void *pl = nullptr;
+    int pl_cs = 0, pl_split = 0;
+};
+typedef __attribute__((ext_vector_type(8))) __bf16 t_bf8;
+typedef __attribute__((ext_vector_type(4))) __bf16 t_bf4;
+typedef __attribute__((ext_vector_type(2))) float t_f32x2;
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Forward (and, with flipped weights, the stride-1 data gradient): D[cout][pixel] = sum_k W[cout][k] * X[k][pixel],
+// k = (ci, ky, kx).  Block = 64 couts x 128 pixels, 4 waves (each 64 couts x 32 pixels = 4 x 2 MFMA tiles), K chunks of 16
+// staged through LDS (weights k-major, the gathered input k-major; lanes run along the pixels, so every global gather is a
+// run of consecutive addresses), next chunk's global loads in flight during the MFMAs of the current one.
+// ---------------------------------------------------------------------------------------------------------------------
+#define TC_KC 16
+#define TC_AP 80      // LDS pitches: 4 k rows x 16 lanes of an MFMA operand read fall on 64 different banks
+#define TC_BP 144
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Reuse-aware block order (round 5).  The dispatcher deals the workgroups of a launch round-robin over the 8 XCDs in linear-id order
+// (x fastest) and every XCD has its own 4 MB L2.  With the plain (tile, cout block) / (ci block, cout block, slice) grids the blocks
+// that read the SAME operand tile -- the cout blocks of one input tile in the forward / data-gradient kernels, the (ci, cout) blocks of
+// one pixel slice in the weight gradient -- sat on different XCDs or ran a whole grid apart in time: every operand tile crossed the
+// fabric once per sharer (a 256 -> 256 weight gradient staged 444 MB for 51 MB of tensors).  t_logical_block() maps the hardware id to
+// a LOGICAL id such that each XCD owns one contiguous range of logical ids (a bijection, the conv kernels' remap of net.hip); the
+// kernels decode the logical id with the sharing dimension fastest, so sharers run at the same time behind the same L2.  Which block
+// computes which tile changes, nothing else: results are bit-identical.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int t_logical_block() {
+    const int nb = (int)(gridDim.x * gridDim.y * gridDim.z);
+    const int L = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    const int xcd = L & 7, idx = L >> 3, qq = nb >> 3, rr = nb & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+}
+// Sixteen loaded values pinned in registers at this point of the program: every one of their loads has been issued before the first is
+// waited for.  Without it the compiler sinks each load to its single use (legal: the addresses are provably distinct from the stores in
+// between) and waits for it there -- a dependent memory round trip per element.
+#define T_PIN16(a) do { _Pragma("unroll") for (int _k = 0; _k < 16; ++_k) asm volatile("" : "+v"((a)[_k])); } while (0)
+// forward-type grids (tiles, cout blocks): the cout blocks of a tile are neighbours in logical order
+#define T_DECODE_TILE_CB(tile, cb) const int _lg = t_logical_block(), cb = _lg % (int)gridDim.y, tile = _lg / (int)gridDim.y
+// weight-gradient grids (column blocks, cout blocks, slices): a slice's blocks are one contiguous logical range
+#define T_DECODE_XYZ(bx, by, bz) const int _lg = t_logical_block(), bx = _lg % (int)gridDim.x, by = (_lg / (int)gridDim.x) % (int)gridDim.y, bz = _lg / (int)(gridDim.x * gridDim.y)
+
+template <int KS, int PL = 0>
+__global__ __launch_bounds__(256) void tconv_fwd_kernel(TConv c) {
+    __shared__ float As[TC_KC][TC_AP];
+    __shared__ float Bs[TC_KC][TC_BP];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
+    T_DECODE_TILE_CB(pblk, cblk);
+    const int p0 = pblk * 128, co0 = cblk * 64;
+    const int HoWo = c.Ho * c.Wo;
+    // staging roles
+    const int b_pn = t & 127, b_k0 = t >> 7;            // B: pixel column, k rows b_k0 + 2j
+    const int a_co = t & 63, a_k0 = (t >> 6) * 4;       // A: cout row, k rows a_k0 + j
+    const int bp = p0 + b_pn;
+    const bool bp_ok = bp < c.P;
+    int bn = 0, iy0 = 0, ix0 = 0;
+    if (bp_ok) {
+        bn = bp / HoWo;
+        const int rem = bp - bn * HoWo, oy = rem / c.Wo, ox = rem - oy * c.Wo;
+        iy0 = oy * c.stride - c.pad;
+        ix0 = ox * c.stride - c.pad;
+    }
+    // every load is unconditional (an out-of-range element reads index 0; it is zeroed when the value goes to LDS, one chunk
+    // later -- a select right after the load would put an s_waitcnt vmcnt(0) in front of the MFMAs the load is meant to
+    // overlap with, and a conditional load becomes a branch of its own: 73 of them in the first version of this loop)
+    const float *xb = c.x + (size_t)bn * c.Cin * c.H * c.W;
+    const bool a_ok = co0 + a_co < c.Cout;
+    const float *wa = c.w + (a_ok ? (size_t)(co0 + a_co) * c.Kdim : 0);
+
+    float ra[4], rb[8];
+    unsigned okm = 0;          // bit j: rb[j] valid, bit 8 + j: ra[j] valid
+    auto load = [&](int k0) {
+        okm = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = k0 + a_k0 + j;
+            const int ok = (int)(a_ok & (k < c.Kdim));
+            ra[j] = wa[k & -ok];
+            okm |= (unsigned)ok << (8 + j);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = k0 + b_k0 + 2 * j;
+            const int ci = k / (KS * KS), rr = k - ci * (KS * KS), ky = rr / KS, kx = rr - ky * KS;
+            const int iy = iy0 + ky, ix = ix0 + kx;
+            const int ok = (int)(bp_ok & (k < c.Kdim) & (iy >= 0) & (iy < c.H) & (ix >= 0) & (ix < c.W));
+            rb[j] = xb[((ci * c.H + iy) * c.W + ix) & -ok];
+            okm |= (unsigned)ok << j;
+        }
+    };
+    t_f32x4 acc[4][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    load(0);
+    for (int k0 = 0; k0 < c.Kdim; k0 += TC_KC) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) As[a_k0 + j][a_co] = (okm >> (8 + j)) & 1u ? ra[j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) Bs[b_k0 + 2 * j][b_pn] = (okm >> j) & 1u ? rb[j] : 0.f;
+        __syncthreads();
+        if (k0 + TC_KC < c.Kdim) load(k0 + TC_KC);
+#pragma unroll
+        for (int ks = 0; ks < TC_KC / 4; ++ks) {
+            float a[4], b[2];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) a[m] = As[4 * ks + q][16 * m + r];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) b[n] = Bs[4 * ks + q][32 * wave + 16 * n + r];
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
+        }
+    }
+    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
+    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
+    float bv[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
+        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
+    }
+    T_PIN16(bv);
+    // epilogue: lane holds couts 16m + 4q + i of pixel 32 wave + 16 n + r; the accumulate form first gathers all old values
+    // (32 independent loads in flight), then adds and stores
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int p = p0 + 32 * wave + 16 * n + r;
+        const int pok = (int)(p < c.P);
+        const int pc = p & -pok;
+        if (PL) {       // planes: this lane's four consecutive couts of a 16-cout tile are one 8-byte (bf16 hi, lo) / 16-byte (f32) store
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int co = co0 + 16 * m + 4 * q;
+                float v[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = acc[m][n][i] + bv[4 * m + i];
+                if (!pok || co >= c.Cout) continue;
+                if (PL == 2) {
+                    *reinterpret_cast<t_f32x4 *>((float *)c.pl + (size_t)pc * c.pl_cs + co) = t_f32x4{v[0], v[1], v[2], v[3]};
+                } else {
+                    t_bf4 h, l;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const __bf16 hi = (__bf16)v[i];
+                        h[i] = hi;
+                        l[i] = (__bf16)(v[i] - (float)hi);
+                    }
+                    __bf16 *o = (__bf16 *)c.pl + (size_t)pc * c.pl_cs + co;
+                    *reinterpret_cast<t_bf4 *>(o) = h;
+                    *reinterpret_cast<t_bf4 *>(o + c.pl_split) = l;
+                }
+            }
+            continue;
+        }
+        const int img = pc / HoWo, rem = pc - img * HoWo;
+        float *yb = c.y + (size_t)img * c.Cout * HoWo + rem;
+        float old[16];
+        if (c.accumulate) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int co = co0 + 16 * m + 4 * q + i;
+                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
+                }
+            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int co = co0 + 16 * m + 4 * q + i;
+                float v = acc[m][n][i];
+                v += bv[4 * m + i];
+                if (c.accumulate) v += old[4 * m + i];
+                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 3x3 stride-1 convolutions (95 % of the step's FLOPs), second generation.  PMC on the gather kernel above: the texture
+// addresser is as busy per CU as the matrix pipe per SIMD (TA/MFMA 1.01, MfmaUtil 28 %) -- every input element is fetched
+// nine times, once per tap, four bytes per lane.  Here a block stages the HALO TILE of 16 input channels once (rows of the
+// image, coalesced) plus the 9 x 16 x 64 weight slice (pre-transposed to [tap][ci][cout] by wpack_kernel, coalesced along
+// cout) and runs 288 MFMAs per wave between two barriers; the nine taps are LDS address offsets.  Output tile = R rows x TW
+// columns of one image, R * TW <= 128 (28-wide maps: 4 x 28, 56: 2 x 56, 112: 1 x 112).  Two blocks per CU overlap one
+// block's staging with the other's MFMAs.
+// ---------------------------------------------------------------------------------------------------------------------
+struct TTile {
+    int TW, R, tiles_x, tiles_y;   // output tile, tiles per image
+    int HC, HR;                    // halo columns / rows = TW + 2, R + 2
+    int CHP;                       // LDS floats per halo channel (HR * HC rounded up to = 16 mod 64: forward, = 4 mod 64: wgrad)
+    int NI;                        // ceil(HR * HC / 256)
+};
+#define TT_AP 80
+#define TT_MAXNI 2
+
+// wp[tap][ci][co] = flip ? W[co_w = ci][ci_w = co][8 - tap] : W[co][ci][tap]   (flip: the data gradient's transposed, rotated weights)
+__global__ void wpack3_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int flip) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 9 * Cin * Cout) return;
+    const int co = i % Cout, ci = (i / Cout) % Cin, tap = i / (Cout * Cin);
+    wp[i] = flip ? w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : w[((size_t)co * Cin + ci) * 9 + tap];
+}
+
+__global__ __launch_bounds__(256, 2) void tconv3_tile_kernel(TConv c, TTile g, const float *__restrict__ wp) {
+    extern __shared__ float t_smem[];
+    float *As = t_smem;                       // [9 * 16][TT_AP]   weights  (tap, channel) x cout
+    float *Hs = t_smem + 144 * TT_AP;         // [16][CHP]         halo tile of 16 input channels
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
+    T_DECODE_TILE_CB(b, cblk);
+    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y, img = b / (g.tiles_x * g.tiles_y);
+    const int y0 = ty * g.R, x0 = tx * g.TW, co0 = cblk * 64;
+    const int HW = c.H * c.W, HoWo = c.Ho * c.Wo;
+    // this lane's two pixel slots (MFMA columns)
+    int hb[2], opix[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int sl = 32 * wave + 16 * n + r;
+        const int ry = sl / g.TW, rx = sl - ry * g.TW;
+        const bool ok = ry < g.R && y0 + ry < c.Ho && x0 + rx < c.Wo;
+        hb[n] = ok ? ry * g.HC + rx : 0;
+        opix[n] = ok ? (y0 + ry) * c.Wo + x0 + rx : -1;
+    }
+    // halo elements this thread stages for every channel: offset inside the image plane (or -1 = zero padding)
+    int hoff[TT_MAXNI], hdst[TT_MAXNI];
+#pragma unroll
+    for (int i = 0; i < TT_MAXNI; ++i) {
+        const int e = t + 256 * i;
+        const int hy = e / g.HC, hx = e - hy * g.HC;
+        const int iy = y0 - c.pad + hy, ix = x0 - c.pad + hx;
+        const bool in = e < g.HR * g.HC;
+        hdst[i] = in ? e : -1;
+        hoff[i] = (in && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
+    }
+    const float *xb = c.x + (size_t)img * c.Cin * HW;
+    const int a_co = t & 63, a_r0 = t >> 6;
+    const bool a_ok = co0 + a_co < c.Cout;
+    const float *wa = wp + (a_ok ? co0 + a_co : 0);
+
+    t_f32x4 acc[4][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // software pipeline: the global loads of chunk c0 + 16 stay in flight (in registers) under the 288 MFMAs of chunk c0, so a
+    // block does not depend on its CU neighbour being in the opposite phase (co-resident blocks start together and stay in
+    // lockstep: both stage, then both compute at half rate each)
+    float rh[16 * TT_MAXNI];
+    float rw[36];
+    auto load = [&](int c0) {
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const int cok = (int)(c0 + kk < c.Cin);
+#pragma unroll
+            for (int i = 0; i < TT_MAXNI; ++i) {
+                const int ok = cok & (int)(hoff[i] >= 0);
+                rh[kk * TT_MAXNI + i] = xb[((c0 + kk) * HW + hoff[i]) & -ok];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 36; ++j) {            // row = tap * 16 + kk
+            const int row = a_r0 + 4 * j, tap = row >> 4, kk = row & 15;
+            const int ok = (int)(c0 + kk < c.Cin);
+            rw[j] = wa[((tap * c.Cin + c0 + kk) * c.Cout) & -ok];
+        }
+    };
+    load(0);
+    for (int c0 = 0; c0 < c.Cin; c0 += 16) {
+        __syncthreads();                          // the previous chunk's MFMAs have read their fragments
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+            for (int i = 0; i < TT_MAXNI; ++i)
+                if (hdst[i] >= 0) Hs[kk * g.CHP + hdst[i]] = (c0 + kk < c.Cin && hoff[i] >= 0) ? rh[kk * TT_MAXNI + i] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 36; ++j) {
+            const int row = a_r0 + 4 * j;
+            As[row * TT_AP + a_co] = (a_ok && c0 + (row & 15) < c.Cin) ? rw[j] : 0.f;
+        }
+        __syncthreads();
+        if (c0 + 16 < c.Cin) load(c0 + 16);
+        // 9 taps x 4 k-quads; the operands of the next step are read from LDS before the 8 MFMAs of the current one issue (the
+        // compiler's own schedule was read -> s_waitcnt lgkmcnt(0) -> 4 MFMAs, every LDS latency exposed).  The tap loop is
+        // NOT unrolled: fully unrolled the hoisted LDS addresses of 36 steps push the kernel past 256 VGPRs.
+        float a[2][4], bb[2][2];
+        auto frag = [&](int tap, int ks, float (&fa)[4], float (&fb)[2]) {
+            const int ty3 = tap / 3;
+            const int toff = ty3 * g.HC + (tap - 3 * ty3);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) fa[m] = As[(tap * 16 + 4 * ks + q) * TT_AP + 16 * m + r];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) fb[n] = Hs[(4 * ks + q) * g.CHP + hb[n] + toff];
+        };
+        frag(0, 0, a[0], bb[0]);
+#pragma unroll 1
+        for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                if (ks < 3) frag(tap, ks + 1, a[(ks + 1) & 1], bb[(ks + 1) & 1]);
+                else frag(tap < 8 ? tap + 1 : 8, 0, a[0], bb[0]);           // (the last one re-reads tap 8: harmless)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks & 1][m], bb[ks & 1][n], acc[m][n], 0, 0, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);      // next step's 6 LDS reads ...
+                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);      // ... then this step's 8 MFMAs
+            }
+        }
+    }
+    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
+    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
+    float bv[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
+        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
+    }
+    T_PIN16(bv);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int pok = (int)(opix[n] >= 0);
+        float *yb = c.y + (size_t)img * c.Cout * HoWo + (opix[n] & -pok);
+        float old[16];
+        if (c.accumulate) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int co = co0 + 16 * m + 4 * q + i;
+                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
+                }
+            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int co = co0 + 16 * m + 4 * q + i;
+                float v = acc[m][n][i];
+                v += bv[4 * m + i];
+                if (c.accumulate) v += old[4 * m + i];
+                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same 3x3 tile convolution on the bf16 matrix instruction with SPLIT operands ("bf16x3", opt-in through
+// pn_train_set_precision): every fp32 value v is staged as hi = bf16(v), lo = bf16(v - hi) (16 mantissa bits together) and
+// a product sum is hi*hi + hi*lo + lo*hi in fp32 accumulators (the dropped lo*lo term is 2^-16 relative) -- three
+// v_mfma_f32_16x16x32_bf16 (16 cycles each, K = 32) do the work of eight v_mfma_f32_16x16x4_f32 (32 cycles each): 5.3x less
+// matrix-pipe time for fp32-class results.  Chunks of 32 input channels; LDS images are [row][32 channels] bf16 with an
+// 80-byte pitch (16-byte fragment reads and 16-byte staging writes both conflict-free); the weight slice is staged one
+// kernel row (3 taps) at a time.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef __bf16 t_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned t_u32x4 __attribute__((ext_vector_type(4)));
+#define TX_PITCH 80                     // bytes per [32 x bf16] row
+#define TX_A_BYTES (3 * 64 * TX_PITCH)  // one plane of the weight slice of one kernel row
+
+__device__ __forceinline__ void t_split8(const float (&v)[8], unsigned okmask, t_bf16x8 &hi, t_bf16x8 &lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float x = (okmask >> j) & 1u ? v[j] : 0.f;
+        const __bf16 h = (__bf16)x;
+        hi[j] = h;
+        lo[j] = (__bf16)(x - (float)h);
+    }
+}
+
+// Weights of the split-bf16 kernel, packed once per launch in the LDS image's own order: wpx[plane][chunk of 32 ci][tap][cout][32 ci]
+// bf16 (plane 0 = hi, 1 = lo; channels beyond Cin are zero), so that staging a kernel row is six 16-byte copies per thread instead
+// of 24 dword loads + the split arithmetic per thread.  flip as in wpack3_kernel (the data gradient's rotated, transposed weights).
+__global__ void wpack3_x3_kernel(const float *__restrict__ w, __bf16 *__restrict__ wpx, int Cout, int Cin, int flip) {
+    const int chunks = (Cin + 31) / 32;
+    const size_t plane = (size_t)chunks * 9 * Cout * 32;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= plane) return;
+    const int ch = (int)(i & 31), co = (int)((i >> 5) % Cout), tap = (int)(((i >> 5) / Cout) % 9), chunk = (int)((i >> 5) / Cout / 9);
+    const int ci = chunk * 32 + ch;
+    float v = 0.f;
+    if (ci < Cin) v = flip ? w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : w[((size_t)co * Cin + ci) * 9 + tap];
+    const __bf16 h = (__bf16)v;
+    wpx[i] = h;
+    wpx[plane + i] = (__bf16)(v - (float)h);
+}
+
+// Every cached pack of a context refreshed by ONE launch (pn_train_pack_refresh): the block finds its descriptor (<= ~70 entries, scanned by
+// every thread: uniform) and runs wpack3_kernel's / wpack3_x3_kernel's element arithmetic on it -- the same values as the per-call packs.
+struct TPackDesc { const float *w; void *dst; int Cout, Cin, flip, x3; unsigned first_block, pad; };
+__global__ void wpack_all_kernel(const TPackDesc *__restrict__ tab, int n) {
+    int e = 0;
+    while (e + 1 < n && blockIdx.x >= tab[e + 1].first_block) ++e;
+    const TPackDesc d = tab[e];
+    const size_t i = (size_t)(blockIdx.x - d.first_block) * blockDim.x + threadIdx.x;
+    const int Cout = d.Cout, Cin = d.Cin;
+    if (d.x3) {
+        const int chunks = (Cin + 31) / 32;
+        const size_t plane = (size_t)chunks * 9 * Cout * 32;
+        if (i >= plane) return;
+        const int ch = (int)(i & 31), co = (int)((i >> 5) % Cout), tap = (int)(((i >> 5) / Cout) % 9), chunk = (int)((i >> 5) / Cout / 9);
+        const int ci = chunk * 32 + ch;
+        float v = 0.f;
+        if (ci < Cin) v = d.flip ? d.w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : d.w[((size_t)co * Cin + ci) * 9 + tap];
+        const __bf16 h = (__bf16)v;
+        __bf16 *wpx = (__bf16 *)d.dst;
+        wpx[i] = h;
+        wpx[plane + i] = (__bf16)(v - (float)h);
+    } else {
+        if (i >= (size_t)9 * Cin * Cout) return;
+        const int co = (int)(i % Cout), ci = (int)((i / Cout) % Cin), tap = (int)(i / ((size_t)Cout * Cin));
+        ((float *)d.dst)[i] = d.flip ? d.w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : d.w[((size_t)co * Cin + ci) * 9 + tap];
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g, const __bf16 *__restrict__ wpx) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char t_smem8[];
+    unsigned char *As_hi = t_smem8, *As_lo = t_smem8 + TX_A_BYTES;          // [3 taps][64 couts][32 ch]
+    unsigned char *Hs_hi = t_smem8 + 2 * TX_A_BYTES;                        // [halo pixel][32 ch]
+    unsigned char *Hs_lo = Hs_hi + g.HR * g.HC * TX_PITCH;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
+    T_DECODE_TILE_CB(b, cblk);
+    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y, img = b / (g.tiles_x * g.tiles_y);
+    const int y0 = ty * g.R, x0 = tx * g.TW, co0 = cblk * 64;
+    const int HW = c.H * c.W, HoWo = c.Ho * c.Wo, nhalo = g.HR * g.HC;
+    int hb[2], opix[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int sl = 32 * wave + 16 * n + r;
+        const int ry = sl / g.TW, rx = sl - ry * g.TW;
+        const bool ok = ry < g.R && y0 + ry < c.Ho && x0 + rx < c.Wo;
+        hb[n] = (ok ? ry * g.HC + rx : 0) * TX_PITCH + 16 * q;
+        opix[n] = ok ? (y0 + ry) * c.Wo + x0 + rx : -1;
+    }
+    // halo staging role: this wave stages channels 8 wave .. 8 wave + 7 of halo pixels lane + 64 i
+    constexpr int NH = 5;               // ceil(320 / 64): halo tiles have at most (2 + 2) x (64 + 2) = 264 pixels
+    int hoff[NH];
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+        const int e = lane + 64 * i;
+        const int hy = e / g.HC, hx = e - hy * g.HC;
+        const int iy = y0 - c.pad + hy, ix = x0 - c.pad + hx;
+        hoff[i] = (e < nhalo && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
+    }
+    const float *xb = c.x + (size_t)img * c.Cin * HW;
+    // weight staging role: per kernel row 3 taps x 64 couts x 4 segments of 8 channels x 2 planes = 1536 16-byte pieces, 6 per thread
+    const size_t wplane = (size_t)((c.Cin + 31) / 32) * 9 * c.Cout * 32;
+
+    t_f32x4 acc[4][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    t_u32x4 wv[6];                                     // the NEXT (chunk, kernel row) step's weight pieces of this thread
+    auto load_w = [&](int wc0, int wky) {
+        const __bf16 *wrow = wpx + ((size_t)(wc0 >> 5) * 9 + wky * 3) * c.Cout * 32;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int piece = t + 256 * j;                    // < 1536: plane, kx, cout, segment
+            const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
+            const int ok = (int)(co0 + co < c.Cout);
+            const size_t off = ((size_t)pl * wplane + ((size_t)kx * c.Cout + (size_t)((co0 + co) & -ok)) * 32 + seg * 8);
+            wv[j] = *reinterpret_cast<const t_u32x4 *>(wrow + off);       // (rows beyond Cout read row 0: zeroed when the piece is stored -- a select here would wait for the load)
+        }
+    };
+    load_w(0, 0);
+
+    for (int c0 = 0; c0 < c.Cin; c0 += 32) {
+        const int cbase = c0 + 8 * wave;
+        unsigned cmask = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cmask |= (unsigned)(cbase + j < c.Cin) << j;
+        // ---- halo tile of 32 channels (all loads first, then split + 16-byte stores) ----
+        float hv[NH][8];
+#pragma unroll
+        for (int i = 0; i < NH; ++i) {
+            const int okp = (int)(hoff[i] >= 0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) hv[i][j] = xb[((cbase + j) * HW + hoff[i]) & -(okp & (int)((cmask >> j) & 1u))];
+        }
+        __syncthreads();                              // the previous chunk's last kernel row has been consumed
+#pragma unroll
+        for (int i = 0; i < NH; ++i) {
+            const int e = lane + 64 * i;
+            if (e < nhalo) {
+                t_bf16x8 hi, lo;
+                t_split8(hv[i], hoff[i] >= 0 ? cmask : 0u, hi, lo);
+                *reinterpret_cast<t_bf16x8 *>(Hs_hi + e * TX_PITCH + 16 * wave) = hi;
+                *reinterpret_cast<t_bf16x8 *>(Hs_lo + e * TX_PITCH + 16 * wave) = lo;
+            }
+        }
+        for (int ky = 0; ky < 3; ++ky) {
+            // ---- weight slice of kernel row ky: [3 taps][64 couts][32 ch], straight 16-byte copies of the packed planes; fetched one
+            // (chunk, kernel row) step AHEAD (round 5): the loads of the next step are in flight under this step's MFMAs instead of in
+            // front of them -- three of a chunk's five exposed memory round trips gone ----
+            if (ky) __syncthreads();                  // the previous kernel row's fragments have been read
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const int piece = t + 256 * j;
+                const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
+                *reinterpret_cast<t_u32x4 *>((pl ? As_lo : As_hi) + (kx * 64 + co) * TX_PITCH + 16 * seg) = co0 + co < c.Cout ? wv[j] : t_u32x4{0u, 0u, 0u, 0u};
+            }
+            __syncthreads();
+            {   // ONE call site, always taken (past the last step: the current slice again, unused): two conditional sites merged the loaded
+                // registers through copies that waited for the loads right here
+                const int nc0 = ky == 2 ? c0 + 32 : c0, nky = ky == 2 ? 0 : ky + 1;
+                const bool more = nc0 < c.Cin;
+                load_w(more ? nc0 : c0, more ? nky : ky);
+            }
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int toff = (ky * g.HC + kx) * TX_PITCH;
+                t_bf16x8 bh[2], bl[2];
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    bh[n] = *reinterpret_cast<const t_bf16x8 *>(Hs_hi + hb[n] + toff);
+                    bl[n] = *reinterpret_cast<const t_bf16x8 *>(Hs_lo + hb[n] + toff);
+                }
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int ao = (kx * 64 + 16 * m + r) * TX_PITCH + 16 * q;
+                    const t_bf16x8 ah = *reinterpret_cast<const t_bf16x8 *>(As_hi + ao);
+                    const t_bf16x8 al = *reinterpret_cast<const t_bf16x8 *>(As_lo + ao);
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
+    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
+    float bv[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
+        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
+    }
+    T_PIN16(bv);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int pok = (int)(opix[n] >= 0);
+        float *yb = c.y + (size_t)img * c.Cout * HoWo + (opix[n] & -pok);
+        float old[16];
+        if (c.accumulate) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int co = co0 + 16 * m + 4 * q + i;
+                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
+                }
+            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int co = co0 + 16 * m + 4 * q + i;
+                float v = acc[m][n][i];
+                v += bv[4 * m + i];
+                if (c.accumulate) v += old[4 * m + i];
+                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
+            }
+    }
+}
+
+// Wide variant: 64 couts x 256 pixel slots per block, a wave owns 64 couts x 64 pixels (4 x 4 MFMA tiles): per tap 8 + 8 fragment
+// reads feed 48 MFMAs (the 128-slot kernel above: 8 + 4 for 24) and a block's packed weight slice -- the larger part of its
+// vector-memory bytes -- serves twice the pixels.  LDS images at a 64-byte pitch with the 16-byte segment XOR-swizzled by
+// (row >> 2) & 3: sixteen consecutive rows x one segment cover sixteen different 16-byte bank groups, for the staging stores and
+// for both operands' fragment reads, and two blocks still fit a CU (76 KB).
+#define TXW2_PITCH 64
+#define TXW2_A_BYTES (3 * 64 * TXW2_PITCH)
+__device__ __forceinline__ int t_swz(int row, int seg) { return row * TXW2_PITCH + 16 * (seg ^ ((row >> 2) & 3)); }
+
+__global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile g, const __bf16 *__restrict__ wpx) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char t_smem8[];
+    unsigned char *As_hi = t_smem8, *As_lo = t_smem8 + TXW2_A_BYTES;
+    unsigned char *Hs_hi = t_smem8 + 2 * TXW2_A_BYTES;
+    unsigned char *Hs_lo = Hs_hi + g.HR * g.HC * TXW2_PITCH;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
+    T_DECODE_TILE_CB(b, cblk);
+    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y, img = b / (g.tiles_x * g.tiles_y);
+    const int y0 = ty * g.R, x0 = tx * g.TW, co0 = cblk * 64;
+    const int HW = c.H * c.W, HoWo = c.Ho * c.Wo, nhalo = g.HR * g.HC;
+    int hbp[4], opix[4];                        // halo pixel of the slot's top-left tap, output pixel (or -1)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int sl = 64 * wave + 16 * n + r;
+        const int ry = sl / g.TW, rx = sl - ry * g.TW;
+        const bool ok = ry < g.R && y0 + ry < c.Ho && x0 + rx < c.Wo;
+        hbp[n] = ok ? ry * g.HC + rx : 0;
+        opix[n] = ok ? (y0 + ry) * c.Wo + x0 + rx : -1;
+    }
+    constexpr int NH = 7;                       // halo tiles have at most 400 pixels (t_tile_geometry_x3w)
+    int hoff[NH];
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+        const int e = lane + 64 * i;
+        const int hy = e / g.HC, hx = e - hy * g.HC;
+        const int iy = y0 - c.pad + hy, ix = x0 - c.pad + hx;
+        hoff[i] = (e < nhalo && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
+    }
+    const float *xb = c.x + (size_t)img * c.Cin * HW;
+    const size_t wplane = (size_t)((c.Cin + 31) / 32) * 9 * c.Cout * 32;
+
+    t_f32x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    t_u32x4 wv[6];                                     // the NEXT (chunk, kernel row) step's weight pieces of this thread
+    auto load_w = [&](int wc0, int wky) {
+        const __bf16 *wrow = wpx + ((size_t)(wc0 >> 5) * 9 + wky * 3) * c.Cout * 32;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int piece = t + 256 * j;
+            const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
+            const int ok = (int)(co0 + co < c.Cout);
+            const size_t off = ((size_t)pl * wplane + ((size_t)kx * c.Cout + (size_t)((co0 + co) & -ok)) * 32 + seg * 8);
+            wv[j] = *reinterpret_cast<const t_u32x4 *>(wrow + off);       // (rows beyond Cout read row 0: zeroed when the piece is stored -- a select here would wait for the load)
+        }
+    };
+    load_w(0, 0);
+
+    for (int c0 = 0; c0 < c.Cin; c0 += 32) {
+        const int cbase = c0 + 8 * wave;
+        unsigned cmask = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cmask |= (unsigned)(cbase + j < c.Cin) << j;
+        // halo of 32 channels, in two halves of the pixel range (56 prefetch registers would not fit next to 64 accumulators)
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            constexpr int I0[2] = {0, 4}, I1[2] = {4, NH};
+            float hv[4][8];
+#pragma unroll
+            for (int i = I0[half]; i < I1[half]; ++i) {
+                const int okp = (int)(hoff[i] >= 0);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    hv[i - I0[half]][j] = xb[((cbase + j) * HW + hoff[i]) & -(okp & (int)((cmask >> j) & 1u))];
+            }
+            if (half == 0) __syncthreads();       // the previous chunk's last kernel row has been consumed
+#pragma unroll
+            for (int i = I0[half]; i < I1[half]; ++i) {
+                const int e = lane + 64 * i;
+                if (e < nhalo) {
+                    t_bf16x8 hi, lo;
+                    t_split8(hv[i - I0[half]], hoff[i] >= 0 ? cmask : 0u, hi, lo);
+                    *reinterpret_cast<t_bf16x8 *>(Hs_hi + t_swz(e, wave)) = hi;
+                    *reinterpret_cast<t_bf16x8 *>(Hs_lo + t_swz(e, wave)) = lo;
+                }
+            }
+        }
+#pragma unroll 1
+        for (int ky = 0; ky < 3; ++ky) {
+            if (ky) __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const int piece = t + 256 * j;
+                const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
+                *reinterpret_cast<t_u32x4 *>((pl ? As_lo : As_hi) + t_swz(kx * 64 + co, seg)) = co0 + co < c.Cout ? wv[j] : t_u32x4{0u, 0u, 0u, 0u};
+            }
+            __syncthreads();
+            {   // the next step's weights, in flight under this step's MFMAs (see tconv3_tile_x3_kernel)
+                const int nc0 = ky == 2 ? c0 + 32 : c0, nky = ky == 2 ? 0 : ky + 1;
+                const bool more = nc0 < c.Cin;
+                load_w(more ? nc0 : c0, more ? nky : ky);
+            }
+#pragma unroll 1
+            for (int kx = 0; kx < 3; ++kx) {          // not unrolled: with three taps' fragments hoisted the kernel spills (124 B / lane)
+                t_bf16x8 bh[4], bl[4];
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const int o = t_swz(hbp[n] + ky * g.HC + kx, q);
+                    bh[n] = *reinterpret_cast<const t_bf16x8 *>(Hs_hi + o);
+                    bl[n] = *reinterpret_cast<const t_bf16x8 *>(Hs_lo + o);
+                }
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int ao = t_swz(kx * 64 + 16 * m + r, q);
+                    const t_bf16x8 ah = *reinterpret_cast<const t_bf16x8 *>(As_hi + ao);
+                    const t_bf16x8 al = *reinterpret_cast<const t_bf16x8 *>(As_lo + ao);
+#pragma unroll
+                    for (int n = 0; n < 4; ++n) {
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
+    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
+    float bv[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
+        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
+    }
+    T_PIN16(bv);
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int pok = (int)(opix[n] >= 0);
+        float *yb = c.y + (size_t)img * c.Cout * HoWo + (opix[n] & -pok);
+        float old[16];
+        if (c.accumulate) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int co = co0 + 16 * m + 4 * q + i;
+                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
+                }
+            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int co = co0 + 16 * m + 4 * q + i;
+                float v = acc[m][n][i];
+                v += bv[4 * m + i];
+                if (c.accumulate) v += old[4 * m + i];
+                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
+            }
+    }
+}
+
+// Weights for the data gradient: Wt[ci][(co, ky', kx')] = W[co][ci][KS-1-ky'][KS-1-kx']
+__global__ void wflip_kernel(const float *__restrict__ w, float *__restrict__ wt, int Cout, int Cin, int KS) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int KK = KS * KS, total = Cout * Cin * KK;
+    if (i >= total) return;
+    const int ci = i / (Cout * KK), rem = i - ci * Cout * KK, co = rem / KK, rr = rem - co * KK;
+    wt[i] = w[((size_t)co * Cin + ci) * KK + (KK - 1 - rr)];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The planes training engine's stem forward (round 6, late): model0.conv1 = 7x7 / 2, ONE input channel, 64 couts, on the same fp32 MFMA with the same
+// k order as tconv_fwd_kernel<7> (k = tap, four taps per v_mfma_f32_16x16x4_f32, k-steps in order: bit-identical), without that kernel's staging: it
+// gathers the [k][pixel] operand element by element for every 16-tap chunk and restages the weights per chunk (13.7 vector instructions per MFMA by
+// SQ_INSTS_VALU / SQ_INSTS_MFMA, 82 us at the head of the step).  With one input channel the operand of tap (ky, kx) IS the input image shifted by
+// (ky, kx): a block stages the 21 x 37 input patch of an 8 x 16 output tile once and every lane reads its B value at  base(pixel) + offset(tap)  --
+// thirteen per-lane tap offsets for the whole kernel; the 64 x 49 weight matrix is 52 A-fragment registers per lane, loaded once per block, and a
+// block walks tiles (two blocks per CU).  Alone 73 -> 41 us; beside the weight packs at the head of the step 82 -> 56 us.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int F32>
+__global__ __launch_bounds__(256) void tstem_fwd_kernel(TConv c, int tiles_x, int tiles_y, int ntiles) {
+    constexpr int TR = 8, TC = 16, IR = (TR - 1) * 2 + 7, IC = (TC - 1) * 2 + 7;      // output tile, input patch (21 x 37)
+    __shared__ float img[IR * IC];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
+    float a[4][13];
+    int tapoff[13];
+#pragma unroll
+    for (int s = 0; s < 13; ++s) {
+        const int k = 4 * s + q;
+        const bool ok = k < 49;
+        tapoff[s] = ok ? (k / 7) * IC + (k % 7) : 0;          // (a padding tap multiplies a zero weight with the patch's own first element)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) a[m][s] = ok ? c.w[(16 * (r >> 2) + 4 * m + (r & 3)) * 49 + k] : 0.f;      // row r of tile m = cout 16 (r >> 2) + 4 m + (r & 3): a lane's sixteen accumulators are couts 16 q ..+15
+    }
+    const int base0 = (2 * (2 * wave)) * IC + 2 * r, base1 = base0 + 2 * IC;      // this wave's two output rows of the tile, pixel column r
+    // the patch of tile n + 1 is fetched (four values per thread, all four loads in flight) while tile n runs: a block's round trip to the input is never exposed
+    // (the first form fetched and stored them one after the other at the head of the tile: four dependent round trips, 60 us for 17 us of MFMA work)
+    constexpr int NS = (IR * IC + 255) / 256;
+    float sv[NS];
+    unsigned sok = 0;
+    auto fetch = [&](int tile) {
+        const int b = tile / (tiles_x * tiles_y), rem = tile - b * (tiles_x * tiles_y), ty = rem / tiles_x, tx = rem - ty * tiles_x;
+        const int iy0 = ty * TR * 2 - 3, ix0 = tx * TC * 2 - 3;
+        const float *xb = c.x + (size_t)b * c.H * c.W;
+        sok = 0;
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+            const int i = t + 256 * u, rr = i / IC, cc = i - rr * IC, iy = iy0 + rr, ix = ix0 + cc;
+            const bool ok = i < IR * IC && (unsigned)iy < (unsigned)c.H && (unsigned)ix < (unsigned)c.W;
+            sv[u] = xb[ok ? iy * c.W + ix : 0];
+            sok |= (unsigned)ok << u;
+        }
+    };
+    if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int b = tile / (tiles_x * tiles_y), rem = tile - b * (tiles_x * tiles_y), ty = rem / tiles_x, tx = rem - ty * tiles_x;
+        const int oy0 = ty * TR, ox0 = tx * TC;
+        __syncthreads();                                       // the previous tile's reads are done
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+            if (t + 256 * u < IR * IC) img[t + 256 * u] = (sok >> u) & 1u ? sv[u] : 0.f;
+        __syncthreads();
+        fetch(min(tile + (int)gridDim.x, ntiles - 1));         // (unconditional: a straight-line loop body keeps the compiler's wait counts exact)
+        t_f32x4 acc[4][2];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[m][0] = acc[m][1] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 13; ++s) {
+            const float b0 = img[base0 + tapoff[s]], b1 = img[base1 + tapoff[s]];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][s], b0, acc[m][0], 0, 0, 0);
+                acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][s], b1, acc[m][1], 0, 0, 0);
+            }
+        }
+        // lane holds couts 16 q + 4 m + i of pixel (row 2 wave + n, column r): 32 contiguous bytes per plane, the four q lanes of a pixel one 128-byte line
+        // (with the natural row order -- couts 16 m + 4 q + i -- a line was written by four 8-byte stores per lane quartet: 76 us, as slow as the gather kernel)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int oy = oy0 + 2 * wave + n, ox = ox0 + r;
+            if (oy >= c.Ho || ox >= c.Wo) continue;
+            const size_t p = ((size_t)b * c.Ho + oy) * c.Wo + ox;
+            float v[16];
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[4 * m + i] = acc[m][n][i] + 0.f;          // (tconv_fwd_kernel adds its zero bias: -0 becomes +0 there as well)
+            if (F32) {
+                float *o = (float *)c.pl + p * c.pl_cs + 16 * q;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<t_f32x4 *>(o + 4 * j) = t_f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+            } else {
+                t_bf8 h[2], l[2];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const __bf16 hi = (__bf16)v[j];
+                    h[j >> 3][j & 7] = hi;
+                    l[j >> 3][j & 7] = (__bf16)(v[j] - (float)hi);
+                }
+                __bf16 *o = (__bf16 *)c.pl + p * c.pl_cs + 16 * q;
+                *reinterpret_cast<t_bf8 *>(o) = h[0];
+                *reinterpret_cast<t_bf8 *>(o + 8) = h[1];
+                *reinterpret_cast<t_bf8 *>(o + c.pl_split) = l[0];
+                *reinterpret_cast<t_bf8 *>(o + c.pl_split + 8) = l[1];
+            }
+        }
+    }
+}
