@@ -27,10 +27,18 @@ def _ctx(device):
     return _lib.Context.for_device(torch.device(device).index or 0)
 
 
+def _input_xy(input_size):
+    """input_size: one int (square) or (input_x, input_y)"""
+    if isinstance(input_size, (tuple, list)):
+        input_x, input_y = input_size
+        return int(input_x), int(input_y)
+    return int(input_size), int(input_size)
+
+
 def target_cfg(input_size=224, stride=8, z_radius=2, sigma=7.0):
     cfg = _lib.TargetCfg()
     _lib.lib().pn_target_cfg_default(C.byref(cfg))
-    cfg.input_x = cfg.input_y = int(input_size)
+    cfg.input_x, cfg.input_y = _input_xy(input_size)
     cfg.stride, cfg.z_radius, cfg.sigma = int(stride), int(z_radius), float(sigma)
     return cfg
 
@@ -60,23 +68,25 @@ def compose_depth(fg_depth, fg_mask, n_src, bg, depth_max=DEPTH_MAX):
 
 def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, stride=8, z_radius=2, sigma=7.0):
     """get_ground_truth for a batch.  kp2d [B,P,15,2] float32 (network-input pixels), kp_z [B,P,15] float64 (metres), n_persons [B]
-    int32, depth_resize [B,h,w] float32 -> (heat [B,16,h,w], paf [B,28,h,w], z [B,15,h,w], fg [B,15,h,w]) float32."""
+    int32, depth_resize [B,h,w] float32 -> (heat [B,16,h,w], paf [B,28,h,w], z [B,15,h,w], fg [B,15,h,w]) float32.
+    input_size: an int, or (input_x, input_y) for a network input that is not square; h = input_y // stride, w = input_x // stride."""
     for t, n in ((kp2d, "kp2d"), (kp_z, "kp_z"), (n_persons, "n_persons"), (depth_resize, "depth_resize")):
         _lib.require_cuda_tensor(t, n)
     if kp2d.dtype != torch.float32 or kp_z.dtype != torch.float64 or n_persons.dtype != torch.int32 or depth_resize.dtype != torch.float32:
         raise _lib.PopnetError("rasterize_targets: kp2d float32, kp_z float64, n_persons int32, depth_resize float32")
     B, P = kp2d.shape[0], kp2d.shape[1]
-    g = int(input_size / stride)
-    if kp2d.shape != (B, P, NUM_JOINTS, 2) or kp_z.shape != (B, P, NUM_JOINTS) or n_persons.shape != (B,) or depth_resize.shape != (B, g, g):
+    input_x, input_y = _input_xy(input_size)
+    gh, gw = int(input_y / stride), int(input_x / stride)
+    if kp2d.shape != (B, P, NUM_JOINTS, 2) or kp_z.shape != (B, P, NUM_JOINTS) or n_persons.shape != (B,) or depth_resize.shape != (B, gh, gw):
         raise _lib.PopnetError("rasterize_targets: shape mismatch")
     dev = kp2d.device
     if P == 0:      # nobody annotated anywhere in the batch: one dummy slot that n_persons = 0 never reads
         kp2d, kp_z, P = torch.zeros((B, 1, NUM_JOINTS, 2), dtype=torch.float32, device=dev), torch.zeros((B, 1, NUM_JOINTS), dtype=torch.float64, device=dev), 1
     kp2d, kp_z, n_persons, depth_resize = kp2d.contiguous(), kp_z.contiguous(), n_persons.contiguous(), depth_resize.contiguous()
-    heat = torch.empty((B, NUM_JOINTS + 1, g, g), dtype=torch.float32, device=dev)
-    paf = torch.empty((B, 2 * NUM_LIMBS, g, g), dtype=torch.float32, device=dev)
-    z = torch.empty((B, NUM_JOINTS, g, g), dtype=torch.float32, device=dev)
-    fg = torch.empty((B, NUM_JOINTS, g, g), dtype=torch.float32, device=dev)
+    heat = torch.empty((B, NUM_JOINTS + 1, gh, gw), dtype=torch.float32, device=dev)
+    paf = torch.empty((B, 2 * NUM_LIMBS, gh, gw), dtype=torch.float32, device=dev)
+    z = torch.empty((B, NUM_JOINTS, gh, gw), dtype=torch.float32, device=dev)
+    fg = torch.empty((B, NUM_JOINTS, gh, gw), dtype=torch.float32, device=dev)
     cfg = target_cfg(input_size, stride, z_radius, sigma)
     ctx = _ctx(dev)
     ctx.check(_lib.lib().pn_rasterize_targets(ctx.handle, C.c_void_p(kp2d.data_ptr()), C.c_void_p(kp_z.data_ptr()), C.c_void_p(n_persons.data_ptr()),
