@@ -1,11 +1,18 @@
-// Which kernel runs a convolution and on what tile geometry: ONE rule set for the inference nets (net.hip::prepare_conv) and the training
-// engine (trainx.hip), so a training-mode convolution runs exactly the kernel / tiling the inference plan would pick for the same shape
-// (and is covered by the same bit-identity tests).  Moved here from net.hip in round 6, unchanged.
+// The convolution launch planner: ONE rule set for the inference nets (net.hip) and the planes training engine (trainx.hip), so a training-mode
+// convolution runs exactly the kernel / tiling / launch the inference plan would pick for the same shape (and is covered by the same bit-identity tests).
+//   pn_plan_level                              what a level of independent convolutions decides together (conv4 or not, shared 128-cout blocks)
+//   pn_plan_conv_kernel / pn_plan_conv_tiles   which kernel runs one convolution, on what tiles
+//   pn_conv_block_couts / pn_conv_cout_pad / pn_conv_pack_frags / pn_conv_pack_bytes     the cout block and the size of the weight pack that follow from it
+//   pn_conv_same_launch                        may two planned convolutions share a kernel instantiation (one launch, blockIdx.y = problem)
+//   pn_fill_conv_problem / pn_fill_conv_launch the geometry fields of the device descriptors
+// What stays with the callers: where weights, biases and tensors live, the epilogue (act, residual, NCHW copy), and the nets' fused tails / pools / mixed launches.
 #pragma once
 #include <algorithm>
+#include <vector>
 #include "pn_internal.h"
 
 struct ConvGeom {
+    int ks = 3, stride = 1;                             // set by the caller; everything below is planned
     int kern = 0, cfg = 0, pitch = 0, R = 0, Wt = 0;
     int wc = 0, wp = 0, nbuf = 0, pt = 7, rpg = 4;      // kern 3: conv3_kernel<ks, wc, wp, nbuf, pt, rpg>
 };
@@ -24,11 +31,53 @@ inline int pn_pick_cfg(int cout) {
     return PN_CFG_C32;
 }
 
-// prec: PN_PREC_BF16 for the bf16 / bf16x3 nets, PN_PREC_F32 otherwise.  H, W: input map; the caller has set g.pt / g.rpg defaults (7 / 4).
-// wc_min / nbuf_min / k4_level: what net.hip::harmonize_level decided for the level this convolution belongs to.  sw: the switches of the
-// net or trainer being compiled.
-inline void pn_plan_conv_kernel(int prec, int max_batch, int num_cus, int H, int W, int cout, int ks, int stride, int cin_chunks, int wc_min, int nbuf_min,
-                                int k4_level, const PnSwitches &sw, ConvGeom &g) {
+// One convolution of a level of independent convolutions (the three branches of a stage; a BasicBlock's 3x3 and its 1x1 shortcut).  In: the input map,
+// rows = output channels (a data gradient: its output plane), ks / stride, cin_gt64 = more than one 64-channel chunk of input.  Out: what the level decided.
+struct PnLevelConv {
+    int H, W, rows, ks, stride;
+    bool cin_gt64;
+    int k4_level = 0, wc_min = 0, nbuf_min = 0;
+};
+
+// conv4: PnSwitches::conv4 (-1 by block count, 0 never, 1 whenever eligible).
+inline void pn_plan_level(std::vector<PnLevelConv> &lv, int max_batch, bool x3, int conv4) {
+    // conv4_kernel: the level has a stride-1 3x3 conv with >= 64 couts and Cin >= 128 (bf16x3: any Cin -- three plane pairs).  Its 128-cout x 224-pixel
+    // blocks need >= 2 per CU to pay (profiles/README.md r02: level of 448 blocks 37.5 vs 40.4 us, level of 224 blocks 18.5 vs 12.5 us against
+    // conv3_kernel): by block count = when the level's 3x3 convs make at least 448 such blocks at max_batch
+    bool k4 = false;
+    long blocks = 0;
+    for (const PnLevelConv &c : lv) {
+        if (c.ks != 3 || c.stride != 1 || c.rows < 64) continue;
+        if (x3 || c.cin_gt64) k4 = true;
+        const long strips = (long)max_batch * ((c.H + 3) / 4) * ((c.W + 29) / 30);
+        blocks += ((strips + 1) / 2) * ((c.rows + 127) / 128);
+    }
+    if (conv4 < 0 ? blocks < 448 : conv4 == 0) k4 = false;
+    for (PnLevelConv &c : lv) c.k4_level = k4 ? 1 : 0;
+    // a 33..64-cout conv next to a wider sibling of the same kernel size takes the sibling's 128-cout block (its two surplus waves only help with the
+    // halo DMA, conv3_kernel.h) and the double-buffered variant -- one launch instead of two
+    for (int ks : {1, 3}) {
+        bool wide = false, multi = false;
+        for (const PnLevelConv &c : lv) {
+            if (c.ks != ks || c.stride != 1) continue;
+            if (c.rows > 64) wide = true;
+            if (c.cin_gt64) multi = true;
+        }
+        if (!wide) continue;
+        for (PnLevelConv &c : lv) {
+            if (c.ks != ks || c.stride != 1 || c.rows <= 32) continue;
+            c.wc_min = 4;
+            if (multi) c.nbuf_min = 2;
+        }
+    }
+}
+
+// prec: PN_PREC_BF16 for the bf16 / bf16x3 nets, PN_PREC_F32 otherwise.  H, W: input map; the caller has set g.ks / g.stride (g.pt / g.rpg at their
+// defaults 7 / 4).  wc_min / nbuf_min / k4_level: what pn_plan_level decided for the level this convolution belongs to (0 for a convolution planned
+// alone).  sw: the switches of the net or trainer being compiled.
+inline void pn_plan_conv_kernel(int prec, int max_batch, int num_cus, int H, int W, int cout, int cin_chunks, int wc_min, int nbuf_min, int k4_level,
+                                const PnSwitches &sw, ConvGeom &g) {
+    const int ks = g.ks, stride = g.stride;
     g.cfg = pn_pick_cfg(cout);
     {   // bf16 stride-1 layers run conv3_kernel (conv3_kernel.h) when the map splits into column strips (<= 30 wide: the
         // halo row is 32 pixels) whose 4-row tiles fill >= 75 % of a wave group's 112 pixel slots
@@ -75,7 +124,8 @@ inline void pn_plan_conv_kernel(int prec, int max_batch, int num_cus, int H, int
 
 // Tile geometry of the chosen kernel (kern 3 / 4: the strip tiles are already in g; the generic kernel: rows x segments of its pixel tile).
 // Returns PN_OK, or a negative status with *why set (the caller formats the message).
-inline int pn_plan_conv_tiles(int prec, int H, int W, int ks, int stride, ConvGeom &g, const char **why) {
+inline int pn_plan_conv_tiles(int prec, int H, int W, ConvGeom &g, const char **why) {
+    const int ks = g.ks, stride = g.stride;
     const int Ho = (H + 2 * (ks / 2) - ks) / stride + 1, Wo = (W + 2 * (ks / 2) - ks) / stride + 1;
     if (g.kern == 3 || g.kern == 4) { g.pitch = 32; return PN_OK; }
     if (g.cfg == PN_CFG_C64 && ks == 3 && stride == 1 && Wo >= 48 && (long)Ho * Wo >= 2048) g.cfg = PN_CFG_C64W;   // wide maps: 224-pixel tiles
@@ -93,4 +143,66 @@ inline int pn_plan_conv_tiles(int prec, int H, int W, int ks, int stride, ConvGe
     g.pitch = pn_pick_pitch((g.Wt - 1) * stride + ks);
     if (g.pitch < 0) { *why = "halo width has no pitch class"; return PN_ERR_UNSUPPORTED; }
     return PN_OK;
+}
+
+// ---- what follows from the chosen kernel and tiles ----------------------------------------------------------------------------------------------------
+// output channels per block, and `cout` padded to whole blocks (the rows of the weight pack and of the padded bias)
+inline int pn_conv_block_couts(const ConvGeom &g) { return g.kern == 4 ? 128 : (g.kern == 3 ? g.wc * 32 : pn_cfg_couts(g.cfg)); }
+inline int pn_conv_cout_pad(const ConvGeom &g, int cout) { const int BC = pn_conv_block_couts(g); return (cout + BC - 1) / BC * BC; }
+// Weight pack: fragments [64 lanes][8 values] (1 KB bf16, 2 KB fp32) that hold weights.  conv4: [cout block][k-step (+3 spare)][8 tiles]; the others:
+// [16-cout tile][k-step], and 5 spare fragments behind the last (the weight queue prefetches up to 5 k-steps ahead) -- counted in the bytes only.
+inline size_t pn_conv_pack_frags(const ConvGeom &g, int cout_pad, int ksteps) {
+    return g.kern == 4 ? (size_t)(cout_pad / 128) * (ksteps + 3) * 8 : (size_t)(cout_pad / 16) * ksteps;
+}
+inline size_t pn_conv_pack_bytes(int prec, const ConvGeom &g, int cout_pad, int ksteps) {
+    return (pn_conv_pack_frags(g, cout_pad, ksteps) + (g.kern == 4 ? 0 : 5)) * (prec == PN_PREC_BF16 ? 1024 : 2048);
+}
+
+// two planned convolutions run the same kernel instantiation
+inline bool pn_conv_same_launch(const ConvGeom &a, const ConvGeom &b) {
+    return b.ks == a.ks && b.stride == a.stride && b.pitch == a.pitch && b.R == a.R && b.Wt == a.Wt && b.kern == a.kern &&
+           (a.kern == 4 || (a.kern == 3 ? (b.wc == a.wc && b.wp == a.wp && b.nbuf == a.nbuf && b.pt == a.pt && b.rpg == a.rpg) : b.cfg == a.cfg));
+}
+
+// The input tensor of a convolution problem: NHWC with channel stride cs; plane = channels of one stored plane (bf16x3: two planes [hi | lo], cs = 2 * plane);
+// bytes = size of the whole tensor at the batch it was allocated for, where its zero page starts (the padding source of the halo DMA).
+struct PnConvInput { const void *p; int H, W, cs, plane; size_t bytes; };
+
+// Fills the geometry of a zeroed ConvProblem.  The caller adds what is its own: weights / bias, in_coff, out / res / nchw, act, yolo_naf (and the nets'
+// fused tail / pool overrides).
+inline void pn_fill_conv_problem(ConvProblem &P, const PnConvInput &in, int B, int cin_chunks, int cout, const ConvGeom &g, int prec, bool x3) {
+    P.in = in.p;
+    P.B = B; P.H = in.H; P.W = in.W;
+    P.Ho = (in.H + 2 * (g.ks / 2) - g.ks) / g.stride + 1;
+    P.Wo = (in.W + 2 * (g.ks / 2) - g.ks) / g.stride + 1;
+    P.cin_chunks = cin_chunks;
+    P.in_cs = in.cs;
+    P.in_wrap = x3 ? 2 * (in.plane / 64) : (1 << 20);      // (conv4_kernel doubles it: halves)
+    P.cout = cout;
+    P.R = g.R;
+    P.Wt = g.Wt;
+    P.tiles_x = (P.Wo + g.Wt - 1) / g.Wt;
+    P.tiles_per_img = ((P.Ho + g.R - 1) / g.R) * P.tiles_x;
+    const int BC = pn_conv_block_couts(g);
+    P.cout_blocks = (cout + BC - 1) / BC;
+    P.nblocks = B * P.tiles_per_img * P.cout_blocks;
+    if (g.kern == 4) P.nblocks = ((B * P.tiles_per_img + 1) / 2) * P.cout_blocks;      // a block = two strips x 128 couts
+    P.ksteps = cin_chunks * g.ks * g.ks * 2;
+    P.ks = g.ks;
+    P.lds_buf_bytes = (int)pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R);
+    P.lds_two = (cin_chunks > 1 && 2 * (size_t)P.lds_buf_bytes <= 160 * 1024) ? 1 : 0;
+    P.in_zero_off = (unsigned)in.bytes;
+}
+
+// Fills a launch of nprob problems that share the geometry g (pn_conv_same_launch); two_bufs: a problem has lds_two set.  probs_dev is the caller's.
+inline void pn_fill_conv_launch(ConvLaunch &L, int prec, const ConvGeom &g, int nprob, int max_blocks, bool two_bufs) {
+    L.prec = prec;
+    L.ks = g.ks; L.stride = g.stride; L.pitch = g.pitch; L.cfg = g.cfg;
+    L.kern = g.kern; L.wc = g.wc; L.wp = g.wp; L.nbuf = g.nbuf; L.pt = g.pt; L.rpg = g.rpg;
+    L.tail = 0; L.mix = 0;
+    L.nprob = nprob;
+    L.max_blocks = max_blocks;
+    L.lds_bytes = pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R) * (two_bufs ? 2 : 1);
+    if (g.kern == 3) L.lds_bytes = pn_conv3_lds_bytes(g.ks, g.wp, g.nbuf, g.rpg);
+    if (g.kern == 4) L.lds_bytes = 0;                        // conv4_launch knows its own size
 }

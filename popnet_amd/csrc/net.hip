@@ -37,10 +37,9 @@ struct Buf {
     int plane = 0;             // bf16x3: channels of one of the two stored planes [hi | lo] (C = 2 * plane); otherwise = C
 };
 
-struct ConvSpec {
+struct ConvSpec : ConvGeom {    // ks / stride as given; kernel and tiles as planned (conv_plan.h)
     std::string w;            // "<prefix>" of "<prefix>.weight" (and ".bias" when present)
     std::string bn;           // BN prefix or ""
-    int ks = 3, stride = 1;
     int in_buf = -1, in_coff = 0, cin = 0;
     std::vector<int> cin_map; // my input channel -> reference input channel (-1 = zero); empty = identity
     int out_buf = -1, out_coff = 0;
@@ -49,8 +48,7 @@ struct ConvSpec {
     int nchw_slot = -1;       // index into pn_net::nchw_ptr or -1
     int cout = 0;
     // derived
-    int cfg = 0, pitch = 0, R = 0, Wt = 0, cin_chunks = 0;
-    int kern = 0, wc = 0, wp = 0, nbuf = 0, pt = 7, rpg = 4;   // kern 3: conv3_kernel<ks, wc, wp, nbuf, pt, rpg> (bf16, stride 1, strip tiles)
+    int cin_chunks = 0;
     int wc_min = 0, nbuf_min = 0;             // set by harmonize_level: share the launch of a wider sibling conv
     int k4_level = 0;                         // set by harmonize_level: a 3x3 conv of this level has Cin >= 128 and >= 64 couts (conv4_kernel)
     void *wpack = nullptr;
@@ -90,14 +88,6 @@ struct Step {
     std::vector<ConvProblem> host_probs;
     ConvProblem *dev_probs = nullptr;
 };
-
-uint16_t f32_to_bf16(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 
 }  // namespace
 
@@ -227,27 +217,18 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
         if (cs.embed3 && tap != 4) return 0.f;
         const float v = (float)((double)w->data[cs.embed3 ? (size_t)co * cin_ref + ci : ((size_t)co * cin_ref + ci) * (ks * ks) + tap] * scale[co]);
         if (!n->x3) return v;
-        uint32_t hb = (uint32_t)f32_to_bf16(v) << 16;
-        float hi;
-        memcpy(&hi, &hb, 4);
+        const float hi = pn_bf16_to_f32(pn_f32_to_bf16(v));
         return wsel[idx] ? v - hi : hi;
     };
 
-    ConvGeom geo;                                  // which kernel, on what tiles: conv_plan.h (shared with the training engine)
-    geo.pt = cs.pt; geo.rpg = cs.rpg;
-    {
-        const Buf &ib0 = n->bufs[cs.in_buf];
-        pn_plan_conv_kernel(n->prec, n->max_batch, n->ctx->num_cus, ib0.H, ib0.W, cout, ks, cs.stride, cs.cin_chunks, cs.wc_min, cs.nbuf_min, cs.k4_level, n->sw, geo);
-    }
-    cs.cfg = geo.cfg; cs.kern = geo.kern; cs.wc = geo.wc; cs.wp = geo.wp; cs.nbuf = geo.nbuf; cs.pt = geo.pt; cs.rpg = geo.rpg; cs.Wt = geo.Wt; cs.R = geo.R;
-    const int BC = cs.kern == 4 ? 128 : (cs.kern == 3 ? cs.wc * 32 : pn_cfg_couts(cs.cfg));
-    const int cout_pad = (cout + BC - 1) / BC * BC;
+    const Buf &ib = n->bufs[cs.in_buf];
+    pn_plan_conv_kernel(n->prec, n->max_batch, n->ctx->num_cus, ib.H, ib.W, cout, cs.cin_chunks, cs.wc_min, cs.nbuf_min, cs.k4_level, n->sw, cs);   // which kernel ...
+    const int cout_pad = pn_conv_cout_pad(cs, cout);
     const int ctiles = cout_pad / 16;
     const int KK = ks * ks;
     const int ksteps = cs.cin_chunks * KK * 2;
-    const size_t fragb = n->prec == PN_PREC_BF16 ? 1024 : 2048;
-    const size_t bytes = cs.kern == 4 ? (size_t)(cout_pad / 128) * (ksteps + 3) * 8192      // conv4: [cout block][k-step (+3 spare)][8 tiles][lane][8]
-                                      : (size_t)ctiles * ksteps * fragb + 5 * fragb;   // + spare fragments (the weight queue prefetches up to 5 k-steps ahead)
+    const size_t kstride4 = pn_conv_pack_frags(cs, 128, ksteps) / 8;      // conv4: k-steps of one cout block, the spare ones included
+    const size_t bytes = pn_conv_pack_bytes(n->prec, cs, cout_pad, ksteps);
     std::vector<unsigned char> host(bytes, 0);
     uint16_t *h16 = reinterpret_cast<uint16_t *>(host.data());
     float *h32 = reinterpret_cast<float *>(host.data());
@@ -258,8 +239,8 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
                     for (int t = 0; t < 8; ++t)
                         for (int lane = 0; lane < 64; ++lane) {
                             const int co = cbk * 128 + pn_conv_row_channel(t, lane & 15, 4), q = lane >> 4;
-                            const size_t base = ((((size_t)cbk * (ksteps + 3) + (size_t)hh * KK + tap) * 8 + t) * 64 + lane) * 8;
-                            for (int j = 0; j < 8; ++j) h16[base + j] = f32_to_bf16(wval(co, hh * 32 + 8 * q + j, tap));
+                            const size_t base = ((((size_t)cbk * kstride4 + (size_t)hh * KK + tap) * 8 + t) * 64 + lane) * 8;
+                            for (int j = 0; j < 8; ++j) h16[base + j] = pn_f32_to_bf16(wval(co, hh * 32 + 8 * q + j, tap));
                         }
     } else
     for (int ct = 0; ct < ctiles; ++ct)
@@ -272,7 +253,7 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
                         const int co = pn_conv_row_channel(ct, lane & 15, cs.kern == 3 ? 2 : pn_cfg_ct(cs.cfg)), q = lane >> 4;
                         for (int j = 0; j < 8; ++j) {
                             const float v = wval(co, chunk * 64 + sub * 32 + 8 * q + j, tap);
-                            if (n->prec == PN_PREC_BF16) h16[(frag * 64 + lane) * 8 + j] = f32_to_bf16(v);
+                            if (n->prec == PN_PREC_BF16) h16[(frag * 64 + lane) * 8 + j] = pn_f32_to_bf16(v);
                             else h32[frag * 512 + (size_t)(j >> 2) * 256 + lane * 4 + (j & 3)] = v;
                         }
                     }
@@ -285,13 +266,9 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
     PN_HIP_CHECK(ctx, hipMemcpy(cs.bias, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
 
     // geometry
-    const Buf &ib = n->bufs[cs.in_buf];
     const int Ho = (ib.H + 2 * (ks / 2) - ks) / cs.stride + 1, Wo = (ib.W + 2 * (ks / 2) - ks) / cs.stride + 1;
-    {
-        const char *why = "";
-        if (int rc = pn_plan_conv_tiles(n->prec, ib.H, ib.W, ks, cs.stride, geo, &why)) return pn_set_error(ctx, rc, "%s: %s", cs.w.c_str(), why);
-        cs.cfg = geo.cfg; cs.pitch = geo.pitch; cs.Wt = geo.Wt; cs.R = geo.R;
-    }
+    const char *why = "";
+    if (int rc = pn_plan_conv_tiles(n->prec, ib.H, ib.W, cs, &why)) return pn_set_error(ctx, rc, "%s: %s", cs.w.c_str(), why);      // ... on what tiles
     cs.flops = 2.0 * Ho * Wo * (double)cout * cin_ref * (cs.embed3 ? 1 : KK);
     if (cs.out_buf >= 0) {
         const Buf &ob = n->bufs[cs.out_buf];
@@ -313,50 +290,25 @@ int add_conv(pn_net *n, const std::string &w, const std::string &bn, int ks, int
     return (int)n->convs.size() - 1;
 }
 
-// Independent convs of one level that could share a launch but for their block shape: a 33..64-cout conv next
-// to a wider sibling of the same kernel size takes the sibling's 128-cout block (its two surplus waves only
-// help with the halo DMA, conv3_kernel.h) and the double-buffered variant -- one launch instead of two.
+// What a level of independent convs decides together (conv_plan.h::pn_plan_level): here only the weight-shape lookup that feeds it.
 void harmonize_level(pn_net *n, const std::vector<int> &ids) {
-    {
-        bool k4 = false;
-        for (int id : ids) {
-            const ConvSpec &c = n->convs[id];
-            const HostTensor *w = find_t(n, c.w + ".weight");
-            if (w && w->shape.size() == 4 && c.ks == 3 && c.stride == 1 && w->shape[0] >= 64 && (n->x3 || std::max<int64_t>(w->shape[1], (int64_t)c.cin_map.size()) > 64)) k4 = true;
-        }
-        // conv4's 128-cout x 224-pixel blocks need >= 2 per CU to pay (profiles/README.md r02: level of 448 blocks 37.5 vs
-        // 40.4 us, level of 224 blocks 18.5 vs 12.5 us against conv3_kernel): POPNET_CONV4 = 0 never, 1 whenever eligible,
-        // unset = when the level's 3x3 convs make at least 448 such blocks at max_batch
-        long blocks = 0;
-        for (int id : ids) {
-            const ConvSpec &c = n->convs[id];
-            const HostTensor *w = find_t(n, c.w + ".weight");
-            if (!w || w->shape.size() != 4 || c.ks != 3 || c.stride != 1 || w->shape[0] < 64) continue;
-            const Buf &ib = n->bufs[c.in_buf];
-            const long strips = (long)n->max_batch * ((ib.H + 3) / 4) * ((ib.W + 29) / 30);
-            blocks += ((strips + 1) / 2) * ((w->shape[0] + 127) / 128);
-        }
-        if (n->sw.conv4 < 0 ? blocks < 448 : n->sw.conv4 == 0) k4 = false;
-        if (k4)
-            for (int id : ids) n->convs[id].k4_level = 1;
+    std::vector<PnLevelConv> lv;
+    std::vector<int> which;
+    for (int id : ids) {
+        const ConvSpec &c = n->convs[id];
+        const HostTensor *w = find_t(n, c.w + ".weight");
+        if (!w || w->shape.size() != 4) continue;          // prepare_conv reports it
+        const Buf &ib = n->bufs[c.in_buf];
+        PnLevelConv l;
+        l.H = ib.H; l.W = ib.W; l.rows = (int)w->shape[0]; l.ks = c.ks; l.stride = c.stride;
+        l.cin_gt64 = std::max<int64_t>(w->shape[1], (int64_t)c.cin_map.size()) > 64;      // (a cin_map is never shorter than the weight's Cin: build_rtpose)
+        lv.push_back(l);
+        which.push_back(id);
     }
-    for (int ks : {1, 3}) {
-        bool wide = false, multi = false;
-        for (int id : ids) {
-            const ConvSpec &c = n->convs[id];
-            const HostTensor *w = find_t(n, c.w + ".weight");
-            if (!w || w->shape.size() != 4 || c.ks != ks || c.stride != 1) continue;
-            if (w->shape[0] > 64) wide = true;
-            if (w->shape[1] > 64) multi = true;
-        }
-        if (!wide) continue;
-        for (int id : ids) {
-            ConvSpec &c = n->convs[id];
-            const HostTensor *w = find_t(n, c.w + ".weight");
-            if (!w || w->shape.size() != 4 || c.ks != ks || c.stride != 1 || w->shape[0] <= 32) continue;
-            c.wc_min = 4;
-            if (multi) c.nbuf_min = 2;
-        }
+    pn_plan_level(lv, n->max_batch, n->x3, n->sw.conv4);
+    for (size_t i = 0; i < lv.size(); ++i) {
+        ConvSpec &c = n->convs[which[i]];
+        c.k4_level = lv[i].k4_level; c.wc_min = lv[i].wc_min; c.nbuf_min = lv[i].nbuf_min;
     }
 }
 
@@ -375,8 +327,7 @@ void add_conv_level(pn_net *n, const std::vector<int> &ids) {
         for (size_t j = i; j < ids.size(); ++j) {
             const ConvSpec &b = n->convs[ids[j]];
             if (used[j]) continue;
-            const bool same = (b.tail_conv >= 0) == (a.tail_conv >= 0) && b.pool_tail == a.pool_tail && b.ks == a.ks && b.stride == a.stride && b.pitch == a.pitch && b.R == a.R && b.Wt == a.Wt && b.kern == a.kern &&
-                (a.kern == 4 || (a.kern == 3 ? (b.wc == a.wc && b.wp == a.wp && b.nbuf == a.nbuf && b.pt == a.pt && b.rpg == a.rpg) : b.cfg == a.cfg));
+            const bool same = (b.tail_conv >= 0) == (a.tail_conv >= 0) && b.pool_tail == a.pool_tail && pn_conv_same_launch(a, b);
             const bool mixed = !n->sw.no_mix && mixable(a) && mixable(b) && b.R == a.R && b.Wt == a.Wt && (a.ks == 3 || b.ks == 3 || (a.tail_conv >= 0) == (b.tail_conv >= 0));
             if (same || mixed) {
                 st.conv_ids.push_back(ids[j]);
@@ -451,12 +402,9 @@ int add_stem(pn_net *n, int out_buf) {
                     for (int j = 0; j < 8; ++j) {
                         float v = 0.f;
                         if (ky < 7 && j >= 1) v = hw[(ky * 7 + (j - 1)) * 64 + co];
-                        const uint16_t hb = f32_to_bf16(v);
+                        const uint16_t hb = pn_f32_to_bf16(v);
                         hf[((t * 2 + s2) * 64 + lane) * 8 + j] = hb;
-                        uint32_t hu = (uint32_t)hb << 16;
-                        float hi;
-                        memcpy(&hi, &hu, 4);
-                        hf[((8 + t * 2 + s2) * 64 + lane) * 8 + j] = f32_to_bf16(v - hi);
+                        hf[((8 + t * 2 + s2) * 64 + lane) * 8 + j] = pn_f32_to_bf16(v - pn_bf16_to_f32(hb));
                     }
                 }
         if (int rc = dev_alloc(n, &st.stem_wfrag, hf.size() * 2, false)) return rc;
@@ -541,12 +489,9 @@ int add_bblock(pn_net *n, int ia, int ib) {
                         for (int j = 0; j < 8; ++j) {
                             const int ci = hh * 32 + 8 * q + j;
                             const float v = (float)((double)w->data[((size_t)co * 64 + ci) * 9 + tap] * scale[co]);
-                            if (!n->x3) { pk[base + j] = f32_to_bf16(v); continue; }
-                            const uint16_t hbits = f32_to_bf16(v);
-                            uint32_t hu = (uint32_t)hbits << 16;
-                            float hi;
-                            memcpy(&hi, &hu, 4);
-                            pk[base + j] = sel ? f32_to_bf16(v - hi) : hbits;
+                            if (!n->x3) { pk[base + j] = pn_f32_to_bf16(v); continue; }
+                            const uint16_t hbits = pn_f32_to_bf16(v);
+                            pk[base + j] = sel ? pn_f32_to_bf16(v - pn_bf16_to_f32(hbits)) : hbits;
                         }
                     }
     }
@@ -666,7 +611,7 @@ int pack_tail(pn_net *n, ConvSpec &a) {
                 const int co = pn_conv_row_channel(t, lane & 15, 2), q = lane >> 4;
                 for (int j = 0; j < 8; ++j) {
                     const int ci = ks * 32 + 8 * q + j;
-                    pk[(((size_t)t * 4 + ks) * 64 + lane) * 8 + j] = f32_to_bf16(co < cout ? w->data[(size_t)co * 128 + ci] : 0.f);
+                    pk[(((size_t)t * 4 + ks) * 64 + lane) * 8 + j] = pn_f32_to_bf16(co < cout ? w->data[(size_t)co * 128 + ci] : 0.f);
                 }
             }
     if (int rc = dev_alloc(n, &a.tail_wpack, pk.size() * 2, false)) return rc;
@@ -841,46 +786,25 @@ int refresh_problems(pn_net *n, int B, hipStream_t stream) {
     for (auto &st : n->steps) {
         if (st.type != Step::CONV) continue;
         const ConvSpec &c0 = n->convs[st.conv_ids[0]];
-        const int BC = c0.kern == 4 ? 128 : (c0.kern == 3 ? c0.wc * 32 : pn_cfg_couts(c0.cfg));
         st.host_probs.clear();
         int max_blocks = 0;
         bool two_bufs = false, has_tail = false, pool_tail = false;
         for (int id : st.conv_ids) {
             const ConvSpec &cs = n->convs[id];
             const Buf &ib = n->bufs[cs.in_buf];
-            ConvProblem P;
-            memset(&P, 0, sizeof P);
-            const size_t es = n->esize();
-            (void)es;
-            P.in = ib.p;
-            P.wpack = cs.wpack;
-            P.bias = cs.bias;
-            P.B = B; P.H = ib.H; P.W = ib.W;
-            P.Ho = (ib.H + 2 * (cs.ks / 2) - cs.ks) / cs.stride + 1;
-            P.Wo = (ib.W + 2 * (cs.ks / 2) - cs.ks) / cs.stride + 1;
-            P.cin_chunks = cs.cin_chunks;
-            P.in_cs = ib.C; P.in_coff = cs.in_coff;
             if (n->x3 && ib.plane % 64)
                 return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "bf16x3: input plane of %d channels is not a multiple of 64 (the K loop wraps to the hi plane per 64-channel chunk)", ib.plane);
-            P.in_wrap = n->x3 ? 2 * (ib.plane / 64) : (1 << 20);      // (conv4_kernel doubles it: halves)
-            P.cout = cs.cout;
+            ConvProblem P;
+            memset(&P, 0, sizeof P);
+            pn_fill_conv_problem(P, {ib.p, ib.H, ib.W, ib.C, ib.plane, (size_t)n->max_batch * ib.H * ib.W * ib.C * n->esize()}, B, cs.cin_chunks, cs.cout, cs, n->prec, n->x3);
+            P.wpack = cs.wpack;
+            P.bias = cs.bias;
+            P.in_coff = cs.in_coff;
             if (cs.out_buf >= 0) { P.out = n->bufs[cs.out_buf].p; P.out_cs = n->bufs[cs.out_buf].C; P.out_coff = cs.out_coff; P.split = n->x3 ? n->bufs[cs.out_buf].plane : 0; }
             if (cs.res_buf >= 0) { P.res = n->bufs[cs.res_buf].p; P.res_cs = n->bufs[cs.res_buf].C; P.res_coff = cs.res_coff; P.res_split = n->x3 ? n->bufs[cs.res_buf].plane : 0; }
             if (cs.nchw_slot >= 0) P.out_nchw = n->nchw_ptr[cs.nchw_slot];
             P.act = cs.act;
             P.yolo_naf = 5 + 3 * n->num_parts;
-            P.R = cs.R;
-            P.Wt = cs.Wt;
-            P.tiles_x = (P.Wo + cs.Wt - 1) / cs.Wt;
-            P.tiles_per_img = ((P.Ho + cs.R - 1) / cs.R) * P.tiles_x;
-            P.cout_blocks = (cs.cout + BC - 1) / BC;
-            P.nblocks = B * P.tiles_per_img * P.cout_blocks;
-            if (cs.kern == 4) P.nblocks = ((B * P.tiles_per_img + 1) / 2) * P.cout_blocks;      // a block = two strips x 128 couts
-            P.ksteps = cs.cin_chunks * cs.ks * cs.ks * 2;
-            P.ks = cs.ks;
-            P.lds_buf_bytes = (int)pn_conv_lds_bytes(n->prec, cs.ks, cs.stride, cs.pitch, cs.R);
-            P.lds_two = (cs.cin_chunks > 1 && 2 * (size_t)P.lds_buf_bytes <= 160 * 1024) ? 1 : 0;
-            P.in_zero_off = (unsigned)((size_t)n->max_batch * ib.H * ib.W * ib.C * es);      // zero page behind every activation buffer
             if (cs.pool_tail) {                        // 3 x 7 pooled pixels per block, the pooled map as the only output
                 const Buf &pb = n->bufs[cs.pool_out_buf];
                 P.tiles_x = (pb.W + 6) / 7;
@@ -903,16 +827,9 @@ int refresh_problems(pn_net *n, int B, hipStream_t stream) {
             max_blocks = std::max(max_blocks, P.nblocks);
             st.host_probs.push_back(P);
         }
-        st.launch.prec = n->prec;
-        st.launch.ks = c0.ks; st.launch.stride = c0.stride; st.launch.pitch = c0.pitch; st.launch.cfg = c0.cfg;
-        st.launch.nprob = (int)st.host_probs.size();
-        st.launch.max_blocks = max_blocks;
-        st.launch.lds_bytes = pn_conv_lds_bytes(n->prec, c0.ks, c0.stride, c0.pitch, c0.R) * (two_bufs ? 2 : 1);
-        st.launch.kern = c0.kern; st.launch.wc = c0.wc; st.launch.wp = c0.wp; st.launch.nbuf = c0.nbuf; st.launch.pt = c0.pt; st.launch.rpg = c0.rpg;
-        if (c0.kern == 3) st.launch.lds_bytes = pn_conv3_lds_bytes(c0.ks, c0.wp, c0.nbuf, c0.rpg);
-        st.launch.tail = (c0.kern == 3 && has_tail) ? 1 : (c0.kern == 3 && pool_tail) ? 2 : 0;
-        st.launch.mix = 0;
-        if (c0.kern == 3) {
+        pn_fill_conv_launch(st.launch, n->prec, c0, (int)st.host_probs.size(), max_blocks, two_bufs);
+        if (c0.kern == 3) {                        // on top of it: fused tails / pools, and launches that mix bodies
+            st.launch.tail = has_tail ? 1 : pool_tail ? 2 : 0;
             for (int id : st.conv_ids) {
                 const ConvSpec &cs = n->convs[id];
                 if (cs.ks != c0.ks || (cs.tail_conv >= 0) != (c0.tail_conv >= 0)) st.launch.mix = 1;   // different bodies in one launch: conv3_mix_kernel
@@ -921,7 +838,6 @@ int refresh_problems(pn_net *n, int B, hipStream_t stream) {
             if (st.launch.tail == 1) st.launch.lds_bytes = std::max<size_t>(st.launch.lds_bytes, 4 * 7 * 1024 + 1024);   // the tail's fragment image
             if (st.launch.tail == 2 && n->x3) st.launch.lds_bytes = std::max<size_t>(st.launch.lds_bytes, 2 * 4 * 7 * 1024);   // fused pool, bf16x3: hi and lo tiles parked
         }
-        if (c0.kern == 4) st.launch.lds_bytes = 0;                        // conv4_launch knows its own size
         st.launch.probs_dev = st.dev_probs;
         PN_HIP_CHECK(n->ctx, hipMemcpyAsync(st.dev_probs, st.host_probs.data(), st.host_probs.size() * sizeof(ConvProblem),
                                             hipMemcpyHostToDevice, stream));

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
 #include <vector>
 #include "../../include/popnet_hip.h"
@@ -70,6 +71,16 @@ struct PnSwitches {
 PnSwitches pn_read_switches();
 
 int pn_set_error(pn_ctx *ctx, int code, const char *fmt, ...);
+
+// host-side bf16 <-> f32: round to nearest even, as the device's float -> __bf16 conversion
+inline uint16_t pn_f32_to_bf16(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+inline float pn_bf16_to_f32(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
 void pn_parse_big_free(pn_ctx *ctx);     // parse_paf.hip
 int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)
 const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned *grid_x, unsigned *grid_y);     // train_yolo.hip: kernel label and grid of pn_conv2d_dgrad_strided

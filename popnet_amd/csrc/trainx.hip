@@ -124,6 +124,8 @@ struct pn_trainer {
     float *loss = nullptr;
     float momentum = 0.1f, eps = 1e-5f;
     double flops_conv = 0;
+
+    int prec() const { return f32 ? PN_PREC_F32 : PN_PREC_BF16; }       // as the convolution kernels see it (bf16x3 = bf16 kernels on [hi | lo] planes)
 };
 
 namespace {
@@ -184,12 +186,10 @@ int new_layer(pn_trainer *t, const std::string &name, int ks, int cin, int cout,
 int new_bn(pn_trainer *t, const std::string &name, int C, int *id) {
     TxBn b;
     b.name = name; b.C = C;
-    float *g = nullptr;
     if (int rc = find_param(t, name + ".weight", (size_t)C, &b.gamma, &b.dgamma)) return rc;
     const float *bp = nullptr;
     if (int rc = find_param(t, name + ".bias", (size_t)C, &bp, &b.dbeta)) return rc;
     b.beta = bp;
-    (void)g;
     auto rm = t->stats.find(name + ".running_mean"), rv = t->stats.find(name + ".running_var");
     if (rm == t->stats.end() || rv == t->stats.end()) return pn_set_error(t->ctx, PN_ERR_INVALID, "pn_trainer: running statistics of %s were not set", name.c_str());
     b.rm = rm->second; b.rv = rv->second;
@@ -206,22 +206,27 @@ unsigned grid_for(long items, int cus) {          // grid-stride elementwise lau
     return (unsigned)std::max<long>(1, std::min<long>(want, (long)cus * 16));
 }
 
+// One 256-thread launch of kern, written once in terms of T: float in the fp32 engine, bf on [hi | lo] planes (TxTensor::split() is 0 / plane accordingly)
+#define TX_LAUNCH_T(t, kern, grid, s, ...)                                                              \
+    do {                                                                                               \
+        if ((t)->f32) { using T = float; hipLaunchKernelGGL((kern), grid, dim3(256), 0, s, __VA_ARGS__); } \
+        else { using T = bf; hipLaunchKernelGGL((kern), grid, dim3(256), 0, s, __VA_ARGS__); }          \
+    } while (0)
+
 // ---- convolution groups (one launch per kernel instantiation, blockIdx.y = problem) -------------------------------------------------
-struct PlannedConv { ConvUse u; ConvGeom g; int rows, kplane, ks, cin_chunks, BC, cout_pad; };
+struct PlannedConv { ConvUse u; ConvGeom g; int rows, kplane, cin_chunks, cout_pad; };
 
 int ensure_pack(pn_trainer *t, const PlannedConv &pc, bf **dst_out) {
     TxLayer &L = t->layers[pc.u.layer];
     bf *&slot = pc.u.dgrad ? L.pack_d : L.pack_f;
     if (slot) { *dst_out = slot; return PN_OK; }
-    const int KK = pc.ks * pc.ks, ksteps = pc.cin_chunks * KK * 2;
+    const int ksteps = pc.cin_chunks * pc.g.ks * pc.g.ks * 2;
     const bool k4 = pc.g.kern == 4;
-    const size_t real_groups = k4 ? (size_t)(pc.cout_pad / 128) * (ksteps + 3) * 8 * 64 : (size_t)(pc.cout_pad / 16) * ksteps * 64;
-    const size_t gbytes = t->f32 ? 32 : 16;                               // one lane's share of a fragment: 8 values
-    const size_t bytes = real_groups * gbytes + (k4 ? 0 : 5 * 64 * gbytes);          // + spare fragments: the weight queue prefetches up to 5 k-steps ahead
-    if (int rc = tx_alloc(t, (void **)&slot, bytes, true)) return rc;
+    const size_t real_groups = pn_conv_pack_frags(pc.g, pc.cout_pad, ksteps) * 64;      // one lane's share of a fragment: 8 values
+    if (int rc = tx_alloc(t, (void **)&slot, pn_conv_pack_bytes(t->prec(), pc.g, pc.cout_pad, ksteps), true)) return rc;
     tx::PackDesc d;
     memset(&d, 0, sizeof d);
-    d.w = L.w; d.dst = slot; d.f32 = t->f32 ? 1 : 0; d.Cout = L.cout; d.Cin = L.cin; d.ks = pc.ks;
+    d.w = L.w; d.dst = slot; d.f32 = t->f32 ? 1 : 0; d.Cout = L.cout; d.Cin = L.cin; d.ks = pc.g.ks;
     d.transpose = pc.u.dgrad ? 1 : 0; d.conv4 = k4 ? 1 : 0;
     d.CT = pc.g.kern == 3 ? 2 : pn_cfg_ct(pc.g.cfg);
     d.rows_valid = pc.rows; d.kplane = pc.kplane; d.ksteps = ksteps;
@@ -238,42 +243,35 @@ int ensure_pack(pn_trainer *t, const PlannedConv &pc, bf **dst_out) {
 
 int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
     pn_ctx *ctx = t->ctx;
+    const int prec = t->prec();
     std::vector<PlannedConv> pcs;
-    // what net.hip::harmonize_level decides for a level of independent convolutions
-    bool k4 = false, wide[4] = {false, false, false, false};
-    long blocks = 0;
-    for (const ConvUse &u : uses) {
-        const TxLayer &L = t->layers[u.layer];
-        const TxTensor &in = t->T[u.in];
-        const int rows = u.dgrad ? t->T[L.x].plane : L.cout;
-        if (L.ks == 3 && rows >= 64) {
-            k4 = true;
-            const long strips = (long)t->B * ((in.H + 3) / 4) * ((in.W + 29) / 30);
-            blocks += ((strips + 1) / 2) * ((rows + 127) / 128);
-        }
-        if (rows > 64) wide[L.ks] = true;
-    }
-    if (blocks < 448) k4 = false;
+    std::vector<PnLevelConv> lv;
     for (const ConvUse &u : uses) {
         const TxLayer &L = t->layers[u.layer];
         const TxTensor &in = t->T[u.in];
         PlannedConv pc;
         pc.u = u;
-        pc.ks = L.ks;
+        pc.g = ConvGeom();
+        pc.g.ks = L.ks;
         pc.rows = u.dgrad ? t->T[L.x].plane : L.cout;
         pc.kplane = in.plane;
         if (pc.kplane % 64) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_trainer: %s: input plane %d is not a multiple of 64", L.name.c_str(), pc.kplane);
         pc.cin_chunks = (t->f32 ? 1 : 3) * pc.kplane / 64;
-        pc.g = ConvGeom();
-        const int wc_min = (wide[L.ks] && pc.rows > 32) ? 4 : 0;
-        const int prec = t->f32 ? PN_PREC_F32 : PN_PREC_BF16;
-        pn_plan_conv_kernel(prec, t->B, ctx->num_cus, in.H, in.W, pc.rows, L.ks, 1, pc.cin_chunks, wc_min, 0, k4 ? 1 : 0, t->sw, pc.g);
-        const char *why = "";
-        if (int rc = pn_plan_conv_tiles(prec, in.H, in.W, L.ks, 1, pc.g, &why)) return pn_set_error(ctx, rc, "pn_trainer: %s: %s", L.name.c_str(), why);
-        if (pc.g.kern == 0 && L.ks == 1 && pc.g.pitch == 16) pc.g.pitch = 32;      // the generic 1x1 kernel is not instantiated for the 16-pixel pitch class (a wider LDS row is always valid)
-        pc.BC = pc.g.kern == 4 ? 128 : (pc.g.kern == 3 ? pc.g.wc * 32 : pn_cfg_couts(pc.g.cfg));
-        pc.cout_pad = (pc.rows + pc.BC - 1) / pc.BC * pc.BC;
         pcs.push_back(pc);
+        PnLevelConv l;
+        l.H = in.H; l.W = in.W; l.rows = pc.rows; l.ks = L.ks; l.stride = 1; l.cin_gt64 = pc.kplane > 64;
+        lv.push_back(l);
+    }
+    pn_plan_level(lv, t->B, !t->f32, -1);          // conv4 by block count: the trainer does not honour POPNET_CONV4
+    for (size_t i = 0; i < pcs.size(); ++i) {
+        PlannedConv &pc = pcs[i];
+        const TxLayer &L = t->layers[pc.u.layer];
+        const TxTensor &in = t->T[pc.u.in];
+        pn_plan_conv_kernel(prec, t->B, ctx->num_cus, in.H, in.W, pc.rows, pc.cin_chunks, lv[i].wc_min, lv[i].nbuf_min, lv[i].k4_level, t->sw, pc.g);
+        const char *why = "";
+        if (int rc = pn_plan_conv_tiles(prec, in.H, in.W, pc.g, &why)) return pn_set_error(ctx, rc, "pn_trainer: %s: %s", L.name.c_str(), why);
+        if (pc.g.kern == 0 && L.ks == 1 && pc.g.pitch == 16) pc.g.pitch = 32;      // the generic 1x1 kernel is not instantiated for the 16-pixel pitch class (a wider LDS row is always valid)
+        pc.cout_pad = pn_conv_cout_pad(pc.g, pc.rows);
     }
     std::vector<bool> used(pcs.size(), false);
     for (size_t i = 0; i < pcs.size(); ++i) {
@@ -283,9 +281,7 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
         for (size_t j = i; j < pcs.size(); ++j) {
             const PlannedConv &b = pcs[j];
             if (used[j]) continue;
-            const bool same = b.ks == a.ks && b.g.pitch == a.g.pitch && b.g.R == a.g.R && b.g.Wt == a.g.Wt && b.g.kern == a.g.kern &&
-                              (a.g.kern == 4 || (a.g.kern == 3 ? (b.g.wc == a.g.wc && b.g.wp == a.g.wp && b.g.nbuf == a.g.nbuf && b.g.pt == a.g.pt && b.g.rpg == a.g.rpg) : b.g.cfg == a.g.cfg));
-            if (same) { members.push_back(j); used[j] = true; }
+            if (pn_conv_same_launch(a.g, b.g)) { members.push_back(j); used[j] = true; }
         }
         std::vector<ConvProblem> probs;
         int max_blocks = 0;
@@ -298,7 +294,8 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
             memset(&P, 0, sizeof P);
             bf *pack = nullptr;
             if (int rc = ensure_pack(t, pc, &pack)) return rc;
-            P.in = in.p; P.wpack = pack;
+            pn_fill_conv_problem(P, {in.p, in.H, in.W, in.cs(), in.plane, (size_t)t->B * in.H * in.W * in.plane * 4}, t->B, pc.cin_chunks, pc.rows, pc.g, prec, !t->f32);
+            P.wpack = pack;
             if (!pc.u.dgrad && L.b) {
                 if (!L.bias_pad) {
                     if (int rc = tx_alloc(t, (void **)&L.bias_pad, (size_t)pad64(std::max(pc.cout_pad, 128)) * 4, true)) return rc;
@@ -308,42 +305,21 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
                 }
                 P.bias = L.bias_pad;
             } else P.bias = t->zero_bias;
-            P.B = t->B; P.H = in.H; P.W = in.W; P.Ho = in.H; P.Wo = in.W;
-            P.cin_chunks = pc.cin_chunks; P.in_cs = in.cs(); P.in_coff = 0;
-            P.in_wrap = t->f32 ? (1 << 20) : 2 * (in.plane / 64);
-            P.cout = pc.rows;
             if (pc.u.out >= 0) { const TxTensor &o = t->T[pc.u.out]; P.out = o.p; P.out_cs = o.cs(); P.out_coff = pc.u.out_coff; P.split = o.split(); }
             if (pc.u.res >= 0) { const TxTensor &r = t->T[pc.u.res]; P.res = r.p; P.res_cs = r.cs(); P.res_coff = 0; P.res_split = r.split(); }
             P.out_nchw = pc.u.out_nchw;
             P.act = pc.u.act;
             P.yolo_naf = 50;
-            P.R = pc.g.R; P.Wt = pc.g.Wt;
-            P.tiles_x = (P.Wo + pc.g.Wt - 1) / pc.g.Wt;
-            P.tiles_per_img = ((P.Ho + pc.g.R - 1) / pc.g.R) * P.tiles_x;
-            P.cout_blocks = (pc.rows + pc.BC - 1) / pc.BC;
-            P.nblocks = t->B * P.tiles_per_img * P.cout_blocks;
-            if (pc.g.kern == 4) P.nblocks = ((t->B * P.tiles_per_img + 1) / 2) * P.cout_blocks;
-            P.ksteps = pc.cin_chunks * pc.ks * pc.ks * 2;
-            P.ks = pc.ks;
-            P.lds_buf_bytes = (int)pn_conv_lds_bytes(t->f32 ? PN_PREC_F32 : PN_PREC_BF16, pc.ks, 1, pc.g.pitch, pc.g.R);
-            P.lds_two = (pc.cin_chunks > 1 && 2 * (size_t)P.lds_buf_bytes <= 160 * 1024) ? 1 : 0;
-            P.in_zero_off = (unsigned)((size_t)t->B * in.H * in.W * in.plane * 4);
             if (P.lds_two) two_bufs = true;
             max_blocks = std::max(max_blocks, P.nblocks);
             probs.push_back(P);
-            t->flops_conv += 2.0 * (t->f32 ? 1.0 : 3.0) * (double)t->B * in.H * in.W * pc.rows * pc.kplane * pc.ks * pc.ks;
+            t->flops_conv += 2.0 * (t->f32 ? 1.0 : 3.0) * (double)t->B * in.H * in.W * pc.rows * pc.kplane * pc.g.ks * pc.g.ks;
         }
         ConvProblem *dev = nullptr;
         if (int rc = tx_alloc(t, (void **)&dev, probs.size() * sizeof(ConvProblem), false)) return rc;
         PN_HIP_CHECK(ctx, hipMemcpy(dev, probs.data(), probs.size() * sizeof(ConvProblem), hipMemcpyHostToDevice));
         ConvLaunch cl;
-        cl.prec = t->f32 ? PN_PREC_F32 : PN_PREC_BF16; cl.ks = a.ks; cl.stride = 1; cl.pitch = a.g.pitch; cl.cfg = a.g.cfg;
-        cl.kern = a.g.kern; cl.wc = a.g.wc; cl.wp = a.g.wp; cl.nbuf = a.g.nbuf; cl.pt = a.g.pt; cl.rpg = a.g.rpg;
-        cl.tail = 0; cl.mix = 0;
-        cl.nprob = (int)probs.size(); cl.max_blocks = max_blocks;
-        cl.lds_bytes = pn_conv_lds_bytes(cl.prec, a.ks, 1, a.g.pitch, a.g.R) * (two_bufs ? 2 : 1);
-        if (a.g.kern == 3) cl.lds_bytes = pn_conv3_lds_bytes(a.ks, a.g.wp, a.g.nbuf, a.g.rpg);
-        if (a.g.kern == 4) cl.lds_bytes = 0;
+        pn_fill_conv_launch(cl, prec, a.g, (int)probs.size(), max_blocks, two_bufs);
         cl.probs_dev = dev;
         t->launches.push_back(cl);
         const size_t li = t->launches.size() - 1;
@@ -357,7 +333,7 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
                 for (int b = 0; b < 3; ++b)
                     if (pc.u.out_nchw && pc.u.out_nchw == t->head_out[st][b]) { hs = st; hb = b; }
             body += jf("%s{\"layer\": \"%s\", \"dgrad\": %d, \"act\": %d, \"bias\": %d, \"ks\": %d, \"cin\": %d, \"cout\": %d, \"cat\": %d, \"rows\": %d, \"R\": %d, \"Wt\": %d, ",
-                       m ? ", " : "", L.name.c_str(), pc.u.dgrad ? 1 : 0, pc.u.act, (!pc.u.dgrad && L.b) ? 1 : 0, pc.ks, L.cin, L.cout, L.cat ? 1 : 0, pc.rows, pc.g.R, pc.g.Wt);
+                       m ? ", " : "", L.name.c_str(), pc.u.dgrad ? 1 : 0, pc.u.act, (!pc.u.dgrad && L.b) ? 1 : 0, pc.g.ks, L.cin, L.cout, L.cat ? 1 : 0, pc.rows, pc.g.R, pc.g.Wt);
             body += "\"in\": " + jref(pc.u.in, 0, t->T[pc.u.in].plane) + ", \"out\": " + jref(pc.u.out, pc.u.out_coff, pc.rows) + ", \"res\": " + jref(pc.u.res, 0, pc.rows);
             body += hs >= 0 ? jf(", \"nchw\": \"head_out.%d.%d\"}", hs, hb) : std::string(", \"nchw\": null}");
         }
@@ -377,24 +353,30 @@ int red_blocks(const pn_trainer *t, long npix, int C, int *ppb) {
 
 int need_partial(pn_trainer *t, size_t doubles) { t->partial_doubles = std::max(t->partial_doubles, doubles); return PN_OK; }
 
+// split per-channel reductions over up to three tensors in one launch (blockIdx.y = tensor), their partial sums side by side in t->partial
+struct RedPlan {
+    struct Geo { long npix; int C, ppb, nblk; size_t poff; } g[3];
+    size_t doubles = 0;
+    int max_nblk = 0, max_c = 0;
+    long max_items = 0;
+    void add(pn_trainer *t, int i, int x, int C) {           // tensor x, its first C channels
+        const TxTensor X = t->T[x];
+        g[i].npix = (long)t->B * X.H * X.W; g[i].C = C;
+        g[i].nblk = red_blocks(t, g[i].npix, C, &g[i].ppb);
+        g[i].poff = doubles; doubles += (size_t)g[i].nblk * C * 2;
+        max_nblk = std::max(max_nblk, g[i].nblk); max_c = std::max(max_c, C); max_items = std::max(max_items, g[i].npix * (C / 8));
+        need_partial(t, doubles);
+    }
+};
+
 struct BnUse { int bn, x, res, y, act; };                 // forward: y = act(bn(x) [+ res])
 struct BnBwdUse { int bn, x, dy, y, dx, dres, act; bool has_res; };
 
 // up to three independent BatchNorm layers (the branches of a stage level) per launch: blockIdx.y = layer
 void op_bn_fwd(pn_trainer *t, std::vector<BnUse> uses) {
     const int n = (int)uses.size();
-    struct Geo { long npix; int C, ppb, nblk; size_t poff; } g[3];
-    size_t poff = 0;
-    int max_nblk = 0, max_c = 0;
-    long max_items = 0;
-    for (int i = 0; i < n; ++i) {
-        const TxTensor X = t->T[uses[i].x];
-        g[i].npix = (long)t->B * X.H * X.W; g[i].C = t->bns[uses[i].bn].C;
-        g[i].nblk = red_blocks(t, g[i].npix, g[i].C, &g[i].ppb);
-        g[i].poff = poff; poff += (size_t)g[i].nblk * g[i].C * 2;
-        max_nblk = std::max(max_nblk, g[i].nblk); max_c = std::max(max_c, g[i].C); max_items = std::max(max_items, g[i].npix * (g[i].C / 8));
-    }
-    need_partial(t, poff);
+    RedPlan rp;
+    for (int i = 0; i < n; ++i) rp.add(t, i, uses[i].x, t->bns[uses[i].bn].C);
     t->ops.push_back([=](hipStream_t s) {
         tx::Multi<tx::RedArgs> r;
         tx::Multi<tx::BnFinArgs> f;
@@ -404,28 +386,26 @@ void op_bn_fwd(pn_trainer *t, std::vector<BnUse> uses) {
             const TxBn &b = t->bns[uses[i].bn];
             const TxTensor X = t->T[uses[i].x], Y = t->T[uses[i].y];
             tx::RedArgs &ri = r.a[i];
-            ri.x = X.p; ri.x_cs = X.cs(); ri.x_split = X.split(); ri.C = g[i].C; ri.npix = g[i].npix; ri.ppb = g[i].ppb; ri.nblk = g[i].nblk; ri.partial = t->partial + g[i].poff;
+            ri.x = X.p; ri.x_cs = X.cs(); ri.x_split = X.split(); ri.C = rp.g[i].C; ri.npix = rp.g[i].npix; ri.ppb = rp.g[i].ppb; ri.nblk = rp.g[i].nblk; ri.partial = t->partial + rp.g[i].poff;
             tx::BnFinArgs &fi = f.a[i];
-            fi.partial = t->partial + g[i].poff; fi.nblk = g[i].nblk; fi.C = g[i].C; fi.n = (double)g[i].npix; fi.gamma = b.gamma; fi.beta = b.beta;
+            fi.partial = t->partial + rp.g[i].poff; fi.nblk = rp.g[i].nblk; fi.C = rp.g[i].C; fi.n = (double)rp.g[i].npix; fi.gamma = b.gamma; fi.beta = b.beta;
             fi.mean = b.mean; fi.invstd = b.invstd; fi.scale = b.scale; fi.shift = b.shift; fi.running_mean = b.rm; fi.running_var = b.rv;
             fi.momentum = t->momentum; fi.eps = t->eps;
             tx::BnApplyArgs &ai = a.a[i];
             ai.x = X.p; ai.x_cs = X.cs(); ai.x_split = X.split();
             if (uses[i].res >= 0) { const TxTensor R = t->T[uses[i].res]; ai.res = R.p; ai.res_cs = R.cs(); ai.res_split = R.split(); }
-            ai.y = Y.p; ai.y_cs = Y.cs(); ai.y_split = Y.split(); ai.scale = b.scale; ai.shift = b.shift; ai.act = uses[i].act; ai.C = g[i].C; ai.npix = g[i].npix;
+            ai.y = Y.p; ai.y_cs = Y.cs(); ai.y_split = Y.split(); ai.scale = b.scale; ai.shift = b.shift; ai.act = uses[i].act; ai.C = rp.g[i].C; ai.npix = rp.g[i].npix;
         }
-        if (t->f32) hipLaunchKernelGGL((tx::reduce_kernel<0, float>), dim3(max_nblk, n), dim3(256), 0, s, r);
-        else hipLaunchKernelGGL((tx::reduce_kernel<0, bf>), dim3(max_nblk, n), dim3(256), 0, s, r);
-        hipLaunchKernelGGL(tx::bn_finish_kernel, dim3((max_c + 3) / 4, n), dim3(256), 0, s, f);
-        if (t->f32) hipLaunchKernelGGL(tx::bn_apply_kernel<float>, dim3(grid_for(max_items, t->ctx->num_cus), n), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(tx::bn_apply_kernel<bf>, dim3(grid_for(max_items, t->ctx->num_cus), n), dim3(256), 0, s, a);
+        TX_LAUNCH_T(t, (tx::reduce_kernel<0, T>), dim3(rp.max_nblk, n), s, r);
+        hipLaunchKernelGGL(tx::bn_finish_kernel, dim3((rp.max_c + 3) / 4, n), dim3(256), 0, s, f);
+        TX_LAUNCH_T(t, tx::bn_apply_kernel<T>, dim3(grid_for(rp.max_items, t->ctx->num_cus), n), s, a);
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
     std::string body = jf("\"kernels\": [\"reduce_kernel<0>\", \"bn_finish_kernel\", \"bn_apply_kernel\"], \"problems\": [");
     for (int i = 0; i < n; ++i) {
-        body += jf("%s{\"bn\": \"%s\", \"act\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, ", i ? ", " : "", t->bns[uses[i].bn].name.c_str(), uses[i].act, g[i].C, g[i].ppb, g[i].nblk);
-        body += "\"x\": " + jref(uses[i].x, 0, g[i].C) + ", \"res\": " + jref(uses[i].res, 0, g[i].C) + ", \"y\": " + jref(uses[i].y, 0, g[i].C) + "}";
+        body += jf("%s{\"bn\": \"%s\", \"act\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, ", i ? ", " : "", t->bns[uses[i].bn].name.c_str(), uses[i].act, rp.g[i].C, rp.g[i].ppb, rp.g[i].nblk);
+        body += "\"x\": " + jref(uses[i].x, 0, rp.g[i].C) + ", \"res\": " + jref(uses[i].res, 0, rp.g[i].C) + ", \"y\": " + jref(uses[i].y, 0, rp.g[i].C) + "}";
     }
     describe(t, "bn_fwd", body + "]");
 }
@@ -433,18 +413,8 @@ void op_bn_fwd(pn_trainer *t, int bn, int x, int res, int y, int act) { op_bn_fw
 
 void op_bn_bwd(pn_trainer *t, std::vector<BnBwdUse> uses) {
     const int n = (int)uses.size();
-    struct Geo { long npix; int C, ppb, nblk; size_t poff; } g[3];
-    size_t poff = 0;
-    int max_nblk = 0, max_c = 0;
-    long max_items = 0;
-    for (int i = 0; i < n; ++i) {
-        const TxTensor X = t->T[uses[i].x];
-        g[i].npix = (long)t->B * X.H * X.W; g[i].C = t->bns[uses[i].bn].C;
-        g[i].nblk = red_blocks(t, g[i].npix, g[i].C, &g[i].ppb);
-        g[i].poff = poff; poff += (size_t)g[i].nblk * g[i].C * 2;
-        max_nblk = std::max(max_nblk, g[i].nblk); max_c = std::max(max_c, g[i].C); max_items = std::max(max_items, g[i].npix * (g[i].C / 8));
-    }
-    need_partial(t, poff);
+    RedPlan rp;
+    for (int i = 0; i < n; ++i) rp.add(t, i, uses[i].x, t->bns[uses[i].bn].C);
     t->ops.push_back([=](hipStream_t s) {
         tx::Multi<tx::RedArgs> r;
         tx::Multi<tx::BnBwdFinArgs> f;
@@ -459,26 +429,24 @@ void op_bn_bwd(pn_trainer *t, std::vector<BnBwdUse> uses) {
             tx::RedArgs &ri = r.a[i];
             ri.x = X.p; ri.x_cs = X.cs(); ri.x_split = X.split(); ri.dy = DY.p; ri.dy_cs = DY.cs(); ri.dy_split = DY.split();
             ri.y = ysrc; ri.y_cs = Y.cs(); ri.mean = b.mean; ri.invstd = b.invstd; ri.scale = b.scale; ri.shift = b.shift; ri.act = u.act;
-            ri.C = g[i].C; ri.npix = g[i].npix; ri.ppb = g[i].ppb; ri.nblk = g[i].nblk; ri.partial = t->partial + g[i].poff;
+            ri.C = rp.g[i].C; ri.npix = rp.g[i].npix; ri.ppb = rp.g[i].ppb; ri.nblk = rp.g[i].nblk; ri.partial = t->partial + rp.g[i].poff;
             tx::BnBwdFinArgs &fi = f.a[i];
-            fi.partial = t->partial + g[i].poff; fi.nblk = g[i].nblk; fi.C = g[i].C; fi.n = (double)g[i].npix; fi.gamma = b.gamma; fi.invstd = b.invstd;
+            fi.partial = t->partial + rp.g[i].poff; fi.nblk = rp.g[i].nblk; fi.C = rp.g[i].C; fi.n = (double)rp.g[i].npix; fi.gamma = b.gamma; fi.invstd = b.invstd;
             fi.dgamma = b.dgamma; fi.dbeta = b.dbeta; fi.k1 = b.k1; fi.k2 = b.k2; fi.k3 = b.k3;
             tx::BnBwdApplyArgs &ai = a.a[i];
             ai.x = X.p; ai.x_cs = X.cs(); ai.x_split = X.split(); ai.dy = DY.p; ai.dy_cs = DY.cs(); ai.dy_split = DY.split();
             ai.y = ysrc; ai.y_cs = Y.cs(); ai.mean = b.mean; ai.invstd = b.invstd; ai.k1 = b.k1; ai.k2 = b.k2; ai.k3 = b.k3; ai.scale = b.scale; ai.shift = b.shift;
             ai.dx = DX.p; ai.dx_cs = DX.cs(); ai.dx_split = DX.split();
             if (u.dres >= 0) { const TxTensor R = t->T[u.dres]; ai.dres = R.p; ai.dres_cs = R.cs(); ai.dres_split = R.split(); }
-            ai.act = u.act; ai.C = g[i].C; ai.npix = g[i].npix;
+            ai.act = u.act; ai.C = rp.g[i].C; ai.npix = rp.g[i].npix;
         }
-        if (t->f32) hipLaunchKernelGGL((tx::reduce_kernel<1, float>), dim3(max_nblk, n), dim3(256), 0, s, r);
-        else hipLaunchKernelGGL((tx::reduce_kernel<1, bf>), dim3(max_nblk, n), dim3(256), 0, s, r);
-        hipLaunchKernelGGL(tx::bn_bwd_finish_kernel, dim3((max_c + 3) / 4, n), dim3(256), 0, s, f);
+        TX_LAUNCH_T(t, (tx::reduce_kernel<1, T>), dim3(rp.max_nblk, n), s, r);
+        hipLaunchKernelGGL(tx::bn_bwd_finish_kernel, dim3((rp.max_c + 3) / 4, n), dim3(256), 0, s, f);
         if (uses[0].dx < 0) {                     // sums and k1 / k2 / k3 only: the consumer applies them itself (the stem's weight gradient)
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return (int)PN_OK;
         }
-        if (t->f32) hipLaunchKernelGGL(tx::bn_bwd_apply_kernel<float>, dim3(grid_for(max_items, t->ctx->num_cus), n), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(tx::bn_bwd_apply_kernel<bf>, dim3(grid_for(max_items, t->ctx->num_cus), n), dim3(256), 0, s, a);
+        TX_LAUNCH_T(t, tx::bn_bwd_apply_kernel<T>, dim3(grid_for(rp.max_items, t->ctx->num_cus), n), s, a);
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
@@ -486,8 +454,8 @@ void op_bn_bwd(pn_trainer *t, std::vector<BnBwdUse> uses) {
                                       : "\"kernels\": [\"reduce_kernel<1>\", \"bn_bwd_finish_kernel\", \"bn_bwd_apply_kernel\"], \"problems\": [";
     for (int i = 0; i < n; ++i) {
         const BnBwdUse &u = uses[i];
-        body += jf("%s{\"bn\": \"%s\", \"act\": %d, \"has_res\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, ", i ? ", " : "", t->bns[u.bn].name.c_str(), u.act, u.has_res ? 1 : 0, g[i].C, g[i].ppb, g[i].nblk);
-        body += "\"x\": " + jref(u.x, 0, g[i].C) + ", \"dy\": " + jref(u.dy, 0, g[i].C) + ", \"y\": " + jref(u.y, 0, g[i].C) + ", \"dx\": " + jref(u.dx, 0, g[i].C) + ", \"dres\": " + jref(u.dres, 0, g[i].C) + "}";
+        body += jf("%s{\"bn\": \"%s\", \"act\": %d, \"has_res\": %d, \"C\": %d, \"ppb\": %d, \"nblk\": %d, ", i ? ", " : "", t->bns[u.bn].name.c_str(), u.act, u.has_res ? 1 : 0, rp.g[i].C, rp.g[i].ppb, rp.g[i].nblk);
+        body += "\"x\": " + jref(u.x, 0, rp.g[i].C) + ", \"dy\": " + jref(u.dy, 0, rp.g[i].C) + ", \"y\": " + jref(u.y, 0, rp.g[i].C) + ", \"dx\": " + jref(u.dx, 0, rp.g[i].C) + ", \"dres\": " + jref(u.dres, 0, rp.g[i].C) + "}";
     }
     describe(t, "bn_bwd", body + "]");
 }
@@ -498,19 +466,17 @@ void op_bn_bwd(pn_trainer *t, int bn, int x, int dy, int y, int dx, int dres, in
 // bias gradient of layer `l` from its output gradient tensor dy (first cout channels)
 void op_dbias(pn_trainer *t, int l, int dy) {
     const TxTensor DY = t->T[dy];
-    const long npix = (long)t->B * DY.H * DY.W;
-    const int C = DY.plane;
-    int ppb;
-    const int nblk = red_blocks(t, npix, C, &ppb);
-    need_partial(t, (size_t)nblk * C * 2);
+    RedPlan rp;
+    rp.add(t, 0, dy, DY.plane);
+    const long npix = rp.g[0].npix;
+    const int C = DY.plane, ppb = rp.g[0].ppb, nblk = rp.g[0].nblk;
     t->ops.push_back([=](hipStream_t s) {
         const TxLayer &L = t->layers[l];
         tx::Multi<tx::RedArgs> r;
         memset(&r, 0, sizeof r);
         tx::RedArgs &ri = r.a[0];
         ri.x = DY.p; ri.x_cs = DY.cs(); ri.x_split = DY.split(); ri.C = C; ri.npix = npix; ri.ppb = ppb; ri.nblk = nblk; ri.partial = t->partial;
-        if (t->f32) hipLaunchKernelGGL((tx::reduce_kernel<2, float>), dim3(nblk, 1), dim3(256), 0, s, r);
-        else hipLaunchKernelGGL((tx::reduce_kernel<2, bf>), dim3(nblk, 1), dim3(256), 0, s, r);
+        TX_LAUNCH_T(t, (tx::reduce_kernel<2, T>), dim3(nblk, 1), s, r);
         hipLaunchKernelGGL(tx::sum_finish_kernel, dim3((L.cout + 3) / 4), dim3(256), 0, s, (const double *)t->partial, nblk, C, L.cout, L.db);
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
@@ -528,8 +494,7 @@ void op_add(pn_trainer *t, std::vector<std::array<int, 2>> ins /* (tensor, chann
     for (int i = 0; i < a.n; ++i) { const TxTensor X = t->T[ins[i][0]]; a.in[i] = X.at(ins[i][1]); a.cs[i] = X.cs(); a.split[i] = X.split(); }
     a.out = O.p; a.out_cs = O.cs(); a.out_split = O.split(); a.C = C; a.npix = npix;
     t->ops.push_back([=](hipStream_t s) {
-        if (t->f32) hipLaunchKernelGGL(tx::add_kernel<float>, dim3(grid_for(npix * (C / 8), t->ctx->num_cus)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(tx::add_kernel<bf>, dim3(grid_for(npix * (C / 8), t->ctx->num_cus)), dim3(256), 0, s, a);
+        TX_LAUNCH_T(t, tx::add_kernel<T>, dim3(grid_for(npix * (C / 8), t->ctx->num_cus)), s, a);
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
@@ -541,7 +506,7 @@ void op_add(pn_trainer *t, std::vector<std::array<int, 2>> ins /* (tensor, chann
 void op_pool_fwd(pn_trainer *t, int x, int y, int out_coff) {
     const TxTensor X = t->T[x], Y = t->T[y];
     t->ops.push_back([=](hipStream_t s) {
-        return pn_launch_pool(t->ctx, t->f32 ? PN_PREC_F32 : PN_PREC_BF16, 0, X.p, Y.p, t->B, X.H, X.W, X.plane, X.cs(), Y.cs(), out_coff, X.split(), Y.split(), s);
+        return pn_launch_pool(t->ctx, t->prec(), 0, X.p, Y.p, t->B, X.H, X.W, X.plane, X.cs(), Y.cs(), out_coff, X.split(), Y.split(), s);
     });
     describe(t, "pool_fwd", jf("\"kernels\": [\"%s\"], \"x\": ", pn_pool_kernel_label(0, !t->f32).c_str()) + jref(x, 0, X.plane) + ", \"y\": " + jref(y, out_coff, X.plane));
 }
@@ -550,10 +515,8 @@ void op_pool_bwd(pn_trainer *t, int dy, int dx) {
     const TxTensor DY = t->T[dy], DX = t->T[dx];
     t->ops.push_back([=](hipStream_t s) {
         const long items = (long)t->B * DX.H * DX.W * (DX.plane / 8);
-        if (t->f32) hipLaunchKernelGGL(tx::avgpool_bwd_kernel<float>, dim3(grid_for(items, t->ctx->num_cus)), dim3(256), 0, s, (const float *)DY.p, DY.cs(), 0, (float *)DX.p, DX.cs(), 0,
-                                       t->B, DX.H, DX.W, DY.H, DY.W, DX.plane);
-        else hipLaunchKernelGGL(tx::avgpool_bwd_kernel<bf>, dim3(grid_for(items, t->ctx->num_cus)), dim3(256), 0, s, (const bf *)DY.p, DY.cs(), DY.plane, (bf *)DX.p, DX.cs(), DX.plane,
-                                t->B, DX.H, DX.W, DY.H, DY.W, DX.plane);
+        TX_LAUNCH_T(t, tx::avgpool_bwd_kernel<T>, dim3(grid_for(items, t->ctx->num_cus)), s, (const T *)DY.p, DY.cs(), DY.split(), (T *)DX.p, DX.cs(), DX.split(),
+                    t->B, DX.H, DX.W, DY.H, DY.W, DX.plane);
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
     });
@@ -588,8 +551,7 @@ void op_heads(pn_trainer *t, int stage, int dcat, const int dv[3]) {
             a.kind = HEAD_KIND[b]; a.C = HEAD_C[b]; a.HW = HW; a.total = total[b]; a.inv_numel = (float)(1.0 / (double)total[b]); a.partial = t->partial + poff[b];
             f.a[b].partial = t->partial + poff[b]; f.a[b].nblocks = nblk[b]; f.a[b].numel = (double)total[b]; f.a[b].loss = t->loss + 3 * stage + b;
         }
-        if (t->f32) hipLaunchKernelGGL(tx::head_kernel<float>, dim3(max_nblk, 3), dim3(256), 0, s, h);
-        else hipLaunchKernelGGL(tx::head_kernel<bf>, dim3(max_nblk, 3), dim3(256), 0, s, h);
+        TX_LAUNCH_T(t, tx::head_kernel<T>, dim3(max_nblk, 3), s, h);
         hipLaunchKernelGGL(tx::loss_finish_kernel, dim3(3), dim3(256), 0, s, f);
         PN_HIP_CHECK(t->ctx, hipGetLastError());
         return (int)PN_OK;
@@ -652,13 +614,8 @@ int op_wgrad(pn_trainer *t, int l, int dy) {
             const TxLayer &LL = t->layers[l];
             const int HW = X.H * X.W;
             const int *cmap = LL.cat ? (const int *)t->cat_ref_map : (const int *)nullptr;
-            if (t->f32) {
-                hipLaunchKernelGGL(tx::planes_to_nchw_kernel<float>, dim3((HW + 63) / 64, (LL.cin + 63) / 64, t->B), dim3(256), 0, s, (const float *)X.p, X.cs(), 0, t->nchw_a, LL.cin, HW, cmap);
-                hipLaunchKernelGGL(tx::planes_to_nchw_kernel<float>, dim3((HW + 63) / 64, (LL.cout + 63) / 64, t->B), dim3(256), 0, s, (const float *)DY.p, DY.cs(), 0, t->nchw_b, LL.cout, HW, (const int *)nullptr);
-            } else {
-                hipLaunchKernelGGL(tx::planes_to_nchw_kernel<bf>, dim3((HW + 63) / 64, (LL.cin + 63) / 64, t->B), dim3(256), 0, s, (const bf *)X.p, X.cs(), X.plane, t->nchw_a, LL.cin, HW, cmap);
-                hipLaunchKernelGGL(tx::planes_to_nchw_kernel<bf>, dim3((HW + 63) / 64, (LL.cout + 63) / 64, t->B), dim3(256), 0, s, (const bf *)DY.p, DY.cs(), DY.plane, t->nchw_b, LL.cout, HW, (const int *)nullptr);
-            }
+            TX_LAUNCH_T(t, tx::planes_to_nchw_kernel<T>, dim3((HW + 63) / 64, (LL.cin + 63) / 64, t->B), s, (const T *)X.p, X.cs(), X.split(), t->nchw_a, LL.cin, HW, cmap);
+            TX_LAUNCH_T(t, tx::planes_to_nchw_kernel<T>, dim3((HW + 63) / 64, (LL.cout + 63) / 64, t->B), s, (const T *)DY.p, DY.cs(), DY.split(), t->nchw_b, LL.cout, HW, (const int *)nullptr);
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return pn_conv2d_wgrad(t->ctx, t->nchw_a, t->nchw_b, LL.dw, LL.db, t->B, LL.cin, X.H, X.W, LL.cout, LL.ks, 1, LL.ks / 2, (void *)s);
         });
@@ -670,13 +627,11 @@ int op_wgrad(pn_trainer *t, int l, int dy) {
     if (int rc = op_fork(t)) return rc;
     const size_t from = t->ops.size();
     tx::WgPlan wp;
-    if (t->f32) {
-        if (int rc = tx::plan_wgrad_f32(t->ctx, t->B, X.H, X.W, (const float *)X.p, X.plane, (const float *)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw,
-                                        &t->wg_partial, &t->wg_partial_floats, t->ops, &wp))
-            return rc;
-    } else if (int rc = tx::plan_wgrad(t->ctx, t->B, X.H, X.W, (const bf *)X.p, X.plane, (const bf *)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw,
-                                       &t->wg_partial, &t->wg_partial_floats, t->ops, &wp))
-        return rc;
+    auto plan = [&](auto *null) {              // typed by the null pointer: const float * or const bf *
+        typedef decltype(null) P;
+        return tx::plan_wgrad(t->ctx, t->B, X.H, X.W, (P)X.p, X.plane, (P)DY.p, DY.plane, L.cin, L.cout, L.ks, L.cat ? t->cat_k_map : nullptr, L.dw, &t->wg_partial, &t->wg_partial_floats, t->ops, &wp);
+    };
+    if (int rc = t->f32 ? plan((const float *)nullptr) : plan((const bf *)nullptr)) return rc;
     describe(t, "wgrad", jf("\"kernels\": [\"%s<%d, 2>\", \"wgrad_reduce_kernel\"], \"layer\": \"%s\", \"ks\": %d, \"cin\": %d, \"cout\": %d, \"cat\": %d, \"tiles_x\": %d, \"Wt\": %d, "
                             "\"rows_per_block\": %d, \"Sr\": %d, \"x\": ", t->f32 ? "wgrad_f32_kernel" : "wgrad_stream_kernel", L.ks, L.name.c_str(), L.ks, L.cin, L.cout, L.cat ? 1 : 0,
                             wp.tiles_x, wp.Wt, wp.rows_per_block, wp.Sr) + jref(L.x, 0, X.plane) + ", \"dy\": " + jref(dy, 0, DY.plane));
@@ -733,8 +688,7 @@ int build(pn_trainer *t) {
             if (!handover) return pn_stem_forward_planes(t->ctx, t->img, w_stem, c0.p, c0.cs(), c0.split(), t->f32, B, 1, H, W, 64, 7, 2, 3, stem_gather, s);
             if (int r = pn_conv2d_forward(t->ctx, t->img, w_stem, nullptr, t->nchw_a, B, 1, H, W, 64, 7, 2, 3, 0, (void *)s)) return r;
             const int HW = H2 * W2;
-            if (t->f32) hipLaunchKernelGGL(tx::nchw_to_planes_kernel<float>, dim3((HW + 63) / 64, 1, B), dim3(256), 0, s, (const float *)t->nchw_a, (float *)c0.p, 64, HW, c0.cs(), 0);
-            else hipLaunchKernelGGL(tx::nchw_to_planes_kernel<bf>, dim3((HW + 63) / 64, 1, B), dim3(256), 0, s, (const float *)t->nchw_a, (bf *)c0.p, 64, HW, c0.cs(), c0.plane);
+            TX_LAUNCH_T(t, tx::nchw_to_planes_kernel<T>, dim3((HW + 63) / 64, 1, B), s, (const float *)t->nchw_a, (T *)c0.p, 64, HW, c0.cs(), c0.split());
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return (int)PN_OK;
         });
@@ -870,7 +824,7 @@ int build(pn_trainer *t) {
     TX(op_wgrad(t, l_c2, dC7));
     TX(add_conv_group(t, {{l_c2, true, dC7, dA6, 0, -1, PN_ACT_NONE, nullptr}}));
 
-    auto block_bwd = [&](const Block &b, int dout, int h, int w, int cin, int cout, int *din, int scratch[6]) -> int {
+    auto block_bwd = [&](const Block &b, int dout, int *din, int scratch[6]) -> int {
         int rc2;
         // scratch: dC2, g (identity gradient / dD), dA1, dC1, dCD, tmp  (reused between the two 112x112 blocks)
         int dC2 = scratch[0], g = scratch[1], dA1 = scratch[2], dC1 = scratch[3];
@@ -888,14 +842,13 @@ int build(pn_trainer *t) {
         } else {
             if ((rc2 = add_conv_group(t, {{b.l1, true, dC1, *din, 0, g, PN_ACT_NONE, nullptr}}))) return rc2;       // dx = dgrad(conv1) + identity gradient
         }
-        (void)h; (void)w; (void)cin; (void)cout;
         return PN_OK;
     };
     int s56[6], dP1;
     for (int i = 0; i < 4; ++i) TX(TT(H4, W4, 128, &s56[i]));
     TX(TT(H4, W4, 128, &s56[4])); TX(TT(H4, W4, 64, &s56[5]));
     TX(TT(H4, W4, 64, &dP1));
-    TX(block_bwd(b20, dA6, H4, W4, 64, 128, &dP1, s56));
+    TX(block_bwd(b20, dA6, &dP1, s56));
     // (own scratch per block: a weight gradient still running on the side stream reads dC2 / dC1 of its block)
     // the stem's BatchNorm backward is applied inside its weight-gradient kernel (train.hip::tstem_wgrad_kernel): dC0 never exists
     const bool stem_handover = t->sw.trainx_stem_handover;                             // A/B: the NCHW f32 hand-over of the round's first builds (bit-identical)
@@ -907,9 +860,9 @@ int build(pn_trainer *t) {
     TX(TT(H2, W2, 64, &dA4)); TX(TT(H2, W2, 64, &dA2));
     if (stem_bn_separate) TX(TT(H2, W2, 64, &dC0));
     op_pool_bwd(t, dP1, dA4);
-    TX(block_bwd(b11, dA4, H2, W2, 64, 64, &dA2, s112));
+    TX(block_bwd(b11, dA4, &dA2, s112));
     dA0 = dA4;                                   // free again: layer1.1's output gradient has been consumed (by launches of the step's own stream)
-    TX(block_bwd(b10, dA2, H2, W2, 64, 64, &dA0, s112b));
+    TX(block_bwd(b10, dA2, &dA0, s112b));
     op_bn_bwd(t, bn_stem, C0, dA0, A0, stem_bn_separate ? dC0 : -1, -1, 1, false);
     {
         const TxTensor d0 = dC0 >= 0 ? t->T[dC0] : TxTensor(), a0 = t->T[dA0], c0 = t->T[C0];
@@ -923,8 +876,7 @@ int build(pn_trainer *t) {
             }
             if (!stem_handover) return pn_stem_wgrad_planes(t->ctx, t->img, d0.p, d0.cs(), d0.split(), t->f32, nullptr, dw_stem, B, 1, H, W, 64, 7, 2, 3, stem_depth, s);
             const int HW = H2 * W2;
-            if (t->f32) hipLaunchKernelGGL(tx::planes_to_nchw_kernel<float>, dim3((HW + 63) / 64, 1, B), dim3(256), 0, s, (const float *)d0.p, d0.cs(), 0, t->nchw_b, 64, HW, (const int *)nullptr);
-            else hipLaunchKernelGGL(tx::planes_to_nchw_kernel<bf>, dim3((HW + 63) / 64, 1, B), dim3(256), 0, s, (const bf *)d0.p, d0.cs(), d0.plane, t->nchw_b, 64, HW, (const int *)nullptr);
+            TX_LAUNCH_T(t, tx::planes_to_nchw_kernel<T>, dim3((HW + 63) / 64, 1, B), s, (const T *)d0.p, d0.cs(), d0.split(), t->nchw_b, 64, HW, (const int *)nullptr);
             PN_HIP_CHECK(t->ctx, hipGetLastError());
             return pn_conv2d_wgrad(t->ctx, t->img, t->nchw_b, dw_stem, nullptr, B, 1, H, W, 64, 7, 2, 3, (void *)s);
         });
@@ -1016,13 +968,19 @@ int pn_trainer_finalize(pn_trainer *t, float *flat_param_dev, float *flat_grad_d
     return PN_OK;
 }
 
+// validates and stores the per-step arguments the ops read when they launch
+static int tx_set_step_args(pn_trainer *t, const char *what, const float *img_dev, const float *heat_gt_dev, const float *paf_gt_dev, const float *z_gt_dev, const float *fg_mask_dev,
+                            float *loss_terms_dev) {
+    if (!t->finalized) return pn_set_error(t->ctx, PN_ERR_STATE, "%s: pn_trainer_finalize has not been called", what);
+    if (!img_dev || !heat_gt_dev || !paf_gt_dev || !z_gt_dev || !fg_mask_dev || !loss_terms_dev) return pn_set_error(t->ctx, PN_ERR_INVALID, "%s: null device pointer", what);
+    t->img = img_dev; t->target[0] = paf_gt_dev; t->target[1] = heat_gt_dev; t->target[2] = z_gt_dev; t->fg = fg_mask_dev; t->loss = loss_terms_dev;
+    return PN_OK;
+}
+
 int pn_trainer_forward_backward(pn_trainer *t, const float *img_dev, const float *heat_gt_dev, const float *paf_gt_dev, const float *z_gt_dev, const float *fg_mask_dev,
                                 float *loss_terms_dev, void *hip_stream) {
     if (!t) return PN_ERR_INVALID;
-    pn_ctx *ctx = t->ctx;
-    if (!t->finalized) return pn_set_error(ctx, PN_ERR_STATE, "pn_trainer_forward_backward: pn_trainer_finalize has not been called");
-    if (!img_dev || !heat_gt_dev || !paf_gt_dev || !z_gt_dev || !fg_mask_dev || !loss_terms_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_forward_backward: null device pointer");
-    t->img = img_dev; t->target[0] = paf_gt_dev; t->target[1] = heat_gt_dev; t->target[2] = z_gt_dev; t->fg = fg_mask_dev; t->loss = loss_terms_dev;
+    if (int rc = tx_set_step_args(t, "pn_trainer_forward_backward", img_dev, heat_gt_dev, paf_gt_dev, z_gt_dev, fg_mask_dev, loss_terms_dev)) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     for (auto &op : t->ops)
         if (int rc = op(s)) return rc;
@@ -1068,23 +1026,12 @@ int pn_trainer_run_ops(pn_trainer *t, const float *img_dev, const float *heat_gt
                        float *loss_terms_dev, int first, int last, void *hip_stream) {
     if (!t) return PN_ERR_INVALID;
     pn_ctx *ctx = t->ctx;
-    if (!t->finalized) return pn_set_error(ctx, PN_ERR_STATE, "pn_trainer_run_ops: pn_trainer_finalize has not been called");
-    if (!img_dev || !heat_gt_dev || !paf_gt_dev || !z_gt_dev || !fg_mask_dev || !loss_terms_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_run_ops: null device pointer");
+    if (int rc = tx_set_step_args(t, "pn_trainer_run_ops", img_dev, heat_gt_dev, paf_gt_dev, z_gt_dev, fg_mask_dev, loss_terms_dev)) return rc;
     if (first < 0 || last < first || last > (int)t->ops.size()) return pn_set_error(ctx, PN_ERR_INVALID, "pn_trainer_run_ops: [%d, %d) outside [0, %zu]", first, last, t->ops.size());
-    t->img = img_dev; t->target[0] = paf_gt_dev; t->target[1] = heat_gt_dev; t->target[2] = z_gt_dev; t->fg = fg_mask_dev; t->loss = loss_terms_dev;
     hipStream_t s = (hipStream_t)hip_stream;
     for (int k = first; k < last; ++k)
         if (int rc = t->ops[k](s)) return rc;
     return tx_sync(t, s);          // both streams: a range may end between a fork and its join
-}
-
-static inline float tx_bf2f(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-static inline uint16_t tx_f2bf(float f) {          // round to nearest even, as the device's float -> __bf16 conversion
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
 }
 
 static int tx_tensor_range(pn_trainer *t, const char *what, int id, int frame0, int nframes, size_t host_elems, size_t *frame_elems) {
@@ -1117,7 +1064,7 @@ int pn_trainer_read_tensor(pn_trainer *t, int id, int which, int frame0, int nfr
                 if (t->f32) v = ((const float *)px)[c];
                 else {
                     const uint16_t *h = (const uint16_t *)px;
-                    const float hi = tx_bf2f(h[c]), lo = tx_bf2f(h[X.plane + c]);
+                    const float hi = pn_bf16_to_f32(h[c]), lo = pn_bf16_to_f32(h[X.plane + c]);
                     v = which == 1 ? hi : which == 2 ? lo : hi + lo;
                 }
                 host_out[((size_t)f * X.plane + c) * HW + p] = v;
@@ -1142,8 +1089,8 @@ int pn_trainer_write_tensor(pn_trainer *t, int id, int frame0, int nframes, cons
                 if (t->f32) ((float *)px)[c] = v;
                 else {                                   // Lay<bf>::st1: hi = bf(v), lo = bf(v - hi)
                     uint16_t *h = (uint16_t *)px;
-                    h[c] = tx_f2bf(v);
-                    h[X.plane + c] = tx_f2bf(v - tx_bf2f(h[c]));
+                    h[c] = pn_f32_to_bf16(v);
+                    h[X.plane + c] = pn_f32_to_bf16(v - pn_bf16_to_f32(h[c]));
                 }
             }
         }

@@ -407,60 +407,46 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 // What a plan decided (diagnostics: the length of the fp32 summation chains of one output element is rows_per_block rows of <= Wt pixels in a block, then Sr slices)
 struct WgPlan { int tiles_x = 0, Wt = 0, rows_per_block = 0, Sr = 0; };
 
-// Plans the weight gradient of one layer and appends its two launches to `ops`.  *partial_floats grows to what the layer needs; the
-// buffer itself (*partial) is allocated by the caller after every layer has been planned (the kernels read the pointer at launch time).
-inline int plan_wgrad_f32(pn_ctx *ctx, int B, int H, int W, const float *x, int x_plane, const float *dy, int dy_plane, int Cin, int Cout, int ks, const int *k_map, float *dw,
-                          float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops, WgPlan *plan = nullptr) {
-    if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "fp32 weight gradient: kernel size %d not built", ks);
-    const int KK = ks * ks, pad = ks / 2, seg_max = 32 - 2 * pad;
-    WgfArgs w;
-    memset(&w, 0, sizeof w);
-    w.x = x; w.x_cs = x_plane; w.x_zero = (unsigned)((size_t)B * H * W * x_plane * 4);
-    w.dy = dy; w.dy_cs = dy_plane; w.dy_zero = (unsigned)((size_t)B * H * W * dy_plane * 4);
-    w.B = B; w.H = H; w.W = W;
-    w.tiles_x = (W + seg_max - 1) / seg_max;
-    w.Wt = (W + w.tiles_x - 1) / w.tiles_x;
-    const int ci_my = k_map ? x_plane : Cin;
-    const int ncot = (Cout + 63) / 64;
-    w.ncit = (ci_my + 63) / 64;
-    w.co_pad = ncot * 64; w.ci_pad = w.ncit * 64;
-    if (w.co_pad > dy_plane || w.ci_pad > x_plane) return pn_set_error(ctx, PN_ERR_INVALID, "fp32 weight gradient: channel tiles exceed the tensors");
-    const int pairs = ncot * w.ncit;
-    w.rows_total = B * w.tiles_x * H;
-    int Sr = std::max(1, std::min(w.rows_total, (ctx->num_cus + pairs - 1) / pairs));          // one block per CU (see plan_wgrad)
-    w.rows_per_block = (w.rows_total + Sr - 1) / Sr;
-    Sr = (w.rows_total + w.rows_per_block - 1) / w.rows_per_block;
-    *partial_floats = std::max(*partial_floats, (size_t)Sr * KK * w.co_pad * w.ci_pad);
-    if (plan) { plan->tiles_x = w.tiles_x; plan->Wt = w.Wt; plan->rows_per_block = w.rows_per_block; plan->Sr = Sr; }
-    const size_t ldss = (size_t)10 * 8192;
-    ops.push_back([=](hipStream_t s) {
-        WgfArgs ww = w;
-        ww.partial = *partial;
-        if (ks == 3) {
-            static PnLdsAttr attr;
-            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_f32_kernel<3, 2>), ldss)) return rc;
-            hipLaunchKernelGGL((wgrad_f32_kernel<3, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
-        } else {
-            static PnLdsAttr attr;
-            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_f32_kernel<1, 2>), ldss)) return rc;
-            hipLaunchKernelGGL((wgrad_f32_kernel<1, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
-        }
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((size_t)KK * ww.co_pad * ww.ci_pad + 15) / 16)), dim3(256), 0, s, (const float *)ww.partial, Sr, KK, ww.co_pad, ww.ci_pad, Cout, Cin, k_map, dw);
-        PN_HIP_CHECK(ctx, hipGetLastError());
-        return (int)PN_OK;
-    });
+// What differs between the two forms: the argument struct, the kernel, the stored planes per tensor and the wording of the errors.
+template <class T> struct Wg;
+template <> struct Wg<bf> {
+    typedef WgsArgs Args;
+    static constexpr int planes = 2;
+    static constexpr const char *name = "weight gradient on planes", *operands = "planes";
+    static void set_split(Args &w, int x_plane, int dy_plane) { w.x_split = x_plane; w.dy_split = dy_plane; }
+    template <int KS> static void (*kernel())(Args) { return wgrad_stream_kernel<KS, 2>; }
+};
+template <> struct Wg<float> {
+    typedef WgfArgs Args;
+    static constexpr int planes = 1;
+    static constexpr const char *name = "fp32 weight gradient", *operands = "tensors";
+    static void set_split(Args &, int, int) {}
+    template <int KS> static void (*kernel())(Args) { return wgrad_f32_kernel<KS, 2>; }
+};
+
+template <class T, int KS>
+int launch_wgrad(pn_ctx *ctx, dim3 grid, size_t lds, hipStream_t s, const typename Wg<T>::Args &w) {
+    static PnLdsAttr attr;                                  // one per kernel instantiation
+    void (*const kern)(typename Wg<T>::Args) = Wg<T>::template kernel<KS>();
+    if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(kern), lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, w);
     return PN_OK;
 }
 
-inline int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const bf *x, int x_plane, const bf *dy, int dy_plane, int Cin, int Cout, int ks, const int *k_map, float *dw,
-                      float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops, WgPlan *plan = nullptr) {
-    if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "weight gradient on planes: kernel size %d not built", ks);
+// Plans the weight gradient of one layer and appends its two launches to `ops`.  *partial_floats grows to what the layer needs; the
+// buffer itself (*partial) is allocated by the caller after every layer has been planned (the kernels read the pointer at launch time).
+// T = bf: [hi | lo] bf16 planes (wgrad_stream_kernel); T = float: one fp32 plane (wgrad_f32_kernel).
+template <class T>
+int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const T *x, int x_plane, const T *dy, int dy_plane, int Cin, int Cout, int ks, const int *k_map, float *dw,
+               float *const *partial, size_t *partial_floats, std::vector<std::function<int(hipStream_t)>> &ops, WgPlan *plan = nullptr) {
+    if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: kernel size %d not built", Wg<T>::name, ks);
     const int KK = ks * ks, pad = ks / 2;
     const int seg_max = 32 - 2 * pad;                      // a halo row holds 32 pixels
-    WgsArgs w;
+    typename Wg<T>::Args w;
     memset(&w, 0, sizeof w);
-    w.x = x; w.x_cs = 2 * x_plane; w.x_split = x_plane; w.x_zero = (unsigned)((size_t)B * H * W * 2 * x_plane * 2);
-    w.dy = dy; w.dy_cs = 2 * dy_plane; w.dy_split = dy_plane; w.dy_zero = (unsigned)((size_t)B * H * W * 2 * dy_plane * 2);
+    w.x = x; w.x_cs = Wg<T>::planes * x_plane; w.x_zero = (unsigned)((size_t)B * H * W * w.x_cs * sizeof(T));
+    w.dy = dy; w.dy_cs = Wg<T>::planes * dy_plane; w.dy_zero = (unsigned)((size_t)B * H * W * w.dy_cs * sizeof(T));
+    Wg<T>::set_split(w, x_plane, dy_plane);
     w.B = B; w.H = H; w.W = W;
     w.tiles_x = (W + seg_max - 1) / seg_max;
     w.Wt = (W + w.tiles_x - 1) / w.tiles_x;
@@ -468,7 +454,7 @@ inline int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const bf *x, int x_plane
     const int ncot = (Cout + 63) / 64;
     w.ncit = (ci_my + 63) / 64;
     w.co_pad = ncot * 64; w.ci_pad = w.ncit * 64;
-    if (w.co_pad > dy_plane || w.ci_pad > x_plane) return pn_set_error(ctx, PN_ERR_INVALID, "weight gradient on planes: channel tiles exceed the planes");
+    if (w.co_pad > dy_plane || w.ci_pad > x_plane) return pn_set_error(ctx, PN_ERR_INVALID, "%s: channel tiles exceed the %s", Wg<T>::name, Wg<T>::operands);
     const int pairs = ncot * w.ncit;
     // split-K slices: ONE block per CU.  Every slice costs a 147 KB partial tile written and read back, and a lone 64 KB block leaves the rest of the CU to
     // the BatchNorm / data-gradient launches of the step's own stream (same box, eager step: 1/2 block per CU 7.10 ms, 1: 6.49-6.68, 1.5: 6.93, 2: 7.03, 3: 7.39)
@@ -480,17 +466,9 @@ inline int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const bf *x, int x_plane
     if (plan) { plan->tiles_x = w.tiles_x; plan->Wt = w.Wt; plan->rows_per_block = w.rows_per_block; plan->Sr = Sr; }
     const size_t ldss = (size_t)(5 + 5) * 8192;            // two rings of five rows
     ops.push_back([=](hipStream_t s) {
-        WgsArgs ww = w;
+        typename Wg<T>::Args ww = w;
         ww.partial = *partial;                             // the host reads the pointer when the step launches (the buffer exists by then)
-        if (ks == 3) {
-            static PnLdsAttr attr;
-            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_stream_kernel<3, 2>), ldss)) return rc;
-            hipLaunchKernelGGL((wgrad_stream_kernel<3, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
-        } else {
-            static PnLdsAttr attr;
-            if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(wgrad_stream_kernel<1, 2>), ldss)) return rc;
-            hipLaunchKernelGGL((wgrad_stream_kernel<1, 2>), dim3(Sr, pairs), dim3(256), ldss, s, ww);
-        }
+        if (int rc = ks == 3 ? launch_wgrad<T, 3>(ctx, dim3(Sr, pairs), ldss, s, ww) : launch_wgrad<T, 1>(ctx, dim3(Sr, pairs), ldss, s, ww)) return rc;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((size_t)KK * ww.co_pad * ww.ci_pad + 15) / 16)), dim3(256), 0, s, (const float *)ww.partial, Sr, KK, ww.co_pad, ww.ci_pad, Cout, Cin, k_map, dw);
         PN_HIP_CHECK(ctx, hipGetLastError());
         return (int)PN_OK;
