@@ -143,6 +143,19 @@ int pn_net_copy_activation(pn_net *net, const char *name, int B, float *dev_out,
 int pn_net_forward_partial(pn_net *net, const float *x_dev, int B, int nsteps, void *hip_stream);
 int pn_net_num_steps(pn_net *net);
 int pn_net_step_info(pn_net *net, int k, char *out, size_t cap);
+/* The plan of one LEVEL of up to three independent convolutions that read the same H x W map, as pn_net_finalize would plan it, without a
+ * net and without a device (a context from pn_create(-1) will do; nothing is launched).  precision: pn_precision, PN_PREC_BF16X3 included;
+ * num_cus: the compute units the plan is made for; cin[i]: the input channels the K loop covers (the input BUFFER's channels where the
+ * buffer is wider than the weight's Cin: bf16x3 reads whole buffers); together != 0: the convolutions decide as one level (conv4 or not, shared
+ * 128-cout blocks: rtpose_light3d's levels), 0: each is planned alone (YoloPoseNet's).  Kernel switches are read from the environment at the call, as
+ * pn_net_finalize reads them.  out: {"convs": [{"kernel", "kern", "cfg", "pitch", "R", "Wt", "wc", "wp", "nbuf", "pt", "rpg", "tiles_x",
+ * "tiles_per_img", "cout_blocks", "nblocks", "lds_two"}, ...]}, the block counts at batch B <= max_batch -- the fields pn_net_step_info
+ * reports for every convolution of a compiled net.  PN_ERR_UNSUPPORTED (message: "conv <i>: <reason>") where pn_net_finalize refuses the
+ * shape.  pn_conv_has_instance: 1 when the generic MFMA convolution is built for (prec = PN_PREC_BF16 / PN_PREC_F32, kernel size, stride,
+ * LDS pitch class, tile configuration "cfg"): the table the launch dispatch and the planner both read. */
+int pn_conv_level_plan_info(pn_ctx *ctx, int precision, int max_batch, int num_cus, int B, int H, int W, int together, int nconv,
+                            const int *cout, const int *cin, const int *ks, const int *stride, char *out, size_t cap);
+int pn_conv_has_instance(int prec, int ks, int stride, int pitch, int cfg);
 /* Algorithmic FLOPs (2*MAC, convolutions only) of one frame through the finalized net. */
 double pn_net_flops_per_frame(pn_net *net);
 /* Freezes the launch descriptors at the batch size / output pointers of the last forward: afterwards a forward with

@@ -118,6 +118,8 @@ _SIGNATURES = {
     "pn_net_forward_partial": (_i, [_vp, _vp, _i, _i, _vp]),
     "pn_net_num_steps": (_i, [_vp]),
     "pn_net_step_info": (_i, [_vp, _i, C.c_char_p, _sz]),
+    "pn_conv_level_plan_info": (_i, [_vp] + [_i] * 8 + [_vp] * 4 + [C.c_char_p, _sz]),
+    "pn_conv_has_instance": (_i, [_i] * 5),
     "pn_net_flops_per_frame": (_d, [_vp]),
     "pn_net_lock": (_i, [_vp, _i]),
     "pn_parse_reserve": (_i, [_vp, _i]),

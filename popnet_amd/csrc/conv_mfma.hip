@@ -1,7 +1,9 @@
 // Launch dispatch of the MFMA convolution (kernel template: conv_mfma_kernel.h).  The
 // instantiations -- {3x3, 1x1} x {stride 1, 2} x LDS pitch class {16, 32, 64, 120 pixels} x tile
-// configuration x {bf16, f32} -- are spread over conv_inst_*.hip so they compile in parallel.
+// configuration x {bf16, f32} -- are spread over conv_inst_*.hip so they compile in parallel; which of them exist
+// is listed once, in conv_inst_table.h.
 #include "pn_internal.h"
+#include "conv_inst_table.h"
 
 int pn_cfg_couts(int cfg) {
     switch (cfg) {
@@ -20,6 +22,16 @@ size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R) {
     size_t pixb = prec == PN_PREC_BF16 ? 128 : 256;
     size_t rows = (size_t)(R - 1) * stride + ks;
     return rows * pitch * pixb;
+}
+
+// Is conv_mfma_kernel<prec, ks, stride, pitch, cfg> built?  The same rows as the dispatch below (conv_inst_table.h).
+extern "C" int pn_conv_has_instance(int prec, int ks, int stride, int pitch, int cfg) {
+    if (prec != PN_PREC_BF16 && prec != PN_PREC_F32) return 0;
+#define PN_HAS_CASE(KS, ST, PITCH, CFG) \
+    if (ks == KS && stride == ST && pitch == PITCH && cfg == CFG) return 1;
+    PN_CONV_INSTANCES(PN_HAS_CASE)
+#undef PN_HAS_CASE
+    return 0;
 }
 
 int pn_launch_conv_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);

@@ -26,6 +26,7 @@
 #pragma once
 #include <type_traits>
 #include "pn_internal.h"
+#include "conv_inst_table.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
 template <int PREC, int KS, int STRIDE, int PITCH, int CFG>
 static int conv_launch_one(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream) {
     auto kern = conv_mfma_kernel<PREC, KS, STRIDE, PITCH, CFG>;
-    if (L.lds_bytes > 160 * 1024)
+    if (L.lds_bytes > PN_CONV_LDS_MAX)
         return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "conv halo tile needs %zu B of LDS", L.lds_bytes);
     if (L.lds_bytes > 48 * 1024) {
         static PnLdsAttr attr;          // per instantiation, per device
@@ -524,12 +525,9 @@ static int conv_launch_one(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream)
         return conv_launch_one<PREC, KS, ST, PITCH, CFG>(ctx, L, stream);
 #define PN_CASES_PREC(KS, ST, PITCH, CFG) \
     PN_CASE(PN_PREC_BF16, KS, ST, PITCH, CFG) PN_CASE(PN_PREC_F32, KS, ST, PITCH, CFG)
-#define PN_CASES_ALLCFG(KS, ST, PITCH)                                                 \
-    PN_CASES_PREC(KS, ST, PITCH, PN_CFG_C128) PN_CASES_PREC(KS, ST, PITCH, PN_CFG_C64) \
-    PN_CASES_PREC(KS, ST, PITCH, PN_CFG_C32) PN_CASES_PREC(KS, ST, PITCH, PN_CFG_C16)
 
-// each conv_inst_*.hip implements one of these for its share of the instantiations; returns
-// 1 when the launch description is not one of its cases
+// each conv_inst_*.hip implements one of these for its share of the instantiations -- PN_CONV_INSTANCES_<n>(PN_CASES_PREC), the rows of
+// conv_inst_table.h and nothing else; returns 1 when the launch description is not one of its cases
 int pn_launch_conv_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part1(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part2(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);

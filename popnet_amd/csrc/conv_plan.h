@@ -135,13 +135,21 @@ inline int pn_plan_conv_tiles(int prec, int H, int W, ConvGeom &g, const char **
     const int segs = (Wo + wt_cap - 1) / wt_cap;
     g.Wt = (Wo + segs - 1) / segs;
     g.R = std::max(1, std::min(Ho, BP / g.Wt));
+    // the narrowest LDS pitch class that holds the halo row AND has a built instance for (prec, ks, stride, cfg): the table (conv_inst_table.h) has
+    // holes -- no 1x1 kernel at pitch 16, no stride-2 kernel below pitch 64 -- and a wider LDS row is always valid
+    const int need = (g.Wt - 1) * stride + ks;
+    g.pitch = -1;
+    for (int c : {16, 32, 64, 120})
+        if (need <= c && pn_conv_has_instance(prec, ks, stride, c, g.cfg)) { g.pitch = c; break; }
+    if (g.pitch < 0) { *why = pn_pick_pitch(need) < 0 ? "halo width has no pitch class" : "no generic kernel instance for this kernel size, stride and cout block at any pitch class"; return PN_ERR_UNSUPPORTED; }
     {   // the register-prefetched staging path holds at most this many halo pixels
-        const int maxpx = pn_conv_stage_maxpx(prec, ks, stride, pn_pick_pitch((g.Wt - 1) * stride + ks), g.cfg);
-        while (maxpx > 0 && g.R > 1 && ((g.R - 1) * stride + ks) * ((g.Wt - 1) * stride + ks) > maxpx) --g.R;
-        if (maxpx > 0 && ((g.R - 1) * stride + ks) * ((g.Wt - 1) * stride + ks) > maxpx) { *why = "halo tile exceeds the staging capacity"; return PN_ERR_UNSUPPORTED; }
+        const int maxpx = pn_conv_stage_maxpx(prec, ks, stride, g.pitch, g.cfg);
+        while (maxpx > 0 && g.R > 1 && ((g.R - 1) * stride + ks) * need > maxpx) --g.R;
+        if (maxpx > 0 && ((g.R - 1) * stride + ks) * need > maxpx) { *why = "halo tile exceeds the staging capacity"; return PN_ERR_UNSUPPORTED; }
     }
-    g.pitch = pn_pick_pitch((g.Wt - 1) * stride + ks);
-    if (g.pitch < 0) { *why = "halo width has no pitch class"; return PN_ERR_UNSUPPORTED; }
+    // one halo image must fit the LDS (conv_launch_one refuses the launch otherwise): tall tiles of a narrow strided map.  R = 1 always fits: at
+    // most 3 rows x 120 pixels x 256 B = 90 KB
+    while (g.R > 1 && pn_conv_lds_bytes(prec, ks, stride, g.pitch, g.R) > PN_CONV_LDS_MAX) --g.R;
     return PN_OK;
 }
 
@@ -190,7 +198,7 @@ inline void pn_fill_conv_problem(ConvProblem &P, const PnConvInput &in, int B, i
     P.ksteps = cin_chunks * g.ks * g.ks * 2;
     P.ks = g.ks;
     P.lds_buf_bytes = (int)pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R);
-    P.lds_two = (cin_chunks > 1 && 2 * (size_t)P.lds_buf_bytes <= 160 * 1024) ? 1 : 0;
+    P.lds_two = (cin_chunks > 1 && 2 * (size_t)P.lds_buf_bytes <= PN_CONV_LDS_MAX) ? 1 : 0;
     P.in_zero_off = (unsigned)in.bytes;
 }
 

@@ -847,6 +847,20 @@ int refresh_problems(pn_net *n, int B, hipStream_t stream) {
     return PN_OK;
 }
 
+// The planned geometry of one convolution as JSON fields (no braces): what pn_net_step_info reports per convolution and pn_conv_level_plan_info
+// per planned convolution -- one writer, so the two views cannot differ in what they mean.  Tile and block counts are those of a launch at batch B.
+std::string geom_json(int prec, bool x3, const ConvGeom &g, int H, int W, int cout, int cin_chunks, int B) {
+    ConvProblem P;
+    memset(&P, 0, sizeof P);
+    pn_fill_conv_problem(P, {nullptr, H, W, 0, 64, 0}, B, cin_chunks, cout, g, prec, x3);
+    char t[384];
+    snprintf(t, sizeof t, "\"kernel\": \"%s\", \"kern\": %d, \"cfg\": %d, \"pitch\": %d, \"R\": %d, \"Wt\": %d, \"wc\": %d, \"wp\": %d, \"nbuf\": %d, \"pt\": %d, \"rpg\": %d, "
+             "\"tiles_x\": %d, \"tiles_per_img\": %d, \"cout_blocks\": %d, \"nblocks\": %d, \"lds_two\": %d",
+             pn_conv_kernel_label(prec, g.kern, false, g.ks, g.stride, g.pitch, g.cfg, g.wc, g.wp, g.nbuf, g.pt, g.rpg).c_str(), g.kern, g.cfg, g.pitch, g.R, g.Wt, g.wc,
+             g.wp, g.nbuf, g.pt, g.rpg, P.tiles_x, P.tiles_per_img, P.cout_blocks, P.nblocks, P.lds_two);
+    return t;
+}
+
 // Kernel label of a step: the profiler's per-instantiation key (pn_net_profile_kernel) and pn_net_step_info's "kernel".
 std::string step_label(const pn_net *n, const Step &st) {
     if (st.type == Step::STEM) {
@@ -1165,6 +1179,10 @@ int pn_net_step_info(pn_net *n, int k, char *out, size_t cap) {
         js += ", \"pool\": ";
         if (c.pool_tail) add("{\"mode\": 0, \"out_buf\": %d, \"out_coff\": %d}", c.pool_out_buf, c.pool_out_coff);
         else js += "null";
+        // the plan (conv_plan.h) as compiled; the counts at the batch of the last forward (max_batch before the first).  A fused pool (\"pool\") tiles
+        // the POOLED map instead (refresh_problems): tiles_x / tiles_per_img / nblocks are then not the launch's
+        const Buf &ib = n->bufs[c.in_buf];
+        js += ", " + geom_json(n->prec, n->x3, c, ib.H, ib.W, c.cout, c.cin_chunks, n->last_B > 0 ? n->last_B : n->max_batch);
         js += "}";
     };
     if (k == -1) {
@@ -1190,6 +1208,40 @@ int pn_net_step_info(pn_net *n, int k, char *out, size_t cap) {
         js += "}";
     }
     if (js.size() + 1 > cap) return pn_set_error(ctx, PN_ERR_INVALID, "pn_net_step_info: %zu bytes needed", js.size() + 1);
+    memcpy(out, js.c_str(), js.size() + 1);
+    return PN_OK;
+}
+
+int pn_conv_level_plan_info(pn_ctx *ctx, int precision, int max_batch, int num_cus, int B, int H, int W, int together, int nconv, const int *cout,
+                            const int *cin, const int *ks, const int *stride, char *out, size_t cap) {
+    if (!ctx) return PN_ERR_INVALID;
+    if (!out || !cout || !cin || !ks || !stride || nconv < 1 || nconv > 3 || max_batch < 1 || B < 1 || B > max_batch || num_cus < 1 || H < 1 || W < 1 ||
+        (precision != PN_PREC_F32 && precision != PN_PREC_BF16 && precision != PN_PREC_BF16X3))
+        return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv_level_plan_info: bad arguments");
+    for (int i = 0; i < nconv; ++i)
+        if (cout[i] < 1 || cin[i] < 1 || (ks[i] != 1 && ks[i] != 3) || (stride[i] != 1 && stride[i] != 2))
+            return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv_level_plan_info: convolution %d: bad arguments", i);
+    const bool x3 = precision == PN_PREC_BF16X3;
+    const int prec = x3 ? PN_PREC_BF16 : precision;
+    const PnSwitches sw = pn_read_switches();
+    std::vector<PnLevelConv> lv(nconv);
+    for (int i = 0; i < nconv; ++i) {
+        lv[i].H = H; lv[i].W = W; lv[i].rows = cout[i]; lv[i].ks = ks[i]; lv[i].stride = stride[i];
+        lv[i].cin_gt64 = cin[i] > 64;
+    }
+    if (together) pn_plan_level(lv, max_batch, x3, sw.conv4);      // build_rtpose; build_yolo plans every convolution alone
+    std::string js = "{\"convs\": [";
+    for (int i = 0; i < nconv; ++i) {
+        const int cin_chunks = ((x3 ? 3 : 1) * cin[i] + 63) / 64;      // bf16x3: the K loop runs over three planes of the input buffer (prepare_conv)
+        ConvGeom g;
+        g.ks = ks[i]; g.stride = stride[i];
+        pn_plan_conv_kernel(prec, max_batch, num_cus, H, W, cout[i], cin_chunks, lv[i].wc_min, lv[i].nbuf_min, lv[i].k4_level, sw, g);
+        const char *why = "";
+        if (int rc = pn_plan_conv_tiles(prec, H, W, g, &why)) return pn_set_error(ctx, rc, "conv %d: %s", i, why);
+        js += (i ? ", {" : "{") + geom_json(prec, x3, g, H, W, cout[i], cin_chunks, B) + "}";
+    }
+    js += "]}";
+    if (js.size() + 1 > cap) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv_level_plan_info: %zu bytes needed", js.size() + 1);
     memcpy(out, js.c_str(), js.size() + 1);
     return PN_OK;
 }

@@ -239,6 +239,8 @@ int pn_launch_bb64(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);       /
 int pn_launch_bb64x3(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);     // bb64x3_inst.hip (6-row tiles: tiles_per_img = ceil(H / 6) * tiles_x)
 size_t pn_conv3_lds_bytes(int ks, int WP, int nbuf, int rpg = 4);
 size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R);
+// LDS one block of the generic kernel may use: what the planner fits a halo image (or two) into and what the launch refuses to exceed
+constexpr size_t PN_CONV_LDS_MAX = 160 * 1024;
 int pn_conv_stage_maxpx(int prec, int ks, int stride, int pitch, int cfg);   // 0 = no limit (direct staging)
 
 // stem: 7x7 stride-2 pad-3, Cin = 1, fused folded-BN bias + ReLU.  x NCHW f32 [B,1,H,W] ->

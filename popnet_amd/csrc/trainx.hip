@@ -270,7 +270,6 @@ int add_conv_group(pn_trainer *t, const std::vector<ConvUse> &uses) {
         pn_plan_conv_kernel(prec, t->B, ctx->num_cus, in.H, in.W, pc.rows, pc.cin_chunks, lv[i].wc_min, lv[i].nbuf_min, lv[i].k4_level, t->sw, pc.g);
         const char *why = "";
         if (int rc = pn_plan_conv_tiles(prec, in.H, in.W, pc.g, &why)) return pn_set_error(ctx, rc, "pn_trainer: %s: %s", L.name.c_str(), why);
-        if (pc.g.kern == 0 && L.ks == 1 && pc.g.pitch == 16) pc.g.pitch = 32;      // the generic 1x1 kernel is not instantiated for the 16-pixel pitch class (a wider LDS row is always valid)
         pc.cout_pad = pn_conv_cout_pad(pc.g, pc.rows);
     }
     std::vector<bool> used(pcs.size(), false);
