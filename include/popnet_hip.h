@@ -295,6 +295,39 @@ int pn_parse_paf_wire(pn_ctx *ctx, const float *heat_dev, const float *paf_dev, 
                       pn_pose_wire *wire_dev, void *hip_stream);
 size_t pn_sizeof_pose_wire(void);
 
+/* ---- depth-ablation arms of the MP-3DHP evaluation (csrc/ablation.hip) ------------------------------------------------------------
+ * The four read-outs tpm/evaluate/evaluation_rtpose_light3d_kdh3d_mpreal_ablation.py compares (2D location from the prediction or
+ * from the ground truth x depth from the pose-depth map or from the "raw depth" frame); pn_parse_paf writes the first
+ * (human_pred_set_3d), these write the other three.  "Raw depth" is the script's un-normalised network input (:183-185, `img *= std;
+ * img += mean` on float32): raw[y, x] = fl32(fl32(norm * depth_std) + depth_mean), norm = the pixel pn_preprocess writes -- re-derived
+ * here from the raw frames with the same arithmetic, so the pre-processed tensor need not exist (pn_rtpose_forward_frames never
+ * writes it).  depth_dev [B, H, W] f16 / f32 metres, resized to the square S = cfg->input_size; an exactly 2S x 2S frame is
+ * PN_ERR_UNSUPPORTED as in pn_preprocess.  One launch per call, no allocation; the two pn_ablation_* calls do not synchronise.
+ *   pn_ablation_pred_raw     human_pred_set_3d_read_raw_depth (:198-218, :245-274): frames_dev = the B records pn_parse_paf wrote; person i,
+ *                            joint j with peak (x, y) = peak_x / peak_y[person_joint[i][j]] reads raw[int(y), int(x)] and gives
+ *                            ((x2 - cx) raw / fx, (y2 - cy) raw / fy, raw) in float64, (x2, y2) = joints_2d[i][j]; a missing joint has raw = -1
+ *                            and (x2, y2) = (-1, -1) through the same expression.  out_dev double [B][PN_MAX_PERSONS][PN_NUM_JOINTS][3], rows at
+ *                            or beyond n_persons zero; the persons of a record with an overflow status are computed all the same.
+ *   pn_ablation_perfect_2d   human_pred_set_3d_perfect_2d and _perfect_2d_read_raw_depth (:220-242, :279-299): gt_2d_dev double [B][Gmax][J][2]
+ *                            (original-frame pixels, straight from the labels), gt_count_dev int32 [B] persons per frame; z_dev [B, L+1, h, w]
+ *                            the pose-depth map as the network emits it, h = w = input_size / downsample.  Joint (gx, gy) reads
+ *                            d = fl32(fl32(z[j][cy][cx] * depth_std) + depth_mean) at cx = clamp(int(gx / w_org * input_size / downsample), 0, w - 1)
+ *                            (float64 left to right, int() truncating toward zero; cy alike with h_org) and raw[py, px] at
+ *                            px = clamp(int(gx / w_org * input_size), 0, input_size - 1); out_map_dev / out_raw_dev double [B][Gmax][J][3] =
+ *                            ((gx - cx) d / fx, (gy - cy) d / fy, d) with d resp. raw, rows at or beyond the frame's count zero.
+ *                            Gmax = 0 or B = 0: nothing to do, PN_OK.
+ *   pn_depth_probe           raw[y, x] of frame b for n points pts_dev int32 [n][3] = (frame, y, x) -> out_dev float [n].  The second-pass
+ *                            entry (frames whose record overflowed are re-parsed without capacities and read their raw depth here) and a
+ *                            test handle for the pixel arithmetic.  A point outside the batch or the S x S frame is PN_ERR_INVALID, never
+ *                            clamped: the points are checked on the host first, so this call waits for the stream.                       */
+int pn_ablation_pred_raw(pn_ctx *ctx, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max,
+                         const pn_parse_cfg *cfg, const pn_pose_frame *frames_dev, double *out_dev, void *hip_stream);
+int pn_ablation_perfect_2d(pn_ctx *ctx, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max,
+                           const float *z_dev, int h, int w, const pn_parse_cfg *cfg, const double *gt_2d_dev,
+                           const int *gt_count_dev, int Gmax, double *out_map_dev, double *out_raw_dev, void *hip_stream);
+int pn_depth_probe(pn_ctx *ctx, const void *depth_dev, int depth_dtype, int B, int H, int W, int S, float depth_max,
+                   float depth_mean, float depth_std, const int *pts_dev, int n, float *out_dev, void *hip_stream);
+
 /* ---- training targets ----------------------------------------------------------
  * The CPU data-loader work of the reference's training dataset, as device kernels:
  *   pn_compose_depth      the z-buffer multi-person compositor of KDH3D_Keypoints.__getitem__

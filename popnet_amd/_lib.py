@@ -179,6 +179,9 @@ _SIGNATURES = {
     "pn_parse_debug_connections": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "pn_parse_paf_unbounded_connections": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "pn_parse_yolo_predvis": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_float), _i, _i, _i, _i, _f, _f, _f, _f, _i, C.POINTER(ParseCfg), _vp, _vp, _vp]),
+    "pn_ablation_pred_raw": (_i, [_vp, _vp, _i, _i, _i, _i, _f, C.POINTER(ParseCfg), _vp, _vp, _vp]),
+    "pn_ablation_perfect_2d": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, C.POINTER(ParseCfg), _vp, _vp, _i, _vp, _vp, _vp]),
+    "pn_depth_probe": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _i, _vp, _vp]),
     "pn_sizeof_pose_frame": (_sz, []),
     "pn_pack_pose_frames": (_i, [_vp, _vp, _i, _vp, _vp]),
     "pn_sizeof_pose_wire": (_sz, []),

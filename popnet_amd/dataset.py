@@ -63,12 +63,39 @@ class MP3DHPFrames:
             yield chunk, np.stack(frames)
 
 
-def pose_records_to_lists(recs, overflow=None):
+ABLATION_KEYS = ("human_pred_set_3d_read_raw_depth", "human_pred_set_3d_perfect_2d", "human_pred_set_3d_perfect_2d_read_raw_depth",
+                 "human_gt_set_2d_visible")
+
+
+def pose_records_to_lists(recs, overflow=None, ablation=None):
     """pn_pose_frame records -> the per-frame entries of human_pred_set_{2d,3d,visibility,part_conf} (float64 lists,
     [-1, -1] / Z = -1 for joints a person does not have, exactly what the evaluation script appends).
     overflow: {frame index: result of utils.paf_to_pose.parse_paf_unbounded} for the frames whose record carries an overflow
-    status (PoseEngine.predict_lists fills it); without it such a frame raises -- it is never truncated silently."""
+    status (PoseEngine.predict_lists fills it); without it such a frame raises -- it is never truncated silently.
+    ablation: the depth-ablation arms of the same frames (PoseEngine.predict_ablation; evaluation_rtpose_light3d_kdh3d_mpreal_ablation.py:
+    197-313) -- {"pred_raw": float64 [F, PN_MAX_PERSONS, 15, 3], "perfect_map" / "perfect_raw": float64 [F, Gmax, 15, 3], "gt_2d": per
+    frame the labels' [n_g][15][2], "overflow_raw": {frame index: [P, 15, 3]} for the frames in `overflow`} -- adds ABLATION_KEYS:
+    the raw arm follows the predicted persons, the perfect_* arms and human_gt_set_2d_visible the ground-truth persons."""
     out = {"human_pred_set_2d": [], "human_pred_set_3d": [], "human_pred_set_visibility": [], "human_pred_set_part_conf": []}
+    if ablation is not None:
+        if len(ablation["gt_2d"]) < len(recs) or any(len(ablation[k]) < len(recs) for k in ("pred_raw", "perfect_map", "perfect_raw")):
+            raise _lib.PopnetError("ablation arms cover fewer frames than the %d records" % len(recs))
+        out.update({k: [] for k in ABLATION_KEYS})
+        for i, fr in enumerate(recs):
+            g = ablation["gt_2d"][i]
+            if len(g) > ablation["perfect_map"].shape[1]:
+                raise _lib.PopnetError("frame %d has %d ground-truth persons, the ablation arms carry %d" % (i, len(g), ablation["perfect_map"].shape[1]))
+            if int(fr["status"]):
+                if i not in ablation.get("overflow_raw", {}):
+                    raise _lib.PopnetError("pose record overflow (status=%d) in frame %d: its raw-depth arm needs the second pass -- use "
+                                           "PoseEngine.ablation_lists" % (int(fr["status"]), i))
+                raw = np.asarray(ablation["overflow_raw"][i], dtype=np.float64)
+            else:
+                raw = np.asarray(ablation["pred_raw"][i][:int(fr["n_persons"])], dtype=np.float64)
+            out["human_pred_set_3d_read_raw_depth"].append(raw.tolist())
+            out["human_pred_set_3d_perfect_2d"].append(np.asarray(ablation["perfect_map"][i][:len(g)], dtype=np.float64).tolist())
+            out["human_pred_set_3d_perfect_2d_read_raw_depth"].append(np.asarray(ablation["perfect_raw"][i][:len(g)], dtype=np.float64).tolist())
+            out["human_gt_set_2d_visible"].append([np.array(h).tolist() for h in g])      # copy.deepcopy(np.array(human_gt)).tolist() (:304-305)
     for i, fr in enumerate(recs):
         if int(fr["status"]):
             if overflow is None or i not in overflow:
@@ -101,9 +128,12 @@ def yolo_records_to_lists(recs):
     return out
 
 
-def run_sweep(engine, frames, batch_size=32, rank=0, world=1, drop_last=False, group=None):
+def run_sweep(engine, frames, batch_size=32, rank=0, world=1, drop_last=False, group=None, ablation=False):
     """Runs `engine` (PoseEngine / YoloEngine) over this rank's shard of `frames` and returns the records of ALL frames
-    in global order as a structured numpy array (one all-gather of fixed-size records when world > 1)."""
+    in global order as a structured numpy array (one all-gather of fixed-size records when world > 1).
+    ablation=True (PoseEngine only): also the depth-ablation arms (PoseEngine.predict_ablation against the labels' 2D joints), as fixed-size
+    per-frame float64 arrays gathered next to the records -- returns (records, {"pred_raw" [n, PN_MAX_PERSONS, 15, 3], "perfect_map" /
+    "perfect_raw" [n, Gmax, 15, 3], "gt_2d"}), Gmax = the split's largest ground-truth person count; eval_data_from_records takes the pair."""
     import torch
     from .pipeline import gather_records, shard_indices
     n = len(frames)
@@ -112,24 +142,46 @@ def run_sweep(engine, frames, batch_size=32, rank=0, world=1, drop_last=False, g
     mine = shard_indices(n, rank, world)
     item = engine.frames.shape[1]
     local = torch.empty((len(mine), item), dtype=torch.uint8, device=engine.device)
+    if ablation:
+        if not hasattr(engine, "predict_ablation"):
+            raise _lib.PopnetError("the depth-ablation arms exist for the Open-Pose+ path (PoseEngine) only")
+        gt_2d = frames.ground_truth()[0]
+        J, P = _lib.PN_NUM_JOINTS, _lib.PN_MAX_PERSONS
+        gmax = max([len(g) for g in gt_2d[:n]] + [0])
+        rows = P + 2 * gmax                          # per frame: the raw arm's rows, then perfect_map's, then perfect_raw's
+        arms = torch.zeros((len(mine), rows, J, 3), dtype=torch.float64, device=engine.device)
     done = 0
     for chunk, host in frames.batches(mine, min(batch_size, engine.max_batch)):
         dev = torch.from_numpy(host).to(engine.device, non_blocking=True)
-        local[done:done + len(chunk)].copy_(engine.predict(dev))
+        if ablation:
+            recs, raw, pm, pr = engine.predict_ablation(dev, [gt_2d[i] for i in chunk], gmax)
+            local[done:done + len(chunk)].copy_(recs)
+            arms[done:done + len(chunk)].copy_(torch.cat([raw, pm, pr], dim=1))
+        else:
+            local[done:done + len(chunk)].copy_(engine.predict(dev))
         done += len(chunk)
+    if ablation:
+        arms = arms.reshape(len(mine), rows * J * 3).view(torch.uint8)
+        if world > 1:
+            arms = gather_records(arms, n, rank, world, group)
+        arms = arms.cpu().numpy().view(np.float64).reshape(-1, rows, J, 3)
+        arms = {"pred_raw": arms[:, :P], "perfect_map": arms[:, P:P + gmax], "perfect_raw": arms[:, P + gmax:], "gt_2d": gt_2d[:n]}
     if world > 1:
         local = gather_records(local, n, rank, world, group)
     dtype = _lib.POSE_FRAME_DTYPE if item == _lib.POSE_FRAME_DTYPE.itemsize else _lib.YOLO_FRAME_DTYPE
-    return local.cpu().numpy().view(dtype).reshape(-1)
+    recs = local.cpu().numpy().view(dtype).reshape(-1)
+    return (recs, arms) if ablation else recs
 
 
-def run_sweep_streaming(se, frames, batch_size=32, rank=0, world=1, drop_last=False, group=None, gather=True):
+def run_sweep_streaming(se, frames, batch_size=32, rank=0, world=1, drop_last=False, group=None, gather=True, ablation=False):
     """Same result as run_sweep, through a pipeline.StreamingEngine: batch k+1 is read from disk, pinned and copied to
     the device (on its slot's stream) while batches k, k-1 are still being computed; a slot's records are collected right
     before the slot is reused.  gather=False returns this rank's shard only (device uint8 [n_local, item], frames
     rank, rank + world, ...) without touching torch.distributed."""
     import torch
     from .pipeline import gather_records, shard_indices
+    if ablation:
+        raise _lib.PopnetError("run_sweep_streaming: the depth-ablation arms are not part of the captured streaming step; use run_sweep(..., ablation=True)")
     n = len(frames)
     if drop_last:
         n -= n % (batch_size * world)
@@ -179,9 +231,12 @@ def run_sweep_streaming(se, frames, batch_size=32, rank=0, world=1, drop_last=Fa
     return local.cpu().numpy().view(dtype).reshape(-1)
 
 
-def eval_data_from_records(recs, frames):
-    """The eval_data.json dictionary for a finished sweep (predictions from the records, ground truth from the labels)."""
-    data = pose_records_to_lists(recs) if recs.dtype == _lib.POSE_FRAME_DTYPE else yolo_records_to_lists(recs)
+def eval_data_from_records(recs, frames, ablation=None):
+    """The eval_data.json dictionary for a finished sweep (predictions from the records, ground truth from the labels).
+    ablation: the arms run_sweep(..., ablation=True) returned next to the records -- all ten keys of the reference's ablation script."""
+    if ablation is not None and recs.dtype != _lib.POSE_FRAME_DTYPE:
+        raise _lib.PopnetError("the depth-ablation arms exist for the Open-Pose+ records only")
+    data = pose_records_to_lists(recs, ablation=ablation) if recs.dtype == _lib.POSE_FRAME_DTYPE else yolo_records_to_lists(recs)
     g2, g3 = frames.ground_truth()
     data["human_gt_set_2d"], data["human_gt_set_3d"] = g2[:len(recs)], g3[:len(recs)]
     return data

@@ -275,9 +275,42 @@ def parse_gt_labels(anno_dic):
     return g2, g3
 
 
-def evaluate_mp_human_3d(gt_file, res_file, verbose=True):
+# The five 3D PCK blocks evaluation_rtpose_light3d_kdh3d_mpreal_ablation.py keeps commented out (:451-544), in its order:
+# (result suffix, the 2D set the persons are matched on, the 3D set that is scored, the title it prints)
+ABLATION_BLOCKS = (
+    ('perfect_2d', 'human_gt_set_2d', 'human_pred_set_3d_perfect_2d', 'evaluating in 3D read from pose depth given perfect 2d'),
+    ('perfect_2d_visible', 'human_gt_set_2d_visible', 'human_pred_set_3d_perfect_2d',
+     'evaluating in 3D read from pose depth given perfect 2d, focusing on visible gt parts'),
+    ('raw', 'human_pred_set_2d', 'human_pred_set_3d_read_raw_depth', 'evaluating in 3D read from raw depth'),
+    ('raw_perfect_2d', 'human_gt_set_2d', 'human_pred_set_3d_perfect_2d_read_raw_depth', 'evaluating in 3D read from raw depth given perfect 2d'),
+    ('raw_perfect_2d_visible', 'human_gt_set_2d_visible', 'human_pred_set_3d_perfect_2d_read_raw_depth',
+     'evaluating in 3D read from raw depth given perfect 2d, focusing on visible gt parts'),
+)
+
+
+def evaluate_ablation_blocks(res, g2, g3, verbose=True):
+    """eval_human_dataset_3d on the five argument sets of ABLATION_BLOCKS; res: the eval_data.json dictionary with the ablation keys.
+    Returns {pck3d_<suffix>, err3d_<suffix>}."""
+    out = {}
+    for suffix, key2, key3, title in ABLATION_BLOCKS:
+        for k in (key2, key3):
+            if k not in res and k != 'human_gt_set_2d':
+                raise KeyError("ablation metrics need '%s' in the results (scripts/evaluate_mpreal.py --ablation writes it)" % k)
+        m2 = g2 if key2 == 'human_gt_set_2d' else res[key2]
+        d, k = eval_human_dataset_3d(m2, g2, res[key3], g3, num_joints=NUM_PARTS, dist_th=0.1, iou_th=0.5)
+        out['pck3d_' + suffix], out['err3d_' + suffix] = k, d
+        if verbose:
+            print('\n' + title)
+            print('     3D threshold: {:03f} meter'.format(0.1))
+            for i, name in enumerate(KEYPOINTS):
+                print('     joint: {},  PCK: {:03f}, avg 3D error: {:03f}'.format(name, k[i], d[i]))
+            print('\n     Overall: PCK: {:03f}, avg 3D error: {:03f} \n'.format(np.average(k), np.average(d)))
+    return out
+
+
+def evaluate_mp_human_3d(gt_file, res_file, verbose=True, ablation=False):
     """The four metric blocks of main_evaluate_mp_human_3D.py:44-99 on a labels.json / results.json pair.
-    Returns a dict of the numbers it prints."""
+    Returns a dict of the numbers it prints.  ablation=True: plus the five depth-ablation blocks (evaluate_ablation_blocks)."""
     res = json.load(open(res_file))
     if 'pop' in res_file and 'human_pred_set_2d_aligned' in res:
         p2, p3 = res['human_pred_set_2d_aligned'], res['human_pred_set_3d_aligned']
@@ -297,6 +330,8 @@ def evaluate_mp_human_3d(gt_file, res_file, verbose=True):
     conf = res.get('human_pred_set_part_conf', [])
     out['ap2d'] = eval_ap_mpii_v2(p2, conf, g2, [], 0, 1, KEYPOINTS, 0.5, verbose).tolist()
     out['ap3d'] = eval_ap_3D(p3, conf, g3, [], KEYPOINTS, 0.1, verbose).tolist()
+    if ablation:
+        out.update(evaluate_ablation_blocks(res, g2, g3, verbose))
     return out
 
 

@@ -180,6 +180,94 @@ class PoseEngine:
         over = {i: parse_paf_unbounded(self.heat[i], self.paf[i], self.z[i], self.cfg) for i in range(len(recs)) if int(recs[i]["status"])}
         return pose_records_to_lists(recs, over)
 
+    # ---- depth-ablation arms (evaluation_rtpose_light3d_kdh3d_mpreal_ablation.py:197-299) ----------
+    def predict_ablation(self, depth, gt_2d, gmax=None):
+        """predict() plus the three depth-ablation read-outs of the reference's evaluation script, on the same stream, no sync.
+        depth [B,H,W] CUDA f16/f32; gt_2d: per frame the labels' [n_g][15][2] joints (original-frame pixels); gmax: rows per frame of the
+        ground-truth arms (default: the batch's largest n_g).  Returns (records, pred_raw, perfect_map, perfect_raw): device tensors, records
+        as predict(), pred_raw float64 [B, PN_MAX_PERSONS, 15, 3] = human_pred_set_3d_read_raw_depth per record row, perfect_map / perfect_raw
+        float64 [B, gmax, 15, 3] = human_pred_set_3d_perfect_2d / _perfect_2d_read_raw_depth per ground-truth person (rows past a frame's count: zero)."""
+        if len(gt_2d) != depth.shape[0]:
+            raise _lib.PopnetError("predict_ablation: %d frames but ground truth for %d" % (depth.shape[0], len(gt_2d)))
+        depth = depth.contiguous()                   # the three calls read the same frames
+        recs = self.predict(depth)
+        return (recs,) + self.ablation_arms(depth, recs, gt_2d, gmax)
+
+    def ablation_arms(self, depth, recs, gt_2d, gmax=None):
+        """The two launches behind predict_ablation: pn_ablation_pred_raw on the device records `recs` and pn_ablation_perfect_2d on the
+        pose-depth maps in self.z, both reading the raw frames `depth` the records and maps came from.  -> (pred_raw, perfect_map, perfect_raw)."""
+        B, args = self._frames_args(depth)
+        if len(gt_2d) != B or recs.shape[0] != B:
+            raise _lib.PopnetError("ablation_arms: %d frames, %d records, ground truth for %d" % (B, recs.shape[0], len(gt_2d)))
+        J = _lib.PN_NUM_JOINTS
+        counts = np.array([len(g) for g in gt_2d], dtype=np.int32)
+        G = int(counts.max()) if gmax is None else int(gmax)
+        if G < int(counts.max()):
+            raise _lib.PopnetError("ablation_arms: gmax %d is below the %d ground-truth persons of a frame" % (G, int(counts.max())))
+        gt = np.zeros((B, G, J, 2), np.float64)
+        for b, g in enumerate(gt_2d):
+            if len(g):
+                a = np.asarray(g, dtype=np.float64)
+                if a.shape != (len(g), J, 2):
+                    raise _lib.PopnetError("ablation_arms: ground truth of frame %d has shape %s, expected [n][%d][2]" % (b, a.shape, J))
+                gt[b, :len(g)] = a
+        depth = depth.contiguous()
+        recs = recs.contiguous()
+        d = self.device
+        gt_dev = torch.from_numpy(gt).to(d, non_blocking=True)
+        cnt_dev = torch.from_numpy(counts).to(d, non_blocking=True)
+        pred_raw = torch.empty((B, _lib.PN_MAX_PERSONS, J, 3), device=d, dtype=torch.float64)
+        pm = torch.empty((B, G, J, 3), device=d, dtype=torch.float64)
+        pr = torch.empty((B, G, J, 3), device=d, dtype=torch.float64)
+        st = _lib.current_stream_ptr(d)
+        dargs = (C.c_void_p(depth.data_ptr()),) + args[1:6]          # frames, dtype, B, H, W, depth_max
+        self.ctx.check(self.L.pn_ablation_pred_raw(self.ctx.handle, *dargs, C.byref(self.cfg), C.c_void_p(recs.data_ptr()),
+                                                   C.c_void_p(pred_raw.data_ptr()), st), "pn_ablation_pred_raw")
+        h = self.S // 8
+        self.ctx.check(self.L.pn_ablation_perfect_2d(self.ctx.handle, *dargs, C.c_void_p(self.z.data_ptr()), h, h, C.byref(self.cfg),
+                                                     C.c_void_p(gt_dev.data_ptr()), C.c_void_p(cnt_dev.data_ptr()), G,
+                                                     C.c_void_p(pm.data_ptr()), C.c_void_p(pr.data_ptr()), st), "pn_ablation_perfect_2d")
+        return pred_raw, pm, pr
+
+    def depth_probe(self, depth, points):
+        """The un-normalised network input ("raw depth" of the evaluation script) at `points` [n][3] = (frame, y, x) of the S x S frames the
+        engine derives from depth [B,H,W]: float32 [n] (host).  A point outside the batch or the frame raises."""
+        B, args = self._frames_args(depth)
+        pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 3)
+        depth = depth.contiguous()
+        pts_dev = torch.from_numpy(pts).to(self.device)
+        out = torch.empty((len(pts),), device=self.device, dtype=torch.float32)
+        self.ctx.check(self.L.pn_depth_probe(self.ctx.handle, C.c_void_p(depth.data_ptr()), *args[1:5], self.S, *args[5:8],
+                                             C.c_void_p(pts_dev.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
+                                             _lib.current_stream_ptr(self.device)), "pn_depth_probe")
+        return out.cpu().numpy()
+
+    def ablation_lists(self, depth, gt_2d, recs, pred_raw, perfect_map, perfect_raw):
+        """The eval_data.json lists of one batch with the four ablation keys (dataset.pose_records_to_lists(..., ablation=...)): recs (numpy
+        records) and the three arms (numpy or device) as predict_ablation returned them for depth / gt_2d, the batch's maps still in
+        self.heat / self.paf / self.z.  A frame whose record overflowed is parsed again without capacities, as in lists_from_records; its raw
+        arm then comes from pn_depth_probe at the re-parsed joints and the reference's float64 back-projection."""
+        from .dataset import pose_records_to_lists
+        from .utils.paf_to_pose import parse_paf_unbounded
+        tonp = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        over, over_raw = {}, {}
+        for i in range(len(recs)):
+            if not int(recs[i]["status"]):
+                continue
+            r = over[i] = parse_paf_unbounded(self.heat[i], self.paf[i], self.z[i], self.cfg)
+            pj = r["person_joint"]
+            vis = pj >= 0
+            raw = np.full(pj.shape, -1.0)
+            if vis.any():
+                xy = r["joint_list"][pj[vis]][:, :2]
+                pts = np.stack([np.full(len(xy), i), xy[:, 1].astype(np.int64), xy[:, 0].astype(np.int64)], axis=1)
+                raw[vis] = self.depth_probe(depth, pts).astype(np.float64)
+            j2 = r["joints_2d"]
+            over_raw[i] = np.stack([(j2[..., 0] - self.cfg.cx) * raw / self.cfg.fx, (j2[..., 1] - self.cfg.cy) * raw / self.cfg.fy, raw], axis=-1)
+        abl = {"pred_raw": tonp(pred_raw), "perfect_map": tonp(perfect_map), "perfect_raw": tonp(perfect_raw), "gt_2d": gt_2d,
+               "overflow_raw": over_raw}
+        return pose_records_to_lists(recs, over, ablation=abl)
+
     def pack(self, frames, wire=None):
         """pn_pose_frame records (device, [B, sizeof]) -> compact pn_pose_wire records (device uint8 [B, sizeof], no sync):
         the form that is gathered across GPUs (6.2 KB instead of 33 KB per frame)."""
