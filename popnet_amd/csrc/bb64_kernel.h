@@ -15,7 +15,7 @@
 //     of x), and y leaves with 16-B stores;
 //   * the input image is double-buffered: the next tile's image is fetched during this tile's conv1, the stores of
 //     this tile drain under the next tile's conv1 -- no lockstep memory phases;
-//   * 8 waves (HV = 1) with FIXED ROLES: waves 0-3 compute (each 64 couts x 5 / 4 pixel tiles: 20 / 16 MFMAs per k-step, B
+//   * 8 waves (HV = 1) with FIXED ROLES: waves 0-3 compute (each 64 couts x 5 / 3 1/2 pixel tiles: 20 / 14 MFMAs per k-step, B
 //     fragments from the images, A fragments from a 6-slot LDS ring), waves 4-7 only issue LDS-DMA and count their own
 //     vmcnt -- a compute wave's instruction stream is MFMA + ds_read only (conv4_kernel's ablations: DMA issue and its
 //     waits cost a lone wave 80 of 717 cycles per k-step).  Round 3: the loaders are split by STREAM -- waves 4, 5 fetch
@@ -29,6 +29,16 @@
 //     bytes of the intermediate image), not by blockIdx.x + k * gridDim.x: a persistent workgroup can only start on a CU that holds no other wave, so among
 //     the other in-flight batches' launches some workgroups start late -- with the static schedule the launch ended when the LATEST starter had walked its
 //     seven tiles; now the early ones take its share.  Which workgroup computes which tile changes, nothing else.
+//   * conv2 has no padding pixel tiles: a full tile's 224 outputs are 14 pixel tiles, three whole ones per compute wave plus tiles 12 and 13 split
+//     by cout-tile pairs (wave 0: tile 12, cout tiles 0-1; wave 1: tile 12, 2-3; wave 2: tile 13, 0-1; wave 3: tile 13, 2-3).  Four tiles per wave
+//     were 16: one MFMA in eight of conv2 computed on padding.  Odd waves hold the cout tiles in the order 2, 3, 0, 1 (addresses only);
+//   * the last phase of each convolution (k-steps 16, 17: both in the weight ring) runs PIXEL TILE OUTER: a tile's accumulators are final while
+//     the tiles after it still have MFMAs to issue, and its epilogue (bias + ReLU + pack + ds_write, or residual + bias + ReLU + pack + store) is
+//     placed among those MFMAs with sched_group_barrier.  Only the last tile's epilogue (conv2: the half tile's) runs with the matrix pipe idle.
+//     The epilogues are branch-free for that (a branch ends the scheduling region): conv1 slots past the tile compute a spare pixel of the images;
+//   * the folded biases sit in spare bytes of the intermediate image, not in 32 registers: 242 VGPRs, no scratch (tests/test_bb64_resources.py).
+// Every (cout tile, pixel tile) accumulator keeps its k order and its MFMA whichever wave owns it: bit-identical to the two-launch plan
+// (tests/test_gpu_bb64_tiles.py, tests/test_gpu_parity.py).
 // Weight pack (net.hip): [36 k-steps = (conv, half, tap)][4 cout tiles][64 lanes][8 bf16], rows permuted with
 // pn_conv_row_channel(tile, row, 4) so that a lane's 16 accumulators are 16 consecutive channels.
 #pragma once
@@ -49,6 +59,16 @@
 #define BB_OFF_A (BB_OFF_MID + BB_MID)
 #define BB_NSLOT 6                              // weight ring: a phase = 2 k-steps; phase p + 2 lands in the slots of phase p - 1
 #define BB_LDS (BB_OFF_A + BB_NSLOT * BB_ASLOT) // 163840 B = all of a CU's LDS
+// The folded biases live in LDS, not in 32 VGPRs per compute wave: pixel columns 30, 31 of the intermediate image are never written (MC <= 30) nor
+// read (x + kx <= 29), so rows 1 (b1) and 2 (b2) of quarter plane q hold that quarter's 16 floats there (64 B); the epilogues read them back.
+#define BB_BIAS(cv, q) (BB_OFF_MID + (q) * BB_MIDQ + (((cv) + 1) * 32 + 30) * 32)
+
+// The (k-step, pixel tile) order of the 18 * PT MFMA groups ("items") of a convolution; the B-fragment queue runs BQ - 1 items ahead of the MFMAs.
+// k-steps 0..15 go k-step outer.  With xch the last phase (k-steps 16, 17: both in the weight ring for the whole phase) goes pixel tile outer, so that
+// a tile's accumulators are final while the tiles after it still have MFMAs to issue -- except that tiles 0 and 1 go (0, 16) (1, 16) (0, 17) (1, 17):
+// k-step 17's weight fragments are read at the head of the phase and have not arrived for the second item.  Every accumulator keeps its k order.
+__host__ __device__ constexpr int bb_item_ks(int n, int PT, bool xch) { return !xch || n < 16 * PT ? n / PT : n - 16 * PT < 4 ? 16 + ((n - 16 * PT) >> 1) : 16 + ((n - 16 * PT) & 1); }
+__host__ __device__ constexpr int bb_item_pt(int n, int PT, bool xch) { return !xch || n < 16 * PT ? n % PT : n - 16 * PT < 4 ? (n - 16 * PT) & 1 : (n - 16 * PT) >> 1; }
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
@@ -68,6 +88,14 @@ template <int HV>
 __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProblem P) {
     typedef __bf16 T;
     constexpr int CT = 4 / HV, NCW = 4 * HV, NP = CT / 2, PT1 = 5, PT2 = 4, KK = 9, BQ = 6;
+    constexpr bool SPLIT = HV == 1;                      // conv2 without padding tiles (below)
+    constexpr bool XCH = HV == 1;                        // last phase of each convolution pixel tile outer, epilogues among its MFMAs
+    constexpr int NKO = XCH ? 16 : 18;                   // k-steps that run k-step outer
+    // Epilogue instructions (VALU / SALU / LDS write or store) placed behind each MFMA of a last phase.  Chosen from the cross-compiled instruction
+    // stream, not tuned on a GPU: conv1 has 28 MFMAs after its first finished tile for four epilogues of about 45 instructions, conv2 16 for three of
+    // about 58; with a smaller number the compiler leaves the rest in one lump at the end of the phase.  An MFMA hides only two VALU, so these
+    // regions are VALU-bound either way.
+    constexpr int FILL1 = 7, FILL2 = 11;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -189,16 +217,29 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
     // ================= compute waves =================
     int t = blockIdx.x;
     if (t >= P.ntiles) return;
-    const float *bias1 = P.bias1, *bias2 = P.bias2;
     const int pw = HV == 2 ? (wave & 3) : wave, hv = HV == 2 ? (wave >> 2) : 0;            // pixel group, cout half
-    float b1[4 * CT], b2[4 * CT];
-#pragma unroll
-    for (int i = 0; i < 4 * CT; ++i) { b1[i] = bias1[16 * q + 4 * CT * hv + i]; b2[i] = bias2[16 * q + 4 * CT * hv + i]; }
-    const int aaddr = BB_OFF_A + lane * 16 + hv * CT * 1024;
+    if (wave == 0) {                                    // lane = channel 16 q + c; published by the second prologue barrier
+        *reinterpret_cast<float *>(smem + BB_BIAS(0, q) + c * 4) = P.bias1[lane];
+        *reinterpret_cast<float *>(smem + BB_BIAS(1, q) + c * 4) = P.bias2[lane];
+    }
+    // HV = 1: a full 8 x 28 tile has 14 pixel tiles of conv2 outputs; four per wave would be 16, two of them padding on the critical path of every
+    // k-step.  Each wave takes three whole pixel tiles (3 pw ..) and HALF of a leftover one: tile 12 + (pw >> 1), cout tiles 2 h, 2 h + 1 with
+    // h = pw & 1 -- 14 MFMAs per k-step instead of 16, the same four A and four B fragment reads.  So that the half tile's cout tiles are
+    // compile-time registers, a wave with h = 1 holds the cout tiles in the order 2, 3, 0, 1: fragment / accumulator slot i is cout tile i ^ 2 h
+    // everywhere (conv1 too), which only moves addresses -- the A fragment, the bias and the 16-byte piece of a pixel's quarter entry.
+    const int h = SPLIT ? (pw & 1) : 0;
+    auto pct = [&](int i) -> int { return SPLIT ? (i ^ (2 * h)) : hv * CT + i; };       // cout tile of slot i
+    auto pc = [&](int k) -> int { return SPLIT ? (k ^ h) : hv * NP + k; };              // 16-byte piece (8 channels) of slot pair k
+    const int biasaddr = BB_BIAS(0, q);                 // this lane's quarter: channels 16 q ..
+    float b1[4 * CT], b2[4 * CT];                       // live in an epilogue only
+    // two bases reach every weight fragment with an immediate offset (slots 0, 1 and slots 2, 3: cout tiles 2 h .. and 2 - 2 h ..); opaque, or the
+    // compiler folds BB_OFF_A into per-ring-slot bases of its own, a dozen registers held for the whole kernel
+    int aaddr0 = BB_OFF_A + lane * 16 + pct(0) * 1024, aaddr1 = aaddr0 ^ 2048;
+    asm volatile("" : "+v"(aaddr0), "+v"(aaddr1));
     bf16x8 aq[2][CT], bq[BQ];
     asm volatile("s_barrier" ::: "memory");             // prologue: first image + weight k-steps 0..2 landed
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) aq[0][ct] = *reinterpret_cast<const bf16x8 *>(smem + aaddr + ct * 1024);
+    for (int ct = 0; ct < CT; ++ct) aq[0][ct] = *reinterpret_cast<const bf16x8 *>(smem + (ct < 2 ? aaddr0 : aaddr1) + (ct & 1) * 1024);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     int cur = 0;
     for (int it = 0; t < P.ntiles; ++it) {
@@ -208,40 +249,104 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
         const int MC = Wc + 2, nmid = (R + 2) * MC, nout = R * Wc;
         const float inv_mc = 1.0f / (float)MC, inv_wc = 1.0f / (float)Wc;
         const int inb = cur * BB_IN;
-        // per-lane image addresses (tap and half are immediates)
+        // conv2's pixel tile of slot pt (SPLIT: slot 3 is the half tile)
+        auto out_tile = [&](int pt) -> int { return !SPLIT ? pw * PT2 + pt : pt < 3 ? pw * 3 + pt : 12 + (pw >> 1); };
+        // per-lane image addresses (tap and half are immediates).  A tile-local copy of c: what is derived from it is recomputed per tile (one or two VALU per slot) instead of being held in eighteen
+        // registers for the whole kernel.  (float)s + 0.5f == fc + (float)(s - c) exactly: small half-integers.
+        int cc = c;
+        asm volatile("" : "+v"(cc));
+        const float fc = (float)cc + 0.5f;
+        const int ba1base = inb + (q >> 1) * BB_INQ + (q & 1) * 16, ba2base = BB_OFF_MID + (q >> 1) * BB_MIDQ + (q & 1) * 16;
+        // conv1 slots past nmid compute pixel (3, 30 + (c & 1)) instead: a real address of the input image to read, and in the intermediate image spare
+        // bytes (pixel columns 30, 31) to write -- their epilogue needs no branch round the write, which would end the scheduling region it is placed in
+        const int dumppix = (3 * 32 + 30 + (cc & 1)) * 32;
         int ba1[PT1], ba2[PT2];
 #pragma unroll
         for (int pt = 0; pt < PT1; ++pt) {
-            const int s0 = (pw * PT1 + pt) * 16 + c, s = s0 < nmid ? s0 : 0;
-            const int r = (int)(((float)s + 0.5f) * inv_mc), x = s - r * MC;
-            ba1[pt] = inb + (q >> 1) * BB_INQ + (q & 1) * 16 + (r * 32 + x) * 32;
+            const int sb = (pw * PT1 + pt) * 16, s = sb + cc;
+            const int r = (int)((fc + (float)sb) * inv_mc), x = s - r * MC;
+            ba1[pt] = ba1base + (s < nmid ? (r * 32 + x) * 32 : dumppix);
         }
 #pragma unroll
         for (int pt = 0; pt < PT2; ++pt) {
-            const int s0 = (pw * PT2 + pt) * 16 + c, s = s0 < nout ? s0 : 0;
-            const int r = (int)(((float)s + 0.5f) * inv_wc), x = s - r * Wc;
-            ba2[pt] = BB_OFF_MID + (q >> 1) * BB_MIDQ + (q & 1) * 16 + (r * 32 + x) * 32;
+            const int sb = out_tile(pt) * 16, s = sb + cc;
+            const int r = (int)((fc + (float)sb) * inv_wc), x = s - r * Wc;
+            ba2[pt] = ba2base + (s < nout ? (r * 32 + x) * 32 : 0);
         }
         f32x4 acc[CT][PT1];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int pt = 0; pt < PT1; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // ---------------- the two epilogues, one pixel tile each, branch-free (a branch would end the scheduling region they are placed in) ----------------
+        // (r, x) of a slot come back out of its image address
+        const bool border = oy0 == 0 || ox0 == 0 || oy0 + R >= H || ox0 + Wc >= W;        // wave-uniform
+        // intermediate: bias + ReLU -> bf16 -> LDS image (zero outside the map).  Piece pc(0) of the lane's quarter entry; with NP = 2 piece pc(1) is ^ 16
+        const int midw = BB_OFF_MID + q * BB_MIDQ + 16 * pc(0);
+        auto epi1 = [&](int pt) {
+            const int pix = ba1[pt] - ba1base, r = pix >> 10, x = (pix >> 5) & 31;
+            const bool inside = (unsigned)(oy0 - 1 + r) < (unsigned)H && (unsigned)(ox0 - 1 + x) < (unsigned)W;
+            const unsigned keep = !border || inside ? 0xffffffffu : 0u;       // conv2's zero padding
+            // bias + ReLU as add + max, two channels per v_cvt_pk_bf16_f32; the zero padding outside the map is applied to the
+            // 8 packed dwords (per pixel), not per channel: a lone wave pays every VALU instruction of this block in full
+            // ReLU on the PACKED bf16 pair (a negative bf16 is a negative int16: one v_pk_max_i16 per two channels; rounding is
+            // monotonic, so relu(bf16(v)) == bf16(relu(v)))
+            u32x4 o[NP];                                 // this lane's 8 * NP channels of the pixel
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                f32x2 lo = {acc[ct][pt][0] + b1[4 * ct + 0], acc[ct][pt][1] + b1[4 * ct + 1]};
+                f32x2 hi = {acc[ct][pt][2] + b1[4 * ct + 2], acc[ct][pt][3] + b1[4 * ct + 3]};
+                o[ct >> 1][2 * (ct & 1)] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2))) & keep;
+                o[ct >> 1][2 * (ct & 1) + 1] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2))) & keep;
+            }
+            const int dsta = midw + pix;                  // (slots past nmid: spare bytes)
+            *reinterpret_cast<u32x4 *>(smem + dsta) = o[0];
+            if (NP == 2) *reinterpret_cast<u32x4 *>(smem + (dsta ^ 16)) = o[NP - 1];
+        };
+        // output: bias + residual (centre of the input image) + ReLU, 16-B stores (two per pixel; one for the half tile)
+        const int resw = inb + q * BB_INQ + (2 * 32 + 2) * 32 + 16 * pc(0);
+        __amdgpu_buffer_rsrc_t orsrc;
+        auto epi2 = [&](int pt) {
+            const int nct = SPLIT && pt == 3 ? 2 : CT, np = nct / 2;
+            const int pix = ba2[pt] - ba2base, r = pix >> 10, x = (pix >> 5) & 31;
+            const bool valid = out_tile(pt) * 16 + cc < nout;
+            u32x4 rr[NP], o[NP];
+            rr[0] = *reinterpret_cast<const u32x4 *>(smem + resw + pix);
+            if (np == 2) rr[NP - 1] = *reinterpret_cast<const u32x4 *>(smem + ((resw + pix) ^ 16));
+#pragma unroll
+            for (int ct = 0; ct < nct; ++ct) {
+                const unsigned ra = rr[ct >> 1][2 * (ct & 1)], rb = rr[ct >> 1][2 * (ct & 1) + 1];
+                // a bf16 is the upper half of its float: residual channels by shift / mask, no conversion instruction
+                f32x2 lo = {acc[ct][pt][0] + b2[4 * ct + 0] + __builtin_bit_cast(float, ra << 16),
+                            acc[ct][pt][1] + b2[4 * ct + 1] + __builtin_bit_cast(float, ra & 0xffff0000u)};
+                f32x2 hi = {acc[ct][pt][2] + b2[4 * ct + 2] + __builtin_bit_cast(float, rb << 16),
+                            acc[ct][pt][3] + b2[4 * ct + 3] + __builtin_bit_cast(float, rb & 0xffff0000u)};
+                o[ct >> 1][2 * (ct & 1)] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2)));
+                o[ct >> 1][2 * (ct & 1) + 1] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2)));
+            }
+            // out-of-range offset for the unused slots: the store is issued unconditionally and dropped by the hardware
+            unsigned vin = (unsigned)(((oy0 + r) * W + ox0 + x) * P.out_cs * 2 + 32 * q);
+            asm volatile("" : "+v"(vin));                  // computed for every slot: the compiler otherwise branches round the multiply
+            const unsigned voff = valid ? vin : 0x80000000u;
+#pragma unroll
+            for (int k = 0; k < np; ++k) __builtin_amdgcn_raw_buffer_store_b128(o[k], orsrc, voff + 16u * (unsigned)pc(k), 0, 0);
+        };
         // (aq[0] holds k-step 0's weight fragments: read in the prologue / prefetched by the previous tile's last phase)
         // ---------------- conv1: 18 k-steps on the input image ----------------
 #define BB_TAPOFF(tap) ((((tap) / 3) * 32 + ((tap) % 3)) * 32)
-#define BB_OFF1(j) ((((j) / PT1) / KK) * 2 * BB_INQ + BB_TAPOFF(((j) / PT1) % KK))
+#define BB_A(k, ct) (*reinterpret_cast<const bf16x8 *>(smem + ((ct) < 2 ? aaddr0 : aaddr1) + ((k) % BB_NSLOT) * BB_ASLOT + ((ct) & 1) * 1024))                    /* weight fragment of k-step k of the tile's 36 */
+#define BB_KOFF1(ks) (((ks) / KK) * 2 * BB_INQ + BB_TAPOFF((ks) % KK))
+#define BB_B1(n) (*reinterpret_cast<const bf16x8 *>(smem + ba1[bb_item_pt(n, PT1, XCH)] + BB_KOFF1(bb_item_ks(n, PT1, XCH))))         /* B fragment of item n */
 #pragma unroll
-        for (int j = 0; j < BQ - 1; ++j) bq[j] = *reinterpret_cast<const bf16x8 *>(smem + ba1[j % PT1] + BB_OFF1(j));
+        for (int j = 0; j < BQ - 1; ++j) bq[j] = BB_B1(j);
 #pragma clang loop unroll(full)
-        for (int ph = 0; ph < 18; ++ph) {
+        for (int ph = 0; ph < NKO; ++ph) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma clang loop unroll(full)
             for (int pt = 0; pt < PT1; ++pt) {
                 const int j = ph * PT1 + pt, jr = j + BQ - 1;
-                if (pt < CT)
-                    aq[(ph + 1) & 1][pt] = *reinterpret_cast<const bf16x8 *>(smem + aaddr + ((ph + 1) % BB_NSLOT) * BB_ASLOT + pt * 1024);
-                if (jr < 18 * PT1) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba1[jr % PT1] + BB_OFF1(jr));
+                if (pt < CT) aq[(ph + 1) & 1][pt] = BB_A(ph + 1, pt);
+                if (jr < 18 * PT1) bq[jr % BQ] = BB_B1(jr);
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
                     acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
@@ -254,101 +359,120 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             // images are stable)
             if (ph & 1) asm volatile("s_barrier" ::: "memory");
         }
-        // ---------------- intermediate: bias + ReLU -> bf16 -> LDS image (zero outside the map) ----------------
+#pragma unroll
+        for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4 *>(b1 + 4 * i) = *reinterpret_cast<const f32x4 *>(smem + biasaddr + 16 * pct(i));
+        if constexpr (XCH) {
+            // last phase, pixel tile outer (bb_item_*): the intermediate epilogue of a finished tile is issued among the MFMAs of the tiles after it
+            // (FILL1 VALU / SALU / ds_write per MFMA); only the last tile's epilogue is exposed.  aq[0] = k-step 16, aq[1] = k-step 17, read here.
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) aq[1][ct] = BB_A(17, ct);
 #pragma clang loop unroll(full)
-        for (int pt = 0; pt < PT1; ++pt) {
-            const int s = (pw * PT1 + pt) * 16 + c;
-            const int r = (int)(((float)s + 0.5f) * inv_mc), x = s - r * MC;
-            const int my = oy0 - 1 + r, mx = ox0 - 1 + x;
-            const bool inside = (unsigned)my < (unsigned)H && (unsigned)mx < (unsigned)W;
-            const bool border = oy0 == 0 || ox0 == 0 || oy0 + R >= H || ox0 + Wc >= W;        // wave-uniform
-            // bias + ReLU as add + max, two channels per v_cvt_pk_bf16_f32; the zero padding outside the map is applied to the
-            // 8 packed dwords (per pixel), not per channel: a lone wave pays every VALU instruction of this block in full
-            // ReLU on the PACKED bf16 pair (a negative bf16 is a negative int16: one v_pk_max_i16 per two channels; rounding is
-            // monotonic, so relu(bf16(v)) == bf16(relu(v)))
-            u32x4 o[NP];                                 // this lane's 8 * NP channels of the pixel: 16-byte pieces hv * NP .. of its quarter entry
+            for (int m = 0; m < 2 * PT1; ++m) {
+                const int n = 16 * PT1 + m, nr = n + BQ - 1, pt = bb_item_pt(n, PT1, true), ks = bb_item_ks(n, PT1, true);
+                if (nr < 18 * PT1) bq[nr % BQ] = BB_B1(nr);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                f32x2 lo = {acc[ct][pt][0] + b1[4 * ct + 0], acc[ct][pt][1] + b1[4 * ct + 1]};
-                f32x2 hi = {acc[ct][pt][2] + b1[4 * ct + 2], acc[ct][pt][3] + b1[4 * ct + 3]};
-                o[ct >> 1][2 * (ct & 1)] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2)));
-                o[ct >> 1][2 * (ct & 1) + 1] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2)));
-            }
-            if (border && !inside) {                     // conv2's zero padding; interior tiles skip the test
+                for (int ct = 0; ct < CT; ++ct)
+                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks & 1][ct], bq[n % BQ], acc[ct][pt], 0, 0, 0);
+                if (m == 2 * PT1 - 2) {                  // k-step 16's fragments have been used up: conv2's first k-step
 #pragma unroll
-                for (int k = 0; k < NP; ++k) o[k] = u32x4{0u, 0u, 0u, 0u};
-            }
-            if (s < nmid) {
-                u32x4 *dst = reinterpret_cast<u32x4 *>(smem + BB_OFF_MID + q * BB_MIDQ + (r * 32 + x) * 32) + hv * NP;
+                    for (int ct = 0; ct < CT; ++ct) aq[0][ct] = BB_A(18, ct);
+                }
+                if (ks == 17 && pt < PT1 - 1) epi1(pt);
+                if (m == 0) __builtin_amdgcn_sched_group_barrier(0x100, CT + 1, 0);
+                else if (nr < 18 * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
-                for (int k = 0; k < NP; ++k) dst[k] = o[k];
+                for (int ct = 0; ct < CT; ++ct) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x206, FILL1, 0);
+                }
+                if (m == 2 * PT1 - 2) __builtin_amdgcn_sched_group_barrier(0x100, CT, 0);
             }
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_barrier" ::: "memory");      // end of the phase
+            epi1(PT1 - 1);
+        } else {
+#pragma clang loop unroll(full)
+            for (int pt = 0; pt < PT1; ++pt) epi1(pt);
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         // ---------------- conv2: 18 k-steps on the intermediate image ----------------
-#define BB_OFF2(j) ((((j) / PT2) / KK) * 2 * BB_MIDQ + BB_TAPOFF(((j) / PT2) % KK))
+#define BB_KOFF2(ks) (((ks) / KK) * 2 * BB_MIDQ + BB_TAPOFF((ks) % KK))
+#define BB_B2(n) (*reinterpret_cast<const bf16x8 *>(smem + ba2[bb_item_pt(n, PT2, XCH)] + BB_KOFF2(bb_item_ks(n, PT2, XCH))))
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int pt = 0; pt < PT2; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < BQ - 1; ++j) bq[j] = *reinterpret_cast<const bf16x8 *>(smem + ba2[j % PT2] + BB_OFF2(j));
+        for (int j = 0; j < BQ - 1; ++j) bq[j] = BB_B2(j);
 #pragma clang loop unroll(full)
-        for (int p2 = 0; p2 < 18; ++p2) {
+        for (int p2 = 0; p2 < NKO; ++p2) {
             const int ph = 18 + p2;
             __builtin_amdgcn_sched_barrier(0);
 #pragma clang loop unroll(full)
             for (int pt = 0; pt < PT2; ++pt) {
                 const int j = p2 * PT2 + pt, jr = j + BQ - 1;
-                if (pt < CT)
-                    aq[(ph + 1) & 1][pt] = *reinterpret_cast<const bf16x8 *>(smem + aaddr + ((ph + 1) % BB_NSLOT) * BB_ASLOT + pt * 1024);
-                if (jr < 18 * PT2) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba2[jr % PT2] + BB_OFF2(jr));
+                if (pt < CT) aq[(ph + 1) & 1][pt] = BB_A(ph + 1, pt);
+                if (jr < 18 * PT2) bq[jr % BQ] = BB_B2(jr);
+                const int nct = SPLIT && pt == 3 ? 2 : CT;           // the half tile: slots 0, 1
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
+                for (int ct = 0; ct < nct; ++ct)
                     acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
                 if (pt < CT && jr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                 else if (pt < CT || jr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
+                if (SPLIT && pt == 3) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (ph & 1) asm volatile("s_barrier" ::: "memory");
         }
-        // ---------------- output: bias + residual (centre of the input image) + ReLU, 2 x 16-B stores per pixel ----------------
-        {
-            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (char *)P.out + ((size_t)b * H * W * P.out_cs + P.out_coff) * 2, 0, (int)((size_t)H * W * P.out_cs * 2), 0x00020000);
+#pragma unroll
+        for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4 *>(b2 + 4 * i) = *reinterpret_cast<const f32x4 *>(smem + biasaddr + 1024 + 16 * pct(i));
+        orsrc = __builtin_amdgcn_make_buffer_rsrc((char *)P.out + ((size_t)b * H * W * P.out_cs + P.out_coff) * 2, 0, (int)((size_t)H * W * P.out_cs * 2), 0x00020000);
+        if constexpr (XCH) {
+            // last phase as in conv1, with the output epilogue (residual read, stores) among the MFMAs; the exposed last epilogue is the half tile's.
+            // aq[0] = k-step 34, aq[1] = k-step 35; the next tile's k-step 0 follows into aq[0]
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) aq[1][ct] = BB_A(35, ct);
 #pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT2; ++pt) {
-                const int s = (pw * PT2 + pt) * 16 + c;
-                const int r = (int)(((float)s + 0.5f) * inv_wc), x = s - r * Wc;
-                const bool valid = s < nout;
-                const u32x4 *rp = reinterpret_cast<const u32x4 *>(smem + inb + q * BB_INQ + (((valid ? r : 0) + 2) * 32 + (valid ? x : 0) + 2) * 32);
-                u32x4 rr[NP], o[NP];
+            for (int m = 0; m < 2 * PT2; ++m) {
+                const int n = 16 * PT2 + m, nr = n + BQ - 1, pt = bb_item_pt(n, PT2, true), ks = bb_item_ks(n, PT2, true);
+                const int nct = pt == 3 ? 2 : CT;
+                if (nr < 18 * PT2) bq[nr % BQ] = BB_B2(nr);
 #pragma unroll
-                for (int k = 0; k < NP; ++k) rr[k] = rp[hv * NP + k];
+                for (int ct = 0; ct < nct; ++ct)
+                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks & 1][ct], bq[n % BQ], acc[ct][pt], 0, 0, 0);
+                if (m == 2 * PT2 - 2) {
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    const unsigned ra = rr[ct >> 1][2 * (ct & 1)], rb = rr[ct >> 1][2 * (ct & 1) + 1];
-                    // a bf16 is the upper half of its float: residual channels by shift / mask, no conversion instruction
-                    f32x2 lo = {acc[ct][pt][0] + b2[4 * ct + 0] + __builtin_bit_cast(float, ra << 16),
-                                acc[ct][pt][1] + b2[4 * ct + 1] + __builtin_bit_cast(float, ra & 0xffff0000u)};
-                    f32x2 hi = {acc[ct][pt][2] + b2[4 * ct + 2] + __builtin_bit_cast(float, rb << 16),
-                                acc[ct][pt][3] + b2[4 * ct + 3] + __builtin_bit_cast(float, rb & 0xffff0000u)};
-                    o[ct >> 1][2 * (ct & 1)] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2)));
-                    o[ct >> 1][2 * (ct & 1) + 1] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2)));
+                    for (int ct = 0; ct < CT; ++ct) aq[0][ct] = BB_A(36, ct);
                 }
-                // out-of-range offset for the unused slots: the store is issued unconditionally and dropped by the hardware
-                const unsigned voff = valid ? (unsigned)(((oy0 + r) * W + ox0 + x) * P.out_cs * 2 + 32 * q) : 0x80000000u;
+                if (ks == 17 && pt < PT2 - 1) epi2(pt);
+                if (m == 0) __builtin_amdgcn_sched_group_barrier(0x100, CT + 1, 0);
+                else if (nr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
-                for (int k = 0; k < NP; ++k) __builtin_amdgcn_raw_buffer_store_b128(o[k], orsrc, voff + 16u * (unsigned)(hv * NP + k), 0, 0);
+                for (int ct = 0; ct < nct; ++ct) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x146, FILL2, 0);
+                }
+                if (m == 2 * PT2 - 2) __builtin_amdgcn_sched_group_barrier(0x100, CT, 0);
             }
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_barrier" ::: "memory");      // end of the phase
+            epi2(PT2 - 1);
+        } else {
+#pragma clang loop unroll(full)
+            for (int pt = 0; pt < PT2; ++pt) epi2(pt);
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // the loader may now refill this image's buffer
         cur ^= 1;
         t = __builtin_amdgcn_readfirstlane(tnx);
     }
-#undef BB_OFF1
-#undef BB_OFF2
+#undef BB_A
+#undef BB_B1
+#undef BB_B2
+#undef BB_KOFF1
+#undef BB_KOFF2
 #undef BB_TAPOFF
 }
 
