@@ -196,8 +196,8 @@ int pn_net_profile_kernel(pn_net *net, int rank, char *name, size_t name_cap, do
 typedef struct pn_parse_cfg {
     float thresh_heatmap;      /* cfg.TEST.THRESH_HEATMAP  = 0.1   tpm/lib/config/default.py:126 */
     float thresh_paf;          /* cfg.TEST.THRESH_PAF      = 0.05  :127 */
-    int   num_intermed_pts;    /* must be 10               :128 */
-    int   downsample;          /* must be 8  cfg.MODEL.DOWNSAMPLE :41 */
+    int   num_intermed_pts;    /* 2 .. 32 (default 10)  cfg.TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS :128 */
+    int   downsample;          /* 1, 2, 4, 8 or 16 (default 8)  cfg.MODEL.DOWNSAMPLE :41 */
     int   input_size;          /* 224: network input side, divisor of the rescale */
     int   w_org, h_org;        /* original frame size for the rescale (480, 640) */
     double fx, fy, cx, cy;     /* pinhole intrinsics  util/util_functions.py:4 */
@@ -227,7 +227,10 @@ typedef struct pn_pose_frame {
 
 void pn_parse_cfg_default(pn_parse_cfg *cfg);
 /* heat [B,J+1,h,w], paf [B,2L,h,w], z [B,L+1,h,w]: f32 NCHW device buffers (z normalised, as
- * the network emits it).  frames_dev: device array of B pn_pose_frame.                          */
+ * the network emits it).  frames_dev: device array of B pn_pose_frame.  cfg->downsample = 8 with
+ * cfg->num_intermed_pts = 10 runs the kernels built for the workload; every other supported pair
+ * (see pn_parse_cfg) runs generic ones with the same results contract, and anything else is
+ * PN_ERR_UNSUPPORTED before any launch -- here, in pn_parse_paf_wire and in pn_parse_paf_unbounded. */
 int pn_parse_paf(pn_ctx *ctx, const float *heat_dev, const float *paf_dev, const float *z_dev,
                  int B, int h, int w, const pn_parse_cfg *cfg, pn_pose_frame *frames_dev,
                  void *hip_stream);
@@ -263,9 +266,19 @@ int pn_parse_paf_unbounded_connections(pn_ctx *ctx, int cap, int *count, int *co
  * [n_maps, h, w] f32 of one frame (any topology: `paf_to_pose_cpp`, paf_to_pose.py:381-385, runs it on the 18 COCO parts before
  * `process_paf`).  No capacity: count_dev [n_maps] int32 receives every map's peak count, peak_x / peak_y / peak_score_dev
  * [n_maps][h*w] f32 the peaks of map m at [m][0 .. count[m]) in the reference's order (row-major cells): refined x, y in
- * up-sampled pixels and the x8 bicubic score.  upsample must be 8.  Asynchronous on hip_stream.                              */
+ * up-sampled pixels and the bicubic score.  upsample: 1, 2, 4, 8 or 16, else PN_ERR_UNSUPPORTED.  Asynchronous on hip_stream, no
+ * allocation.                                                                                                                 */
 int pn_nms_peaks(pn_ctx *ctx, const float *heat_dev, int n_maps, int h, int w, float thresh, int upsample, int *count_dev,
                  float *peak_x_dev, float *peak_y_dev, float *peak_score_dev, void *hip_stream);
+/* The same with the reference's other two arguments.  refine_center = 0 (bool_refine_center=False): x = (px + 0.5) * upsample - 0.5, y
+ * alike, score = the map's own value at the peak; no patch is up-sampled and gaussian_filt is ignored, as in the reference (:143-146).
+ * gaussian_filt != 0 (bool_gaussian_filt=True): scipy.ndimage.gaussian_filter(patch_up, sigma=3) on the float32 up-sampled patch in
+ * front of the arg-max, bit for bit (radius 12, float64 accumulation per axis, 'reflect' border).  pn_nms_opt_default sets
+ * {8, 1, 0}: with those pn_nms_peaks_opt is pn_nms_peaks(..., 8, ...), the same launch.  Outputs as pn_nms_peaks.                  */
+typedef struct pn_nms_opt { int upsample; int refine_center; int gaussian_filt; } pn_nms_opt;
+void pn_nms_opt_default(pn_nms_opt *opt);
+int pn_nms_peaks_opt(pn_ctx *ctx, const float *heat_dev, int n_maps, int h, int w, float thresh, const pn_nms_opt *opt, int *count_dev,
+                     float *peak_x_dev, float *peak_y_dev, float *peak_score_dev, void *hip_stream);
 
 /* retrieve_depth_heat_weighted(center, depthmap, heatmap, radius) (tpm/lib/utils/common.py:272-293)
  * for n centres (x, y int32 pairs) on one [h, w] f32 map pair; like the reference it first clamps

@@ -54,6 +54,11 @@ class AugmentItem(C.Structure):
                 ("src_w", C.c_int), ("src_h", C.c_int)]
 
 
+class NmsOpt(C.Structure):
+    """pn_nms_opt"""
+    _fields_ = [("upsample", C.c_int), ("refine_center", C.c_int), ("gaussian_filt", C.c_int)]
+
+
 class ParseCfg(C.Structure):
     """pn_parse_cfg"""
     _fields_ = [("thresh_heatmap", C.c_float), ("thresh_paf", C.c_float),
@@ -173,6 +178,8 @@ _SIGNATURES = {
     "pn_trainer_read_vector": (_i, [_vp, C.c_char_p, _vp, _sz, _vp]),
     "pn_retrieve_depth": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "pn_nms_peaks": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn_nms_opt_default": (None, [C.POINTER(NmsOpt)]),
+    "pn_nms_peaks_opt": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(NmsOpt), _vp, _vp, _vp, _vp, _vp]),
     "pn_parse_yolo": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_float), _i, _i, _i, _i, _f, _f, _f, _f, _i, C.POINTER(ParseCfg), _vp, _vp]),
     "pn_parse_paf_unbounded": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(ParseCfg), C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
     "pn_parse_paf_unbounded_fetch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -28,32 +28,13 @@
 #pragma clang fp contract(off)
 #include <algorithm>
 #include <cmath>
-#include "pn_internal.h"
-
-#define J_ PN_NUM_JOINTS
-#define L_ PN_NUM_LIMBS
-#define MAXP PN_MAX_PEAKS_PER_JOINT
-#define MAXC PN_MAX_CONN_PER_LIMB
-#define MAX_MAP 4096      // largest h*w the parse kernels stage in LDS (64 KB static-LDS budget)
+#include "parse_ws.h"      // ParseWs / BigWs, the capacities, and the launches of the generic path (parse_generic.hip)
 
 // limb topology: util/util_functions.py:17-34 == tpm/lib/datasets/datasets_itop_rtpose.py:45-62
 __constant__ int c_limb_src[L_] = {8, 9, 11, 8, 10, 12, 8, 1, 2, 4, 1, 3, 5, 1};
 __constant__ int c_limb_dst[L_] = {9, 11, 13, 10, 12, 14, 1, 2, 4, 6, 3, 5, 7, 0};
 
 struct CubicTab { float c[8][4]; };   // phase p: fractional offset (2p+1)/16
-
-// LDS hand-over between lanes of ONE wave (a wave's LDS instructions execute in order; the waits and the compiler fence
-// make the earlier writes visible to the later reads of other lanes).  Used where the waves of a block run loops of
-// different trip counts, so a block barrier is not available.
-#define WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-
-struct ParseWs {                       // per-frame scratch between the three kernels
-    int peak_count[J_];                // uncapped count (overflow detection)
-    float peak_x[J_][MAXP], peak_y[J_][MAXP], peak_s[J_][MAXP];
-    int conn_count[L_];
-    int conn_i[L_][MAXC], conn_j[L_][MAXC];
-    double conn_s[L_][MAXC];
-};
 
 // interpolateCubic(x, coeffs), A = -0.75, float32 -- same expression order as oracle/cv2_resize.py
 static void host_cubic_coeffs(float x, float *c) {
@@ -626,8 +607,11 @@ extern "C" int pn_parse_paf_wire(pn_ctx *ctx, const float *heat_dev, const float
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_parse_paf: bad arguments");
     if (h * w > MAX_MAP || h < 1 || w < 1)
         return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_parse_paf: map %dx%d exceeds %d cells", h, w, MAX_MAP);
-    if (cfg->downsample != 8 || cfg->num_intermed_pts != 10)
-        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_parse_paf: built for downsample=8, 10 intermediate points");
+    if (pn_parse_factor_log2(cfg->downsample) < 0 || !pn_parse_pts_ok(cfg->num_intermed_pts))
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_parse_paf: downsample %d / num_intermed_pts %d: supported are downsample in {" PN_PARSE_FACTORS_TEXT "} and %d..%d intermediate points",
+                            cfg->downsample, cfg->num_intermed_pts, PN_PARSE_MIN_PTS, PN_PARSE_MAX_PTS);
+    // the kernels of this file serve the default arguments; anything else goes to the generic ones (parse_generic.hip), same scratch, same read-out
+    const bool generic = cfg->downsample != 8 || cfg->num_intermed_pts != 10;
     const size_t need = (size_t)B * sizeof(ParseWs);
     if (ctx->parse_ws_bytes < need) {
         // never move the scratch under a graph: not while this stream is capturing, not once its size was fixed
@@ -646,6 +630,17 @@ extern "C" int pn_parse_paf_wire(pn_ctx *ctx, const float *heat_dev, const float
     for (int p = 0; p < 8; ++p) host_cubic_coeffs((float)(2 * p + 1) / 16.0f, tab.c[p]);
     hipStream_t s = (hipStream_t)hip_stream;
     ParseWs *ws = (ParseWs *)ctx->parse_ws;
+    if (generic) {
+        const PnPeakOut po = {ws->peak_count, &ws->peak_x[0][0], &ws->peak_y[0][0], &ws->peak_s[0][0], MAXP, sizeof(ParseWs)};
+        int rc = pn_gen_launch_peaks(ctx, s, heat_dev, J_, B, h, w, J_ + 1, cfg->thresh_heatmap, cfg->downsample, 1, 0, po);
+        if (rc == PN_OK) rc = pn_gen_launch_limbs(ctx, s, paf_dev, B, h, w, cfg->thresh_paf, cfg->downsample, cfg->num_intermed_pts, ws);
+        if (rc != PN_OK) return rc;
+        hipLaunchKernelGGL(group_readout_kernel, dim3(B), dim3(256), 0, s, heat_dev, z_dev, h, w, J_ + 1, L_ + 1, *cfg,
+                           (const ParseWs *)ws, frames_dev, wire_dev);
+        PN_HIP_CHECK(ctx, hipGetLastError());
+        ctx->parse_last_b = B;
+        return PN_OK;
+    }
     // (rows beyond n_peaks / n_persons read as zero: group_readout_kernel zeroes its own record first)
     hipLaunchKernelGGL(peaks_refine_kernel, dim3(J_, B), dim3(256), 0, s, heat_dev, h, w, J_ + 1, cfg->thresh_heatmap, tab, ws);
     hipLaunchKernelGGL(limb_match_kernel, dim3(L_, B), dim3(256), 0, s, paf_dev, h, w, 2 * L_, cfg->thresh_paf,
@@ -701,28 +696,6 @@ extern "C" int pn_parse_reserve(pn_ctx *ctx, int max_batch) {
 // LDS, the greedy matching as repeated arg-max instead of a rank sort) but the same arithmetic in the same order, so a frame
 // that fits the records gives the same values through either path (tests/test_gpu_parity.py).
 // ---------------------------------------------------------------------------------------------
-struct BigWs {
-    int *peak_count;                 // [J]
-    float *px, *py, *ps;             // [J][hw]
-    int *conn_count;                 // [L]
-    int *conn_i, *conn_j;            // [L][hw]
-    double *conn_s;                  // [L][hw]
-    double *cand_s;                  // candidates of all limbs, limb l at cand_off[l]
-    unsigned short *cand_i, *cand_j;
-    long long cand_off[L_ + 1];
-    double *rows, *rows2;            // [maxp][J + 2]
-    int maxp;
-    int *keep_idx;                   // [maxp]
-    int *counts;                     // [0] peaks, [1] persons
-    // results
-    float *o_peak;                   // [npeaks][3]: x, y, score
-    int *o_peak_type;                // [npeaks]
-    int *o_person_joint;             // [P][J]
-    double *o_person_score;          // [P]
-    int *o_person_count;             // [P]
-    double *o_j2d, *o_j3d, *o_conf;  // [P][J][2], [P][J][3], [P][J]
-};
-
 __global__ __launch_bounds__(256) void big_peaks_kernel(const float *__restrict__ heat, int h, int w, float thresh, CubicTab tab, BigWs W) {
     __shared__ float map[MAX_MAP];
     __shared__ int s_wave_cnt[4];
@@ -1107,7 +1080,10 @@ extern "C" int pn_parse_paf_unbounded(pn_ctx *ctx, const float *heat_dev, const 
     if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
     if (!heat_dev || !paf_dev || !z_dev || !cfg || !n_peaks || !n_persons) return pn_set_error(ctx, PN_ERR_INVALID, "pn_parse_paf_unbounded: bad arguments");
     if (h * w > MAX_MAP || h < 1 || w < 1) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_parse_paf_unbounded: map %dx%d exceeds %d cells", h, w, MAX_MAP);
-    if (cfg->downsample != 8 || cfg->num_intermed_pts != 10) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_parse_paf_unbounded: built for downsample=8, 10 intermediate points");
+    if (pn_parse_factor_log2(cfg->downsample) < 0 || !pn_parse_pts_ok(cfg->num_intermed_pts))
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_parse_paf_unbounded: downsample %d / num_intermed_pts %d: supported are downsample in {" PN_PARSE_FACTORS_TEXT "} and %d..%d intermediate points",
+                            cfg->downsample, cfg->num_intermed_pts, PN_PARSE_MIN_PTS, PN_PARSE_MAX_PTS);
+    const bool generic = cfg->downsample != 8 || cfg->num_intermed_pts != 10;      // -> parse_generic.hip
     hipStream_t s = (hipStream_t)hip_stream;
     BigHost *B = (BigHost *)ctx->parse_big;
     if (!B) { B = new BigHost(); ctx->parse_big = B; }
@@ -1134,7 +1110,13 @@ extern "C" int pn_parse_paf_unbounded(pn_ctx *ctx, const float *heat_dev, const 
     B->hw = hw;
     CubicTab tab;
     for (int p = 0; p < 8; ++p) host_cubic_coeffs((float)(2 * p + 1) / 16.0f, tab.c[p]);
-    hipLaunchKernelGGL(big_peaks_kernel, dim3(J_), dim3(256), 0, s, heat_dev, h, w, cfg->thresh_heatmap, tab, B->w);
+    if (generic) {
+        const PnPeakOut po = {B->w.peak_count, B->w.px, B->w.py, B->w.ps, hw, 0};
+        const int rc = pn_gen_launch_peaks(ctx, s, heat_dev, J_, 1, h, w, J_, cfg->thresh_heatmap, cfg->downsample, 1, 0, po);
+        if (rc != PN_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(big_peaks_kernel, dim3(J_), dim3(256), 0, s, heat_dev, h, w, cfg->thresh_heatmap, tab, B->w);
+    }
     int pc[J_];
     PN_HIP_CHECK(ctx, hipMemcpyAsync(pc, B->w.peak_count, sizeof pc, hipMemcpyDeviceToHost, s));
     PN_HIP_CHECK(ctx, hipStreamSynchronize(s));
@@ -1172,7 +1154,12 @@ extern "C" int pn_parse_paf_unbounded(pn_ctx *ctx, const float *heat_dev, const 
         B->w.o_j3d = (double *)bump(p, (size_t)maxp * J_ * 24);
         B->w.o_conf = (double *)bump(p, (size_t)maxp * J_ * 8);
     }
-    hipLaunchKernelGGL(big_limb_kernel, dim3(L_), dim3(256), 0, s, paf_dev, h, w, cfg->thresh_paf, h * cfg->downsample, tab, B->w);
+    if (generic) {
+        const int rc = pn_gen_launch_big_limbs(ctx, s, paf_dev, h, w, cfg->thresh_paf, cfg->downsample, cfg->num_intermed_pts, B->w);
+        if (rc != PN_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(big_limb_kernel, dim3(L_), dim3(256), 0, s, paf_dev, h, w, cfg->thresh_paf, h * cfg->downsample, tab, B->w);
+    }
     hipLaunchKernelGGL(big_group_kernel, dim3(1), dim3(256), 0, s, heat_dev, z_dev, h, w, *cfg, B->w);
     int cnt[2] = {0, 0};
     PN_HIP_CHECK(ctx, hipMemcpyAsync(cnt, B->w.counts, sizeof cnt, hipMemcpyDeviceToHost, s));
@@ -1225,21 +1212,46 @@ extern "C" int pn_parse_paf_unbounded_connections(pn_ctx *ctx, int cap, int *cou
 // Stand-alone NMS (tpm/lib/utils/paf_to_pose.py:75-153 with bool_refine_center=True, no Gaussian filter) on ANY number of maps of one
 // frame: what `paf_to_pose_cpp` (paf_to_pose.py:381-385) runs before it hands the peaks to `process_paf` -- there with the 18 COCO parts, a
 // topology the three fixed-size parse kernels (15 joints / 14 limbs) do not serve.  Same kernel as the unbounded second pass: no capacity, peaks
-// of map m at [m][0 .. count[m]) in row-major cell order (= the reference's ids), refined x / y in up-sampled (x8) pixels and the bicubic score.
-extern "C" int pn_nms_peaks(pn_ctx *ctx, const float *heat_dev, int n_maps, int h, int w, float thresh, int upsample, int *count_dev,
-                            float *peak_x_dev, float *peak_y_dev, float *peak_score_dev, void *hip_stream) {
+// of map m at [m][0 .. count[m]) in row-major cell order (= the reference's ids), refined x / y in up-sampled pixels and the bicubic score.
+extern "C" void pn_nms_opt_default(pn_nms_opt *opt) {
+    if (!opt) return;
+    opt->upsample = 8;
+    opt->refine_center = 1;
+    opt->gaussian_filt = 0;
+}
+
+// pn_nms_peaks with the reference's other arguments (paf_to_pose.py:75): any supported up-sampling factor, bool_refine_center off (the cell centre
+// and the map's own value), bool_gaussian_filt on (scipy's gaussian_filter(sigma=3) of the up-sampled patch in front of the arg-max).  The default
+// options launch big_peaks_kernel exactly as before; everything else is parse_generic.hip's kernel.
+extern "C" int pn_nms_peaks_opt(pn_ctx *ctx, const float *heat_dev, int n_maps, int h, int w, float thresh, const pn_nms_opt *opt, int *count_dev,
+                                float *peak_x_dev, float *peak_y_dev, float *peak_score_dev, void *hip_stream) {
     if (!ctx) return PN_ERR_INVALID;
     if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
-    if (!heat_dev || !count_dev || !peak_x_dev || !peak_y_dev || !peak_score_dev || n_maps < 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_nms_peaks: bad arguments");
+    if (!heat_dev || !opt || !count_dev || !peak_x_dev || !peak_y_dev || !peak_score_dev || n_maps < 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_nms_peaks: bad arguments");
     if (h * w > MAX_MAP || h < 1 || w < 1) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_nms_peaks: map %dx%d exceeds %d cells", h, w, MAX_MAP);
-    if (upsample != 8) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_nms_peaks: built for upsampFactor = 8 (MODEL.DOWNSAMPLE)");
-    CubicTab tab;
-    for (int p = 0; p < 8; ++p) host_cubic_coeffs((float)(2 * p + 1) / 16.0f, tab.c[p]);
-    BigWs W = {};
-    W.peak_count = count_dev; W.px = peak_x_dev; W.py = peak_y_dev; W.ps = peak_score_dev;
-    hipLaunchKernelGGL(big_peaks_kernel, dim3(n_maps), dim3(256), 0, (hipStream_t)hip_stream, heat_dev, h, w, thresh, tab, W);
+    if (pn_parse_factor_log2(opt->upsample) < 0)
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_nms_peaks: upsampFactor %d: supported are " PN_PARSE_FACTORS_TEXT, opt->upsample);
+    if (opt->upsample == 8 && opt->refine_center && !opt->gaussian_filt) {
+        CubicTab tab;
+        for (int p = 0; p < 8; ++p) host_cubic_coeffs((float)(2 * p + 1) / 16.0f, tab.c[p]);
+        BigWs W = {};
+        W.peak_count = count_dev; W.px = peak_x_dev; W.py = peak_y_dev; W.ps = peak_score_dev;
+        hipLaunchKernelGGL(big_peaks_kernel, dim3(n_maps), dim3(256), 0, (hipStream_t)hip_stream, heat_dev, h, w, thresh, tab, W);
+    } else {
+        const PnPeakOut po = {count_dev, peak_x_dev, peak_y_dev, peak_score_dev, h * w, 0};
+        const int rc = pn_gen_launch_peaks(ctx, (hipStream_t)hip_stream, heat_dev, n_maps, 1, h, w, n_maps, thresh, opt->upsample, opt->refine_center, opt->gaussian_filt, po);
+        if (rc != PN_OK) return rc;
+    }
     PN_HIP_CHECK(ctx, hipGetLastError());
     return PN_OK;
+}
+
+extern "C" int pn_nms_peaks(pn_ctx *ctx, const float *heat_dev, int n_maps, int h, int w, float thresh, int upsample, int *count_dev,
+                            float *peak_x_dev, float *peak_y_dev, float *peak_score_dev, void *hip_stream) {
+    pn_nms_opt opt;
+    pn_nms_opt_default(&opt);
+    opt.upsample = upsample;
+    return pn_nms_peaks_opt(ctx, heat_dev, n_maps, h, w, thresh, &opt, count_dev, peak_x_dev, peak_y_dev, peak_score_dev, hip_stream);
 }
 
 void pn_parse_big_free(pn_ctx *ctx) {

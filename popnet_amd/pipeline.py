@@ -25,9 +25,12 @@ from .utils.paf_to_pose import make_parse_cfg
 
 class PoseEngine:
     def __init__(self, precision="bf16", state_dict=None, device=None, max_batch=32, input_size=224,
-                 w_org=480, h_org=640, intrinsics=INTRINSICS, weight_seed=0, private_ctx=False, calib_gain=1.0):
+                 w_org=480, h_org=640, intrinsics=INTRINSICS, weight_seed=0, private_ctx=False, calib_gain=1.0, parse_config=None):
         """private_ctx: give this engine its own pn_ctx (parse workspace), so that several engines can
         run concurrently on different HIP streams (bench.py pipelines consecutive batches that way).
+        parse_config: a reference-style config namespace (TEST.THRESH_HEATMAP, TEST.THRESH_PAF, TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS,
+        MODEL.DOWNSAMPLE, MODEL.NUM_KEYPOINTS) for the parse in place of default_cfg(); None = the defaults and the kernels built for them.
+        Any other supported MODEL.DOWNSAMPLE (1, 2, 4, 8, 16) or number of sample points (2..32) runs the generic parse kernels.
         calib_gain: synthetic weights only -- logit gain of the heat head before calibrate_heads (1 = heat values crowd
         the detection threshold, the worst case for a reduced-precision forward; > 1 = peaks comfortably separated)."""
         if not torch.cuda.is_available():
@@ -43,8 +46,8 @@ class PoseEngine:
         self.model.precision = precision
         self.ctx = _lib.Context(self.device.index) if private_ctx else _lib.Context.for_device(self.device.index)
         self.L = _lib.lib()
-        self.cfg = make_parse_cfg(default_cfg(), input_size=self.S, w_org=w_org, h_org=h_org, intrinsics=intrinsics,
-                                  depth_mean=DEPTH_MEAN, depth_std=DEPTH_STD)
+        self.cfg = make_parse_cfg(default_cfg() if parse_config is None else parse_config, input_size=self.S, w_org=w_org, h_org=h_org,
+                                  intrinsics=intrinsics, depth_mean=DEPTH_MEAN, depth_std=DEPTH_STD)
         # a PRIVATE context's parse scratch is sized once for max_batch and never moves again (a captured graph keeps the
         # pointer).  The shared per-device context keeps growing on demand: fixing it here would make an unrelated later
         # call with a larger batch (utils.paf_to_pose.parse_paf_batch) fail depending on construction order
@@ -412,6 +415,8 @@ class StreamingEngine:
 
     wire=True: what leaves the GPU per step is the compact pn_pose_wire form (6.2 KB instead of 33 KB per frame; PAF
     path only): `host_records()` then holds pn_pose_wire records, `records()` still the full pn_pose_frame ones.
+
+    Engine arguments (PoseEngine's parse_config among them) pass through **engine_kw to every slot's engine.
 
     Every engine gets its own context and its net is locked after the warm-up (pn_net_lock): nothing a captured graph
     points at (parse scratch, launch descriptors) can be reallocated or rewritten by a later eager call."""

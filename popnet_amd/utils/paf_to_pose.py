@@ -3,7 +3,8 @@
 Drop-in for tpm/lib/utils/paf_to_pose.py:354-377 (NMS :75-153, find_connected_joints :156-264,
 group_limbs_of_same_person :267-351): takes the HWC float32 network maps of ONE frame and returns
 ``(joint_list [N,5] float64, person_to_joint_assoc [P,J+2] float64)`` exactly as the reference
-does -- but the work happens in three HIP kernels (csrc/parse_paf.hip) instead of Python loops over
+does -- but the work happens in three HIP kernels (csrc/parse_paf.hip; csrc/parse_generic.hip for any
+MODEL.DOWNSAMPLE in {1, 2, 4, 8, 16} / TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS in 2..32 other than 8 / 10) instead of Python loops over
 scipy/cv2 calls.  For throughput use ``popnet_amd.pipeline.PoseEngine`` (whole batches stay on the
 device); this per-frame wrapper exists for API compatibility and parity tests.
 """
@@ -170,14 +171,26 @@ def paf_to_pose(heatmaps, pafs, config):
     return frame_joint_list(fr), frame_assoc(fr)
 
 
+NMS_FACTORS = (1, 2, 4, 8, 16)
+
+
 def NMS(heatmaps, upsampFactor=1., bool_refine_center=True, bool_gaussian_filt=False, config=None):
-    """tpm/lib/utils/paf_to_pose.py:75-153 on the GPU (pn_nms_peaks): heatmaps [h, w, >= NUM_KEYPOINTS] float32 (ndarray or CUDA tensor)
+    """tpm/lib/utils/paf_to_pose.py:75-153 on the GPU (pn_nms_peaks_opt): heatmaps [h, w, >= NUM_KEYPOINTS] float32 (ndarray or CUDA tensor)
     -> a list of NUM_KEYPOINTS float64 arrays [n_j, 4] (x, y, score, running id), any number of maps (the COCO-18 caller included).
-    Only the reference's default path is built: refined centres, no Gaussian filter, upsampFactor = 8."""
-    if not bool_refine_center or bool_gaussian_filt:
-        raise _lib.PopnetError("NMS: only bool_refine_center=True, bool_gaussian_filt=False is built (the reference's defaults)")
-    if int(upsampFactor) != upsampFactor or int(upsampFactor) != 8:
-        raise _lib.PopnetError("NMS: built for upsampFactor = 8 (MODEL.DOWNSAMPLE)")
+    Every argument of the reference is served: upsampFactor 1, 2, 4, 8 or 16 (a float with one of these values is fine),
+    bool_refine_center=False (the cell centre (p + 0.5) * upsampFactor - 0.5 and the map's own value; the filter flag is then ignored, as in the
+    reference) and bool_gaussian_filt=True (scipy's gaussian_filter(sigma=3) of the up-sampled patch in front of the arg-max, bit for bit).
+    The reference's defaults for the parse (8, refined, no filter) run the kernel built for them, everything else a generic one; any other
+    factor raises PopnetError before anything is launched."""
+    if config is None:
+        raise _lib.PopnetError("NMS: config (MODEL.NUM_KEYPOINTS, TEST.THRESH_HEATMAP) is required")
+    try:
+        integral = float(upsampFactor) == int(upsampFactor)
+    except (TypeError, ValueError, OverflowError):
+        integral = False
+    if not integral or int(upsampFactor) not in NMS_FACTORS:
+        raise _lib.PopnetError("NMS: upsampFactor %r is not supported (PN_ERR_UNSUPPORTED): supported are %s" % (upsampFactor, ", ".join(map(str, NMS_FACTORS))))
+    opt = _lib.NmsOpt(int(upsampFactor), 1 if bool_refine_center else 0, 1 if bool_gaussian_filt else 0)
     dev = _device_of(heatmaps)
     hm = torch.as_tensor(np.ascontiguousarray(heatmaps) if isinstance(heatmaps, np.ndarray) else heatmaps)
     nk = int(config.MODEL.NUM_KEYPOINTS)
@@ -188,9 +201,9 @@ def NMS(heatmaps, upsampFactor=1., bool_refine_center=True, bool_gaussian_filt=F
     cnt = torch.zeros((nk,), device=dev, dtype=torch.int32)
     xs, ys, sc = (torch.empty((nk, h * w), device=dev, dtype=torch.float32) for _ in range(3))
     ctx = _lib.Context.for_device(dev.index)
-    ctx.check(_lib.lib().pn_nms_peaks(ctx.handle, C.c_void_p(hm.data_ptr()), nk, h, w, float(config.TEST.THRESH_HEATMAP), 8,
-                                      C.c_void_p(cnt.data_ptr()), C.c_void_p(xs.data_ptr()), C.c_void_p(ys.data_ptr()),
-                                      C.c_void_p(sc.data_ptr()), _lib.current_stream_ptr(dev)), "pn_nms_peaks")
+    ctx.check(_lib.lib().pn_nms_peaks_opt(ctx.handle, C.c_void_p(hm.data_ptr()), nk, h, w, float(config.TEST.THRESH_HEATMAP), C.byref(opt),
+                                          C.c_void_p(cnt.data_ptr()), C.c_void_p(xs.data_ptr()), C.c_void_p(ys.data_ptr()),
+                                          C.c_void_p(sc.data_ptr()), _lib.current_stream_ptr(dev)), "pn_nms_peaks_opt")
     cnt = cnt.cpu().numpy()
     xs, ys, sc = xs.cpu().numpy(), ys.cpu().numpy(), sc.cpu().numpy()
     out, total = [], 0

@@ -1,0 +1,265 @@
+"""GPU: NMS and the pose parse for every argument the reference accepts (popnet_amd/csrc/parse_generic.hip and the launchers in
+parse_paf.hip) against tests/golden/parse_options.npz -- the reference's own NMS / paf_to_pose on the hand-built cases of tests/parse_cases.py
+(tests/golden/make_golden_parse_options.py).  Every comparison is an equality.
+
+  NMS           all four columns for upsampFactor in {1, 2, 4, 8, 16} x refined / not x filtered / not, on 28x28, 20x36, 36x20, 9x13, 5x7 and 3x3
+                maps, plus the 64x64 map at x16 with the filter (4096 cells and an 80x80 patch: the LDS ceiling)
+  parse         joint_list, person_to_joint_assoc and the connection lists for (downsample, points) in PARSE_OPTIONS, through paf_to_pose
+                (second pass included), parse_paf_batch + parse_connections, and parse_paf_unbounded; a frame alone == the frame in its batch
+  defaults      pn_nms_peaks_opt with default options == pn_nms_peaks(8); a config of 8 / 10 == no config
+  unsupported   other factors / point counts: PN_ERR_UNSUPPORTED from every entry point, nothing launched, the supported set in the message
+  engine        PoseEngine(parse_config=...) == parse_paf_batch on its own maps, eagerly and as a captured graph
+
+The limb scores are compared as float64 bit patterns, the default option set (8, 10) included: the reference's point score
+intermed_paf.dot(limb_dir) is x * dx + y * dy with both products rounded on every BLAS core type but the AVX-512 one, which the recipe of
+the golden rules out (tests/golden/make_golden_parse_options.py); the default and the generic kernels both compute that form.
+"""
+import ctypes as C
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import popnet_amd  # noqa: F401
+from popnet_amd import _lib
+from popnet_amd.utils import paf_to_pose as P2P
+
+import parse_cases as PC
+import parse_options_reference as PR
+
+pytestmark = pytest.mark.gpu
+
+GOLD = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "parse_options.npz"), allow_pickle=False))
+PN_ERR_UNSUPPORTED = -4
+
+
+def ref_cfg(f=8, n=10):
+    return SimpleNamespace(MODEL=SimpleNamespace(DOWNSAMPLE=f, NUM_KEYPOINTS=PC.J),
+                           TEST=SimpleNamespace(THRESH_HEATMAP=0.1, THRESH_PAF=0.05, NUM_INTERMED_PTS_BETWEEN_KEYPOINTS=n))
+
+
+def parse_cfg(f, n):
+    return P2P.make_parse_cfg(ref_cfg(f, n), w_org=PC.W_ORG, h_org=PC.H_ORG)
+
+
+def _dev(cs, gpu):
+    return tuple(torch.from_numpy(np.ascontiguousarray(np.stack([getattr(c, k) for c in cs]).transpose(0, 3, 1, 2))).to(gpu)
+                 for k in ("heat", "paf", "z"))
+
+
+# ---------------------------------------------------------------------------------------------
+# 1. NMS
+# ---------------------------------------------------------------------------------------------
+def _nms_mismatch(c, f, refine, gauss):
+    if (f, refine, gauss) == (1, True, False):
+        got = P2P.NMS(c.heat.copy(), config=ref_cfg(f))          # the reference's own default call
+    else:
+        got = P2P.NMS(c.heat.copy(), upsampFactor=float(f), bool_refine_center=refine, bool_gaussian_filt=gauss, config=ref_cfg(f))
+    assert len(got) == PC.J and all(p.dtype == np.float64 and p.shape[1] == 4 for p in got)
+    peaks, counts = PR.flat_peaks(got)
+    key = "nms/%s/%s" % (c.name, PR.nms_key(f, refine, gauss))
+    want, wcounts = GOLD[key + "/peaks"], GOLD[key + "/counts"]
+    if not np.array_equal(counts, wcounts):
+        return "%s: counts %s, reference %s" % (key, counts.tolist(), wcounts.tolist())
+    if not np.array_equal(peaks, want):
+        rows = np.nonzero((peaks != want).any(axis=1))[0]
+        return "%s: %d of %d peak rows differ, first %s got %s reference %s" % (key, len(rows), len(want), rows[0], peaks[rows[0]], want[rows[0]])
+    return None
+
+
+@pytest.mark.parametrize("name", PR.NMS_CASES)
+def test_nms_equals_golden_for_every_option_set(gpu, name):
+    c = PC.case(name)
+    bad = [m for m in (_nms_mismatch(c, *o) for o in PR.NMS_OPTIONS) if m]
+    print("%s %dx%d: %d option sets, %d mismatches" % (name, c.h, c.w, len(PR.NMS_OPTIONS), len(bad)))
+    assert not bad, "\n".join(bad)
+
+
+def test_nms_on_the_largest_map_at_x16_with_the_filter(gpu):
+    c = PC.case(PR.NMS_BIG[0])
+    assert c.h * c.w == 4096
+    assert _nms_mismatch(c, *PR.NMS_BIG[1]) is None
+
+
+# ---------------------------------------------------------------------------------------------
+# 2. the whole parse
+# ---------------------------------------------------------------------------------------------
+def _conn_rows(conns, joint_list):
+    """per-limb [m, 3] (i, j, score) lists -> the golden's [M, 6] rows (limb, src_id, dst_id, score, i, j)"""
+    jl = np.asarray(joint_list, dtype=np.float64).reshape(-1, 5)
+    base = [int(np.count_nonzero(jl[:, 4] < j)) for j in range(PC.J)]
+    rows = []
+    for limb, c in enumerate(conns):
+        s, d = PC.O.LIMBS[limb]
+        for i, j, sc in c:
+            rows.append((limb, base[s] + i, base[d] + j, sc, i, j))
+    return np.array(rows, dtype=np.float64).reshape(-1, 6)
+
+
+def _diff(what, got, want, out):
+    got, want = np.asarray(got, dtype=np.float64).reshape((-1,) + want.shape[1:]), np.asarray(want, dtype=np.float64)
+    if got.shape != want.shape:
+        out.append("%s: shape %s, reference %s" % (what, got.shape, want.shape))
+    elif not np.array_equal(got, want):
+        ne = got != want
+        out.append("%s: %d of %d values differ, max abs %.3g" % (what, int(ne.sum()), want.size, np.abs(got - want)[ne].max()))
+
+
+@pytest.mark.parametrize("f,n", PR.PARSE_OPTIONS, ids=[PR.parse_key(*o) for o in PR.PARSE_OPTIONS])
+def test_parse_equals_golden(gpu, f, n):
+    cfg, key = parse_cfg(f, n), PR.parse_key(f, n)
+    bad = []
+    by_shape = {}
+    for name in PR.PARSE_CASES:
+        by_shape.setdefault(PC.case(name).shape, []).append(PC.case(name))
+    assert len(by_shape[(28, 28)]) > 1
+    for shape, cs in by_shape.items():
+        maps = _dev(cs, gpu)
+        recs = P2P.parse_paf_batch(*maps, cfg)
+        conns = [P2P.parse_connections(b, gpu) for b in range(len(cs))]
+        for b, c in enumerate(cs):
+            g = {leaf: GOLD["parse/%s/%s/%s" % (c.name, key, leaf)] for leaf in ("joint_list", "assoc", "conn")}
+            tag = "%s %s" % (c.name, key)
+            # the reference-style call (second pass for an overflowing record included)
+            jl, assoc = P2P.paf_to_pose(c.heat.copy(), c.paf.copy(), ref_cfg(f, n))
+            _diff(tag + " paf_to_pose joint_list", jl, g["joint_list"], bad)
+            _diff(tag + " paf_to_pose assoc", assoc, g["assoc"], bad)
+            # the fixed-size record of the batch and its connection lists
+            fr = recs[b]
+            if int(fr["status"]) == 0:
+                _diff(tag + " batch joint_list", P2P.frame_joint_list(fr), g["joint_list"], bad)
+                _diff(tag + " batch assoc", P2P.frame_assoc(fr), g["assoc"], bad)
+                _diff(tag + " batch connections", _conn_rows(conns[b], g["joint_list"]), g["conn"], bad)
+            # (an overflowing record -- peaks33, rows33, plateau_9x13 at some factors -- is compared through the two calls that run the second pass)
+            one = P2P.parse_paf_batch(*(t[b:b + 1] for t in maps), cfg)
+            if one[0].tobytes() != fr.tobytes():
+                bad.append(tag + ": the record of the frame alone differs from its record in the batch")
+            # the unbounded pass
+            r = P2P.parse_paf_unbounded(maps[0][b], maps[1][b], maps[2][b], cfg)
+            _diff(tag + " unbounded joint_list", r["joint_list"], g["joint_list"], bad)
+            _diff(tag + " unbounded assoc", r["person_to_joint_assoc"], g["assoc"], bad)
+            _diff(tag + " unbounded connections", _conn_rows(P2P.unbounded_connections(len(g["joint_list"]), gpu), g["joint_list"]), g["conn"], bad)
+    print("%s: %d cases, %d mismatches" % (key, len(PR.PARSE_CASES), len(bad)))
+    for m in bad:
+        print("  " + m)
+    assert not bad, "\n".join(bad)
+
+
+# ---------------------------------------------------------------------------------------------
+# 3. the defaults are today's path
+# ---------------------------------------------------------------------------------------------
+def _nms_raw(gpu, fn, heat, *mid):
+    nk, h, w = heat.shape
+    cnt = torch.full((nk,), -7, device=gpu, dtype=torch.int32)
+    xs, ys, sc = (torch.full((nk, h * w), -7.0, device=gpu) for _ in range(3))
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    ctx = _lib.Context.for_device(gpu.index)
+    rc = fn(ctx.handle, vp(heat), nk, h, w, 0.1, *mid, vp(cnt), vp(xs), vp(ys), vp(sc), _lib.current_stream_ptr(gpu))
+    torch.cuda.synchronize()
+    return rc, ctx.last_error(), [t.cpu().numpy().tobytes() for t in (cnt, xs, ys, sc)]
+
+
+def test_default_options_write_the_same_bytes_as_the_default_entries(gpu):
+    L = _lib.lib()
+    opt = _lib.NmsOpt()
+    L.pn_nms_opt_default(C.byref(opt))
+    assert (opt.upsample, opt.refine_center, opt.gaussian_filt) == (8, 1, 0)
+    for name in ("corners", "plateau_5x7"):
+        heat = _dev([PC.case(name)], gpu)[0][0, :PC.J].contiguous()
+        rc_a, _, a = _nms_raw(gpu, L.pn_nms_peaks_opt, heat, C.byref(opt))
+        rc_b, _, b = _nms_raw(gpu, L.pn_nms_peaks, heat, 8)
+        assert rc_a == rc_b == _lib.PN_OK and a == b
+    cs = [PC.case(n) for n in ("corners", "edges", "ties", "peaks33")]
+    maps = _dev(cs, gpu)
+    a = P2P.parse_paf_batch(*maps, P2P.make_parse_cfg(ref_cfg(8, 10), w_org=PC.W_ORG, h_org=PC.H_ORG))
+    b = P2P.parse_paf_batch(*maps, P2P.make_parse_cfg(w_org=PC.W_ORG, h_org=PC.H_ORG))
+    assert a.tobytes() == b.tobytes()
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. unsupported values
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("f,n", [(3, 10), (32, 10), (8, 1), (8, 33), (0, 10), (-8, 10)])
+def test_unsupported_parse_arguments_are_refused_and_nothing_is_written(gpu, f, n):
+    L = _lib.lib()
+    ctx = _lib.Context.for_device(gpu.index)
+    cfg = P2P.make_parse_cfg(w_org=PC.W_ORG, h_org=PC.H_ORG)
+    cfg.downsample, cfg.num_intermed_pts = f, n
+    heat, paf, z = _dev([PC.case("corners")], gpu)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    frames = torch.full((1, _lib.POSE_FRAME_DTYPE.itemsize), 0x5a, device=gpu, dtype=torch.uint8)
+    wire = torch.full((1, _lib.POSE_WIRE_DTYPE.itemsize), 0x5a, device=gpu, dtype=torch.uint8)
+    s = _lib.current_stream_ptr(gpu)
+    msgs = []
+    assert L.pn_parse_paf(ctx.handle, vp(heat), vp(paf), vp(z), 1, 28, 28, C.byref(cfg), vp(frames), s) == PN_ERR_UNSUPPORTED
+    msgs.append(ctx.last_error())
+    assert L.pn_parse_paf_wire(ctx.handle, vp(heat), vp(paf), vp(z), 1, 28, 28, C.byref(cfg), vp(frames), vp(wire), s) == PN_ERR_UNSUPPORTED
+    msgs.append(ctx.last_error())
+    npk, npers = C.c_int(-7), C.c_int(-7)
+    assert L.pn_parse_paf_unbounded(ctx.handle, vp(heat[0]), vp(paf[0]), vp(z[0]), 28, 28, C.byref(cfg), C.byref(npk), C.byref(npers), s) == PN_ERR_UNSUPPORTED
+    msgs.append(ctx.last_error())
+    torch.cuda.synchronize()
+    assert bool((frames == 0x5a).all()) and bool((wire == 0x5a).all()) and (npk.value, npers.value) == (-7, -7)
+    for m in msgs:
+        assert "1, 2, 4, 8, 16" in m and "2..32" in m, m
+    with pytest.raises(_lib.PopnetError, match="1, 2, 4, 8, 16"):
+        P2P.parse_paf_batch(heat, paf, z, cfg)
+    with pytest.raises(_lib.PopnetError, match="1, 2, 4, 8, 16"):
+        P2P.paf_to_pose(PC.case("corners").heat.copy(), PC.case("corners").paf.copy(), ref_cfg(f, n))
+
+
+@pytest.mark.parametrize("f", [3, 32, 0, -1])
+def test_unsupported_nms_factors_are_refused_and_nothing_is_written(gpu, f):
+    L = _lib.lib()
+    heat = _dev([PC.case("corners")], gpu)[0][0, :PC.J].contiguous()
+    sentinel = _nms_raw(gpu, lambda *a: _lib.PN_OK, heat)[2]
+    rc, msg, out = _nms_raw(gpu, L.pn_nms_peaks, heat, f)
+    assert rc == PN_ERR_UNSUPPORTED and out == sentinel and "1, 2, 4, 8, 16" in msg, msg
+    for refine, gauss in ((1, 0), (0, 0), (1, 1)):
+        rc, msg, out = _nms_raw(gpu, L.pn_nms_peaks_opt, heat, C.byref(_lib.NmsOpt(f, refine, gauss)))
+        assert rc == PN_ERR_UNSUPPORTED and out == sentinel and "1, 2, 4, 8, 16" in msg, msg
+    with pytest.raises(_lib.PopnetError, match="1, 2, 4, 8, 16"):
+        P2P.NMS(PC.case("corners").heat.copy(), upsampFactor=f, config=ref_cfg())
+
+
+def test_a_fractional_upsamp_factor_is_refused_and_an_integral_float_is_served(gpu):
+    heat = PC.case("corners").heat
+    with pytest.raises(_lib.PopnetError, match="1, 2, 4, 8, 16"):
+        P2P.NMS(heat.copy(), upsampFactor=2.5, config=ref_cfg())
+    a, b = P2P.NMS(heat.copy(), upsampFactor=2.0, config=ref_cfg()), P2P.NMS(heat.copy(), upsampFactor=2, config=ref_cfg())
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+# ---------------------------------------------------------------------------------------------
+# 5. the engine
+# ---------------------------------------------------------------------------------------------
+def test_pose_engine_with_a_parse_config_eager_and_captured(gpu):
+    from popnet_amd import synth
+    from popnet_amd.pipeline import PoseEngine
+    B = 4
+    eng = PoseEngine(precision="bf16", device=gpu, max_batch=B, private_ctx=True, parse_config=ref_cfg(8, 16))
+    assert (eng.cfg.downsample, eng.cfg.num_intermed_pts) == (8, 16)
+    depth = torch.from_numpy(synth.synth_depth(B, 640, 480, seed=7)).to(gpu)
+    out = torch.zeros((B, _lib.POSE_FRAME_DTYPE.itemsize), device=gpu, dtype=torch.uint8)
+    for _ in range(2):
+        eng.predict(depth, out)
+    torch.cuda.synchronize()
+    eager = out.cpu().numpy().view(_lib.POSE_FRAME_DTYPE).reshape(B).copy()
+    want = P2P.parse_paf_batch(eng.heat[:B], eng.paf[:B], eng.z[:B], eng.cfg)
+    assert eager.tobytes() == want.tobytes()
+    assert sum(int(f["n_peaks"]) for f in eager) > 0
+    side = torch.cuda.Stream(device=gpu)
+    side.wait_stream(torch.cuda.current_stream(gpu))
+    with torch.cuda.stream(side):
+        eng.predict(depth, out)
+    torch.cuda.current_stream(gpu).wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        eng.predict(depth, out)
+    out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    assert out.cpu().numpy().tobytes() == eager.tobytes()
