@@ -45,7 +45,8 @@ enum pn_precision {
 
 enum pn_net_kind {
     PN_NET_RTPOSE_LIGHT3D = 0,  /* "Open-Pose+"  tpm/lib/network/rtpose_light3d.py:249-356 */
-    PN_NET_YOLO_POSENET = 1     /* "Yolo-Pose+"  tpm/lib/network/yolo_posenet.py:87-158   */
+    PN_NET_YOLO_POSENET = 1,    /* "Yolo-Pose+"  tpm/lib/network/yolo_posenet.py:87-158   */
+    PN_NET_A2J = 2              /* "Yolo-A2J" second stage: A2J_model  third_party_methods/A2J_experiments/model.py:145-186, resnet.py:61-164 */
 };
 
 enum pn_depth_dtype { PN_DEPTH_F16 = 0, PN_DEPTH_F32 = 1 };
@@ -605,6 +606,70 @@ size_t pn_sizeof_yolo_frame(void);
 /* Host-only diagnostic: the four float32 bicubic taps (OpenCV interpolateCubic, A = -0.75) the
  * parse kernels use for fractional offset x.  Lets CPU tests pin the table against the oracle.   */
 void pn_debug_cubic_coeffs(float x, float *out4);
+
+/* ---- Yolo-A2J: per-box crops, A2J_model, anchor vote -------------------------------------------
+ * The third baseline of the reference's results table (third_party_methods/A2J_experiments/): YoloPoseNet finds the boxes
+ * (evaluation_yolo_posenet_kdh3d_mpreal_a2j_preprocess.py:153-228: rows [x0, y0, x1, y1, conf] in original-frame pixels, one row
+ * [-1, -1, -1, -1, 0] for a frame without a detection), A2J regresses 15 joints per box crop.
+ * A net of kind PN_NET_A2J (pn_net_create(ctx, PN_NET_A2J, 15, 16, 1)) takes the reference's A2J_model state dict ("Backbone.model.*",
+ * "regressionModel.*", "classificationModel.*", "DepthRegressionModel.*"; Backbone.model.fc.* and *.num_batches_tracked are accepted and
+ * ignored) and any input size that is a multiple of 16, in PN_PREC_F32 or PN_PREC_BF16 (PN_PREC_BF16X3: PN_ERR_UNSUPPORTED).  The three
+ * identical input channels of ResNetBackBone.forward (model.py:155-156) are one channel with the 7x7 weights summed over Cin in double.
+ * layer4's blocks 1 and 2 run conv2 at dilation 2 (resnet.py:112,145): pn_net_step_info reports "dil": 2 for those steps only.
+ * In PN_PREC_F32 the convolutions of this net accumulate in blocks (the 32 products of a k-step are summed from zero, then added to the running
+ * sum; "blocked_acc": 1 in pn_net_step_info): its K loops run to 18 432 terms, where one serial fp32 chain is several times the reference's own
+ * fp32 error away from an fp64 run.  The other nets keep the serial chain they are tested bit for bit with.                                 */
+typedef struct pn_a2j_cfg {
+    int img_w, img_h;          /* the module constants imgWidth / imgHeight of a2j_test_pred_box_new.py:30-31 (480, 512): a box that leaves
+                                  [0, img_w] x [0, img_h] is pasted into a zero image -- independent of the frame's real shape */
+    int crop_w, crop_h;        /* cropWidth / cropHeight (:32-33), 288 x 288 */
+    float mean, std;           /* MEAN / STD (:61-62), 3 and 2 */
+    float conf_min;            /* a row with conf <= conf_min is an all-zero crop (:273), 0.01 */
+    double fx, fy, cx, cy;     /* intrinsics (:35) */
+} pn_a2j_cfg;
+void pn_a2j_cfg_default(pn_a2j_cfg *cfg);
+/* One fixed-size record per crop (a2j_test_pred_box_new.py:373-421): per joint x, y (original-frame pixels), X, Y, Z (metres), then the
+ * box confidence (the part confidence of every joint, :385) and the frame index of the row. */
+typedef struct pn_a2j_record {
+    float joint[PN_NUM_JOINTS][5];
+    float conf;
+    int32_t frame;
+} pn_a2j_record;
+size_t pn_sizeof_a2j_record(void);
+/* dataPreprocess (a2j_test_pred_box_new.py:268-313), one launch for all rows, bit for bit, quirks included.  frames_dev [F, H, W] f16 / f32
+ * (device); rows_dev [n][6] f32 (device): frame index, x0, y0, x1, y1, conf.  out_dev [n, 1, crop_h, crop_w] f32: what the net's stem reads.
+ *   conf <= conf_min: zeros.  Otherwise the box is clipped to the frame (max(., 0), min(., W - 1 / H - 1)), depth[int(ymin):int(ymax),
+ *   int(xmin):int(xmax)] is taken (last row and column excluded); if the RAW box leaves [0, img_w] x [0, img_h] the crop is pasted into a zero
+ *   image of int(y1 - y0) x int(x1 - x0) whose paste loop tests start < i < end strictly (the first pasted row and column stay zero); then
+ *   cv2.resize(INTER_NEAREST) (source index min(floor(d * (1 / (dsize / ssize))), ssize - 1) in double) and (v - mean) / std in fp32, no clamp.
+ *   Where the reference raises -- the image handed to cv2.resize is empty: a clipped region without rows or columns that is not pasted, or a
+ *   paste image without rows or columns -- the crop is zeros and flags_dev[row] (may be NULL) is 1, else 0.  A box whose clipped END is negative
+ *   (Python's slice would count it from the far edge) is treated as empty as well. */
+int pn_a2j_crop(pn_ctx *ctx, const void *frames_dev, int depth_dtype, int F, int H, int W, const float *rows_dev, int n,
+                const pn_a2j_cfg *cfg, float *out_dev, int32_t *flags_dev, void *hip_stream);
+/* A2J_model.forward (model.py:179-186) on crops_dev [B, 1, in_h, in_w] f32.  The head maps stay on the device as the last convolutions
+ * left them: NHWC [B, h, w, 16 x 15] (classification, depth) and [B, h, w, 16 x 15 x 2] (regression), h = in_h / 16, bf16 or f32 by the
+ * net's precision (pn_a2j_head_shape).  The pointers stay valid until the net is destroyed; the next forward overwrites the maps. */
+int pn_a2j_forward(pn_net *net, const float *crops_dev, int B, const void **cls_dev, const void **reg_dev, const void **dep_dev,
+                   void *hip_stream);
+int pn_a2j_head_shape(pn_net *net, int *h, int *w, int *precision);
+/* post_process.forward (anchor.py:57-82): per crop and joint w = softmax(cls over all K anchors), P_yx = sum w (anchor + reg),
+ * P_z = sum w dep -- max-subtracted softmax and sums in fp32, one block per (crop, joint), one launch.  anchors_dev [K][2] f32 (y, x) is
+ * shift([h, w], stride, generate_anchors()) (anchor.py:7-42) computed by the caller in the reference's own arithmetic: anchor k belongs to
+ * cell k / A, column (k / A) / h, row (k / A) % h (W-major, as the reference's permute(0, 3, 2, 1)).
+ * h > 0: the heads are the NHWC maps of pn_a2j_forward (precision = the net's), read in place.  h == 0: the heads are f32 tensors in the
+ * reference's layout [B, K, P] / [B, K, P, 2] (K = w: pass the anchor count as w).  A = anchors per cell, P = joints.
+ * votes_dev [B, P, 3] f32 (y, x, z), may be NULL when records are wanted only.
+ * rows_dev / cfg / records_dev (all or none): the map back to the frame (a2j_test_pred_box_new.py:373-421) in the same launch, in the
+ * script's float32 arithmetic -- x = x_crop (x1 - x0) / crop_w + x0, X = (x - cx) Z / fx. */
+int pn_a2j_vote(pn_ctx *ctx, const void *cls_dev, const void *reg_dev, const void *dep_dev, int precision, int B, int h, int w, int A, int P,
+                const float *anchors_dev, float *votes_dev, const float *rows_dev, const pn_a2j_cfg *cfg, pn_a2j_record *records_dev,
+                void *hip_stream);
+/* frames + box rows -> records: pn_a2j_crop, pn_a2j_forward and pn_a2j_vote for n <= the net's max_batch rows.  crops_dev: scratch
+ * [n, 1, crop_h, crop_w] f32; the net must be finalized for crop_h x crop_w; anchors_dev as in pn_a2j_vote for stride 16. */
+int pn_a2j_predict(pn_net *net, const void *frames_dev, int depth_dtype, int F, int H, int W, const float *rows_dev, int n,
+                   const pn_a2j_cfg *cfg, const float *anchors_dev, float *crops_dev, int32_t *flags_dev, float *votes_dev,
+                   pn_a2j_record *records_dev, void *hip_stream);
 
 /* ---- legacy plug-in ABI: the SWIG module `pafprocess` -----------------------------------------
  * Same seven symbols, same argument meaning and the same (non re-entrant, global-state)

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("POPNET_LIB_PATH") or os.path.join(_HERE, "libpopnet_h
 
 PN_OK = 0
 PN_PREC_F32, PN_PREC_BF16, PN_PREC_BF16X3 = 0, 1, 2
-PN_NET_RTPOSE_LIGHT3D, PN_NET_YOLO_POSENET = 0, 1
+PN_NET_RTPOSE_LIGHT3D, PN_NET_YOLO_POSENET, PN_NET_A2J = 0, 1, 2
 PN_DEPTH_F16, PN_DEPTH_F32 = 0, 1
 
 PN_NUM_JOINTS = 15
@@ -193,6 +193,13 @@ _SIGNATURES = {
     "pn_pack_pose_frames": (_i, [_vp, _vp, _i, _vp, _vp]),
     "pn_sizeof_pose_wire": (_sz, []),
     "pn_sizeof_yolo_frame": (_sz, []),
+    "pn_a2j_cfg_default": (None, [_vp]),
+    "pn_sizeof_a2j_record": (_sz, []),
+    "pn_a2j_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pn_a2j_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pn_a2j_head_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "pn_a2j_vote": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_a2j_predict": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn_debug_cubic_coeffs": (None, [_f, C.POINTER(C.c_float)]),
     "process_paf": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "get_num_humans": (_i, []),

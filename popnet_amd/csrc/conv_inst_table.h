@@ -34,4 +34,12 @@
     X(1, 2, 120, PN_CFG_C128)        \
     X(1, 2, 120, PN_CFG_C64)
 
+// Dilation 2 (conv_mfma_kernel<..., DIL = 2>): A2J's dilated 3x3 layer4 convolutions, 512 -> 512 channels at stride 1 -- the 128-cout block and the
+// 64-cout block the planner takes on small maps, every pitch class.  Rows of their own: the rows above are the DIL = 1 instances they always were.
+#define PN_CONV_INSTANCES_D2_0(X) \
+    X(3, 1, 16, PN_CFG_C128) X(3, 1, 16, PN_CFG_C64) X(3, 1, 32, PN_CFG_C128) X(3, 1, 32, PN_CFG_C64)
+#define PN_CONV_INSTANCES_D2_1(X) \
+    X(3, 1, 64, PN_CFG_C128) X(3, 1, 64, PN_CFG_C64) X(3, 1, 120, PN_CFG_C128) X(3, 1, 120, PN_CFG_C64)
+#define PN_CONV_INSTANCES_D2(X) PN_CONV_INSTANCES_D2_0(X) PN_CONV_INSTANCES_D2_1(X)
+
 #define PN_CONV_INSTANCES(X) PN_CONV_INSTANCES_0(X) PN_CONV_INSTANCES_1(X) PN_CONV_INSTANCES_2(X) PN_CONV_INSTANCES_3(X)

@@ -18,9 +18,9 @@ int pn_cfg_couts(int cfg) {
 
 int pn_cfg_pixels(int cfg) { return cfg == PN_CFG_C128 ? 112 : (cfg == PN_CFG_C64W ? 224 : 128); }
 
-size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R) {
+size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R, int dil) {
     size_t pixb = prec == PN_PREC_BF16 ? 128 : 256;
-    size_t rows = (size_t)(R - 1) * stride + ks;
+    size_t rows = (size_t)(R - 1) * stride + (size_t)(ks - 1) * dil + 1;
     return rows * pitch * pixb;
 }
 
@@ -34,7 +34,22 @@ extern "C" int pn_conv_has_instance(int prec, int ks, int stride, int pitch, int
     return 0;
 }
 
+// the dilation-2 rows of the table
+int pn_conv_has_instance_d2(int prec, int ks, int stride, int pitch, int cfg) {
+    if (prec != PN_PREC_BF16 && prec != PN_PREC_F32) return 0;
+#define PN_HAS_CASE(KS, ST, PITCH, CFG) \
+    if (ks == KS && stride == ST && pitch == PITCH && cfg == CFG) return 1;
+    PN_CONV_INSTANCES_D2(PN_HAS_CASE)
+#undef PN_HAS_CASE
+    return 0;
+}
+
 int pn_launch_conv_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_d2_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_d2_part1(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_acc_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_acc_part1(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_acc_part2(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part1(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part2(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part3(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
@@ -43,6 +58,19 @@ int pn_launch_conv(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream) {
     int rc;
     if (L.kern == 4) return pn_launch_conv4(ctx, L, stream);
     if (L.kern == 3) return pn_launch_conv3(ctx, L, stream);
+    if (L.acc) {      // fp32 blocked accumulation: the same rows, instances of their own
+        if (L.prec == PN_PREC_F32 && (L.dil == 1 || L.dil == 2)) {
+            if ((rc = pn_launch_conv_acc_part0(ctx, L, stream)) != 1) return rc;
+            if ((rc = pn_launch_conv_acc_part1(ctx, L, stream)) != 1) return rc;
+            if ((rc = pn_launch_conv_acc_part2(ctx, L, stream)) != 1) return rc;
+        }
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "no blocked-accumulation conv kernel for prec=%d ks=%d stride=%d dilation=%d pitch=%d cfg=%d", L.prec, L.ks, L.stride, L.dil, L.pitch, L.cfg);
+    }
+    if (L.dil != 1) {
+        if (L.dil == 2 && (rc = pn_launch_conv_d2_part0(ctx, L, stream)) != 1) return rc;
+        if (L.dil == 2 && (rc = pn_launch_conv_d2_part1(ctx, L, stream)) != 1) return rc;
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "no conv kernel for prec=%d ks=%d stride=%d dilation=%d pitch=%d cfg=%d", L.prec, L.ks, L.stride, L.dil, L.pitch, L.cfg);
+    }
     if ((rc = pn_launch_conv_part0(ctx, L, stream)) != 1) return rc;
     if ((rc = pn_launch_conv_part1(ctx, L, stream)) != 1) return rc;
     if ((rc = pn_launch_conv_part2(ctx, L, stream)) != 1) return rc;

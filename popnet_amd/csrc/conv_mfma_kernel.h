@@ -149,6 +149,17 @@ template <int PREC, int KS, int STRIDE, int PITCH, int CFG> struct StageCfg {
 // Weight fragments are addressed as (wave-uniform 64-bit base in SGPRs) + (32-bit lane offset): the
 // compiler then emits the saddr form of global_load and bumps the base with scalar adds -- no vector
 // ALU work per k-step.
+// acc += t as four v_add_f32 the compiler may not move: written as plain C++ the 252 block additions of a chunk were all sunk behind its last MFMA,
+// every block sum parked in scratch until then and the MFMA pipeline drained at every item to store it.  t was produced one item (16 MFMAs) earlier.
+// `after` is a register the CURRENT item's last MFMA writes: named as an operand and not read, it keeps the additions behind that item's MFMAs, so
+// what they do read is at least 16 MFMAs old whatever the hazard recogniser knows about inline assembly.
+__device__ __forceinline__ void pn_block_add(f32x4 &a, const f32x4 &t, float after) {
+    float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
+    asm volatile("v_add_f32 %0, %0, %4\n\tv_add_f32 %1, %1, %5\n\tv_add_f32 %2, %2, %6\n\tv_add_f32 %3, %3, %7"
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3]), "v"(after));
+    a = f32x4{a0, a1, a2, a3};
+}
+
 template <int PREC> __device__ __forceinline__ typename Elem<PREC>::Frag load_a_frag2(gcptr base, unsigned voff) {
     return load_a_frag<PREC>(base + voff);
 }
@@ -166,14 +177,20 @@ template <> __device__ __forceinline__ Elem<PN_PREC_F32>::Frag load_a_frag_buf<P
     return f;
 }
 
-template <int PREC, int KS, int STRIDE, int PITCH, int CFG>
+// DIL: distance of the taps in input pixels (A2J's ResNet-50 layer4 blocks 1 and 2: 3x3, dilation 2, padding 2 -- taps at 0, +-2, a halo of 5 rows
+// and columns; third_party_methods/A2J_experiments/resnet.py:112,145).  DIL = 1 is every other convolution: each expression below reduces to what it was.
+// ACC (fp32 only): 1 = blocked accumulation.  The default fp32 path adds every 4-product MFMA onto ONE running sum, a serial chain of K / 4 roundings whose
+// error grows like K; with ACC = 1 the eight MFMAs of a k-step (32 products) start from zero and their sum is added to the running sum once, so the long
+// chain has K / 32 links -- about a third of the rounding error on the K = 4608 .. 18432 convolutions of the A2J net, which is what puts its fp32 heads
+// within the reference's own fp32 error of the fp64 run.  ACC = 0 is every other fp32 net: the bit-exact FMA chain they are tested for.
+template <int PREC, int KS, int STRIDE, int PITCH, int CFG, int DIL = 1, int ACC = 0>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__restrict__ probs) {
     typedef Elem<PREC> E;
     typedef typename E::T T;
     typedef typename E::Frag Frag;
     constexpr int PIXB = E::PIXB, FRAGB = E::FRAGB, SUBX = E::SUBX;
     constexpr int WC = TileCfg<CFG>::WC, WP = TileCfg<CFG>::WP, CT = TileCfg<CFG>::CT, PT = TileCfg<CFG>::PT;
-    constexpr int KK = KS * KS, PAD = KS / 2;
+    constexpr int KK = KS * KS, PAD = DIL * (KS / 2), KSD = (KS - 1) * DIL + 1;      // KSD: rows / columns the taps span
     constexpr int NCH = PIXB / 16;      // 16-B pieces per halo pixel
     constexpr int PPI = 256 / NCH;      // halo pixels staged per block pass
     constexpr int ES = (int)sizeof(T);
@@ -207,8 +224,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     const int Wo = P.Wo;
     const int Wc = min(P.Wt, Wo - ox0);          // output columns of this tile
     const int npix = R * Wc;
-    const int HRa = (R - 1) * STRIDE + KS;       // halo rows actually needed
-    const int HC = (Wc - 1) * STRIDE + KS;       // halo columns
+    const int HRa = (R - 1) * STRIDE + KSD;      // halo rows actually needed
+    const int HC = (Wc - 1) * STRIDE + KSD;      // halo columns
     const int iy0 = oy0 * STRIDE - PAD, ix0 = ox0 * STRIDE - PAD;
     const float inv_wc = 1.0f / (float)Wc;
 
@@ -223,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
         int hp0 = ry * STRIDE * PITCH + rx * STRIDE;
 #pragma unroll
         for (int kx = 0; kx < KS; ++kx) {
-            int hp = hp0 + kx;
+            int hp = hp0 + kx * DIL;
             baddr[pt][kx] = hp * PIXB + ((q ^ (hp & 7)) << (PREC == PN_PREC_BF16 ? 4 : 5));
         }
     }
@@ -247,7 +264,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     constexpr int NA = (PREC == PN_PREC_BF16) ? ((NSTEP % 6 == 0) ? 6 : 2) : ((NSTEP % 3 == 0) ? 3 : 2);
     constexpr int NITEM = NSTEP * PT;                   // (k-step, pixel tile) items per chunk
     constexpr int DB = (PREC == PN_PREC_BF16) ? ((NITEM % 3 == 0) ? 3 : 2) : 1;   // B fragments in flight
-    constexpr int MAXST = StageCfg<PREC, KS, STRIDE, PITCH, CFG>::MAXST;   // 0: stage without register prefetch
+    // 0: stage without register prefetch (ACC = 1 always: the 48 prefetch registers are what the block sums need -- with them the 128-cout instances,
+    // already at 256 VGPRs, kept the accumulators in scratch and drained the MFMA pipeline at every item)
+    constexpr int MAXST = (ACC == 1) ? 0 : StageCfg<PREC, KS, STRIDE, PITCH, CFG>::MAXST;
     const int nchunks = P.cin_chunks;
     const int in_wrap = P.in_wrap;
 
@@ -348,14 +367,16 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
         if (MAXST > 0 && more) stage_load(chunk + 1);
 
         // item j = (k-step s = half * KK + tap, pixel tile pt); the half is selected by the XOR state of baddr
-#define PN_BADDR(j) (baddr[(j) % PT][(((j) / PT) % KK) % KS] + ((((j) / PT) % KK) / KS) * PITCH * PIXB)
+#define PN_BADDR(j) (baddr[(j) % PT][(((j) / PT) % KK) % KS] + ((((j) / PT) % KK) / KS) * DIL * PITCH * PIXB)
         Frag bq[DB];
+        f32x4 tq[2][CT];                                 // ACC = 1: the blocks of the current and the previous item
+        (void)tq;
         if (DB > 1) {
 #pragma unroll
             for (int j = 0; j < DB - 1; ++j) bq[j] = read_b_frag<PREC>(sm, PN_BADDR(j));
             __builtin_amdgcn_sched_barrier(0);          // keep the primed reads out of the pinned sequence below
         }
-#define PN_BADDRX(j) ((baddr[(j) % PT][(((j) / PT) % KK) % KS] ^ SUBX) + ((((j) / PT) % KK) / KS) * PITCH * PIXB)
+#define PN_BADDRX(j) ((baddr[(j) % PT][(((j) / PT) % KK) % KS] ^ SUBX) + ((((j) / PT) % KK) / KS) * DIL * PITCH * PIXB)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {                    // the two 32-channel halves of the chunk
 #pragma unroll
@@ -374,8 +395,21 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
                     if (jr / (KK * PT) != h) bq[jr % DB] = read_b_frag<PREC>(sm, PN_BADDRX(jr));
                     else bq[jr % DB] = read_b_frag<PREC>(sm, PN_BADDR(jr));
                 }
+                if constexpr (ACC == 1 && PREC == PN_PREC_F32) {
+                    // blocked accumulation: this item's 32 products summed from zero; the PREVIOUS item's block, long finished, joins its running sum
+                    // while these MFMAs run.  The fence keeps MFMAs and adds in item order (global loads may cross, LDS reads may not: hoisted, they are what fills the registers): without it the
+                    // scheduler interleaves the blocks of many items and spills.
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) acc[ct][pt] = mma(aq[s % NA][ct], bq[j % DB], acc[ct][pt]);
+                    for (int ct = 0; ct < CT; ++ct) tq[j & 1][ct] = mma(aq[s % NA][ct], bq[j % DB], f32x4{0.f, 0.f, 0.f, 0.f});
+                    if (j > 0) {
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) pn_block_add(acc[ct][(j - 1) % PT], tq[(j - 1) & 1][ct], tq[j & 1][CT - 1][3]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                } else {
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) acc[ct][pt] = mma(aq[s % NA][ct], bq[j % DB], acc[ct][pt]);
+                }
                 if (DB > 1) {
                     // pin the issue order (the scheduler otherwise sinks every prefetch down to its use)
                     if (pt == 0) __builtin_amdgcn_sched_group_barrier(0x020, CT, 0);             // weight loads
@@ -390,6 +424,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
         }
 #undef PN_BADDRX
 #undef PN_BADDR
+        if constexpr (ACC == 1 && PREC == PN_PREC_F32) {      // the chunk's last block
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) acc[ct][(NITEM - 1) % PT] = acc[ct][(NITEM - 1) % PT] + tq[(NITEM - 1) & 1][ct];
+        }
         if (more) {
             if (!P.lds_two) __syncthreads();             // single LDS image: wait for every wave's reads
             if (MAXST > 0) stage_store(nbuf);
@@ -505,9 +543,9 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
 }
 
 
-template <int PREC, int KS, int STRIDE, int PITCH, int CFG>
+template <int PREC, int KS, int STRIDE, int PITCH, int CFG, int DIL = 1, int ACC = 0>
 static int conv_launch_one(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream) {
-    auto kern = conv_mfma_kernel<PREC, KS, STRIDE, PITCH, CFG>;
+    auto kern = conv_mfma_kernel<PREC, KS, STRIDE, PITCH, CFG, DIL, ACC>;
     if (L.lds_bytes > PN_CONV_LDS_MAX)
         return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "conv halo tile needs %zu B of LDS", L.lds_bytes);
     if (L.lds_bytes > 48 * 1024) {
@@ -523,6 +561,19 @@ static int conv_launch_one(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream)
 #define PN_CASE(PREC, KS, ST, PITCH, CFG)                                                       \
     if (L.prec == PREC && L.ks == KS && L.stride == ST && L.pitch == PITCH && L.cfg == CFG)     \
         return conv_launch_one<PREC, KS, ST, PITCH, CFG>(ctx, L, stream);
+// the dilation-2 rows (PN_CONV_INSTANCES_D2_*): pn_launch_conv sends a launch with L.dil == 2 to these shares only
+#define PN_CASE_D2(PREC, KS, ST, PITCH, CFG)                                                    \
+    if (L.prec == PREC && L.ks == KS && L.stride == ST && L.pitch == PITCH && L.cfg == CFG)     \
+        return conv_launch_one<PREC, KS, ST, PITCH, CFG, 2>(ctx, L, stream);
+// the fp32 blocked-accumulation instances (ConvLaunch::acc, conv_inst_acc_*.hip): every row of the table, dilation 1 and 2
+#define PN_CASE_ACC(KS, ST, PITCH, CFG)                                                         \
+    if (L.ks == KS && L.stride == ST && L.pitch == PITCH && L.cfg == CFG)                       \
+        return conv_launch_one<PN_PREC_F32, KS, ST, PITCH, CFG, 1, 1>(ctx, L, stream);
+#define PN_CASE_ACC_D2(KS, ST, PITCH, CFG)                                                      \
+    if (L.ks == KS && L.stride == ST && L.pitch == PITCH && L.cfg == CFG)                       \
+        return conv_launch_one<PN_PREC_F32, KS, ST, PITCH, CFG, 2, 1>(ctx, L, stream);
+#define PN_CASES_PREC_D2(KS, ST, PITCH, CFG) \
+    PN_CASE_D2(PN_PREC_BF16, KS, ST, PITCH, CFG) PN_CASE_D2(PN_PREC_F32, KS, ST, PITCH, CFG)
 #define PN_CASES_PREC(KS, ST, PITCH, CFG) \
     PN_CASE(PN_PREC_BF16, KS, ST, PITCH, CFG) PN_CASE(PN_PREC_F32, KS, ST, PITCH, CFG)
 
@@ -532,3 +583,5 @@ int pn_launch_conv_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part1(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part2(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
 int pn_launch_conv_part3(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_d2_part0(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);
+int pn_launch_conv_d2_part1(pn_ctx *ctx, const ConvLaunch &L, hipStream_t stream);

@@ -13,6 +13,8 @@
 
 struct ConvGeom {
     int ks = 3, stride = 1;                             // set by the caller; everything below is planned
+    int dil = 1;                                        // set by the caller: tap distance (2: A2J's dilated layer4 blocks, generic kernel only)
+    int acc = 0;                                        // set by the caller: 1 = fp32 blocked accumulation (the A2J net in fp32; generic kernel, which is all fp32 runs)
     int kern = 0, cfg = 0, pitch = 0, R = 0, Wt = 0;
     int wc = 0, wp = 0, nbuf = 0, pt = 7, rpg = 4;      // kern 3: conv3_kernel<ks, wc, wp, nbuf, pt, rpg>
 };
@@ -93,7 +95,7 @@ inline void pn_plan_conv_kernel(int prec, int max_batch, int num_cus, int H, int
             }
         }
         // (cout > 32: the <= 32-cout heads stay on the generic kernel -- on conv3_kernel<3, 1, 1, 1> the two head launches took 64 us per step against 25, round 6)
-        if (prec == PN_PREC_BF16 && stride == 1 && (ks == 3 || ks == 1) && best >= 0.75 && cout > 32 && !sw.no_conv3) {
+        if (prec == PN_PREC_BF16 && stride == 1 && (ks == 3 || ks == 1) && best >= 0.75 && cout > 32 && !sw.no_conv3 && g.dil == 1) {
             g.kern = 3;
             g.wc = std::max(cout > 64 ? 4 : (cout > 32 ? 2 : 1), wc_min);
             const long tiles112 = (long)max_batch * ((H + rows - 1) / rows) * segs;   // strip tiles of one wave group
@@ -126,30 +128,31 @@ inline void pn_plan_conv_kernel(int prec, int max_batch, int num_cus, int H, int
 // Returns PN_OK, or a negative status with *why set (the caller formats the message).
 inline int pn_plan_conv_tiles(int prec, int H, int W, ConvGeom &g, const char **why) {
     const int ks = g.ks, stride = g.stride;
+    const int ksd = (ks - 1) * g.dil + 1;                        // rows / columns the taps span; padding dil * (ks / 2) keeps the stride-1 size
     const int Ho = (H + 2 * (ks / 2) - ks) / stride + 1, Wo = (W + 2 * (ks / 2) - ks) / stride + 1;
     if (g.kern == 3 || g.kern == 4) { g.pitch = 32; return PN_OK; }
-    if (g.cfg == PN_CFG_C64 && ks == 3 && stride == 1 && Wo >= 48 && (long)Ho * Wo >= 2048) g.cfg = PN_CFG_C64W;   // wide maps: 224-pixel tiles
+    if (g.cfg == PN_CFG_C64 && ks == 3 && stride == 1 && g.dil == 1 && Wo >= 48 && (long)Ho * Wo >= 2048) g.cfg = PN_CFG_C64W;   // wide maps: 224-pixel tiles
     const int BP = pn_cfg_pixels(g.cfg);
     // a block owns R full rows when they fit its pixel tile, else one row cut into equal segments
-    const int wt_cap = std::min(BP, (120 - ks) / stride + 1);     // widest segment the largest pitch class holds
+    const int wt_cap = std::min(BP, (120 - ksd) / stride + 1);     // widest segment the largest pitch class holds
     const int segs = (Wo + wt_cap - 1) / wt_cap;
     g.Wt = (Wo + segs - 1) / segs;
     g.R = std::max(1, std::min(Ho, BP / g.Wt));
     // the narrowest LDS pitch class that holds the halo row AND has a built instance for (prec, ks, stride, cfg): the table (conv_inst_table.h) has
     // holes -- no 1x1 kernel at pitch 16, no stride-2 kernel below pitch 64 -- and a wider LDS row is always valid
-    const int need = (g.Wt - 1) * stride + ks;
+    const int need = (g.Wt - 1) * stride + ksd;                  // the dilated halo is (ks - 1) * dil + 1 wide
     g.pitch = -1;
     for (int c : {16, 32, 64, 120})
-        if (need <= c && pn_conv_has_instance(prec, ks, stride, c, g.cfg)) { g.pitch = c; break; }
+        if (need <= c && (g.dil == 1 ? pn_conv_has_instance(prec, ks, stride, c, g.cfg) : g.dil == 2 && pn_conv_has_instance_d2(prec, ks, stride, c, g.cfg))) { g.pitch = c; break; }
     if (g.pitch < 0) { *why = pn_pick_pitch(need) < 0 ? "halo width has no pitch class" : "no generic kernel instance for this kernel size, stride and cout block at any pitch class"; return PN_ERR_UNSUPPORTED; }
     {   // the register-prefetched staging path holds at most this many halo pixels
         const int maxpx = pn_conv_stage_maxpx(prec, ks, stride, g.pitch, g.cfg);
-        while (maxpx > 0 && g.R > 1 && ((g.R - 1) * stride + ks) * need > maxpx) --g.R;
-        if (maxpx > 0 && ((g.R - 1) * stride + ks) * need > maxpx) { *why = "halo tile exceeds the staging capacity"; return PN_ERR_UNSUPPORTED; }
+        while (maxpx > 0 && g.R > 1 && ((g.R - 1) * stride + ksd) * need > maxpx) --g.R;
+        if (maxpx > 0 && ((g.R - 1) * stride + ksd) * need > maxpx) { *why = "halo tile exceeds the staging capacity"; return PN_ERR_UNSUPPORTED; }
     }
     // one halo image must fit the LDS (conv_launch_one refuses the launch otherwise): tall tiles of a narrow strided map.  R = 1 always fits: at
     // most 3 rows x 120 pixels x 256 B = 90 KB
-    while (g.R > 1 && pn_conv_lds_bytes(prec, ks, stride, g.pitch, g.R) > PN_CONV_LDS_MAX) --g.R;
+    while (g.R > 1 && pn_conv_lds_bytes(prec, ks, stride, g.pitch, g.R, g.dil) > PN_CONV_LDS_MAX) --g.R;
     return PN_OK;
 }
 
@@ -168,7 +171,7 @@ inline size_t pn_conv_pack_bytes(int prec, const ConvGeom &g, int cout_pad, int 
 
 // two planned convolutions run the same kernel instantiation
 inline bool pn_conv_same_launch(const ConvGeom &a, const ConvGeom &b) {
-    return b.ks == a.ks && b.stride == a.stride && b.pitch == a.pitch && b.R == a.R && b.Wt == a.Wt && b.kern == a.kern &&
+    return b.ks == a.ks && b.stride == a.stride && b.dil == a.dil && b.acc == a.acc && b.pitch == a.pitch && b.R == a.R && b.Wt == a.Wt && b.kern == a.kern &&
            (a.kern == 4 || (a.kern == 3 ? (b.wc == a.wc && b.wp == a.wp && b.nbuf == a.nbuf && b.pt == a.pt && b.rpg == a.rpg) : b.cfg == a.cfg));
 }
 
@@ -197,7 +200,7 @@ inline void pn_fill_conv_problem(ConvProblem &P, const PnConvInput &in, int B, i
     if (g.kern == 4) P.nblocks = ((B * P.tiles_per_img + 1) / 2) * P.cout_blocks;      // a block = two strips x 128 couts
     P.ksteps = cin_chunks * g.ks * g.ks * 2;
     P.ks = g.ks;
-    P.lds_buf_bytes = (int)pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R);
+    P.lds_buf_bytes = (int)pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R, g.dil);
     P.lds_two = (cin_chunks > 1 && 2 * (size_t)P.lds_buf_bytes <= PN_CONV_LDS_MAX) ? 1 : 0;
     P.in_zero_off = (unsigned)in.bytes;
 }
@@ -206,11 +209,12 @@ inline void pn_fill_conv_problem(ConvProblem &P, const PnConvInput &in, int B, i
 inline void pn_fill_conv_launch(ConvLaunch &L, int prec, const ConvGeom &g, int nprob, int max_blocks, bool two_bufs) {
     L.prec = prec;
     L.ks = g.ks; L.stride = g.stride; L.pitch = g.pitch; L.cfg = g.cfg;
+    L.dil = g.dil; L.acc = g.acc;
     L.kern = g.kern; L.wc = g.wc; L.wp = g.wp; L.nbuf = g.nbuf; L.pt = g.pt; L.rpg = g.rpg;
     L.tail = 0; L.mix = 0;
     L.nprob = nprob;
     L.max_blocks = max_blocks;
-    L.lds_bytes = pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R) * (two_bufs ? 2 : 1);
+    L.lds_bytes = pn_conv_lds_bytes(prec, g.ks, g.stride, g.pitch, g.R, g.dil) * (two_bufs ? 2 : 1);
     if (g.kern == 3) L.lds_bytes = pn_conv3_lds_bytes(g.ks, g.wp, g.nbuf, g.rpg);
     if (g.kern == 4) L.lds_bytes = 0;                        // conv4_launch knows its own size
 }

@@ -279,9 +279,9 @@ int prepare_conv(pn_net *n, ConvSpec &cs) {
 
 int add_conv(pn_net *n, const std::string &w, const std::string &bn, int ks, int stride, int in_buf, int in_coff,
              int out_buf, int out_coff, int act, int res_buf = -1, int nchw_slot = -1,
-             std::vector<int> cin_map = std::vector<int>()) {
+             std::vector<int> cin_map = std::vector<int>(), int dil = 1) {
     ConvSpec cs;
-    cs.w = w; cs.bn = bn; cs.ks = ks; cs.stride = stride;
+    cs.w = w; cs.bn = bn; cs.ks = ks; cs.stride = stride; cs.dil = dil;
     cs.in_buf = in_buf; cs.in_coff = in_coff;
     cs.out_buf = out_buf; cs.out_coff = out_coff;
     cs.res_buf = res_buf; cs.act = act; cs.nchw_slot = nchw_slot;
@@ -345,14 +345,23 @@ void add_pool(pn_net *n, int mode, int in_buf, int out_buf, int C, int out_coff)
     n->steps.push_back(st);
 }
 
-int add_stem(pn_net *n, int out_buf) {
+// sum_cin > 1 (build_a2j): the weight is [64, sum_cin, 7, 7] and every input channel is the SAME image (ResNetBackBone.forward expands the depth
+// crop to three identical channels, third_party_methods/A2J_experiments/model.py:155-156), so the convolution is the single-channel one with the
+// weights summed over Cin -- in double, before the BatchNorm scale -- and runs the fused matrix-core stem.
+int add_stem(pn_net *n, int out_buf, const std::string &conv = "model0.conv1", const std::string &bn = "model0.bn1", int sum_cin = 1) {
     pn_ctx *ctx = n->ctx;
-    const HostTensor *w = find_t(n, "model0.conv1.weight");
-    if (!w || w->shape.size() != 4 || w->shape[0] != 64 || w->shape[1] != n->input_dim || w->shape[2] != 7 || w->shape[3] != 7)
-        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "model0.conv1.weight must be [64,%d,7,7] (input_dim = %d)", n->input_dim, n->input_dim);
-    const HostTensor *g = find_t(n, "model0.bn1.weight"), *be = find_t(n, "model0.bn1.bias");
-    const HostTensor *mu = find_t(n, "model0.bn1.running_mean"), *var = find_t(n, "model0.bn1.running_var");
-    if (!g || !be || !mu || !var) return pn_set_error(ctx, PN_ERR_INVALID, "missing model0.bn1.*");
+    const HostTensor *w = find_t(n, conv + ".weight");
+    if (!w || w->shape.size() != 4 || w->shape[0] != 64 || w->shape[1] != (sum_cin > 1 ? sum_cin : n->input_dim) || w->shape[2] != 7 || w->shape[3] != 7)
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s.weight must be [64,%d,7,7] (input_dim = %d)", conv.c_str(), sum_cin > 1 ? sum_cin : n->input_dim, n->input_dim);
+    auto wd = [&](int o, int t) -> double {      // the weight the stem folds, in double
+        if (sum_cin <= 1) return (double)w->data[o * 49 + t];
+        double s = 0;
+        for (int c = 0; c < sum_cin; ++c) s += (double)w->data[((size_t)o * sum_cin + c) * 49 + t];
+        return s;
+    };
+    const HostTensor *g = find_t(n, bn + ".weight"), *be = find_t(n, bn + ".bias");
+    const HostTensor *mu = find_t(n, bn + ".running_mean"), *var = find_t(n, bn + ".running_var");
+    if (!g || !be || !mu || !var) return pn_set_error(ctx, PN_ERR_INVALID, "missing %s.*", bn.c_str());
     if (n->input_dim != 1) {
         // multi-channel input (the reference constructors default to input_dim = 3, rtpose_light3d.py:250 / yolo_posenet.py:88): the folded
         // 7x7 convolution runs on the generic fp32 primitive (pn_conv2d_forward, any Cin), its NCHW map is handed to the NHWC layers by
@@ -381,7 +390,7 @@ int add_stem(pn_net *n, int out_buf) {
     std::vector<float> hw(49 * 64), hb(64);
     for (int o = 0; o < 64; ++o) {
         double s = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-        for (int t = 0; t < 49; ++t) hw[t * 64 + o] = (float)((double)w->data[o * 49 + t] * s);
+        for (int t = 0; t < 49; ++t) hw[t * 64 + o] = (float)(wd(o, t) * s);
         hb[o] = (float)((0.0 - (double)mu->data[o]) * s + (double)be->data[o]);
     }
     Step st;
@@ -782,6 +791,85 @@ int build_yolo(pn_net *n) {
     return PN_OK;
 }
 
+// A2J_model (third_party_methods/A2J_experiments/model.py:145-186): ResNet-50 (resnet.py:61-164: Bottleneck layers [3, 4, 6, 3], the stride on conv2, a 1x1
+// strided downsample; layer4 at stride 1 with conv2 of its blocks 1 and 2 at dilation 2 / padding 2, block 0 not dilated: resnet.py:112,142-145), output
+// stride 16, and three heads of 4 x (3x3 conv + bias + BN + ReLU) + a 3x3 output conv with bias: classification on layer3's map, regression and depth on
+// layer4's.  The head maps stay NHWC [B, h, w, 16 anchors x 15 joints (x 2)] in the buffers "cls" / "reg" / "dep": pn_a2j_vote reads them there.
+// Backbone.model.fc.* is never executed (model.py:158-167) and is skipped at load.
+int build_a2j(pn_net *n) {
+    const int H = n->in_h, W = n->in_w;
+    if (H % 16 || W % 16 || H < 16 || W < 16) return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "input size must be a multiple of 16");
+    if (n->x3) return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "the A2J net is built for fp32 and bf16 (bf16x3: its 64 -> 256 and 240 / 480-channel tensors are not laid out as plane pairs)");
+    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H16 = H / 16, W16 = W / 16;
+    n->out_h = H16; n->out_w = W16;
+    const int A1 = new_buf(n, H2, W2, 64), X0 = new_buf(n, H4, W4, 64);
+    if (int rc = add_stem(n, A1, "Backbone.model.conv1", "Backbone.model.bn1", 3)) return rc;
+    std::vector<std::vector<int>> levels;
+    auto level = [&](std::vector<int> ids) { levels.push_back(ids); };
+    if (n->prec == PN_PREC_BF16 && !n->sw.no_stempool) n->steps.back().stem_pool_buf = X0;     // conv1 - bn1 - relu - maxpool as one launch, as build_yolo
+    else levels.push_back({-1, 1, A1, X0, 64, 0});
+    int cur = X0, ch = H4, cw = W4;
+    const int nblocks[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512}, strides[4] = {1, 2, 2, 1}, dils[4] = {1, 1, 1, 2};
+    int x3 = -1;
+    for (int l = 0; l < 4; ++l) {
+        const int p = planes[l], s = strides[l], oh = ch / s, ow = cw / s;
+        const int t1 = new_buf(n, ch, cw, p), t1b = s == 1 ? t1 : new_buf(n, oh, ow, p), t2 = new_buf(n, oh, ow, p);
+        const int d = new_buf(n, oh, ow, 4 * p);
+        int a = new_buf(n, oh, ow, 4 * p), b = new_buf(n, oh, ow, 4 * p);
+        const std::string L = "Backbone.model.layer" + std::to_string(l + 1) + ".";
+        // block 0: conv1 and the (strided) downsample read the same map: one level
+        level({add_conv(n, L + "0.conv1", L + "0.bn1", 1, 1, cur, 0, t1, 0, PN_ACT_RELU),
+               add_conv(n, L + "0.downsample.0", L + "0.downsample.1", 1, s, cur, 0, d, 0, PN_ACT_NONE)});
+        level({add_conv(n, L + "0.conv2", L + "0.bn2", 3, s, t1, 0, t2, 0, PN_ACT_RELU)});
+        level({add_conv(n, L + "0.conv3", L + "0.bn3", 1, 1, t2, 0, a, 0, PN_ACT_RELU, d)});
+        for (int i = 1; i < nblocks[l]; ++i) {
+            const std::string P = L + std::to_string(i);
+            level({add_conv(n, P + ".conv1", P + ".bn1", 1, 1, a, 0, t1b, 0, PN_ACT_RELU)});
+            level({add_conv(n, P + ".conv2", P + ".bn2", 3, 1, t1b, 0, t2, 0, PN_ACT_RELU, -1, -1, std::vector<int>(), dils[l])});
+            level({add_conv(n, P + ".conv3", P + ".bn3", 1, 1, t2, 0, b, 0, PN_ACT_RELU, a)});
+            std::swap(a, b);
+        }
+        cur = a; ch = oh; cw = ow;
+        if (l == 2) x3 = cur;
+    }
+    const int x4 = cur;
+    n->named["x3"] = {x3, {0, 1024}};
+    n->named["x4"] = {x4, {0, 2048}};
+    const int na = 16 * n->num_parts;
+    const char *hn[3] = {"classificationModel", "regressionModel", "DepthRegressionModel"}, *on[3] = {"cls", "reg", "dep"};
+    int hin[3] = {x3, x4, x4}, ha[3], hb[3], ho[3];
+    for (int k = 0; k < 3; ++k) {
+        ha[k] = new_buf(n, H16, W16, 256); hb[k] = new_buf(n, H16, W16, 256);
+        ho[k] = new_buf(n, H16, W16, k == 1 ? 2 * na : na);
+        n->named[on[k]] = {ho[k], {0, k == 1 ? 2 * na : na}};
+    }
+    for (int i = 1; i <= 4; ++i) {
+        std::vector<int> ids;
+        for (int k = 0; k < 3; ++k) {
+            const std::string P = std::string(hn[k]) + ".";
+            ids.push_back(add_conv(n, P + "conv" + std::to_string(i), P + "bn" + std::to_string(i), 3, 1, hin[k], 0, ha[k], 0, PN_ACT_RELU));
+            hin[k] = ha[k];
+            std::swap(ha[k], hb[k]);
+        }
+        level(ids);
+    }
+    level({add_conv(n, std::string(hn[0]) + ".output", "", 3, 1, hin[0], 0, ho[0], 0, PN_ACT_NONE),
+           add_conv(n, std::string(hn[1]) + ".output", "", 3, 1, hin[1], 0, ho[1], 0, PN_ACT_NONE),
+           add_conv(n, std::string(hn[2]) + ".output", "", 3, 1, hin[2], 0, ho[2], 0, PN_ACT_NONE)});
+    // fp32: blocked accumulation (conv_mfma_kernel<..., ACC = 1>) -- this net's K loops run to 18 432 terms, and a serial fp32 chain of that length
+    // leaves the heads about four times the reference's own fp32 error away from its fp64 run
+    if (n->prec == PN_PREC_F32)
+        for (auto &cs : n->convs) cs.acc = 1;
+    for (auto &cs : n->convs)
+        if (int rc = prepare_conv(n, cs)) return rc;
+    for (auto &cs : n->convs) n->flops_per_frame += cs.flops;
+    for (auto &lv : levels) {
+        if (lv[0] == -1) add_pool(n, lv[1], lv[2], lv[3], lv[4], lv[5]);
+        else add_conv_level(n, lv);
+    }
+    return PN_OK;
+}
+
 int refresh_problems(pn_net *n, int B, hipStream_t stream) {
     for (auto &st : n->steps) {
         if (st.type != Step::CONV) continue;
@@ -856,7 +944,7 @@ std::string geom_json(int prec, bool x3, const ConvGeom &g, int H, int W, int co
     char t[384];
     snprintf(t, sizeof t, "\"kernel\": \"%s\", \"kern\": %d, \"cfg\": %d, \"pitch\": %d, \"R\": %d, \"Wt\": %d, \"wc\": %d, \"wp\": %d, \"nbuf\": %d, \"pt\": %d, \"rpg\": %d, "
              "\"tiles_x\": %d, \"tiles_per_img\": %d, \"cout_blocks\": %d, \"nblocks\": %d, \"lds_two\": %d",
-             pn_conv_kernel_label(prec, g.kern, false, g.ks, g.stride, g.pitch, g.cfg, g.wc, g.wp, g.nbuf, g.pt, g.rpg).c_str(), g.kern, g.cfg, g.pitch, g.R, g.Wt, g.wc,
+             (g.dil != 1 ? pn_conv_kernel_label_dil(prec, g.ks, g.stride, g.pitch, g.cfg, g.dil) : pn_conv_kernel_label(prec, g.kern, false, g.ks, g.stride, g.pitch, g.cfg, g.wc, g.wp, g.nbuf, g.pt, g.rpg)).c_str(), g.kern, g.cfg, g.pitch, g.R, g.Wt, g.wc,
              g.wp, g.nbuf, g.pt, g.rpg, P.tiles_x, P.tiles_per_img, P.cout_blocks, P.nblocks, P.lds_two);
     return t;
 }
@@ -877,6 +965,7 @@ std::string step_label(const pn_net *n, const Step &st) {
         const ConvSpec &cs = n->convs[id];
         if (cs.ks != c0.ks || (cs.tail_conv >= 0) != (c0.tail_conv >= 0)) mix = true;
     }
+    if (c0.dil != 1) return pn_conv_kernel_label_dil(n->prec, c0.ks, c0.stride, c0.pitch, c0.cfg, c0.dil);
     return pn_conv_kernel_label(n->prec, c0.kern, mix, c0.ks, c0.stride, c0.pitch, c0.cfg, c0.wc, c0.wp, c0.nbuf, c0.pt, c0.rpg);
 }
 
@@ -974,12 +1063,16 @@ extern "C" {
 
 pn_net *pn_net_create(pn_ctx *ctx, int kind, int num_parts, int a, int input_dim) {
     if (!ctx) return nullptr;
-    if (kind != PN_NET_RTPOSE_LIGHT3D && kind != PN_NET_YOLO_POSENET) {
+    if (kind != PN_NET_RTPOSE_LIGHT3D && kind != PN_NET_YOLO_POSENET && kind != PN_NET_A2J) {
         pn_set_error(ctx, PN_ERR_INVALID, "unknown net kind %d", kind);
         return nullptr;
     }
     if (input_dim < 1 || input_dim > 16) {
         pn_set_error(ctx, PN_ERR_UNSUPPORTED, "input_dim %d outside [1, 16]", input_dim);
+        return nullptr;
+    }
+    if (kind == PN_NET_A2J && input_dim != 1) {
+        pn_set_error(ctx, PN_ERR_UNSUPPORTED, "the A2J net takes one-channel depth crops (input_dim = 1)");
         return nullptr;
     }
     pn_net *n = new pn_net();
@@ -999,6 +1092,8 @@ int pn_net_set_tensor(pn_net *n, const char *name, const float *host_data, const
     if (n->finalized) return pn_set_error(n->ctx, PN_ERR_STATE, "net already finalized");
     std::string s(name);
     if (s.rfind("module.", 0) == 0) s = s.substr(7);
+    if (n->kind == PN_NET_A2J && (s.rfind("Backbone.model.fc.", 0) == 0 || (s.size() > 19 && s.compare(s.size() - 19, 19, "num_batches_tracked") == 0)))
+        return PN_OK;      // built by the reference, never executed (model.py:158-167)
     HostTensor t;
     size_t numel = 1;
     for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); numel *= (size_t)shape[i]; }
@@ -1017,7 +1112,7 @@ int pn_net_finalize(pn_net *n, int precision, int max_batch, int in_h, int in_w)
     n->x3 = precision == PN_PREC_BF16X3;                      // kernels and packing run as bf16; tensors carry three planes
     n->prec = n->x3 ? PN_PREC_BF16 : precision; n->max_batch = max_batch; n->in_h = in_h; n->in_w = in_w;
     n->sw = pn_read_switches();
-    int rc = n->kind == PN_NET_RTPOSE_LIGHT3D ? build_rtpose(n) : build_yolo(n);
+    int rc = n->kind == PN_NET_RTPOSE_LIGHT3D ? build_rtpose(n) : n->kind == PN_NET_A2J ? build_a2j(n) : build_yolo(n);
     if (rc) return rc;
     for (auto &b : n->bufs) {
         size_t bytes = (size_t)max_batch * b.H * b.W * b.C * n->esize() + 2048;   // + zero page (halo padding source of conv3_kernel / conv4_kernel: 64 B per 32-channel half + 16)
@@ -1056,6 +1151,42 @@ int pn_yolo_forward(pn_net *n, const float *x_dev, int B, float *out_dev, void *
     if (!x_dev || !out_dev) return pn_set_error(n->ctx, PN_ERR_INVALID, "null device pointer");
     n->nchw_ptr[3] = out_dev;
     return run_forward(n, x_dev, B, (hipStream_t)hip_stream);
+}
+
+// A2J_model.forward (third_party_methods/A2J_experiments/model.py:179-186): the heads stay on the device, NHWC
+int pn_a2j_forward(pn_net *n, const float *crops_dev, int B, const void **cls_dev, const void **reg_dev, const void **dep_dev, void *hip_stream) {
+    if (!n) return PN_ERR_INVALID;
+    if (n->kind != PN_NET_A2J) return pn_set_error(n->ctx, PN_ERR_INVALID, "not an A2J net");
+    if (!crops_dev) return pn_set_error(n->ctx, PN_ERR_INVALID, "null device pointer");
+    if (int rc = run_forward(n, crops_dev, B, (hipStream_t)hip_stream)) return rc;
+    if (cls_dev) *cls_dev = n->bufs[n->named["cls"].first].p;
+    if (reg_dev) *reg_dev = n->bufs[n->named["reg"].first].p;
+    if (dep_dev) *dep_dev = n->bufs[n->named["dep"].first].p;
+    return PN_OK;
+}
+
+int pn_a2j_head_shape(pn_net *n, int *h, int *w, int *precision) {
+    if (!n) return PN_ERR_INVALID;
+    if (n->kind != PN_NET_A2J || !n->finalized) return pn_set_error(n->ctx, PN_ERR_STATE, "not a finalized A2J net");
+    if (h) *h = n->out_h;
+    if (w) *w = n->out_w;
+    if (precision) *precision = n->prec;
+    return PN_OK;
+}
+
+int pn_a2j_predict(pn_net *n, const void *frames_dev, int depth_dtype, int F, int H, int W, const float *rows_dev, int nrows, const pn_a2j_cfg *cfg,
+                   const float *anchors_dev, float *crops_dev, int32_t *flags_dev, float *votes_dev, pn_a2j_record *records_dev, void *hip_stream) {
+    if (!n) return PN_ERR_INVALID;
+    pn_ctx *ctx = n->ctx;
+    if (n->kind != PN_NET_A2J || !n->finalized) return pn_set_error(ctx, PN_ERR_STATE, "not a finalized A2J net");
+    if (!cfg || !crops_dev || !anchors_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_predict: null argument");
+    if (cfg->crop_h != n->in_h || cfg->crop_w != n->in_w)
+        return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_predict: crops of %dx%d into a net finalized for %dx%d", cfg->crop_h, cfg->crop_w, n->in_h, n->in_w);
+    if (nrows < 1 || nrows > n->max_batch) return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_predict: %d rows outside [1, %d]", nrows, n->max_batch);
+    if (int rc = pn_a2j_crop(ctx, frames_dev, depth_dtype, F, H, W, rows_dev, nrows, cfg, crops_dev, flags_dev, hip_stream)) return rc;
+    const void *cls = nullptr, *reg = nullptr, *dep = nullptr;
+    if (int rc = pn_a2j_forward(n, crops_dev, nrows, &cls, &reg, &dep, hip_stream)) return rc;
+    return pn_a2j_vote(ctx, cls, reg, dep, n->prec, nrows, n->out_h, n->out_w, 16, n->num_parts, anchors_dev, votes_dev, rows_dev, cfg, records_dev, hip_stream);
 }
 
 // frames in: the 7x7 stem computes its input tile from the raw depth frames with pn_preprocess's arithmetic (preproc_pixel.h)
@@ -1183,6 +1314,8 @@ int pn_net_step_info(pn_net *n, int k, char *out, size_t cap) {
         // the POOLED map instead (refresh_problems): tiles_x / tiles_per_img / nblocks are then not the launch's
         const Buf &ib = n->bufs[c.in_buf];
         js += ", " + geom_json(n->prec, n->x3, c, ib.H, ib.W, c.cout, c.cin_chunks, n->last_B > 0 ? n->last_B : n->max_batch);
+        if (c.dil != 1) add(", \"dil\": %d", c.dil);      // the dilated convolutions only (A2J layer4 blocks 1 and 2)
+        if (c.acc) add(", \"blocked_acc\": %d", c.acc);   // fp32 A2J only
         js += "}";
     };
     if (k == -1) {

@@ -193,6 +193,8 @@ struct ConvLaunch {
     int pitch;     // LDS halo row pitch in pixels (multiple of 8, >= halo columns)
     int cfg;       // pn_conv_cfg
     int kern = 0, wc = 0, wp = 0, nbuf = 0, pt = 7, rpg = 4;   // kern 3: conv3_kernel<ks, wc, wp, nbuf, pt, rpg>
+    int dil = 1;             // generic kernel only: tap distance (conv_mfma_kernel<..., DIL>), 1 or 2
+    int acc = 0;             // generic kernel, fp32 only: 1 = blocked accumulation (conv_mfma_kernel<..., ACC = 1>)
     int tail = 0;            // kern 3: 1 = every problem of the launch carries a fused 1x1 tail (ConvProblem::tail_w); 2 = a fused average pool (net.hip::fuse_pool_tails)
     int mix = 0;             // kern 3: 3x3 problems and fused-tail 1x1 problems share the launch (conv3_mix_kernel)
     int nprob;
@@ -208,6 +210,11 @@ inline std::string pn_conv_kernel_label(int prec, int kern, bool mix, int ks, in
     else if (kern == 3 && mix) snprintf(lb, sizeof lb, "conv3_mix_kernel");
     else if (kern == 3) snprintf(lb, sizeof lb, "conv3_kernel<%d, %d, %d, %d, %d, %d>", ks, wc, wp, nbuf, pt, rpg);
     else snprintf(lb, sizeof lb, "conv_mfma_kernel<%d, %d, %d, %d, %d>", prec, ks, stride, pitch, cfg);
+    return lb;
+}
+inline std::string pn_conv_kernel_label_dil(int prec, int ks, int stride, int pitch, int cfg, int dil) {
+    char lb[96];
+    snprintf(lb, sizeof lb, "conv_mfma_kernel<%d, %d, %d, %d, %d, %d>", prec, ks, stride, pitch, cfg, dil);
     return lb;
 }
 inline std::string pn_pool_kernel_label(int mode, bool split) {
@@ -238,7 +245,8 @@ struct BBProblem {
 int pn_launch_bb64(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);       // bb64_inst.hip
 int pn_launch_bb64x3(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);     // bb64x3_inst.hip (6-row tiles: tiles_per_img = ceil(H / 6) * tiles_x)
 size_t pn_conv3_lds_bytes(int ks, int WP, int nbuf, int rpg = 4);
-size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R);
+size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R, int dil = 1);
+int pn_conv_has_instance_d2(int prec, int ks, int stride, int pitch, int cfg);      // conv_mfma.hip: the dilation-2 rows of conv_inst_table.h
 // LDS one block of the generic kernel may use: what the planner fits a halo image (or two) into and what the launch refuses to exceed
 constexpr size_t PN_CONV_LDS_MAX = 160 * 1024;
 int pn_conv_stage_maxpx(int prec, int ks, int stride, int pitch, int cfg);   // 0 = no limit (direct staging)

@@ -363,6 +363,138 @@ class YoloEngine:
         return self.predict(depth).cpu().numpy().view(_lib.YOLO_FRAME_DTYPE).reshape(-1)
 
 
+class A2JEngine:
+    """The second stage of the Yolo-A2J baseline: depth frames + box rows -> per-box crops (pn_a2j_crop) -> A2J_model (pn_a2j_forward) ->
+    anchor vote and map back to the frame (pn_a2j_vote) -> pn_a2j_record per box.  The per-box body of
+    third_party_methods/A2J_experiments/a2j_test_pred_box_new.py:268-313,340-421 minus Python.  boxes: [n, 6] float32 rows
+    (frame index, x0, y0, x1, y1, conf) in original-frame pixels, sorted by frame; a frame without a detection carries one row
+    (f, -1, -1, -1, -1, 0) and comes out as one person at (-1, -1) with confidence 0, as in the reference."""
+
+    def __init__(self, precision="bf16", state_dict=None, device=None, max_batch=32, crop=288, img_wh=(480, 512), intrinsics=None, weight_seed=3):
+        from .network.a2j import A2J_model, A2JCfg, A2J_RECORD_DTYPE, generate_anchors, shift
+        if not torch.cuda.is_available():
+            raise _lib.PopnetError("A2JEngine needs a GPU: the HIP path has no CPU fallback")
+        if str(precision).lower() == "bf16x3":
+            raise _lib.PopnetError("A2JEngine: precision is 'fp32' or 'bf16'")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_batch = int(max_batch)
+        self.crop_h, self.crop_w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))
+        if state_dict is None:
+            with torch.random.fork_rng(devices=[]):      # the module's own seeded initialisation (nothing is downloaded); the caller's RNG stays as it was
+                torch.manual_seed(weight_seed)
+                self.model = A2J_model(15).eval()
+        else:
+            self.model = A2J_model(15).eval()
+            self.model.load_state_dict(state_dict)
+        self.model.precision = precision
+        self.L = _lib.lib()
+        self.ctx = _lib.Context.for_device(self.device.index)
+        self.cfg = A2JCfg()
+        self.L.pn_a2j_cfg_default(C.byref(self.cfg))
+        self.cfg.img_w, self.cfg.img_h = int(img_wh[0]), int(img_wh[1])
+        self.cfg.crop_w, self.cfg.crop_h = self.crop_w, self.crop_h
+        if intrinsics is not None:
+            self.cfg.fx, self.cfg.fy, self.cfg.cx, self.cfg.cy = (float(intrinsics[k]) for k in ("fx", "fy", "cx", "cy"))
+        if self.L.pn_sizeof_a2j_record() != A2J_RECORD_DTYPE.itemsize:
+            raise _lib.PopnetError("pn_a2j_record layout mismatch")
+        self.record_dtype = A2J_RECORD_DTYPE
+        d = self.device
+        self.anchors = torch.from_numpy(shift([self.crop_h // 16, self.crop_w // 16], 16, generate_anchors())).float().to(d)
+        self.x = torch.empty((self.max_batch, 1, self.crop_h, self.crop_w), device=d, dtype=torch.float32)
+        self.last_flags = None
+        self.votes = torch.empty((self.max_batch, 15, 3), device=d, dtype=torch.float32)
+
+    @property
+    def net(self):
+        """The compiled pn_net (built on first use: the crops need none)."""
+        return self.model._compile(self.device, self.max_batch, self.crop_h, self.crop_w)
+
+    def _frames(self, frames):
+        _lib.require_cuda_tensor(frames, "frames")
+        if frames.dim() != 3 or frames.dtype not in (torch.float16, torch.float32):
+            raise _lib.PopnetError("frames must be a [F, H, W] float16 / float32 tensor")
+        return frames.contiguous(), (_lib.PN_DEPTH_F16 if frames.dtype == torch.float16 else _lib.PN_DEPTH_F32)
+
+    def _rows(self, boxes):
+        rows = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 6).to(self.device).contiguous()
+        return rows
+
+    def crops(self, frames, boxes):
+        """-> ([n, 1, crop_h, crop_w] float32 crops, [n] int32 flags: 1 where the reference would raise, the crop is zeros)."""
+        frames, dt = self._frames(frames)
+        rows = self._rows(boxes)
+        n = rows.shape[0]
+        out = torch.empty((n, 1, self.crop_h, self.crop_w), device=self.device, dtype=torch.float32)
+        flags = torch.zeros((n,), device=self.device, dtype=torch.int32)
+        self.ctx.check(self.L.pn_a2j_crop(self.ctx.handle, C.c_void_p(frames.data_ptr()), dt, frames.shape[0], frames.shape[1], frames.shape[2],
+                                          C.c_void_p(rows.data_ptr()), n, C.byref(self.cfg), C.c_void_p(out.data_ptr()), C.c_void_p(flags.data_ptr()),
+                                          _lib.current_stream_ptr(self.device)), "pn_a2j_crop")
+        return out, flags
+
+    def predict(self, frames, boxes):
+        """-> device uint8 tensor [n, sizeof(pn_a2j_record)], the rows in chunks of max_batch (no sync).  self.last_flags: device int32 [n],
+        1 where the reference would raise on the row's box (zero crop, see crops())."""
+        frames, dt = self._frames(frames)
+        rows = self._rows(boxes)
+        n = rows.shape[0]
+        recs = torch.zeros((n, self.record_dtype.itemsize), device=self.device, dtype=torch.uint8)
+        flags = torch.zeros((n,), device=self.device, dtype=torch.int32)
+        self.last_flags = flags
+        net = self.net
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            self.ctx.check(self.L.pn_a2j_predict(
+                net, C.c_void_p(frames.data_ptr()), dt, frames.shape[0], frames.shape[1], frames.shape[2], C.c_void_p(rows[i:].data_ptr()), m,
+                C.byref(self.cfg), C.c_void_p(self.anchors.data_ptr()), C.c_void_p(self.x.data_ptr()), C.c_void_p(flags[i:].data_ptr()),
+                C.c_void_p(self.votes.data_ptr()), C.c_void_p(recs[i:].data_ptr()), _lib.current_stream_ptr(self.device)), "pn_a2j_predict")
+        return recs
+
+    def predict_host(self, frames, boxes):
+        return self.predict(frames, boxes).cpu().numpy().view(self.record_dtype).reshape(-1)
+
+    def predict_lists(self, frames, boxes, n_frames=None):
+        """-> (pred_2d, pred_3d, part_conf): per frame a list of persons, each 15 x [x, y] / [X, Y, Z] / confidences -- the reference's
+        human_pred_set_2d / _3d / part_conf lists (a2j_test_pred_box_new.py:397-421)."""
+        recs = self.predict_host(frames, boxes)
+        return lists_from_a2j_records(recs, frames.shape[0] if n_frames is None else n_frames)
+
+
+def lists_from_a2j_records(recs, n_frames):
+    p2, p3, pc = [[] for _ in range(n_frames)], [[] for _ in range(n_frames)], [[] for _ in range(n_frames)]
+    for r in recs:
+        f = int(r["frame"])
+        p2[f].append(r["joint"][:, 0:2].astype(np.float64).tolist())
+        p3[f].append(r["joint"][:, 2:5].astype(np.float64).tolist())
+        pc[f].append([float(r["conf"])] * 15)
+    return p2, p3, pc
+
+
+def yolo_box_rows(yolo_frames):
+    """pn_yolo_frame records (host) -> A2J box rows [n, 6]: per detection (frame, bbox_org x0, y0, x1, y1, conf); a frame without a
+    detection gives (frame, -1, -1, -1, -1, 0) (evaluation_yolo_posenet_kdh3d_mpreal_a2j_preprocess.py:197-228)."""
+    rows = []
+    for f, fr in enumerate(yolo_frames):
+        n = int(fr["n_det"])
+        if n == 0:
+            rows.append([f, -1, -1, -1, -1, 0])
+        for k in range(n):
+            rows.append([f] + [float(v) for v in fr["bbox_org"][k]] + [float(fr["bbox"][k][4])])
+    return np.asarray(rows, dtype=np.float32).reshape(-1, 6)
+
+
+class YoloA2JEngine:
+    """YoloEngine -> A2JEngine: the boxes of pn_yolo_frame.bbox_org with their confidences become the A2J rows; the crops are chunked by
+    the A2J engine's max_batch."""
+
+    def __init__(self, precision="bf16", yolo_state_dict=None, a2j_state_dict=None, device=None, max_batch=32, crop=288, img_wh=(480, 512), **yolo_kw):
+        self.yolo = YoloEngine(precision=precision, state_dict=yolo_state_dict, device=device, max_batch=max_batch, **yolo_kw)
+        self.a2j = A2JEngine(precision=precision, state_dict=a2j_state_dict, device=device, max_batch=max_batch, crop=crop, img_wh=img_wh)
+
+    def predict_lists(self, depth):
+        rows = yolo_box_rows(self.yolo.predict_host(depth))
+        return self.a2j.predict_lists(depth, rows, n_frames=depth.shape[0])
+
+
 def calibrate_yolo_conf(model, device=None, frac=0.012, calib_frames=8, seed=99):
     """Synthetic-checkpoint calibration for YoloPoseNet (bench / smoke only; never applied to user
     weights).  Seeded random weights put every cell's confidence near sigmoid(0) = 0.5, i.e. ~200
