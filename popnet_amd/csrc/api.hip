@@ -11,6 +11,7 @@
 // f16 frame per output pixel (614 KB per 480x640 frame), writes S*S*4 B.
 #pragma clang fp contract(off)
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -98,6 +99,21 @@ void pn_destroy(pn_ctx *ctx) {
     if (ctx->train_pack_table) (void)hipFree(ctx->train_pack_table);
     delete ctx;
 }
+
+}  // extern "C"
+
+// Every translation unit reports through this: the message is kept on the context for pn_last_error, the code is returned
+int pn_set_error(pn_ctx *ctx, int code, const char *fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (ctx) ctx->err = buf;
+    return code;
+}
+
+extern "C" {
 
 int pn_last_error(pn_ctx *ctx, char *buf, size_t buf_len) {
     if (!ctx) return 0;

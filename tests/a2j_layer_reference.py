@@ -3,7 +3,7 @@
 * Dilation: a convolution that pn_net_step_info reports with "dil": 2 (layer4 blocks 1 and 2, conv2) is
   F.conv2d(..., dilation=2, padding=2): taps at 0 and +-2.  The products, their count and the allowance rule are those of
   layer_reference.conv_ref -- only where the taps land changes -- so conv_ref runs unchanged with the convolution it calls replaced.
-* The stem: ResNetBackBone.forward feeds three identical channels, net.hip::add_stem sums the [64, 3, 7, 7] weights over Cin in
+* The stem: ResNetBackBone.forward feeds three identical channels, net_pack.hip::pack_stem sums the [64, 3, 7, 7] weights over Cin in
   double, multiplies by the BatchNorm scale and rounds to float32: the same single-channel stem as the other nets with
   model0.conv1.weight = sum over Cin (kept in double) and model0.bn1 = Backbone.model.bn1.
 

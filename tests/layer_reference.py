@@ -4,7 +4,7 @@ The reference computes, in float64 on the CPU, exactly the operation the kernels
 actually read -- so a kernel may sum in any order, tile any way, and still pass, while a wrong operand moves the
 result by far more than the allowance.  How the kernels define their operands (read from the packing / launch code):
 
-* Folded weights (net.hip::prepare_conv, wval): s = gamma / sqrt(var + 1e-5) in double, w_f = float32(w * s) with
+* Folded weights (net_pack.hip::prepare_conv): s = gamma / sqrt(var + 1e-5) in double, w_f = float32(w * s) with
   the product in double.  bf16 packs RNE(w_f); bf16x3 packs W_hi = RNE(w_f) and W_lo = RNE(float32(w_f - W_hi)) and
   the K loop reads [x_hi | x_lo | x_hi] against [W_hi | W_hi | W_lo]: x_hi W_hi + x_lo W_hi + x_hi W_lo, with NO
   x_lo W_lo term.  fp32 packs w_f.  The bias is float32((b - mean) * s + beta) (b = 0 without a conv bias); a conv
@@ -15,7 +15,7 @@ result by far more than the allowance.  How the kernels define their operands (r
   5 + 3J channels, (s - 0.5) * 2, s * 2, s, (s - 0.5) * 4).  Then the store: bf16 RNE, or the two planes
   hi = RNE(v), lo = RNE(v - hi); fp32 buffers and the NCHW heads store v.
 * Special cases:
-  - 1x1 tails (net.hip::pack_tail, conv3_kernel.h TAIL == 1): the 128-channel tile after its activation is rounded
+  - 1x1 tails (net_pack.hip::pack_tail, conv3_kernel.h TAIL == 1): the 128-channel tile after its activation is rounded
     to bf16 in LDS; the tail reads it against raw RNE(w) (no BatchNorm) plus float32(bias).
   - embed3: a 1x1 stride-2 convolution packed as the centre tap of a 3x3 one: the same products plus exact zeros.
   - stage-2 input-channel map: buffer channel i carries reference channel cin_map[i]; -1 (the pad channels) has
