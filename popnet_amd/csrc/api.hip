@@ -49,6 +49,7 @@ PnSwitches pn_read_switches() {
     s.bblock_x3 = num("POPNET_BBLOCK_X3", 0) != 0;
     s.bb64_static = set("POPNET_BB64_STATIC");
     s.bb64_halves = num("POPNET_BB64_HALVES", 1) == 2 ? 2 : 1;
+    if (set("POPNET_BB64_STRIP")) { const int v = num("POPNET_BB64_STRIP", 0); s.bb64_strip = v == 1 || v == 2 ? v : 0; }
     s.no_tailfuse = set("POPNET_NO_TAILFUSE");
     s.no_poolfuse = set("POPNET_NO_POOLFUSE");
     s.no_stempool = set("POPNET_NO_STEMPOOL");

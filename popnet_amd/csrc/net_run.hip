@@ -196,7 +196,19 @@ int run_forward(pn_net *n, const float *x, int B, hipStream_t stream, int nsteps
             P.in_split = n->x3 ? ib.plane : 0; P.out_split = n->x3 ? ob.plane : 0;
             P.tickets = (n->x3 || n->sw.bb64_static || P.ntiles < 4 * ctx->num_cus) ? nullptr : (int *)n->dev(st.bb_tickets);      // nullptr: blockIdx.x + k * gridDim.x
             P.halves = n->sw.bb64_halves;
-            rc = n->x3 ? pn_launch_bb64x3(ctx, P, stream) : pn_launch_bb64(ctx, P, stream);
+            // The strip kernel (bb64s_kernel.h) walks column segments top-down and carries the intermediate's two overlap rows.  S segments per column: the
+            // smallest count that gives every CU a segment, at most T / 2 (a segment has two tiles at least), lengths differing by at most one.  Default:
+            // where a segment averages four row tiles -- the tile tickets' threshold; 56 x 56 maps, small batches and bf16x3 nets keep their kernels, and
+            // so do POPNET_BB64_STATIC / POPNET_BB64_HALVES=2, which ask for a form of bb64_kernel.
+            const int T = (ib.H + 7) / 8, ncols = B * P.tiles_x;
+            int S = std::max(1, std::min((ctx->num_cus + ncols - 1) / ncols, T / 2));
+            if (n->sw.bb64_strip == 2) S = std::max(1, std::min(2 * S, T / 2));
+            const bool strip = !n->x3 && T >= 2 && (n->sw.bb64_strip >= 1 || (n->sw.bb64_strip < 0 && !n->sw.bb64_static && n->sw.bb64_halves != 2 && T >= 4 * S));
+            if (strip) {
+                P.strip_S = S; P.strip_T = T; P.nseg = ncols * S;
+                P.tickets = (n->sw.bb64_static || P.nseg <= ctx->num_cus) ? nullptr : (int *)n->dev(st.bb_tickets);
+            }
+            rc = n->x3 ? pn_launch_bb64x3(ctx, P, stream) : strip ? pn_launch_bb64s(ctx, P, stream) : pn_launch_bb64(ctx, P, stream);
         } else {
             rc = pn_launch_conv(ctx, st.launch, stream);
         }

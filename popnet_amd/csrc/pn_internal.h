@@ -52,6 +52,8 @@ struct PnSwitches {
     bool bblock_x3 = false;         // POPNET_BBLOCK_X3=<nonzero>: the fused BasicBlock kernel in bf16x3 nets as well
     bool bb64_static = false;       // POPNET_BB64_STATIC: bb64_kernel's static tile schedule
     int bb64_halves = 1;            // POPNET_BB64_HALVES=2: bb64_kernel<2>
+    int bb64_strip = -1;            // POPNET_BB64_STRIP: unset -1 (bb64s_strip_kernel where a column segment averages four row tiles), 0 never, 1 wherever a column has
+                                    // two row tiles, 2 as 1 with twice as many segments (the finer, ticketed cut: measurements only)
     bool no_tailfuse = false;       // POPNET_NO_TAILFUSE: no fused 1x1 tails
     bool no_poolfuse = false;       // POPNET_NO_POOLFUSE: no fused average pools
     bool no_stempool = false;       // POPNET_NO_STEMPOOL: YoloPoseNet's stem and max pool as two launches
@@ -241,8 +243,12 @@ struct BBProblem {
     // one resets both, so a replayed graph finds zeros again).  nullptr = the static schedule (tile = blockIdx.x + k * gridDim.x)
     int *tickets;
     int halves;          // bb64_kernel<halves>: 2 = eight compute waves (opt-in), anything else = four
+    // bb64s_strip_kernel (bb64s_kernel.h): every column (frame x tiles_x) of strip_T = ceil(H / 8) row tiles is cut into strip_S segments, nseg in all; there
+    // `tickets` hands out SEGMENTS past the first of a workgroup (nullptr: segment = blockIdx.x + k * gridDim.x)
+    int strip_S, strip_T, nseg;
 };
 int pn_launch_bb64(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);       // bb64_inst.hip
+int pn_launch_bb64s(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);      // bb64s_inst.hip (needs strip_T >= 2 strip_S)
 int pn_launch_bb64x3(pn_ctx *ctx, const BBProblem &P, hipStream_t stream);     // bb64x3_inst.hip (6-row tiles: tiles_per_img = ceil(H / 6) * tiles_x)
 size_t pn_conv3_lds_bytes(int ks, int WP, int nbuf, int rpg = 4);
 size_t pn_conv_lds_bytes(int prec, int ks, int stride, int pitch, int R, int dil = 1);
