@@ -643,6 +643,10 @@ int build(pn_trainer *t) {
     const int B = t->B, H = t->H, W = t->W;
     if (H % 8 || W % 8) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_trainer: input size must be a multiple of 8");
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
+    // one frame on a 1 x 1 stage map: the stage BatchNorms would see ONE value per channel -- batch variance 0, xhat == 0, and the gradient behind every one
+    // of them identically zero: nothing trains (nn.BatchNorm2d raises for it, pn_bn_train_forward of the NCHW engine refuses it as well)
+    if ((long)B * H8 * W8 < 2)
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_trainer: model1_1.1: train-mode BatchNorm over one value per channel (batch %d on a %d x %d stage map): no batch statistics", B, H8, W8);
     int rc;
     if ((rc = tx_alloc(t, (void **)&t->zero_bias, 1024 * 4, true))) return rc;
     {   // channel maps of the stage-2 input: mine [feat 0..127 | paf 128.. | heat 156.. | z 172.. | pad] <-> reference [paf, heat, z, feat] (rtpose_light3d.py:339)

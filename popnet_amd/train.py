@@ -102,7 +102,11 @@ class TrainEngine:
                 self._check(self.L.pn_trainer_set_param(tr, k.encode(), off, n), "pn_trainer_set_param")
             for k, v in self.stats.items():
                 self._check(self.L.pn_trainer_set_stat(tr, k.encode(), self._ptr(v)), "pn_trainer_set_stat")
-            self._check(self.L.pn_trainer_finalize(tr, self._ptr(self.flat_p), self._ptr(self.flat_g), N, H, W, BN_MOMENTUM, BN_EPS), "pn_trainer_finalize")
+            try:
+                self._check(self.L.pn_trainer_finalize(tr, self._ptr(self.flat_p), self._ptr(self.flat_g), N, H, W, BN_MOMENTUM, BN_EPS), "pn_trainer_finalize")
+            except _lib.PopnetError:
+                self.L.pn_trainer_destroy(tr)          # a refused shape (PN_ERR_UNSUPPORTED) leaves nothing behind
+                raise
             self._trainers[(N, H, W)] = tr
         return tr
 

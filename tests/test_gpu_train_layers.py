@@ -261,11 +261,12 @@ class Step:
         assert kind == "pack", kind
         return lambda: []
 
-    def check_all(self):
-        """Replays the step op by op; records in CHECKED the (op kind, kernel label) pairs that produced a compared result."""
+    def check_all(self, which=None):
+        """Replays the step op by op; records in CHECKED the (op kind, kernel label) pairs that produced a compared result.  which: a predicate over ops --
+        only those are compared (the others still run, in order, so every compared op reads the operands the step gives it); None: all."""
         results = []
         for k, op in enumerate(self.ops):
-            post = None if op["kind"] in QUIET else self.prepare(op)
+            post = None if op["kind"] in QUIET or (which is not None and not which(op)) else self.prepare(op)
             self.run(k, k + 1)
             if post:
                 reports = post()
@@ -316,26 +317,61 @@ def _to_mine(ref, cat, plane):
     return out
 
 
-@pytest.mark.parametrize("cfg", CONFIGS, ids=[c[0] for c in CONFIGS])
-def test_integer_probes_of_every_convolution_and_weight_gradient_are_bit_exact(gpu, golden, cfg):
-    """Single ops on planted integer operands in [-3, 3] (weights written into the flat parameter buffer, then the pack op): every hi / lo split is exact and
-    every fp32 partial sum is an integer below 2^24 (test_train_layer_reference.py checks the limits at these shapes), so whatever the summation order, forward,
-    data gradient (with and without residual) and weight gradient must equal F.conv2d / conv2d_input / the weight-gradient sum in float64 BIT FOR BIT: a single
-    missing pixel, strip seam, tile edge or slice shows.  Every convolution problem without an activation (first, middle and last frame) and every
-    weight-gradient op (whole); then impulses: one non-zero dy element at a corner, at the last pixel of the last image, on both sides of a column-strip
-    seam and of a rows_per_block boundary -- dW must be the shifted x patch."""
+def impulse_spots(op, B, Ht, Wd, extended=False):
+    """(image, row, column) of the dy impulses for weight-gradient op `op` on a B x Ht x Wd map: a corner, the last pixel of the last image, both sides of a
+    column-strip seam and of a rows_per_block boundary.  extended (the shape sweep): both sides of EVERY column-strip seam, of the first and the last
+    rows_per_block boundary, of every image seam that lies inside one block (the first and the last such), and the first and last row of the last block."""
+    rpb, tiles_x, wt = op["rows_per_block"], op["tiles_x"], op["Wt"]
+    rows_total = B * tiles_x * Ht
+    spots = {(0, 0, 0), (B - 1, Ht - 1, Wd - 1)}
+
+    def at(row, last_col=False):             # flattened (image, column strip, row) index -> (image, row, first | last column of the strip)
+        strip, y = divmod(row, Ht)
+        b, tx = divmod(strip, tiles_x)
+        if 0 <= row < rows_total:
+            spots.add((b, y, min(Wd, (tx + 1) * wt) - 1 if last_col else tx * wt))
+    if tiles_x > 1:
+        spots |= {(B - 1, Ht // 2, wt - 1), (B - 1, Ht // 2, wt)}
+    for row in (rpb - 1, rpb):
+        at(row)
+    if extended:
+        for t in range(1, tiles_x):
+            spots |= {(0, Ht - 1, t * wt - 1), (0, Ht - 1, t * wt), (B - 1, 0, t * wt - 1), (B - 1, 0, t * wt)}
+        last0 = (rows_total - 1) // rpb * rpb
+        for row in (last0 - 1, last0, rows_total - 1):
+            at(row)
+            at(row, last_col=True)
+        seams = [b * tiles_x * Ht for b in range(1, B) if (b * tiles_x * Ht) % rpb != 0]         # image seams that fall inside a block
+        for r in seams[:1] + seams[-1:]:
+            for row in (r - 1, r):
+                at(row)
+                at(row, last_col=True)
+    return sorted(spots)
+
+
+def impulse_ops(st, extended=False):
+    """[(op index, op)] of the weight gradients that get impulses: the 3x3 one with the widest map; extended: one of every (kernel size, map, plan) the step has."""
+    wg = [(k, op) for k, op in enumerate(st.ops) if op["kind"] == "wgrad" and not op["cat"]]
+    if not extended:
+        return [max((ko for ko in wg if ko[1]["ks"] == 3), key=lambda ko: st.net["tensors"][ko[1]["x"]["t"]][1])]
+    seen = {}
+    for k, op in wg:
+        seen.setdefault((op["ks"], tuple(st.net["tensors"][op["x"]["t"]][:2]), op["rows_per_block"], op["Sr"]), (k, op))
+    return list(seen.values())
+
+
+def integer_probes(st, tag, extended=False, which=None):
+    """The body of the integer-probe test for a built Step: returns (convolution problems, weight gradients, impulses, differences).  which: a predicate
+    over ops -- only those are probed, and no impulses are run."""
     import torch.nn.functional as F
-    tag, prec, B, H, W = cfg
-    t0 = time.time()
-    st = Step(golden, gpu, prec, B, H, W)
-    conv_max, wgrad_max = TL.integer_limits(B, H, W)
-    assert conv_max < 2 ** 16 and wgrad_max < 2 ** 24
+    B = st.B
     layers = sorted({p["layer"] for op in st.ops if op["kind"] == "conv" for p in op["problems"]})
     for i, name in enumerate(layers):
         st.eng.p[name + ".weight"].copy_(TL.integer_operand(tuple(st.eng.p[name + ".weight"].shape), 1000 + i).float())
         if name + ".bias" in st.eng.p:
             st.eng.p[name + ".bias"].copy_(TL.integer_operand(tuple(st.eng.p[name + ".bias"].shape), 2000 + i).float())
     torch.cuda.synchronize()
+    conv_max, wgrad_max = TL.integer_limits(B, st.net["H"], st.net["W"])
     kpack = next(k for k, op in enumerate(st.ops) if op["kind"] == "pack")
     st.run(kpack, kpack + 1)
     F_ = st.frames
@@ -349,9 +385,11 @@ def test_integer_probes_of_every_convolution_and_weight_gradient_are_bit_exact(g
         st.write(tid, v)
         planted[tid] = v
         return v
-    nconv = nwg = 0
+    nconv = nwg = nimp = 0
     bad = []
     for k, op in enumerate(st.ops):
+        if which is not None and not which(op):
+            continue
         if op["kind"] == "conv":
             probs = [p for p in op["problems"] if p["act"] == 0]
             if not probs:
@@ -397,31 +435,41 @@ def test_integer_probes_of_every_convolution_and_weight_gradient_are_bit_exact(g
             if not torch.equal(got, ref):
                 d = (got - ref).abs()
                 bad.append("op %d %s wgrad %s: %d elements differ, first at (co, ci, ky, kx) %s" % (k, op["kernels"], op["layer"], int((d > 0).sum()), tuple(int(i) for i in torch.nonzero(d)[0])))
-    # impulses on the 3x3 weight gradient with the widest map
-    k, op = max(((k, op) for k, op in enumerate(st.ops) if op["kind"] == "wgrad" and op["ks"] == 3), key=lambda ko: st.net["tensors"][ko[1]["x"]["t"]][1])
-    Ht, Wt_, plane = st.net["tensors"][op["dy"]["t"]]
-    x = plant(op["x"]["t"], op["cin"], 77)
-    rpb, tiles_x, wt = op["rows_per_block"], op["tiles_x"], op["Wt"]
-    spots = {(0, 0, 0), (B - 1, Ht - 1, Wt_ - 1)}
-    if tiles_x > 1:
-        spots |= {(B - 1, Ht // 2, wt - 1), (B - 1, Ht // 2, wt)}
-    for row in (rpb - 1, rpb):                                   # flattened (image, column strip, row) index -> (image, row, first column of the strip)
-        strip, y = divmod(row, Ht)
-        b, tx = divmod(strip, tiles_x)
-        if b < B:
-            spots.add((b, y, tx * wt))
-    xp = F.pad(x[:, :op["cin"]], (1, 1, 1, 1))
-    for n, (b, y, xc) in enumerate(sorted(spots)):
-        dy = torch.zeros((B, plane, Ht, Wt_), dtype=torch.float64)
-        co = (7 * n + 3) % op["cout"]
-        dy[b, co, y, xc] = 1.0
-        st.write(op["dy"]["t"], dy)
-        st.run(k, k + 1)
-        ref = torch.zeros((op["cout"], op["cin"], 3, 3), dtype=torch.float64)
-        ref[co] = xp[b, :, y:y + 3, xc:xc + 3]
-        if not torch.equal(st.grad(op["layer"] + ".weight"), ref):
-            bad.append("impulse at (image %d, row %d, col %d) of %s: dW is not the shifted x patch" % (b, y, xc, op["layer"]))
-    print("\nINTEGER PROBES %s: %d convolution problems, %d weight gradients, %d impulses; %d differ; %.0f s" % (tag, nconv, nwg, len(spots), len(bad), time.time() - t0))
+    chosen = [] if which is not None else impulse_ops(st, extended)
+    for k, op in chosen:
+        Ht, Wt_, plane = st.net["tensors"][op["dy"]["t"]]
+        pad = op["ks"] // 2
+        x = plant(op["x"]["t"], op["cin"], 77)
+        xp = F.pad(x[:, :op["cin"]], (pad, pad, pad, pad))
+        for n, (b, y, xc) in enumerate(impulse_spots(op, B, Ht, Wt_, extended)):
+            dy = torch.zeros((B, plane, Ht, Wt_), dtype=torch.float64)
+            co = (7 * n + 3) % op["cout"]
+            dy[b, co, y, xc] = 1.0
+            st.write(op["dy"]["t"], dy)
+            st.run(k, k + 1)
+            ref = torch.zeros((op["cout"], op["cin"], op["ks"], op["ks"]), dtype=torch.float64)
+            ref[co] = xp[b, :, y:y + op["ks"], xc:xc + op["ks"]]
+            nimp += 1
+            if not torch.equal(st.grad(op["layer"] + ".weight"), ref):
+                bad.append("impulse at (image %d, row %d, col %d) of %s: dW is not the shifted x patch" % (b, y, xc, op["layer"]))
+    return nconv, nwg, nimp, bad
+
+
+@pytest.mark.parametrize("cfg", CONFIGS, ids=[c[0] for c in CONFIGS])
+def test_integer_probes_of_every_convolution_and_weight_gradient_are_bit_exact(gpu, golden, cfg):
+    """Single ops on planted integer operands in [-3, 3] (weights written into the flat parameter buffer, then the pack op): every hi / lo split is exact and
+    every fp32 partial sum is an integer below 2^24 (test_train_layer_reference.py checks the limits at these shapes), so whatever the summation order, forward,
+    data gradient (with and without residual) and weight gradient must equal F.conv2d / conv2d_input / the weight-gradient sum in float64 BIT FOR BIT: a single
+    missing pixel, strip seam, tile edge or slice shows.  Every convolution problem without an activation (first, middle and last frame) and every
+    weight-gradient op (whole); then impulses: one non-zero dy element at a corner, at the last pixel of the last image, on both sides of a column-strip
+    seam and of a rows_per_block boundary -- dW must be the shifted x patch.  (The body is integer_probes: tests/test_gpu_train_layer_shapes.py runs it too.)"""
+    tag, prec, B, H, W = cfg
+    t0 = time.time()
+    st = Step(golden, gpu, prec, B, H, W)
+    conv_max, wgrad_max = TL.integer_limits(B, H, W)
+    assert conv_max < 2 ** 16 and wgrad_max < 2 ** 24
+    nconv, nwg, nimp, bad = integer_probes(st, tag)
+    print("\nINTEGER PROBES %s: %d convolution problems, %d weight gradients, %d impulses; %d differ; %.0f s" % (tag, nconv, nwg, nimp, len(bad), time.time() - t0))
     assert nconv >= 38 and nwg == sum(op["kind"] == "wgrad" for op in st.ops)
     assert not bad, "\n".join(bad)
 

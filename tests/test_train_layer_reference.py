@@ -1,6 +1,8 @@
 """tests/train_layer_reference.py on the CPU (no GPU): the reference accepts a float32 emulation of each op of the planes training step evaluated
 in two summation orders, and rejects injected faults, at the stage-level map sizes of every configuration of tests/test_gpu_train_layers.py
-(28x28 at B = 32 -- reduced to 4 frames for the element-wise ops --, 13x17 at B = 1, 9x5 at B = 3) and at the ragged quarter-size maps for the pools.
+(28x28 at B = 32 -- reduced to 4 frames for the element-wise ops --, 13x17 at B = 1, 9x5 at B = 3) and at the ragged quarter-size maps for the pools; and at
+the maps of the shape sweep (tests/train_plan_cases.py::SWEEP) that bring a summation chain those three do not have: one slice, one row per block, a single
+partial reduction block (NEW_CHAINS).  The transcriptions of plan_wgrad / red_blocks live in tests/train_plan_cases.py.
 
 Which check catches which fault (none may go uncaught):
   per-element allowance of test_gpu_train_layers.py: a shifted tap, a dropped halo row / column at an image edge (convolutions), the missing lo * hi
@@ -24,11 +26,32 @@ import torch.nn.functional as F
 
 import layer_reference as LR
 import train_layer_reference as TL
+import train_plan_cases as TP
+from train_plan_cases import NUM_CUS, _red_chain, _wgrad_plan          # the transcriptions of red_blocks / plan_wgrad (moved there: one copy)
 
 PRECS = ("bf16x3", "fp32")
 STAGE_MAPS = [(name, B, H // 8, W // 8) for name, B, H, W in TL.SHAPES]
 QUARTER_MAPS = [(name, B, H // 4, W // 4) for name, B, H, W in TL.SHAPES]
-NUM_CUS = 256
+
+
+def _new_chains():
+    """The sweep shapes (tests/train_plan_cases.py::SWEEP) whose stage maps bring a summation chain SHAPES does not have: the first with one slice
+    (Sr == 1), with one row per block (rows_per_block == 1, Sr > 1) and with a single partial reduction block (nblk == 1, npix < ppb)."""
+    want = {"Sr == 1": lambda w, r: w["Sr"] == 1, "rows_per_block == 1": lambda w, r: w["rows_per_block"] == 1 and w["Sr"] > 1,
+            "nblk == 1": lambda w, r: r["nblk"] == 1 and r["npix"] < r["ppb"]}
+    out = {}
+    for name, B, H, W, _ in TP.SWEEP:
+        w, r = TP.wgrad_plan(B, H // 8, W // 8, 64, 64, 3), TP.red_plan(B * (H // 8) * (W // 8), 128)
+        for k, pred in want.items():
+            if k not in out and name not in TP.FILTERED and pred(w, r):
+                out[k] = (name, B, H, W)
+    assert set(out) == set(want), sorted(set(want) - set(out))
+    return sorted(set(out.values()))
+
+
+NEW_CHAINS = _new_chains()
+STAGE_MAPS_SWEEP = [(name, B, H // 8, W // 8) for name, B, H, W in NEW_CHAINS]
+QUARTER_MAPS_SWEEP = [(name, B, H // 4, W // 4) for name, B, H, W in NEW_CHAINS]
 
 
 def _r(shape, seed, scale=1.0, shift=0.0):
@@ -46,26 +69,6 @@ def _f(t):
 def _stored(v32, prec):
     """what a planes tensor holds after storing the float32 value v32"""
     return TL.split_act(v32.double(), prec).v
-
-
-def _red_chain(npix, C):
-    """trainx.hip::red_blocks: pixels per thread of the channel reductions"""
-    PL = 256 // (C // 8)
-    per = max(-(-npix // (4 * NUM_CUS)), 8 * PL)
-    per = -(-per // PL) * PL
-    return dict(C=C, ppb=per)
-
-
-def _wgrad_plan(B, H, W, cin_my, cout, ks):
-    """trainx_wgrad.h::plan_wgrad"""
-    seg = 32 - 2 * (ks // 2)
-    tiles_x = -(-W // seg)
-    Wt = -(-W // tiles_x)
-    pairs = -(-cout // 64) * -(-cin_my // 64)
-    rows_total = B * tiles_x * H
-    Sr = max(1, min(rows_total, -(-NUM_CUS // pairs)))
-    rpb = -(-rows_total // Sr)
-    return dict(tiles_x=tiles_x, Wt=Wt, rows_per_block=rpb, Sr=-(-rows_total // rpb))
 
 
 # ---- convolutions ---------------------------------------------------------------------------------------
@@ -176,7 +179,7 @@ def _emu_bn_stats(x, gamma, beta, rm, rv, m, order, biased=False):
 
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("shape", STAGE_MAPS, ids=[s[0] for s in STAGE_MAPS])
+@pytest.mark.parametrize("shape", STAGE_MAPS + STAGE_MAPS_SWEEP, ids=[s[0] for s in STAGE_MAPS + STAGE_MAPS_SWEEP])
 def test_batchnorm_reference_accepts_fp32_orders_and_rejects_faults(shape, prec):
     _, B, h, w_ = shape
     Cn = 128
@@ -239,7 +242,7 @@ def test_batchnorm_reference_accepts_fp32_orders_and_rejects_faults(shape, prec)
         assert _worst(vec["k2"], *sums["k2"]) > 1 and _worst(vec["k3"], *sums["k3"]) > 1, "k2 / k3 divided by n - 1"
         if act:
             good, _, _ = emu(0)
-            _, dx, _ = emu(0, flip=777)
+            _, dx, _ = emu(0, flip=777 % min(mask.numel(), 4 * Cn * h * w_))
             r, d, _, _ = TL.bn_bwd_apply_ref(x[:4], dy[:4], mask[:4], mean, istd, good["k1"], good["k2"], good["k3"], act)
             assert _worst(dx, r, LR.allowance(r, d, TL.fmt_of(prec))) > 1, "mask from the wrong tensor in one element"
             assert TL.mask_disagreements(dx, x[:4], dy[:4], mask[:4], mean, istd, good["k1"], good["k2"], good["k3"], act, TL.fmt_of(prec)) == 1
@@ -247,7 +250,7 @@ def test_batchnorm_reference_accepts_fp32_orders_and_rejects_faults(shape, prec)
 
 # ---- heads, pools, add ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("shape", STAGE_MAPS, ids=[s[0] for s in STAGE_MAPS])
+@pytest.mark.parametrize("shape", STAGE_MAPS + STAGE_MAPS_SWEEP, ids=[s[0] for s in STAGE_MAPS + STAGE_MAPS_SWEEP])
 def test_heads_reference_accepts_fp32_and_rejects_faults(shape, prec):
     _, B, h, w_ = shape
     dcat = TL.split_act(_r((B, TL.CAT_PLANE, h, w_), 21, 1e-4), prec).v
@@ -280,7 +283,7 @@ def test_heads_reference_accepts_fp32_and_rejects_faults(shape, prec):
 
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("shape", QUARTER_MAPS + STAGE_MAPS, ids=["quarter_" + s[0] for s in QUARTER_MAPS] + ["stage_" + s[0] for s in STAGE_MAPS])
+@pytest.mark.parametrize("shape", QUARTER_MAPS + STAGE_MAPS + QUARTER_MAPS_SWEEP, ids=["quarter_" + s[0] for s in QUARTER_MAPS] + ["stage_" + s[0] for s in STAGE_MAPS] + ["quarter_" + s[0] for s in QUARTER_MAPS_SWEEP])
 def test_pool_and_add_references_accept_fp32_and_reject_faults(shape, prec):
     _, B, H, W = shape
     B = min(B, 2)
@@ -309,7 +312,9 @@ def test_pool_and_add_references_accept_fp32_and_reject_faults(shape, prec):
 def _emu_wgrad(op, prec, x, dy, order, drop=None, lo_hi=True, shift_tap=False):
     """Blocks of rows_per_block rows of the flattened (image, column strip, row) space summed in float32, then the slices in float32 (order 1:
     slices in reverse).  drop: ("row" | "col" | "seam", ...) leaves out the x halo row below each image's last row pair / the x column right of the
-    last column / the x column across the column-strip seam, as a kernel that does not fetch it would."""
+    last column / the x column across the column-strip seam, as a kernel that does not fetch it would.  The plan mutants of tests/test_train_plan_cases.py:
+    "strip_col" leaves out dy column Wt - 1 of every full-width strip, "reprime" the first row of a segment a block enters after a column seam, "last_block"
+    the short last block, "last_slice" slice Sr - 1."""
     cout, cin, ks, Wt, tiles_x, rpb = op["cout"], op["cin"], op["ks"], op["Wt"], op["tiles_x"], op["rows_per_block"]
     B, _, H, W = dy.v.shape
     pad = ks // 2
@@ -320,10 +325,14 @@ def _emu_wgrad(op, prec, x, dy, order, drop=None, lo_hi=True, shift_tap=False):
     slices = []
     for s0 in range(0, len(rows), rpb):
         acc = torch.zeros((cout, cin, ks, ks), dtype=torch.float32)
-        for b, t, y in rows[s0:s0 + rpb]:
+        for i, (b, t, y) in enumerate(rows[s0:s0 + rpb]):
             x0, x1 = t * Wt, min(W, (t + 1) * Wt)
+            if drop == "reprime" and i > 0 and y == 0:
+                continue
             for d_, x_ in parts:
-                drow = _f(d_[b, :, y, x0:x1])                                             # [cout, px]
+                drow = _f(d_[b, :, y, x0:x1]).clone()                                     # [cout, px]
+                if drop == "strip_col" and x1 - x0 == 32 - 2 * pad:
+                    drow[:, -1] = 0
                 for ky in range(ks):
                     yy = y + ky - pad
                     if not 0 <= yy < H or (drop == "row" and y == H - 2 and yy == H - 1):
@@ -340,6 +349,8 @@ def _emu_wgrad(op, prec, x, dy, order, drop=None, lo_hi=True, shift_tap=False):
                         xs[:, a0 - lo:a1 - lo] = seg
                         acc[:, :, ky, (kx + 1) % ks if shift_tap else kx] += drow @ xs.t()
         slices.append(acc)
+    if (drop == "last_block" and len(rows) % rpb) or drop == "last_slice":
+        slices[-1] = torch.zeros_like(slices[-1])
     if order:
         slices = slices[::-1]
     tot = torch.zeros_like(slices[0])
@@ -377,6 +388,22 @@ def test_weight_gradient_reference_accepts_fp32_orders_and_rejects_faults(shape,
     for name, kw in faults.items():
         if name != "lo * hi left out":
             assert not torch.equal(_emu_wgrad(op, prec, x, dy, 0, **kw), exact), name
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("shape", STAGE_MAPS_SWEEP, ids=[s[0] for s in STAGE_MAPS_SWEEP])
+def test_weight_gradient_allowance_at_the_sweeps_new_chain_lengths(shape, prec):
+    """One slice (Sr == 1: the reduce kernel adds nothing, depth = Wt (3 | 1) + 1 + 16) and one row per block (rows_per_block == 1) on one-row stage maps:
+    both summation orders pass, a shifted tap and (bf16x3) the missing lo * hi term do not.  (A one-row map has no halo row or column to drop.)"""
+    _, B, h, w_ = shape
+    op, x, dy = _wgrad_case(prec, B, h, w_, 53)
+    assert op["rows_per_block"] == 1 and TL.wgrad_depth(op, prec) == op["Wt"] * (3 if prec == "bf16x3" else 1) + 1 + 16
+    r, a = TL.wgrad_ref(op, prec, x, dy)
+    for order in (0, 1):
+        assert 0 < _worst(_emu_wgrad(op, prec, x, dy, order), r, a) <= 1
+    assert _worst(_emu_wgrad(op, prec, x, dy, 0, shift_tap=True), r, a) > 1
+    if prec == "bf16x3":
+        assert _worst(_emu_wgrad(op, prec, x, dy, 0, lo_hi=False), r, a) > 1
 
 
 def test_at_the_bench_shape_a_dropped_row_is_seen_by_the_allowance_and_a_single_dropped_pixel_needs_the_integer_probe():
@@ -424,7 +451,7 @@ def test_at_the_bench_shape_stage_level_a_missing_lo_hi_term_is_left_to_the_othe
 
 
 # ---- integer probes: a condition on the inputs ----------------------------------------------------------
-@pytest.mark.parametrize("shape", TL.SHAPES, ids=[s[0] for s in TL.SHAPES])
+@pytest.mark.parametrize("shape", TL.SHAPES + NEW_CHAINS, ids=[s[0] for s in TL.SHAPES + NEW_CHAINS])
 def test_integer_probe_operands_are_exact_at_every_configured_shape(shape):
     _, B, H, W = shape
     conv_max, wgrad_max = TL.integer_limits(B, H, W)
