@@ -3,7 +3,7 @@
 // un-normalised network input at one pixel -- and / or its 2D location by the ground truth.  The pre-processed [B,1,S,S] tensor need not
 // exist (pn_rtpose_forward_frames never writes it): a pixel is re-derived from the raw frame with pn_preprocess's arithmetic
 // (preproc_pixel.h), then un-normalised as the script does (:183-185, `img *= std; img += mean` on float32), and back-projected in
-// float64 in the order of group_readout_kernel (parse_paf.hip).
+// float64 in the order of joint_readout (parse_device.h).
 #include "pn_internal.h"
 #include "preproc_pixel.h"
 

@@ -1,5 +1,6 @@
-// Scratch layouts and launch entries shared by the two pose-parse translation units: parse_paf.hip (the default path: x8 up-sampling,
-// ten sample points, and the launchers of every path) and parse_generic.hip (any supported up-sampling factor / sample count / NMS option).
+// Scratch layouts, capacities, argument checks and the one cross-file launcher of the pose-parse translation units: parse_paf.hip (the
+// bounded batch path), parse_unbounded.hip (the second pass and pn_nms_peaks), parse_peaks.hip (the NMS kernels of both), parse_utils.hip.
+// The arithmetic they share is parse_device.h.
 #pragma once
 #include "pn_internal.h"
 
@@ -44,8 +45,8 @@ struct BigWs {                       // the unbounded second pass: every list in
     double *o_j2d, *o_j3d, *o_conf;  // [P][J][2], [P][J][3], [P][J]
 };
 
-// ---- parse_generic.hip: the launches that stand in for peaks_refine_kernel / limb_match_kernel / big_peaks_kernel / big_limb_kernel whenever an
-// argument differs from the default (x8, ten points, refined centres, no filter).  None allocates or synchronises.
+// ---- the arguments every path accepts: up-sampling factor f in {1, 2, 4, 8, 16} (powers of two: the bicubic phases are exact in float32), 2..32
+// sample points per limb.  The workload's own (x8, ten points, refined centres, no filter) get the specialised kernel instantiations.
 #define PN_PARSE_FACTORS_TEXT "1, 2, 4, 8, 16"
 #define PN_PARSE_MIN_PTS 2
 #define PN_PARSE_MAX_PTS 32
@@ -53,9 +54,21 @@ struct BigWs {                       // the unbounded second pass: every list in
 inline int pn_parse_factor_log2(int f) { return f == 1 ? 0 : f == 2 ? 1 : f == 4 ? 2 : f == 8 ? 3 : f == 16 ? 4 : -1; }
 inline bool pn_parse_pts_ok(int n) { return n >= PN_PARSE_MIN_PTS && n <= PN_PARSE_MAX_PTS; }
 
+// the checks of pn_parse_paf(_wire) and pn_parse_paf_unbounded (`who`), PN_OK or the error set on ctx
+inline int pn_parse_check_map(pn_ctx *ctx, const char *who, int h, int w) {
+    if (h * w > MAX_MAP || h < 1 || w < 1) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: map %dx%d exceeds %d cells", who, h, w, MAX_MAP);
+    return PN_OK;
+}
+inline int pn_parse_check_cfg(pn_ctx *ctx, const char *who, const pn_parse_cfg *cfg) {
+    if (pn_parse_factor_log2(cfg->downsample) < 0 || !pn_parse_pts_ok(cfg->num_intermed_pts))
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: downsample %d / num_intermed_pts %d: supported are downsample in {" PN_PARSE_FACTORS_TEXT "} and %d..%d intermediate points",
+                            who, cfg->downsample, cfg->num_intermed_pts, PN_PARSE_MIN_PTS, PN_PARSE_MAX_PTS);
+    return PN_OK;
+}
+
 // where the peaks of map m of frame b go: count[m], x / y / s [m][cap], frame b `frame_stride` bytes further on; peaks past cap are counted only
 struct PnPeakOut { int *count; float *x, *y, *s; int cap; size_t frame_stride; };
-int pn_gen_launch_peaks(pn_ctx *ctx, hipStream_t s, const float *heat_dev, int n_maps, int B, int h, int w, int heat_c, float thresh, int f, int refine,
-                        int gauss, const PnPeakOut &out);
-int pn_gen_launch_limbs(pn_ctx *ctx, hipStream_t s, const float *paf_dev, int B, int h, int w, float thresh_paf, int f, int npts, ParseWs *ws);
-int pn_gen_launch_big_limbs(pn_ctx *ctx, hipStream_t s, const float *paf_dev, int h, int w, float thresh_paf, int f, int npts, const BigWs &W);
+// parse_peaks.hip: the NMS launch of every path -- peaks_refine_kernel for (x8, refined centres, no filter), gen_peaks_kernel for anything else.
+// Neither allocates nor synchronises.
+int pn_launch_peaks(pn_ctx *ctx, hipStream_t s, const float *heat_dev, int n_maps, int B, int h, int w, int heat_c, float thresh, int f, int refine,
+                    int gauss, const PnPeakOut &out);

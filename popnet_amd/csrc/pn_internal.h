@@ -16,7 +16,7 @@ struct pn_ctx {
     size_t parse_ws_bytes = 0;
     bool parse_ws_fixed = false;     // pn_parse_reserve: the scratch never moves again
     int parse_last_b = 0;            // batch size of the last pn_parse_paf / pn_parse_paf_wire on this context (0 = none; pn_parse_debug_connections)
-    void *parse_big = nullptr;       // workspace of the unbounded second pass (parse_paf.hip::BigHost), freed by pn_parse_big_free
+    void *parse_big = nullptr;       // workspace of the unbounded second pass (parse_unbounded.hip::BigHost), freed by pn_parse_big_free
     // scratch of the training kernels (flipped weights, split-reduction partials; train.hip), stream-ordered reuse
     void *train_ws = nullptr;
     size_t train_ws_bytes = 0;
@@ -83,7 +83,18 @@ inline uint16_t pn_f32_to_bf16(float f) {
     return (uint16_t)(u >> 16);
 }
 inline float pn_bf16_to_f32(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-void pn_parse_big_free(pn_ctx *ctx);     // parse_paf.hip
+void pn_parse_big_free(pn_ctx *ctx);     // parse_unbounded.hip
+
+// limb topology, host and device (util/util_functions.py:17-34 == tpm/lib/datasets/datasets_itop_rtpose.py:45-62): limb l joins joint
+// pn_limb_src(l) to joint pn_limb_dst(l)
+__host__ __device__ inline int pn_limb_src(int l) {
+    constexpr int t[PN_NUM_LIMBS] = {8, 9, 11, 8, 10, 12, 8, 1, 2, 4, 1, 3, 5, 1};
+    return t[l];
+}
+__host__ __device__ inline int pn_limb_dst(int l) {
+    constexpr int t[PN_NUM_LIMBS] = {9, 11, 13, 10, 12, 14, 1, 2, 4, 6, 3, 5, 7, 0};
+    return t[l];
+}
 int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)
 const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned *grid_x, unsigned *grid_y);     // train_yolo.hip: kernel label and grid of pn_conv2d_dgrad_strided
 

@@ -14,9 +14,6 @@
 #include <cmath>
 #include "pn_internal.h"
 
-__constant__ int t_limb_a[PN_NUM_LIMBS] = {8, 9, 11, 8, 10, 12, 8, 1, 2, 4, 1, 3, 5, 1};
-__constant__ int t_limb_b[PN_NUM_LIMBS] = {9, 11, 13, 10, 12, 14, 1, 2, 4, 6, 3, 5, 7, 0};
-
 template <typename T>
 __global__ void compose_depth_kernel(const T *__restrict__ fg_depth, const unsigned char *__restrict__ fg_mask, const int *__restrict__ n_src,
                                      const T *__restrict__ bg, int S, size_t HW, double depth_max, float *__restrict__ out) {
@@ -75,7 +72,7 @@ __global__ __launch_bounds__(256) void rasterize_kernel(const float *__restrict_
     for (int l = 0; l < PN_NUM_LIMBS; ++l) {
         double vx = 0.0, vy = 0.0, cnt = 0.0;
         for (int j = 0; j < P; ++j) {
-            const float *ca = kp + ((size_t)j * PN_NUM_JOINTS + t_limb_a[l]) * 2, *cb = kp + ((size_t)j * PN_NUM_JOINTS + t_limb_b[l]) * 2;
+            const float *ca = kp + ((size_t)j * PN_NUM_JOINTS + pn_limb_src(l)) * 2, *cb = kp + ((size_t)j * PN_NUM_JOINTS + pn_limb_dst(l)) * 2;
             if (!t_inb(ca, cfg.input_x, cfg.input_y) || !t_inb(cb, cfg.input_x, cfg.input_y)) continue;
             const double ax = (double)ca[0] / stride, ay = (double)ca[1] / stride, bx = (double)cb[0] / stride, by = (double)cb[1] / stride;
             const double lx = bx - ax, ly = by - ay;

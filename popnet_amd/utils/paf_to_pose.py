@@ -3,8 +3,8 @@
 Drop-in for tpm/lib/utils/paf_to_pose.py:354-377 (NMS :75-153, find_connected_joints :156-264,
 group_limbs_of_same_person :267-351): takes the HWC float32 network maps of ONE frame and returns
 ``(joint_list [N,5] float64, person_to_joint_assoc [P,J+2] float64)`` exactly as the reference
-does -- but the work happens in three HIP kernels (csrc/parse_paf.hip; csrc/parse_generic.hip for any
-MODEL.DOWNSAMPLE in {1, 2, 4, 8, 16} / TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS in 2..32 other than 8 / 10) instead of Python loops over
+does -- but the work happens in three HIP kernels (csrc/parse_peaks.hip, csrc/parse_paf.hip; literal instantiations
+for 8 / 10, the run-time ones for any other MODEL.DOWNSAMPLE in {1, 2, 4, 8, 16} / TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS in 2..32) instead of Python loops over
 scipy/cv2 calls.  For throughput use ``popnet_amd.pipeline.PoseEngine`` (whole batches stay on the
 device); this per-frame wrapper exists for API compatibility and parity tests.
 """

@@ -1,6 +1,6 @@
 """Hand-built edge-case maps for the part-affinity parse, a census of what they contain, and mutants of the oracle (no GPU).
 
-The parse kernels (popnet_amd/csrc/parse_paf.hip) promise bit-exact agreement with oracle/parse_paf.py.  The cases here put
+The parse kernels (popnet_amd/csrc/parse_*.hip) promise bit-exact agreement with oracle/parse_paf.py.  The cases here put
 that promise where random planted persons never go: corner patches, non-square and tiny maps, the largest map, the record
 capacities on both sides, bit-equal candidate scores, the 8-of-10 rule, the length penalty, negative heat in the read-out.
 

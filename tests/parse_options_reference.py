@@ -1,6 +1,6 @@
 """numpy restatement of the pose parse for every argument the reference accepts (tpm/lib/utils/paf_to_pose.py:75
 NMS(heatmaps, upsampFactor, bool_refine_center, bool_gaussian_filt); MODEL.DOWNSAMPLE and TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS in
-find_connected_joints :156-264).  What the generic HIP kernels (popnet_amd/csrc/parse_generic.hip) are written against, and itself pinned
+find_connected_joints :156-264).  What the HIP parse kernels' run-time instantiations and gen_peaks_kernel (popnet_amd/csrc/parse_device.h, parse_peaks.hip) are written against, and itself pinned
 by tests/golden/parse_options.npz -- the reference's own functions under the cv2.resize restatement and the installed scipy
 (tests/test_parse_options_reference.py).
 

@@ -1,10 +1,10 @@
-"""GPU: the part-affinity parse kernels (popnet_amd/csrc/parse_paf.hip) on the hand-built edge cases of tests/parse_cases.py,
+"""GPU: the part-affinity parse kernels (popnet_amd/csrc/parse_paf.hip, parse_unbounded.hip, parse_peaks.hip) on the hand-built edge cases of tests/parse_cases.py,
 stage by stage against oracle/parse_paf.py.  Every comparison is an equality: bit-exact agreement is the contract stated at
-the top of parse_paf.hip.
+the top of parse_device.h.
 
-  peaks        peak_x / peak_y / peak_score / peak_type == O.nms row for row -- through peaks_refine_kernel (batch), big_peaks_kernel
-               (unbounded pass) and pn_nms_peaks, the three copies of the peak code
-  connections  per limb the count, (i, j) and the float64 score == O.find_connected_joints, in order (limb_match_kernel, big_limb_kernel)
+  peaks        peak_x / peak_y / peak_score / peak_type == O.nms row for row -- through peaks_refine_kernel's two instantiations: <MAXP> (batch)
+               and the uncapped one (unbounded pass, pn_nms_peaks)
+  connections  per limb the count, (i, j) and the float64 score == O.find_connected_joints, in order (limb_match_kernel, limb_unbounded_kernel)
   persons      person_joint / person_count / person_score / joints_2d / joints_3d / part_conf == O.frame_to_records
                (group_readout_kernel, big_group_kernel).  person_score is compared for equality too: the kernels add in the
                oracle's order, (a + b) + c for a new row and row + (b + c) for an extension.

@@ -1,5 +1,5 @@
-"""GPU: NMS and the pose parse for every argument the reference accepts (popnet_amd/csrc/parse_generic.hip and the launchers in
-parse_paf.hip) against tests/golden/parse_options.npz -- the reference's own NMS / paf_to_pose on the hand-built cases of tests/parse_cases.py
+"""GPU: NMS and the pose parse for every argument the reference accepts (gen_peaks_kernel and pn_launch_peaks in
+popnet_amd/csrc/parse_peaks.hip, the run-time instantiations of the limb kernels) against tests/golden/parse_options.npz -- the reference's own NMS / paf_to_pose on the hand-built cases of tests/parse_cases.py
 (tests/golden/make_golden_parse_options.py).  Every comparison is an equality.
 
   NMS           all four columns for upsampFactor in {1, 2, 4, 8, 16} x refined / not x filtered / not, on 28x28, 20x36, 36x20, 9x13, 5x7 and 3x3
