@@ -514,6 +514,45 @@ int pn_build_prior_targets(pn_ctx *ctx, const double *boxes_dev, const float *kp
                            const int *n_persons_dev, int B, int Pmax, const pn_yolo_target_cfg *cfg, float *prior_map_dev,
                            float *mask_conf_dev, float *mask_coord_dev, float *weight_map_dev, void *hip_stream);
 
+/* ---- A2J training primitives (csrc/train_a2j.hip; the dilated convolutions in csrc/train.hip) ---------------------------------
+ * What A2J_model's train-mode forward / loss / backward / optimizer step (third_party_methods/A2J_experiments/train_a2j_mpaug_new.py)
+ * needs beyond the primitives above; fp32, asynchronous on the stream, fixed summation orders (a repeated call gives the same bits),
+ * no float atomics.
+ *   pn_conv2d_forward_dil / _dgrad_dil / _wgrad_dil   pn_conv2d_forward / _dgrad / _wgrad with the taps `dil` pixels apart
+ *                       (layer4.1 / layer4.2 conv2, resnet.py:112,145: kernel 3, padding = dilation = 2).  Accepted: ks == 3, stride 1,
+ *                       dil >= 1, 0 <= pad <= 2 dil, Ho = H + 2 pad - 2 dil >= 1; anything else is PN_ERR_INVALID before any launch.
+ *                       dil == 1 IS the undilated entry (same bits).  dil > 1: the matrix-core implicit GEMM of the generic path
+ *                       (v_mfma_f32_16x16x4_f32, k = (ci, ky, kx) in order) gathering at iy0 + ky dil; the data gradient is that forward
+ *                       on the rotated, transposed weights with padding 2 dil - pad; the weight gradient sums pixel slices in slice order.
+ *   pn_a2j_loss         A2J_loss.forward (anchor.py:84-154) and its gradient on the three raw head maps where the last convolutions left
+ *                       them: cls / dep [B, A P, h, w], reg [B, A P 2, h, w] NCHW, channel a P + p (reg: (a P + p) 2 + c), anchor
+ *                       k = (x h + y) A + a of anchors_dev [K, 2] (the array pn_a2j_vote takes).  h == 0: the reference's own layout
+ *                       [B, K, P] / [B, K, P, 2] with K = w and A = 1.  labels_dev [B, P, 3]: two columns in the anchors' coordinate order, then z.
+ *                       Per crop and joint: w_k = softmax_k(cls) (max-subtracted); Cls = mean over (P, 2) of smooth-L1 (beta 1) of
+ *                       |gt - sum_k w_k anchor_k|; Reg = spatial_factor x the same with anchor_k + reg_k, plus mean_P |gt_z - sum_k w_k dep_k|
+ *                       (the PLAIN L1: anchor.py:151 adds regression_diff_depth.mean(), not its smooth form).  Both are means over the batch.
+ *                       terms_dev [2] = (Cls, Reg).  dcls / dreg / ddep (all three or all NULL; the inputs' layout) receive
+ *                       d (s_cls Cls + s_reg Reg) / d input with (s_cls, s_reg) read from scale_dev [2] ON THE DEVICE (an autograd backward
+ *                       passes its incoming gradients without a host synchronisation); d|x|/dx = 0 at 0, as torch.abs.  One workgroup per
+ *                       (crop, joint), lanes along x; the per-(crop, joint) partials are summed by a second launch in a fixed order.
+ *   pn_adam             torch.optim.Adam(betas, eps, weight_decay) on a flat buffer, step t >= 1 counted by the caller:
+ *                       g = grad_scale g + wd p; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g;
+ *                       p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps), the hyperparameters as the doubles torch holds them, the element
+                       arithmetic in double, p / m / v rounded to float once each.  Any n; 16-byte accesses only when all four buffers are
+ *                       16-byte aligned, and then only on the first n - n % 4 elements.  Marks the context's cached weight packs stale, as
+ *                       pn_sgd_nesterov does. */
+int pn_conv2d_forward_dil(pn_ctx *ctx, const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int N, int Cin,
+                          int H, int W, int Cout, int ks, int stride, int pad, int dil, int accumulate, void *hip_stream);
+int pn_conv2d_dgrad_dil(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int H, int W, int Cout,
+                        int ks, int pad, int dil, int accumulate, void *hip_stream);
+int pn_conv2d_wgrad_dil(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float *dw_dev, float *dbias_dev, int N, int Cin, int H,
+                        int W, int Cout, int ks, int stride, int pad, int dil, void *hip_stream);
+int pn_a2j_loss(pn_ctx *ctx, const float *cls_dev, const float *reg_dev, const float *dep_dev, int B, int h, int w, int A, int P,
+                const float *anchors_dev, const float *labels_dev, float spatial_factor, const float *scale_dev, float *terms_dev,
+                float *dcls_dev, float *dreg_dev, float *ddep_dev, void *hip_stream);
+int pn_adam(pn_ctx *ctx, float *param_dev, const float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, size_t n, double lr,
+            double beta1, double beta2, double eps, double weight_decay, int t, double grad_scale, void *hip_stream);
+
 /* ---- training step on NHWC [hi | lo] bf16 planes (round 6; csrc/trainx.hip) -------------------------------------------------
  * One object runs forward + loss + backward of rtpose_light3d(15, 14, 2, input_dim = 1) in train mode for ONE batch shape:
  * the per-batch body of tpm/train_rtpose_light3d_kdh3d_mpaug.py:160-180 (CR) up to (not including) optimizer.step(), i.e.

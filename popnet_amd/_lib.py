@@ -160,6 +160,11 @@ _SIGNATURES = {
     "pn_maxpool_forward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "pn_maxpool_backward": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "pn_yolo_loss": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 4),
+    "pn_conv2d_forward_dil": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
+    "pn_conv2d_dgrad_dil": (_i, [_vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
+    "pn_conv2d_wgrad_dil": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
+    "pn_a2j_loss": (_i, [_vp, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _f] + [_vp] * 6),
+    "pn_adam": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _d, _d, _d, _d, _d, _i, _d, _vp]),
     "pn_yolo_target_cfg_default": (None, [C.POINTER(YoloTargetCfg)]),
     "pn_build_prior_targets": (_i, [_vp] * 6 + [_i, _i, C.POINTER(YoloTargetCfg)] + [_vp] * 5),
     "pn_trainer_create": (_vp, [_vp]),

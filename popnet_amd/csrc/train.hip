@@ -858,6 +858,81 @@ int pn_conv2d_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float 
     return PN_OK;
 }
 
+// ---- dilated 3x3 convolutions (A2J_model's layer4.1 / layer4.2 conv2; the contract is in popnet_hip.h next to pn_a2j_loss) --------------
+// The gather kernels with the taps `dil` apart: tconv_fwd_kernel<3, 0, true> (forward; on the rotated pack with padding 2 dil - pad, the data
+// gradient) and tconv_wgrad_kernel<3, true>, with the grids, slices and reductions of the undilated generic path.  dil == 1 IS the undilated entry.
+static int t_dil_desc(pn_ctx *ctx, TConv *c, const char *who, int N, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int dil, int accumulate) {
+    if (N < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || ks != 3 || stride != 1 || dil < 1 || pad < 0 || pad > 2 * dil)
+        return pn_set_error(ctx, PN_ERR_INVALID, "%s: bad arguments (kernel 3, stride 1, dil >= 1, 0 <= pad <= 2 dil)", who);
+    c->N = N; c->Cin = Cin; c->H = H; c->W = W; c->Cout = Cout; c->stride = 1; c->pad = pad; c->accumulate = accumulate; c->dil = dil;
+    c->Ho = H + 2 * pad - 2 * dil;
+    c->Wo = W + 2 * pad - 2 * dil;
+    c->Kdim = Cin * 9;
+    const long P = (long)N * c->Ho * c->Wo;
+    if (c->Ho < 1 || c->Wo < 1 || P > 0x7fffffffL || (long)Cin * H * W > 0x7fffffffL || (long)Cout * c->Ho * c->Wo > 0x7fffffffL)
+        return pn_set_error(ctx, PN_ERR_INVALID, "%s: size out of range", who);
+    c->P = (int)P;
+    return PN_OK;
+}
+
+int pn_conv2d_forward_dil(pn_ctx *ctx, const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int N, int Cin, int H, int W,
+                          int Cout, int ks, int stride, int pad, int dil, int accumulate, void *hip_stream) {
+    T_CTX_CHECK("pn_conv2d_forward_dil")
+    if (!x_dev || !w_dev || !y_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_forward_dil: null tensor");
+    TConv c;
+    c.x = x_dev; c.w = w_dev; c.bias = bias_dev; c.y = y_dev;
+    if (int rc = t_dil_desc(ctx, &c, "pn_conv2d_forward_dil", N, Cin, H, W, Cout, ks, stride, pad, dil, accumulate)) return rc;
+    if (dil == 1) return pn_conv2d_forward(ctx, x_dev, w_dev, bias_dev, y_dev, N, Cin, H, W, Cout, ks, stride, pad, accumulate, hip_stream);
+    const dim3 grid((unsigned)(((long)c.P + 127) / 128), (unsigned)((Cout + 63) / 64));
+    hipLaunchKernelGGL((tconv_fwd_kernel<3, 0, true>), grid, dim3(256), 0, (hipStream_t)hip_stream, c);
+    PN_HIP_CHECK(ctx, hipGetLastError());
+    return PN_OK;
+}
+
+int pn_conv2d_dgrad_dil(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int H, int W, int Cout, int ks, int pad,
+                        int dil, int accumulate, void *hip_stream) {
+    T_CTX_CHECK("pn_conv2d_dgrad_dil")
+    if (!dy_dev || !w_dev || !dx_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_dgrad_dil: null tensor");
+    TConv f;        // the forward convolution this is the gradient of: range checks and the shape of dy
+    if (int rc = t_dil_desc(ctx, &f, "pn_conv2d_dgrad_dil", N, Cin, H, W, Cout, ks, 1, pad, dil, accumulate)) return rc;
+    if (dil == 1) return pn_conv2d_dgrad(ctx, dy_dev, w_dev, dx_dev, N, Cin, H, W, Cout, ks, pad, accumulate, hip_stream);
+    const size_t wn = (size_t)Cout * Cin * 9;
+    void *ws = nullptr;
+    if (int rc = t_ws(ctx, wn * sizeof(float), &ws)) return rc;
+    hipLaunchKernelGGL(wflip_kernel, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, w_dev, (float *)ws, Cout, Cin, 3);
+    // dX = conv(dY [N, Cout, Ho, Wo], Wt [Cin, Cout, 3, 3], padding 2 dil - pad, the same dilation): Ho + 2 (2 dil - pad) - 2 dil = H
+    return pn_conv2d_forward_dil(ctx, dy_dev, (const float *)ws, nullptr, dx_dev, N, Cout, f.Ho, f.Wo, Cin, 3, 1, 2 * dil - pad, dil, accumulate, hip_stream);
+}
+
+int pn_conv2d_wgrad_dil(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float *dw_dev, float *dbias_dev, int N, int Cin, int H, int W, int Cout,
+                        int ks, int stride, int pad, int dil, void *hip_stream) {
+    T_CTX_CHECK("pn_conv2d_wgrad_dil")
+    if (!x_dev || !dy_dev || !dw_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_wgrad_dil: null tensor");
+    TConv c;
+    c.x = x_dev; c.w = nullptr; c.bias = nullptr; c.y = (float *)dy_dev;
+    if (int rc = t_dil_desc(ctx, &c, "pn_conv2d_wgrad_dil", N, Cin, H, W, Cout, ks, stride, pad, dil, 0)) return rc;
+    if (dil == 1) return pn_conv2d_wgrad(ctx, x_dev, dy_dev, dw_dev, dbias_dev, N, Cin, H, W, Cout, ks, stride, pad, hip_stream);
+    // pn_conv2d_wgrad's generic path: pixel slices, partial sums reduced in slice order, the bias gradient's partials behind them
+    long slices, pps;
+    t_wgrad_pixel_slices(c.P, c.Kdim, Cout, &slices, &pps);
+    const int csl = t_slices(c.P, Cout);
+    const size_t wn = (size_t)Cout * c.Kdim;
+    const size_t part_off = (wn * (size_t)slices * sizeof(float) + 15) & ~(size_t)15;
+    void *ws = nullptr;
+    if (int rc = t_ws(ctx, part_off + 16 + (size_t)Cout * csl * 2 * sizeof(double), &ws)) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const dim3 grid((unsigned)((c.Kdim + 63) / 64), (unsigned)((Cout + 63) / 64), (unsigned)slices);
+    hipLaunchKernelGGL((tconv_wgrad_kernel<3, true>), grid, dim3(256), 0, s, c, (float *)ws, (int)pps);
+    t_wgrad_reduce(s, (const float *)ws, dw_dev, wn, (int)slices);
+    if (dbias_dev) {
+        double *part = (double *)((char *)ws + part_off);
+        t_chan_reduce<2>(s, nullptr, dy_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, Cout, c.Ho * c.Wo, csl, part);
+        hipLaunchKernelGGL(sums_finish_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(64), 0, s, (const double *)part, Cout, csl, dbias_dev, nullptr, nullptr);
+    }
+    PN_HIP_CHECK(ctx, hipGetLastError());
+    return PN_OK;
+}
+
 }   // extern "C"
 // ---- the planes training engine's stem (trainx.hip; internal, not part of the C ABI) --------------------------------------------------
 // model0.conv1 (rtpose_light3d.py:144: 7x7 / 2, Cin = 1) with its output / its output gradient as a planes tensor (TConv::pl): the kernels,

@@ -24,6 +24,7 @@ struct TConv {
     // NCHW form followed / preceded by trainx_kernels.h's layout pass: bit-identical, one 103 MB round trip less each way.
     void *pl = nullptr;
     int pl_cs = 0, pl_split = 0;
+    int dil = 1;         // tap spacing; read by the DIL instantiations of tconv_fwd_kernel / tconv_wgrad_kernel only (pn_conv2d_*_dil)
 };
 typedef __attribute__((ext_vector_type(8))) __bf16 t_bf8;
 typedef __attribute__((ext_vector_type(4))) __bf16 t_bf4;
@@ -64,7 +65,9 @@ __device__ __forceinline__ int t_logical_block() {
 // weight-gradient grids (column blocks, cout blocks, slices): a slice's blocks are one contiguous logical range
 #define T_DECODE_XYZ(bx, by, bz) const int _lg = t_logical_block(), bx = _lg % (int)gridDim.x, by = (_lg / (int)gridDim.x) % (int)gridDim.y, bz = _lg / (int)(gridDim.x * gridDim.y)
 
-template <int KS, int PL = 0>
+// DIL: the taps are c.dil pixels apart (A2J's layer4.1 / layer4.2 conv2, third_party_methods/A2J_experiments/resnet.py:112,145) -- the gather address
+// changes, the k order and the MFMA order do not.  DIL = false is the kernel as it always was.
+template <int KS, int PL = 0, bool DIL = false>
 __global__ __launch_bounds__(256) void tconv_fwd_kernel(TConv c) {
     __shared__ float As[TC_KC][TC_AP];
     __shared__ float Bs[TC_KC][TC_BP];
@@ -106,7 +109,7 @@ __global__ __launch_bounds__(256) void tconv_fwd_kernel(TConv c) {
         for (int j = 0; j < 8; ++j) {
             const int k = k0 + b_k0 + 2 * j;
             const int ci = k / (KS * KS), rr = k - ci * (KS * KS), ky = rr / KS, kx = rr - ky * KS;
-            const int iy = iy0 + ky, ix = ix0 + kx;
+            const int iy = DIL ? iy0 + ky * c.dil : iy0 + ky, ix = DIL ? ix0 + kx * c.dil : ix0 + kx;
             const int ok = (int)(bp_ok & (k < c.Kdim) & (iy >= 0) & (iy < c.H) & (ix >= 0) & (ix < c.W));
             rb[j] = xb[((ci * c.H + iy) * c.W + ix) & -ok];
             okm |= (unsigned)ok << j;

@@ -550,7 +550,7 @@ __global__ __launch_bounds__(512, 1) void tconv3_wgrad_x3v_kernel(TConv c, TTile
 #define TW_RC 32
 #define TW_P 81
 
-template <int KS>
+template <int KS, bool DIL = false>       // DIL: taps c.dil pixels apart, as tconv_fwd_kernel's
 __global__ __launch_bounds__(256) void tconv_wgrad_kernel(TConv c, float *__restrict__ partial, int pix_per_slice) {
     __shared__ float As[TW_RC][TW_P];      // dY  [pixel][cout]
     __shared__ float Bs[TW_RC][TW_P];      // X   [pixel][k column]
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(256) void tconv_wgrad_kernel(TConv c, float *__rest
             const int co = co0 + g + 8 * j;
             const int oka = (int)(ok & (co < c.Cout));
             ra[j] = dyb[(co * HoWo) & -oka];
-            const int iy = iy0 + kky[j], ix = ix0 + kkx[j];
+            const int iy = DIL ? iy0 + kky[j] * c.dil : iy0 + kky[j], ix = DIL ? ix0 + kkx[j] * c.dil : ix0 + kkx[j];
             const int okb = (int)(ok & (kci[j] >= 0) & (iy >= 0) & (iy < c.H) & (ix >= 0) & (ix < c.W));
             rb[j] = xb[((kci[j] * c.H + iy) * c.W + ix) & -okb];
             okm |= ((unsigned)oka << (8 + j)) | ((unsigned)okb << j);

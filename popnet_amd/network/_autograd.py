@@ -10,6 +10,7 @@ ORDERS the calls; every convolution, BatchNorm and pooling, forward and backward
     pn_avgpool3s2_forward / pn_avgpool3s2_backward               nn.AvgPool2d(3, 2, 1)
     pn_maxpool_forward / pn_maxpool_backward                     nn.MaxPool2d (YoloPoseNet)
     pn_conv2d_dgrad_strided                                      the data gradient of a strided nn.Conv2d (YoloPoseNet's layer2.0)
+    pn_conv2d_forward_dil / _dgrad_dil / _wgrad_dil              a dilated 3x3 nn.Conv2d (A2J_model's layer4.1 / layer4.2 conv2)
 
 (the same kernels popnet_amd.train.TrainEngine drives without autograd; the engine stays the fast path: flat buffers, fused
 head + loss kernels, one hipGraph per step).  No PyTorch convolution / normalisation kernel is ever run; there is no CPU fallback.
@@ -38,38 +39,48 @@ class Conv2dFn(torch.autograd.Function):
     """y = conv2d(x, w, b, stride, padding)   x [N, Cin, H, W], w [Cout, Cin, k, k] (k in 1, 3, 7), NCHW float32."""
 
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad):
+    def forward(ctx, x, w, b, stride, pad, dil=1):
         x, w = x.contiguous(), w.contiguous()
         c, s = _ctx(x)
         N, Cin, H, W = x.shape
         Cout, ks = w.shape[0], w.shape[-1]
-        Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+        Ho, Wo = (H + 2 * pad - dil * (ks - 1) - 1) // stride + 1, (W + 2 * pad - dil * (ks - 1) - 1) // stride + 1
+        if dil != 1 and (Ho < 1 or Wo < 1):
+            raise _lib.PopnetError("popnet_amd: Conv2d(dilation=%d, padding=%d) leaves no output on a %d x %d map" % (dil, pad, H, W))
         y = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
-        c.check(_lib.lib().pn_conv2d_forward(c.handle, _ptr(x), _ptr(w), _ptr(b), _ptr(y), N, Cin, H, W, Cout, ks, stride, pad, 0, s), "pn_conv2d_forward")
+        if dil != 1:                           # A2J_model's layer4.1 / layer4.2 conv2
+            c.check(_lib.lib().pn_conv2d_forward_dil(c.handle, _ptr(x), _ptr(w), _ptr(b), _ptr(y), N, Cin, H, W, Cout, ks, stride, pad, dil, 0, s), "pn_conv2d_forward_dil")
+        else:
+            c.check(_lib.lib().pn_conv2d_forward(c.handle, _ptr(x), _ptr(w), _ptr(b), _ptr(y), N, Cin, H, W, Cout, ks, stride, pad, 0, s), "pn_conv2d_forward")
         ctx.save_for_backward(x, w)
-        ctx.geom = (stride, pad, b is not None)
+        ctx.geom = (stride, pad, b is not None, dil)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        stride, pad, has_bias = ctx.geom
+        stride, pad, has_bias, dil = ctx.geom
         dy = dy.contiguous()
         c, s = _ctx(dy)
         N, Cin, H, W = x.shape
         Cout, ks = w.shape[0], w.shape[-1]
         dw = torch.empty_like(w)
         db = torch.empty((Cout,), device=x.device, dtype=torch.float32) if has_bias else None
-        c.check(_lib.lib().pn_conv2d_wgrad(c.handle, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, Cin, H, W, Cout, ks, stride, pad, s), "pn_conv2d_wgrad")
+        if dil != 1:
+            c.check(_lib.lib().pn_conv2d_wgrad_dil(c.handle, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, Cin, H, W, Cout, ks, stride, pad, dil, s), "pn_conv2d_wgrad_dil")
+        else:
+            c.check(_lib.lib().pn_conv2d_wgrad(c.handle, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, Cin, H, W, Cout, ks, stride, pad, s), "pn_conv2d_wgrad")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            if stride != 1:                    # YoloPoseNet's layer2.0.conv1 / downsample.0 (csrc/train_yolo.hip)
+            if dil != 1:
+                c.check(_lib.lib().pn_conv2d_dgrad_dil(c.handle, _ptr(dy), _ptr(w), _ptr(dx), N, Cin, H, W, Cout, ks, pad, dil, 0, s), "pn_conv2d_dgrad_dil")
+            elif stride != 1:                    # YoloPoseNet's layer2.0.conv1 / downsample.0 (csrc/train_yolo.hip)
                 c.check(_lib.lib().pn_conv2d_dgrad_strided(c.handle, _ptr(dy), _ptr(w), _ptr(dx), N, Cin, H, W, Cout, ks, stride, pad, 0, s),
                         "pn_conv2d_dgrad_strided")
             else:
                 c.check(_lib.lib().pn_conv2d_dgrad(c.handle, _ptr(dy), _ptr(w), _ptr(dx), N, Cin, H, W, Cout, ks, pad, 0, s), "pn_conv2d_dgrad")
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
 class BatchNormActFn(torch.autograd.Function):
@@ -168,12 +179,16 @@ def maxpool(x, m):
 
 def conv(x, m):
     """nn.Conv2d parameter holder `m` applied through Conv2dFn.  The HIP primitive is the reference's convolution -- square stride and
-    zero padding, no dilation, no groups (rtpose_light3d.py:24-34, 222-246) -- anything else is refused rather than silently ignored."""
-    if (tuple(m.dilation) != (1, 1) or m.groups != 1 or m.stride[0] != m.stride[1] or isinstance(m.padding, str)
-            or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"):
-        raise _lib.PopnetError("popnet_amd: Conv2d(dilation=%s, groups=%s, stride=%s, padding=%s, padding_mode=%r) is outside what pn_conv2d_forward "
-                               "computes (square stride / zero padding, no dilation, no groups)" % (m.dilation, m.groups, m.stride, m.padding, m.padding_mode))
-    return Conv2dFn.apply(x, m.weight, m.bias, m.stride[0], m.padding[0])
+    zero padding, no groups (rtpose_light3d.py:24-34, 222-246), and the dilated 3x3 of A2J's layer4 (pn_conv2d_*_dil) -- anything else is
+    refused rather than silently ignored."""
+    dil = tuple(m.dilation)
+    if (dil[0] != dil[1] or m.groups != 1 or m.stride[0] != m.stride[1] or isinstance(m.padding, str)
+            or m.padding[0] != m.padding[1] or m.padding_mode != "zeros"
+            or (dil[0] != 1 and (m.kernel_size != (3, 3) or m.stride[0] != 1 or m.padding[0] > 2 * dil[0]))):
+        raise _lib.PopnetError("popnet_amd: Conv2d(kernel_size=%s, dilation=%s, groups=%s, stride=%s, padding=%s, padding_mode=%r) is outside what "
+                               "pn_conv2d_forward / pn_conv2d_forward_dil compute (square stride / zero padding, no groups; a dilated convolution is "
+                               "3x3, stride 1, padding <= 2 x dilation)" % (m.kernel_size, m.dilation, m.groups, m.stride, m.padding, m.padding_mode))
+    return Conv2dFn.apply(x, m.weight, m.bias, m.stride[0], m.padding[0], dil[0])
 
 
 def bn_act(x, m, act, res=None):

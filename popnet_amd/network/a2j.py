@@ -4,7 +4,9 @@ Drop-in for third_party_methods/A2J_experiments/model.py:145-186 (+ resnet.py:61
 anchor.py:7-82: the same 410 ``state_dict`` keys, so a reference ``.pth`` loads -- including ``Backbone.model.fc.*``, which the
 reference builds and never executes and which is held here and skipped at compile time -- the same
 ``forward(x) -> (classification [B, K, P], regression [B, K, P, 2], depth [B, K, P])`` with K = (W/16) (H/16) 16 anchors in the
-reference's W-major order, and ``post_process(...).forward(heads) -> [B, P, 3]`` (y, x, z).  Nothing is downloaded: the reference's
+reference's W-major order, and ``post_process(...).forward(heads) -> [B, P, 3]`` (y, x, z).  In train mode ``forward`` runs the autograd-wrapped training primitives
+(network/_autograd.py) and returns the same three heads with ``grad_fn``; ``A2J_loss`` is anchor.py:84-154 on one HIP kernel, so the loop of
+train_a2j_mpaug_new.py:226-238 runs with the imports swapped (at most 31 crops per call, see ``A2J_model.max_train_batch``).  Nothing is downloaded: the reference's
 constructor fetches ImageNet weights, this one starts from its own initialisation.
 """
 import ctypes as C
@@ -126,14 +128,65 @@ class A2J_model(HipNetModule):
         x = self._check_input(x)
         B, _, H, W = x.shape
         if self.training:
-            raise _lib.PopnetError("A2J_model: inference only -- call .eval()")
+            raise _lib.PopnetError("A2J_model.run: the NHWC head maps are the compiled eval-mode net's -- call .eval(); in train mode use forward()")
         net = self._compile(x.device, B, H, W)
         ptrs = [C.c_void_p() for _ in range(3)]
         self._ctx.check(_lib.lib().pn_a2j_forward(net, C.c_void_p(x.data_ptr()), B, *(C.byref(p) for p in ptrs), _lib.current_stream_ptr(x.device)),
                         "pn_a2j_forward")
         return ptrs, (H // 16, W // 16), self._net[1][1]
 
+    # ---- train mode: the reference's forward (model.py:152-186, resnet.py Bottleneck) on the autograd-wrapped HIP primitives ----
+    max_train_batch = 31          # pn_bn_train_* takes N * C <= 65535 and layer4 has C = 2048
+
+    def _forward_train(self, x):
+        from . import _autograd as ag
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        if H % 16 or W % 16:
+            raise _lib.PopnetError("A2J_model: the input size must be a multiple of 16, got %d x %d" % (H, W))
+        if B > self.max_train_batch:
+            raise _lib.PopnetError("A2J_model: train mode takes at most %d crops per call (the BatchNorm primitives take N * C <= 65535 and layer4 "
+                                   "has 2048 channels); split the batch over data-parallel replicas, got %d" % (self.max_train_batch, B))
+        if B * (H // 16) * (W // 16) == 1:
+            raise _lib.PopnetError("A2J_model: train mode needs more than one value per channel (one %d x %d crop leaves a 1 x 1 map)" % (H, W))
+        for p in self.parameters():
+            if p.device != x.device:
+                raise _lib.PopnetError("popnet_amd: module parameters are on %s, the input on %s -- call model.cuda() (the HIP path has no CPU fallback)" % (p.device, x.device))
+
+        def block(u, a):                       # Bottleneck (resnet.py:61-104): conv2 carries the stride and the dilation
+            y = ag.bn_act(ag.conv(a, u.conv1), u.bn1, ag.ACT_RELU)
+            y = ag.bn_act(ag.conv(y, u.conv2), u.bn2, ag.ACT_RELU)
+            y = ag.conv(y, u.conv3)
+            idn = a if u.downsample is None else ag.bn_act(ag.conv(a, u.downsample[0]), u.downsample[1], ag.ACT_NONE)
+            return ag.bn_act(y, u.bn3, ag.ACT_RELU, res=idn)
+
+        def head(m, a):
+            for i in (1, 2, 3, 4):
+                a = ag.bn_act(ag.conv(a, getattr(m, "conv%d" % i)), getattr(m, "bn%d" % i), ag.ACT_RELU)
+            return ag.conv(a, m.output)
+
+        r = self.Backbone.model
+        a = ag.bn_act(ag.conv(x.expand(B, 3, H, W), r.conv1), r.bn1, ag.ACT_RELU)        # model.py:155-156: the depth channel three times
+        a = ag.MaxPoolFn.apply(a, 3, 2, 1)[0]
+        for layer in (r.layer1, r.layer2, r.layer3):
+            for u in layer:
+                a = block(u, a)
+        x3 = a
+        for u in r.layer4:
+            a = block(u, a)
+        x4 = a
+        A, P = self.num_anchors, self.num_classes
+        h, w = H // 16, W // 16
+        # the reference's re-layout of the NCHW maps (model.py:47-50, 93-96, 139-142) is element-wise glue: left to torch (autograd orders it)
+        cls = head(self.classificationModel, x3).permute(0, 3, 2, 1).reshape(B, w, h, A, P).reshape(B, -1, P)
+        reg = head(self.regressionModel, x4).permute(0, 3, 2, 1).reshape(B, w, h, A, P, 2).reshape(B, -1, P, 2)
+        dep = head(self.DepthRegressionModel, x4).permute(0, 3, 2, 1).reshape(B, w, h, A, P).reshape(B, -1, P)
+        self.invalidate()                      # the weights are about to change: the eval-mode net is re-folded on its next use
+        return cls, reg, dep
+
     def forward(self, x):
+        if self.training:
+            return self._forward_train(x)
         self.run(x)
         B, dev = x.shape[0], x.device
         h, w = x.shape[2] // 16, x.shape[3] // 16
@@ -173,3 +226,63 @@ class post_process(nn.Module):
                                          B, 0, K, 1, P, C.c_void_p(self.all_anchors.data_ptr()), C.c_void_p(out.data_ptr()), None, None, None,
                                          _lib.current_stream_ptr(dev)), "pn_a2j_vote")
         return out
+
+
+class _A2JLossFn(torch.autograd.Function):
+    """terms [2] = (Cls_loss, Reg_loss) of pn_a2j_loss on heads in the reference's layout; backward is the kernel's gradient mode with the
+    incoming gradient of the two terms as (s_cls, s_reg), read on the device."""
+
+    @staticmethod
+    def _call(cls, reg, dep, anchors, labels, sf, scale, grads):
+        B, K, P = cls.shape
+        dev = cls.device
+        terms = torch.empty((2,), device=dev, dtype=torch.float32)
+        ctx = _lib.Context.for_device(dev.index)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        ctx.check(_lib.lib().pn_a2j_loss(ctx.handle, ptr(cls), ptr(reg), ptr(dep), B, 0, K, 1, P, ptr(anchors), ptr(labels), float(sf), ptr(scale), ptr(terms),
+                                         ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), _lib.current_stream_ptr(dev)), "pn_a2j_loss")
+        return terms
+
+    @staticmethod
+    def forward(ctx, cls, reg, dep, anchors, labels, sf):
+        cls, reg, dep, labels = (t.contiguous() for t in (cls, reg, dep, labels))
+        ctx.save_for_backward(cls, reg, dep, anchors, labels)
+        ctx.sf = sf
+        return _A2JLossFn._call(cls, reg, dep, anchors, labels, sf, None, (None, None, None))
+
+    @staticmethod
+    def backward(ctx, gterms):
+        cls, reg, dep, anchors, labels = ctx.saved_tensors
+        grads = (torch.empty_like(cls), torch.empty_like(reg), torch.empty_like(dep))
+        _A2JLossFn._call(cls, reg, dep, anchors, labels, ctx.sf, gterms.contiguous().float(), grads)
+        return grads + (None, None, None)
+
+
+class A2J_loss(nn.Module):
+    """anchor.py:84-154 with the reference's constructor.  forward(heads, annotations): heads = (classification [B, K, P], regression
+    [B, K, P, 2], depth [B, K, P]) CUDA tensors in the reference's layout, annotations [B, P, 3] (two columns in the anchors' (y, x) order,
+    then z) -> (Cls_loss [1], Reg_loss [1]), differentiable with respect to the heads.  One HIP kernel (pn_a2j_loss) per direction.
+    `thres` and `img_shape` are kept and, as in the reference's forward, never used."""
+
+    def __init__(self, P_h=[2, 6], P_w=[2, 6], shape=[8, 4], stride=8, thres=[10.0, 20.0], spatialFactor=0.1, img_shape=[0, 0], is_3D=True):
+        super().__init__()
+        if not is_3D:
+            raise _lib.PopnetError("A2J_loss: built with the depth head (is_3D=True)")
+        self.all_anchors_np = shift(shape, stride, generate_anchors(P_h=P_h, P_w=P_w))
+        self.all_anchors = torch.from_numpy(self.all_anchors_np).float()
+        self.thres, self.spatialFactor, self.img_shape, self.is_3D = thres, float(spatialFactor), img_shape, is_3D
+
+    def forward(self, heads, annotations):
+        cls, reg, dep = heads
+        _lib.require_cuda_tensor(cls, "classification")
+        dev = cls.device
+        if self.all_anchors.device != dev:
+            self.all_anchors = self.all_anchors.to(dev)
+        B, K, P = cls.shape
+        if (K != self.all_anchors.shape[0] or tuple(reg.shape) != (B, K, P, 2) or tuple(dep.shape) != (B, K, P) or tuple(annotations.shape) != (B, P, 3)
+                or any(t.dtype != torch.float32 for t in (cls, reg, dep))):
+            raise _lib.PopnetError("A2J_loss: float32 heads of %s / %s / %s and labels %s against %d anchors" % (
+                tuple(cls.shape), tuple(reg.shape), tuple(dep.shape), tuple(annotations.shape), self.all_anchors.shape[0]))
+        labels = annotations.to(device=dev, dtype=torch.float32)
+        terms = _A2JLossFn.apply(cls, reg, dep, self.all_anchors, labels, self.spatialFactor)
+        return terms[0:1], terms[1:2]

@@ -31,6 +31,10 @@ def _is_stat(k):
 class TrainEngine:
     """state_dict: reference-format (optionally `module.`-prefixed) rtpose_light3d(15, 14, 2, input_dim=1) checkpoint."""
 
+    # tensors under this prefix are carried through state_dict() unchanged and never trained: sub-modules the reference builds and never runs
+    # (YoloPoseNet's model0.layer3; A2JTrainEngine: Backbone.model.fc)
+    _carry_prefix = "model0.layer3"
+
     def __init__(self, state_dict, device="cuda:0", lr=1.0, momentum=0.9, weight_decay=0.0, process_group=None, world_size=1, precision="fp32"):
         """precision: "fp32" (every product an exact fp32 FMA chain on v_mfma_f32_16x16x4_f32: the parity mode) or "bf16x3" (split-bf16 MFMA: 16
         significant bits per operand, fp32 accumulate; 2.5x faster) -- both on the round-6 planes engine (csrc/trainx.hip); "fp32-nchw" / "bf16x3-nchw":
@@ -56,8 +60,8 @@ class TrainEngine:
         self.lr, self.momentum, self.weight_decay = float(lr), float(momentum), float(weight_decay)
         self.group, self.world = process_group, int(world_size)
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
-        self.extra = {k: v.clone() for k, v in sd.items() if k.startswith("model0.layer3")}       # carried, never trained
-        names = [k for k in sd if not _is_stat(k) and not k.startswith("model0.layer3")]
+        self.extra = {k: v.clone() for k, v in sd.items() if k.startswith(self._carry_prefix)}       # carried, never trained
+        names = [k for k in sd if not _is_stat(k) and not k.startswith(self._carry_prefix)]
         sizes = [sd[k].numel() for k in names]
         self.n_params = sum(sizes)
         # every tensor starts on a 16-byte boundary of the flat buffers (the kernels take their 16-byte paths only on aligned
@@ -203,6 +207,27 @@ class TrainEngine:
         N, Cc, H, W = self.A["pool:" + name]
         dx = self._buf("dp:" + name, (N, Cc, H, W))
         self._check(self.L.pn_avgpool3s2_backward(self.ctx.handle, self._ptr(dy), self._ptr(dx), N * Cc, H, W, self._s()), "pn_avgpool3s2_backward")
+        return dx
+
+    # nn.MaxPool2d (csrc/train_yolo.hip): YoloPoseNet's stem and model2_1, A2J's stem
+    def _maxpool(self, name, x, k, stride, pad):
+        N, Cc, H, W = x.shape
+        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        y = self._buf("mp:" + name, (N, Cc, Ho, Wo))
+        key = ("mi:" + name, (N, Cc, Ho, Wo))
+        idx = self._bufs.get(key)
+        if idx is None:
+            idx = self._bufs[key] = torch.empty((N, Cc, Ho, Wo), dtype=torch.int32, device=self.device)
+        self._check(self.L.pn_maxpool_forward(self.ctx.handle, self._ptr(x), self._ptr(y), self._ptr(idx), N * Cc, H, W, k, stride, pad, self._s()), "pn_maxpool_forward")
+        self.A["mp:" + name] = (x.shape, idx, k, stride, pad)
+        return y
+
+    def _maxpool_bwd(self, name, dy):
+        shape, idx, k, stride, pad = self.A["mp:" + name]
+        N, Cc, H, W = shape
+        dx = self._buf("dmp:" + name, shape)
+        self._check(self.L.pn_maxpool_backward(self.ctx.handle, self._ptr(dy), self._ptr(idx), self._ptr(dx), N * Cc, H, W, k, stride, pad, self._s()),
+                    "pn_maxpool_backward")
         return dx
 
     # ---- composite modules ----

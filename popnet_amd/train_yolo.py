@@ -59,27 +59,6 @@ class YoloTrainEngine(TrainEngine):
     def capture(self, *a, **k):
         raise _lib.PopnetError("popnet_amd.train_yolo: the YoloPoseNet step is not captured as a hipGraph; call step()")
 
-    # ---- layers the rtpose engine does not have ----
-    def _maxpool(self, name, x, k, stride, pad):
-        N, Cc, H, W = x.shape
-        Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        y = self._buf("mp:" + name, (N, Cc, Ho, Wo))
-        key = ("mi:" + name, (N, Cc, Ho, Wo))
-        idx = self._bufs.get(key)
-        if idx is None:
-            idx = self._bufs[key] = torch.empty((N, Cc, Ho, Wo), dtype=torch.int32, device=self.device)
-        self._check(self.L.pn_maxpool_forward(self.ctx.handle, self._ptr(x), self._ptr(y), self._ptr(idx), N * Cc, H, W, k, stride, pad, self._s()), "pn_maxpool_forward")
-        self.A["mp:" + name] = (x.shape, idx, k, stride, pad)
-        return y
-
-    def _maxpool_bwd(self, name, dy):
-        shape, idx, k, stride, pad = self.A["mp:" + name]
-        N, Cc, H, W = shape
-        dx = self._buf("dmp:" + name, shape)
-        self._check(self.L.pn_maxpool_backward(self.ctx.handle, self._ptr(dy), self._ptr(idx), self._ptr(dx), N * Cc, H, W, k, stride, pad, self._s()),
-                    "pn_maxpool_backward")
-        return dx
-
     def _block(self, p, x, stride=1):
         """BasicBlock of resnet34 (conv1 and the 1x1 downsample carry the stride)"""
         a1 = self._bn(p + ".bn1", self._conv(p + ".conv1", x, 3, stride, 1), ACT_RELU)
