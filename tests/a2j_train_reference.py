@@ -7,6 +7,7 @@
   adam_step       torch.optim.Adam's update (L2 weight decay) on arrays
   dilated_conv    F.conv2d with dilation, and its two gradients
   smooth_l1       the loss's element function
+  loss_fp64       a2j_loss and its gradients in fp64 on NCHW (or flat) head maps, with the per-element error bound of an fp32 evaluation
 """
 import numpy as np
 import torch
@@ -14,6 +15,7 @@ import torch.nn.functional as F
 
 LAYERS = (("layer1", 3, 1, 1), ("layer2", 4, 2, 1), ("layer3", 6, 2, 1), ("layer4", 3, 1, 2))      # name, blocks, stride of block 0, dilation of blocks >= 1
 HEADS = ("classificationModel", "regressionModel", "DepthRegressionModel")
+U = 2.0 ** -24
 
 
 def smooth_l1(d):
@@ -121,3 +123,54 @@ def dilated_conv(x, w, b, pad, dil, dy=None):
         return y.detach()
     dx, dw = torch.autograd.grad(y, (x, w), dy.double())
     return y.detach(), dx, dw, dy.double().sum((0, 2, 3))
+
+
+def loss_fp64(cls, reg, dep, geom, anchors, labels, sf, scale):
+    """fp64: terms, the gradients in the inputs' layout, and the per-element error bounds derived below"""
+    B, h, w, A, P = geom
+    raw = [t.double().requires_grad_() for t in (cls, reg, dep)]
+    if h:
+        heads = (nchw_to_reference(raw[0], A, P), nchw_to_reference(raw[1], A, P, two=True), nchw_to_reference(raw[2], A, P))
+    else:
+        heads = raw
+    an, lab = anchors.double(), labels.double()
+    c, r = a2j_loss(heads, lab, an, sf)
+    grads = torch.autograd.grad(scale[0] * c + scale[1] * r, raw)
+    # ---- the bound.  K = anchors per (crop, joint), u = 2^-24, eps = K u.
+    # A prediction is V = N / D with N = sum_k e_k v_k, D = sum_k e_k, e_k = exp(cls_k - max).  A K-term fp32 sum in any order is within
+    # K u sum|addends| of the exact sum of its addends; an addend e_k v_k itself carries e_k's error: the rounding of cls_k - max (|cls_k - max| u
+    # relative in e_k), expf (2 ulp) and one product -- (3 + |cls_k - max|) u, which is <= K u on every case here (asserted), so
+    #   dN <= 2 eps sum|e_k v_k|,  dD <= 2 eps D,  and through the division  dV <= dN / D + |V| dD / D + u |V| = 2 eps (sum_k w_k |v_k| + |V|) + u |V|.
+    # The smooth L1 and |.| are 1-Lipschitz: an element of a term moves by at most dV (+ u-level roundings of gt - V and of the few products),
+    # and a term is a weighted mean of its elements.
+    with torch.no_grad():
+        K = heads[0].shape[1]
+        eps = K * U
+        assert float((heads[0].max(1, keepdim=True)[0] - heads[0]).max()) + 3 <= K
+        wk = torch.softmax(heads[0], 1)                                       # [B, K, P]
+        va = an[None, :, None, :].expand(B, K, P, 2)
+        vr = va + heads[1]
+        vals = torch.cat([va, vr, heads[2].unsqueeze(3)], 3)                  # [B, K, P, 5]: anchor y x, anchor + reg y x, depth
+        V = (wk.unsqueeze(3) * vals).sum(1)                                   # [B, P, 5]
+        dV = 2 * eps * ((wk.unsqueeze(3) * vals.abs()).sum(1) + V.abs()) + U * V.abs()
+        gt = torch.cat([lab[:, :, :2], lab[:, :, :2], lab[:, :, 2:]], 2)
+        d = gt - V
+        dV = dV + 4 * U * (gt.abs() + V.abs())                                # gt - V and the element function's own roundings
+        coef = torch.tensor([1 / (2.0 * P * B)] * 2 + [sf / (2.0 * P * B)] * 2 + [1.0 / (P * B)], dtype=torch.float64)
+        t_allow = torch.stack([(dV[:, :, :2] * coef[:2]).sum(), (dV[:, :, 2:] * coef[2:]).sum()]) + 8 * U * torch.stack([c, r]).reshape(2).abs()
+        # gradients: g_i = s c_i f'(d_i) (f' is 1-Lipschitz; the sign of the depth term is exact while |d_z| > dV: asserted), w_k = e_k / D within 3 eps w_k,
+        #   d cls_k = w_k sum_i g_i (v_ik - V_i),  d reg_k = w_k g_R,  d dep_k = w_k g_z
+        assert bool((d[:, :, 4].abs() > dV[:, :, 4]).all() | (d[:, :, 4] == 0).all())
+        sc = torch.tensor([scale[0]] * 2 + [scale[1]] * 3, dtype=torch.float64) * coef
+        fp = torch.where(d.abs() <= 1, -d, -torch.sign(d))
+        fp[:, :, 4] = -torch.sign(d[:, :, 4])
+        g = sc * fp                                                           # [B, P, 5]
+        dg = sc.abs() * dV
+        dg[:, :, 4] = 0
+        dev = (vals - V.unsqueeze(1)).abs()                                   # [B, K, P, 5]
+        a_cls = wk * ((dg.unsqueeze(1) * dev).sum(3) + (g.abs() * dV).unsqueeze(1).sum(3) + (3 * eps + 8 * U) * (g.abs().unsqueeze(1) * dev).sum(3))
+        a_reg = wk.unsqueeze(3) * (dg[:, :, 2:4].unsqueeze(1) + (3 * eps + 4 * U) * g[:, :, 2:4].abs().unsqueeze(1))
+        a_dep = wk * (3 * eps + 4 * U) * g[:, :, 4].abs().unsqueeze(1)
+        if h:
+            a_cls, a_reg, a_dep = reference_to_nchw(a_cls, h, w, A), reference_to_nchw(a_reg, h, w, A), reference_to_nchw(a_dep, h, w, A)
+    return torch.stack([c, r]).reshape(2).detach(), grads, t_allow, (a_cls, a_reg, a_dep)

@@ -27,6 +27,11 @@ definitions, read from the kernels:
   (per_slice tiles of R x TW pixels, or per_slice pixels for the generic kernel), then wgrad_reduce_kernel adds the slices in order:
   depth = pixels per slice x (3 | 1) + slices, |error| <= depth U S + float32 rounding.  dbias[co] = sum dy (chan_reduce_kernel<2> in DOUBLE
   over t_slices slices, sums_finish_kernel): P 2^-53 sum|dy| + float32 rounding.
+* dilated 3x3 convolutions (pn_conv2d_forward_dil / _dgrad_dil / _wgrad_dil: tconv_fwd_kernel<3, 0, true>, tconv_wgrad_kernel<3, true>; fp32,
+  stride 1): the three definitions above with the taps dil apart, x[n, ci, oy + ky dil - p, ox + kx dil - p].  The data gradient is the
+  forward kernel on dy with the wflip_kernel weights at padding 2 dil - p.  n and S as for the undilated fp32 arm (a tap in the padding
+  contributes nothing to S).  The weight gradient's slices are t_wgrad_pixel_slices(N Ho Wo, 9 Cin, Cout), the generic path's
+  (dil_wgrad_plan()): depth = pixels per slice + slices.  dil = 1 forwards to the undilated entry.
 * BatchNorm forward (pn_bn_train_forward: chan_reduce_kernel<0>, bn_apply_kernel): sum x and sum x^2 in double (slices, then the slices in
   order, in double); mean = s / n; var = max(ss / n - mean^2, 0); save_mean = float32(mean), save_invstd = float32(1 / sqrt(var + eps));
   running_mean' = float32((1 - m) running_mean + m mean), running_var' the same with var n / (n - 1) (m = float32(0.1), eps = float32(1e-5),
@@ -126,10 +131,11 @@ def split(v):
 
 
 # ---- convolutions -------------------------------------------------------------------------------------------
-def conv_fwd_ref(x, w, bias, prev, stride, pad, x3):
-    """-> (r, allowance).  x [N, Cin, H, W], w [Cout, Cin, k, k], bias [Cout] or None, prev = the y accumulated into or None."""
+def conv_fwd_ref(x, w, bias, prev, stride, pad, x3, dilation=1):
+    """-> (r, allowance).  x [N, Cin, H, W], w [Cout, Cin, k, k], bias [Cout] or None, prev = the y accumulated into or None.
+    dilation: the spacing of the taps (pn_conv2d_forward_dil: x[oy + ky dil - p, ox + kx dil - p])."""
     x, w = f32(x), f32(w)
-    conv = lambda a, b: F.conv2d(a, b, stride=stride, padding=pad)      # noqa: E731
+    conv = lambda a, b: F.conv2d(a, b, stride=stride, padding=pad, dilation=dilation)      # noqa: E731
     n = w.shape[1] * w.shape[2] * w.shape[3]
     if x3:
         xh, xl = split(x)
@@ -147,13 +153,13 @@ def conv_fwd_ref(x, w, bias, prev, stride, pad, x3):
     return r, allowance(r, n * U * S, "fp32")
 
 
-def conv_dgrad_ref(dy, w, prev, shape, stride, pad, x3):
-    """-> (r, allowance) of dx [shape]; stride > 1: the strided primitive (always fp32)."""
+def conv_dgrad_ref(dy, w, prev, shape, stride, pad, x3, dilation=1):
+    """-> (r, allowance) of dx [shape]; stride > 1: the strided primitive (always fp32).  dilation: the forward convolution's tap spacing."""
     dy, w = f32(dy), f32(w)
     N, Cin, H, W = shape
-    k = w.shape[2]
-    op = (H + 2 * pad - k - (dy.shape[2] - 1) * stride, W + 2 * pad - k - (dy.shape[3] - 1) * stride)
-    tr = lambda a, b: F.conv_transpose2d(a, b, stride=stride, padding=pad, output_padding=op)      # noqa: E731
+    ke = dilation * (w.shape[2] - 1) + 1                          # the extent of the dilated window
+    op = (H + 2 * pad - ke - (dy.shape[2] - 1) * stride, W + 2 * pad - ke - (dy.shape[3] - 1) * stride)
+    tr = lambda a, b: F.conv_transpose2d(a, b, stride=stride, padding=pad, output_padding=op, dilation=dilation)      # noqa: E731
     if x3:
         dh, dl = split(dy)
         wh, wl = split(w)
@@ -169,23 +175,33 @@ def conv_dgrad_ref(dy, w, prev, shape, stride, pad, x3):
     return r, allowance(r, n * U * S, "fp32")
 
 
-def _cw(dy, x, ks, stride, pad):
-    """sum over (n, oy, ox) of dy[n, co, oy, ox] x[n, ci, oy s + ky - p, ox s + kx - p] -> [co, ci, ks, ks]"""
-    cols = F.unfold(x, ks, padding=pad, stride=stride)                       # [N, Cin k k, Ho Wo]
+def _cw(dy, x, ks, stride, pad, dilation=1):
+    """sum over (n, oy, ox) of dy[n, co, oy, ox] x[n, ci, oy s + ky d - p, ox s + kx d - p] -> [co, ci, ks, ks]"""
+    cols = F.unfold(x, ks, dilation=dilation, padding=pad, stride=stride)    # [N, Cin k k, Ho Wo]
     return torch.einsum("ncp,nkp->ck", dy.flatten(2), cols).view(dy.shape[1], x.shape[1], ks, ks)
 
 
-def conv_wgrad_ref(x, dy, ks, stride, pad, p):
-    """p: plan(..., "wgrad", ...).  -> (r, allowance) of dw"""
+def conv_wgrad_ref(x, dy, ks, stride, pad, p, dilation=1):
+    """p: plan(..., "wgrad", ...) -- for a dilated call dil_wgrad_plan(...).  -> (r, allowance) of dw"""
     x, dy = f32(x), f32(dy)
     if is_x3(p["kernel"]):
         xh, xl = split(x)
         dh, dl = split(dy)
-        r = _cw(dh + dl, xh, ks, stride, pad) + _cw(dh, xl, ks, stride, pad)
-        S = _cw(dh.abs() + dl.abs(), xh.abs(), ks, stride, pad) + _cw(dh.abs(), xl.abs(), ks, stride, pad)
+        r = _cw(dh + dl, xh, ks, stride, pad, dilation) + _cw(dh, xl, ks, stride, pad, dilation)
+        S = _cw(dh.abs() + dl.abs(), xh.abs(), ks, stride, pad, dilation) + _cw(dh.abs(), xl.abs(), ks, stride, pad, dilation)
     else:
-        r, S = _cw(dy, x, ks, stride, pad), _cw(dy.abs(), x.abs(), ks, stride, pad)
+        r, S = _cw(dy, x, ks, stride, pad, dilation), _cw(dy.abs(), x.abs(), ks, stride, pad, dilation)
     return r, _round32(r, wgrad_depth(p) * U * S)
+
+
+def dil_wgrad_plan(handle, N, Cin, Ho, Wo, Cout):
+    """The slices of pn_conv2d_wgrad_dil for an output of N x Ho x Wo pixels.  The dilated entry is not described by pn_train_conv_plan_info;
+    it calls t_wgrad_pixel_slices(P = N Ho Wo, Kdim = 9 Cin, Cout) exactly as pn_conv2d_wgrad's generic path does, and the slices depend on
+    nothing else.  So the plan is read from an undilated call the planner sends down the generic path with the same P, Kdim and Cout:
+    3x3, stride 2, pad 1 on a (2 Ho - 1) x (2 Wo - 1) map, whose output is Ho x Wo."""
+    p = plan(handle, "wgrad", N, Cin, 2 * Ho - 1, 2 * Wo - 1, Cout, 3, 2, 1)
+    assert p["kernel"] == "tconv_wgrad_kernel<3>" and p["per_slice_unit"] == "pixels" and (p["Ho"], p["Wo"]) == (Ho, Wo), p
+    return p
 
 
 def double_chain(count):

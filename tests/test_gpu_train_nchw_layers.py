@@ -12,6 +12,8 @@ popnet_amd.train_yolo.YoloTrainEngine) against the fp64 references of tests/nchw
     of each threshold; outputs sit inside sentinel-filled buffers; every row asserts the labels it expects.
 (c) small-integer operands: exact in fp32 and in bf16 hi planes, so the result must equal the integer reference bit for bit.
 (d) coverage guard: the labels the engines' steps use at their training shapes (from the plan description alone) are among those checked.
+The replay mixin also serves tests/test_gpu_train_a2j_layers.py (A2JTrainEngine): its _conv / _conv_bwd take the dilation that engine passes and
+check pn_conv2d_*_dil under the literal labels FD / GD (the plan description does not cover the dilated entries); the table's last rows are ResNet-50's shapes.
 
 The tall one- and three-column rows of (b) (106 x 1, 87 x 3) exceed the 56-row limit of the other rows on purpose: they are the only shapes at
 which t_tile_geometry_x3 / t_tile_geometry_x3w refuse a map (their halo tile outgrows the LDS image); they hold ~300 pixels.  t_tile_geometry and
@@ -89,7 +91,7 @@ class _Checked:
         self.tag, self.prec, self.x3 = tag, prec, prec == "bf16x3"
         self.hplan = NR.plan_context(self.x3)
         self.reports, self.called, self.checked, self.labels, self.calls = [], set(), set(), set(), set()
-        self.flips, self.light, self.img_hw = 0, False, None
+        self.flips, self.light, self.img_hw, self.kept = 0, False, None, {}
         self.L = _Proxy(self.L, self)
 
     # -- bookkeeping
@@ -103,6 +105,11 @@ class _Checked:
         _note(entry, self.prec, rep, what)
         return rep
 
+    def _keep(self, key, *operands):
+        """The operands of one comparison, for a test that re-runs it against a deliberately wrong reference (self.want: the keys to keep)."""
+        if key in getattr(self, "want", ()) and key not in self.kept:
+            self.kept[key] = operands
+
     def _plan(self, which, x_shape, Cout, ks, stride, pad):
         N, Cin, H, W = x_shape
         p = NR.plan(self.hplan, which, N, Cin, H, W, Cout, ks, stride, pad)
@@ -112,7 +119,8 @@ class _Checked:
     def _view(self, ptr, N, ld, Cc, HW):
         """The [N, Cc, HW] tensor a raw pointer argument with an image stride of ld channels addresses (a slice of one of the engine's tensors)."""
         addr = ptr.value if isinstance(ptr, C.c_void_p) else ptr
-        for t in list(self._bufs.values()) + list(self._batch) + [self.loss_terms]:
+        more = list(getattr(self, "_anchors", {}).values()) + [t for t in (getattr(self, "_scale", None),) if t is not None]      # A2JTrainEngine's
+        for t in list(self._bufs.values()) + list(self._batch) + [self.loss_terms] + more:
             off = addr - t.data_ptr()
             if t.dtype == torch.float32 and 0 <= off < t.numel() * 4:
                 assert off % 4 == 0 and off // 4 + (N - 1) * ld * HW + Cc * HW <= t.numel()
@@ -120,23 +128,33 @@ class _Checked:
         raise AssertionError("pointer outside the engine's tensors")
 
     # -- the primitive methods
-    def _conv(self, name, x, ks, stride=1, pad=0):
+    def _conv(self, name, x, ks, stride=1, pad=0, dil=1):
+        """dil > 1 (A2JTrainEngine only): pn_conv2d_forward_dil, the same definition with the taps dil apart."""
         if self.img_hw is None:
             self.img_hw = tuple(x.shape[2:])
         w, b = self.p[name + ".weight"], self.p.get(name + ".bias")
         N, Cin, H, W = x.shape
-        Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+        Ho, Wo = (H + 2 * pad - dil * (ks - 1) - 1) // stride + 1, (W + 2 * pad - dil * (ks - 1) - 1) // stride + 1
         self._buf("c:" + name, (N, w.shape[0], Ho, Wo)).fill_(float("nan"))
+        if dil != 1:
+            y = super()._conv(name, x, ks, stride, pad, dil=dil)
+            r, a = NR.conv_fwd_ref(_d(x), _d(w), _d(b), None, stride, pad, False, dilation=dil)
+            self._cmp("pn_conv2d_forward_dil", FD, name, y, r, a)
+            self._keep(("forward", name), _d(y), _d(x), _d(w), _d(b), stride, pad, dil)
+            return y
         y = super()._conv(name, x, ks, stride, pad)
         p = self._plan("forward", x.shape, w.shape[0], ks, stride, pad)
         r, a = NR.conv_fwd_ref(_d(x), _d(w), _d(b), None, stride, pad, NR.is_x3(p["kernel"]))
         self._cmp("pn_conv2d_forward", p["kernel"], name, y, r, a)
         return y
 
-    def _conv_bwd(self, name, dy, ks, stride=1, pad=0, dx=None, accumulate=False, need_dx=True):
+    def _conv_bwd(self, name, dy, ks, stride=1, pad=0, dx=None, accumulate=False, need_dx=True, dil=1):
+        """dil > 1 (A2JTrainEngine only): pn_conv2d_wgrad_dil and pn_conv2d_dgrad_dil.  The weight gradient's depth is pixels per slice + slices
+        with the slices of NR.dil_wgrad_plan (the launch code's own t_wgrad_pixel_slices, read through an undilated call of the same P, Kdim, Cout)."""
         x, w = self.A["x:" + name], self.p[name + ".weight"]
+        kw = {"dil": dil} if dil != 1 else {}
         if self.light and not (need_dx and stride == 1 and ks == 3):
-            return super()._conv_bwd(name, dy, ks, stride, pad, dx=dx, accumulate=accumulate, need_dx=need_dx)
+            return super()._conv_bwd(name, dy, ks, stride, pad, dx=dx, accumulate=accumulate, need_dx=need_dx, **kw)
         if need_dx and dx is None:
             dx = self._buf("dx:" + name, x.shape)
         prev = _d(dx) if (need_dx and accumulate) else None
@@ -145,20 +163,29 @@ class _Checked:
         self.g[name + ".weight"].fill_(float("nan"))
         if name + ".bias" in self.g:
             self.g[name + ".bias"].fill_(float("nan"))
-        out = super()._conv_bwd(name, dy, ks, stride, pad, dx=dx, accumulate=accumulate, need_dx=need_dx)
+        out = super()._conv_bwd(name, dy, ks, stride, pad, dx=dx, accumulate=accumulate, need_dx=need_dx, **kw)
         xd, dyd = _d(x), _d(dy)
         if not self.light:
-            p = self._plan("wgrad", x.shape, w.shape[0], ks, stride, pad)
-            r, a = NR.conv_wgrad_ref(xd, dyd, ks, stride, pad, p)
-            self._cmp("pn_conv2d_wgrad", p["kernel"], name + " dw", self.g[name + ".weight"], r, a)
+            if dil != 1:
+                p = NR.dil_wgrad_plan(self.hplan, x.shape[0], x.shape[1], dy.shape[2], dy.shape[3], w.shape[0])
+                entry, label = "pn_conv2d_wgrad_dil", GD
+            else:
+                p = self._plan("wgrad", x.shape, w.shape[0], ks, stride, pad)
+                entry, label = "pn_conv2d_wgrad", p["kernel"]
+            r, a = NR.conv_wgrad_ref(xd, dyd, ks, stride, pad, p, dilation=dil)
+            self._cmp(entry, label, name + " dw", self.g[name + ".weight"], r, a)
             if name + ".bias" in self.g:
                 r, a = NR.conv_dbias_ref(dyd)
-                self._cmp("pn_conv2d_wgrad", "", name + " dbias", self.g[name + ".bias"], r, a)
-        if need_dx:
+                self._cmp(entry, "", name + " dbias", self.g[name + ".bias"], r, a)
+        if need_dx and dil != 1:
+            r, a = NR.conv_dgrad_ref(dyd, _d(w), prev, tuple(x.shape), stride, pad, False, dilation=dil)
+            self._cmp("pn_conv2d_dgrad_dil", FD, name + " dx", out, r, a)
+        elif need_dx:
             which = "dgrad" if stride == 1 else "dgrad_strided"
             p = self._plan(which, x.shape, w.shape[0], ks, stride, pad)
             r, a = NR.conv_dgrad_ref(dyd, _d(w), prev, tuple(x.shape), stride, pad, NR.is_x3(p["kernel"]))
             self._cmp("pn_conv2d_" + which, p["kernel"], name + " dx", out, r, a)
+            self._keep(("dgrad", name), _d(out), dyd, _d(w), prev, tuple(x.shape), stride, pad, NR.is_x3(p["kernel"]))
         return out
 
     def _bn(self, name, x, act, res=None):
@@ -172,8 +199,10 @@ class _Checked:
         got = {"mean": mean, "invstd": invstd, "running_mean": self.stats[name + ".running_mean"], "running_var": self.stats[name + ".running_var"]}
         for k, (r, a) in ref.items():
             self._cmp("pn_bn_train_forward", "", "%s %s" % (name, k), got[k], r, a)
-        r, a = NR.bn_apply_ref(_d(x), _d(mean), _d(invstd), _d(self.p[name + ".weight"]), _d(self.p[name + ".bias"]), _d(res), act)
+        args = (_d(x), _d(mean), _d(invstd), _d(self.p[name + ".weight"]), _d(self.p[name + ".bias"]), _d(res), act)
+        r, a = NR.bn_apply_ref(*args)
         self._cmp("pn_bn_train_forward", "", name + " y", y, r, a)
+        self._keep(("bn", name), _d(y), *args)
         return y
 
     def _bn_bwd(self, name, dy, dres=None, dres_accumulate=False):
@@ -285,8 +314,8 @@ class _Checked:
         return rc
 
 
-def _engine_class(base):
-    return type("Checked" + base.__name__, (_Checked, base), {})
+def _engine_class(base, mixin=_Checked):
+    return type("Checked" + base.__name__, (mixin, base), {})
 
 
 def _replay(golden, gpu, net, prec, B, H, W, rarity=True):
@@ -372,6 +401,7 @@ T, X, XW, WT, W3, WPP, WV = ("tconv3_tile_kernel", "tconv3_tile_x3_kernel", "tco
                             "tconv3_wgrad_x3pp_kernel", "tconv3_wgrad_x3v_kernel")
 F1, F3, F7, G1, G3, G7, S1, S3 = ("tconv_fwd_kernel<1>", "tconv_fwd_kernel<3>", "tconv_fwd_kernel<7>", "tconv_wgrad_kernel<1>", "tconv_wgrad_kernel<3>",
                                   "tconv_wgrad_kernel<7>", "dgrad_strided_kernel<1>", "dgrad_strided_kernel<3>")
+FD, GD = "tconv_fwd_kernel<3> dil", "tconv_wgrad_kernel<3> dil"      # the dilated entries' launches: tconv_fwd_kernel<3, 0, true>, tconv_wgrad_kernel<3, true>
 ALL = "fdw"
 ROWS = [
     # Cin 15 | 16 and 31 | 32 (the data gradient's K is Cout)
@@ -412,6 +442,19 @@ ROWS = [
     ((2, 1, 40, 56, 64, 7, 2, 3), {}, (F7, None, G7), (F7, None, G7), "fw"),
     ((2, 3, 9, 11, 20, 7, 1, 3), {}, (F7, F7, G7), (F7, F7, G7), ALL),
     ((2, 128, 12, 16, 28, 1, 1, 0), {}, (F1, F1, G1), (F1, F1, G1), ALL),
+    # ResNet-50 (A2J): the longest 1x1 K (128 chunks of 16 channels) and the widest Cout (32 blocks of 64), on layer4's 2 x 3 map
+    ((2, 2048, 2, 3, 512, 1, 1, 0), {}, (F1, F1, G1), (F1, F1, G1), ALL),
+    ((2, 1024, 2, 3, 2048, 1, 1, 0), {}, (F1, F1, G1), (F1, F1, G1), ALL),
+    ((2, 64, 8, 12, 256, 1, 1, 0), {}, (F1, F1, G1), (F1, F1, G1), ALL),
+    # its downsample and conv2 at stride 2, with their strided data gradients at 256 .. 512 channels
+    ((2, 256, 8, 12, 512, 1, 2, 0), {}, (F1, S1, G1), (F1, S1, G1), ALL),
+    ((2, 128, 8, 12, 128, 3, 2, 1), {}, (F3, S3, G3), (F3, S3, G3), ALL),
+    ((2, 256, 4, 6, 256, 3, 2, 1), {}, (F3, S3, G3), (F3, S3, G3), ALL),
+    # the tile kernels on a map smaller than any tile; the heads' output convolution (Cout % 64 = 32)
+    ((2, 512, 2, 3, 512, 3, 1, 1), {}, (T, T, WT), (X, X, WPP), ALL),
+    ((2, 256, 2, 3, 480, 3, 1, 1), {}, (T, T, WT), (X, X, WPP), ALL),
+    # its stem: the depth channel three times
+    ((2, 3, 32, 48, 64, 7, 2, 3), {}, (F7, None, G7), (F7, None, G7), "fw"),
 ]
 ROW_IDS = ["%dx%dx%dx%d_to_%d_k%ds%dp%d%s" % (r[0] + ("_" + "_".join(k[7:].lower() for k in r[1]) if r[1] else "",)) for r in ROWS]
 
@@ -590,11 +633,13 @@ def test_integer_probes_of_every_convolution_of_the_steps_are_bit_exact(gpu, gol
 
 
 # ---- element-wise primitives the table above does not hold -------------------------------------------------------------------------
-@pytest.mark.parametrize("N,Cc,H,W", [(3, 70, 13, 9), (3, 70, 12, 8), (3, 64, 48, 64), (1, 5, 1, 2)])
+@pytest.mark.parametrize("N,Cc,H,W", [(3, 70, 13, 9), (3, 70, 12, 8), (3, 64, 48, 64), (1, 5, 1, 2), (31, 2048, 1, 2), (2, 2048, 2, 3)])
 @pytest.mark.parametrize("act,with_res", [(0, False), (1, False), (1, True), (2, False), (2, True)])
 def test_batchnorm_forward_backward_within_fp64_allowance(gpu, N, Cc, H, W, act, with_res):
     """Odd H W (the scalar kernels), H W a multiple of 4 (the 16-byte ones), several reduction slices (3 x 48 x 64 over 64 channels), the smallest
-    count (2); with and without a residual; the mask from `out` and recomputed from x; dres overwritten and accumulated."""
+    count (2); with and without a residual; the mask from `out` and recomputed from x; dres overwritten and accumulated.  31 x 2048 planes
+    (grid.y = 63488, next to the 65535 the entries refuse above) and 2 x 2048 x 2 x 3: ResNet-50's layer4 at the A2J trainer's largest batch
+    and on the replayed maps."""
     from popnet_amd import _lib
     L, ctx, s = _lib.lib(), _lib.Context.for_device(gpu.index), _lib.current_stream_ptr(gpu)
     g = torch.Generator().manual_seed(N + Cc + H + act)

@@ -403,3 +403,66 @@ def test_head_copy_sgd_and_yolo_references_accept_emulations_and_reject_faults()
         assert _ok(o32.detach(), *ref["out"])["n_bad"] == 0 and _ok(t32.detach().float(), *ref["terms"])["n_bad"] == 0
         assert _ok(v32.grad, *ref["dv"])["n_bad"] == 0
         assert _ok(v32.grad * (1 + 1e-5), *ref["dv"])["n_bad"] > 0 and _ok((t32.detach() * (1 + 1e-5)).float(), *ref["terms"])["n_bad"] > 0
+
+
+# ---- the dilated arms (pn_conv2d_forward_dil / _dgrad_dil / _wgrad_dil) ----------------------------------------------------------
+# N, Cin, H, W, Cout, dil, pad.  The first two are shapes of tests/test_gpu_train_a2j.py's primitive test; in both pad = dil, so the data
+# gradient's padding 2 dil - pad IS pad and "pad for 2 dil - pad" changes nothing there: that fault is injected at the third shape (pad 1, dil 2).
+DIL = [(2, 5, 7, 9, 7, 2, 2), (1, 20, 9, 13, 70, 3, 3), (2, 8, 6, 5, 8, 2, 1)]
+
+
+@pytest.mark.parametrize("shape", DIL, ids=["%dx%dx%dx%d_to_%d_d%dp%d" % s for s in DIL])
+def test_dilated_references_equal_autograd_accept_fp32_and_reject_faults(shape):
+    N, Cin, H, W, Cout, dil, pad = shape
+    Ho, Wo = H + 2 * pad - 2 * dil, W + 2 * pad - 2 * dil
+    g = torch.Generator().manual_seed(sum(shape))
+    x, w, b = torch.randn((N, Cin, H, W), generator=g), torch.randn((Cout, Cin, 3, 3), generator=g) / np.sqrt(9.0 * Cin), torch.randn(Cout, generator=g)
+    dy, y0, dx0 = torch.randn((N, Cout, Ho, Wo), generator=g), torch.randn((N, Cout, Ho, Wo), generator=g), torch.randn((N, Cin, H, W), generator=g)
+    p = NR.dil_wgrad_plan(NR.plan_context(False), N, Cin, Ho, Wo, Cout)
+    assert p["slices"] >= 1 and p["slices"] * p["per_slice"] >= N * Ho * Wo > (p["slices"] - 1) * p["per_slice"]
+    # the references are torch autograd in fp64
+    x64, w64 = x.double().requires_grad_(), w.double().requires_grad_()
+    y64 = F.conv2d(x64, w64, b.double(), padding=pad, dilation=dil)
+    dx64, dw64 = torch.autograd.grad(y64, (x64, w64), dy.double())
+    refs = {"forward": NR.conv_fwd_ref(x.double(), w.double(), b.double(), None, 1, pad, False, dilation=dil),
+            "forward +=": NR.conv_fwd_ref(x.double(), w.double(), b.double(), y0.double(), 1, pad, False, dilation=dil),
+            "dgrad": NR.conv_dgrad_ref(dy.double(), w.double(), None, tuple(x.shape), 1, pad, False, dilation=dil),
+            "dgrad +=": NR.conv_dgrad_ref(dy.double(), w.double(), dx0.double(), tuple(x.shape), 1, pad, False, dilation=dil),
+            "wgrad": NR.conv_wgrad_ref(x.double(), dy.double(), 3, 1, pad, p, dilation=dil)}
+    close = lambda a, r: torch.allclose(a, r, rtol=1e-12, atol=1e-13)          # noqa: E731
+    assert close(refs["forward"][0], y64.detach()) and close(refs["forward +="][0], y64.detach() + y0.double())
+    assert close(refs["dgrad"][0], dx64) and close(refs["dgrad +="][0], dx64 + dx0.double()) and close(refs["wgrad"][0], dw64)
+    # a float32 evaluation of the same operations -- the data gradient as the entry computes it: a forward convolution of dy with the
+    # rotated, transposed weights (wflip_kernel) at padding 2 dil - pad
+
+    def emu(fault=None):
+        d = 1 if fault == "spacing" else dil
+        shift = dil - d                                        # spacing 1: the padding moves with the taps, the centre tap stays
+        ww = w
+        if fault == "mirror":
+            ww = w.clone()
+            ww[:, :, 0, 1], ww[:, :, 2, 1] = w[:, :, 2, 1], w[:, :, 0, 1]
+        wt = ww.flip(2, 3).transpose(0, 1).contiguous()
+        y = F.conv2d(x, ww, b, padding=pad - shift, dilation=d)
+        q = 2 * dil - pad
+        if fault == "dgrad_pad":                               # the window starts at iy - pad, not at iy - (2 dil - pad)
+            dx = F.conv2d(F.pad(dy, (pad, 2 * q - pad, pad, 2 * q - pad)), wt, dilation=d)
+        else:
+            dx = F.conv2d(dy, wt, padding=q - shift, dilation=d)
+        dw = NR._cw(dy, x, 3, 1, pad - shift, d)
+        if fault == "mirror":
+            dw = dw.clone()
+            dw[:, :, 0, 1], dw[:, :, 2, 1] = dw[:, :, 2, 1].clone(), dw[:, :, 0, 1].clone()
+        return {"forward": y, "forward +=": y + y0, "dgrad": dx, "dgrad +=": dx + dx0, "wgrad": dw}
+    good = emu()
+    for k, (r, a) in refs.items():
+        rep = _ok(good[k], r, a)
+        assert rep["n_bad"] == 0 and 0 < rep["worst"] <= 1, (k, rep)
+    faults = {"spacing": ("forward", "dgrad", "wgrad"), "mirror": ("forward", "dgrad", "wgrad")}
+    if 2 * dil - pad != pad:
+        faults["dgrad_pad"] = ("dgrad",)
+    else:
+        assert torch.equal(emu("dgrad_pad")["dgrad"], good["dgrad"])          # invisible here by construction, not by tolerance
+    missed = [(f, k) for f, ks in faults.items() for k in ks if _ok(emu(f)[k], *refs[k])["n_bad"] == 0]
+    assert not missed, missed
+    assert any(2 * s[5] - s[6] != s[6] for s in DIL)
