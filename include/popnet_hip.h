@@ -194,6 +194,15 @@ int pn_net_profile_kernel(pn_net *net, int rank, char *name, size_t name_cap, do
 #define PN_FRAME_OVERFLOW_PEAKS 1u
 #define PN_FRAME_OVERFLOW_PERSONS 2u
 
+/* The joint depth read-out of the two evaluation scripts:
+ *   HEAT_WEIGHTED  retrieve_depth_heat_weighted(radius=1) around cell (int(x / downsample), int(y / downsample)) of joint j's heat and z maps
+ *                  (evaluation_rtpose_light3d_kdh3d_mpreal_ablation.py)
+ *   CELL           the one cell z[z_chn[j]][int(y / downsample)][int(x / downsample)] * depth_std + depth_mean in float32
+ *                  (evaluation_rtpose_light3d_itop.py:176-191).  The script indexes without a check and raises IndexError for a refined peak
+ *                  whose cell index lies past the last row or column; here the index is clamped to the last cell, nothing else is read. */
+#define PN_Z_READOUT_HEAT_WEIGHTED 0
+#define PN_Z_READOUT_CELL 1
+
 typedef struct pn_parse_cfg {
     float thresh_heatmap;      /* cfg.TEST.THRESH_HEATMAP  = 0.1   tpm/lib/config/default.py:126 */
     float thresh_paf;          /* cfg.TEST.THRESH_PAF      = 0.05  :127 */
@@ -203,6 +212,9 @@ typedef struct pn_parse_cfg {
     int   w_org, h_org;        /* original frame size for the rescale (480, 640) */
     double fx, fy, cx, cy;     /* pinhole intrinsics  util/util_functions.py:4 */
     float depth_mean, depth_std; /* 3, 2   util/util_functions.py:11-12 */
+    int   z_readout;           /* PN_Z_READOUT_*: how a joint's depth is read from the pose-depth map (default HEAT_WEIGHTED) */
+    int   z_chn[PN_NUM_JOINTS]; /* PN_Z_READOUT_CELL only: the pose-depth channel of joint j (joint2chn), each in 0 .. PN_NUM_LIMBS;
+                                  the heat-weighted rule reads channel j, as its script does (joint2chn = range(num_parts)) */
 } pn_parse_cfg;
 
 /* One frame of results.  Doubles where the reference keeps float64 (everything after NMS). */
@@ -227,6 +239,7 @@ typedef struct pn_pose_frame {
 } pn_pose_frame;
 
 void pn_parse_cfg_default(pn_parse_cfg *cfg);
+size_t pn_sizeof_parse_cfg(void);
 /* heat [B,J+1,h,w], paf [B,2L,h,w], z [B,L+1,h,w]: f32 NCHW device buffers (z normalised, as
  * the network emits it).  frames_dev: device array of B pn_pose_frame.  cfg->downsample = 8 with
  * cfg->num_intermed_pts = 10 runs the kernels built for the workload; every other supported pair
@@ -374,6 +387,8 @@ int pn_rasterize_targets(pn_ctx *ctx, const float *kp2d_dev, const double *kp_z_
  * pn_preprocess, as ONE launch for the batch: composed [B,H,W] f32 (what pn_compose_depth writes) -> out [B,1,S,S] f32
  *   out = (clamp(Resize(Crop(RenderDepth(Rotate(frame)))), 0, depth_max) - depth_mean) / depth_std
  * bit for bit what OpenCV 4.2's scalar float32 paths of warpAffine(INTER_LINEAR, constant border 0) and resize(INTER_LINEAR) give.
+ * An item with hflip set is the ITOP trainers' chain, Hflip (:452-493) between RenderDepth and Crop: np.flip(axis=1) of the render image, as an
+ * index reflection inside the same launch; items with hflip clear are computed exactly as before.
  * Each item has its own record.  The host decides every integer of the geometry (the int() truncations of RenderDepth and Crop,
  * numpy's clamping of slice ends) and inverts the rotation matrix in double, in warpAffine's own operation order.
  * items_host holds the B records; the call checks them, enqueues their upload into items_dev (room for B records, the caller's
@@ -389,6 +404,8 @@ typedef struct pn_augment_item {
     int render_w, render_h;       /* size of the render image                                                                        */
     int crop_x0, crop_y0, crop_x1, crop_y1;   /* Crop's slice of the render image, ends exclusive and already clamped to its size    */
     int src_w, src_h;             /* the size Resize sees: crop_x1 - crop_x0, crop_y1 - crop_y0                                      */
+    int hflip;                    /* Hflip (data_augmentation_2d3d.py:452-493), between RenderDepth and Crop: 1 = column x of the render
+                                     image reads column render_w - 1 - x, 0 = no flip                                                */
 } pn_augment_item;
 size_t pn_sizeof_augment_item(void);
 int pn_augment_resize(pn_ctx *ctx, const float *composed_dev, const pn_augment_item *items_host, pn_augment_item *items_dev,

@@ -51,7 +51,7 @@ class AugmentItem(C.Structure):
     """pn_augment_item"""
     _fields_ = [("m", C.c_double * 6), ("scale", C.c_float), ("render_x", C.c_int), ("render_y", C.c_int), ("render_w", C.c_int),
                 ("render_h", C.c_int), ("crop_x0", C.c_int), ("crop_y0", C.c_int), ("crop_x1", C.c_int), ("crop_y1", C.c_int),
-                ("src_w", C.c_int), ("src_h", C.c_int)]
+                ("src_w", C.c_int), ("src_h", C.c_int), ("hflip", C.c_int)]
 
 
 class NmsOpt(C.Structure):
@@ -65,8 +65,11 @@ class ParseCfg(C.Structure):
                 ("num_intermed_pts", C.c_int), ("downsample", C.c_int), ("input_size", C.c_int),
                 ("w_org", C.c_int), ("h_org", C.c_int),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
-                ("depth_mean", C.c_float), ("depth_std", C.c_float)]
+                ("depth_mean", C.c_float), ("depth_std", C.c_float),
+                ("z_readout", C.c_int), ("z_chn", C.c_int * 15)]
 
+
+PN_Z_READOUT_HEAT_WEIGHTED, PN_Z_READOUT_CELL = 0, 1
 
 # numpy mirror of pn_pose_frame / pn_yolo_frame (align=True reproduces the C struct layout; the
 # sizes are cross-checked against pn_sizeof_* at load time)
@@ -138,6 +141,7 @@ _SIGNATURES = {
     "pn_compose_depth": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "pn_rasterize_targets": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(TargetCfg), _vp, _vp, _vp, _vp, _vp]),
     "pn_sizeof_augment_item": (_sz, []),
+    "pn_sizeof_parse_cfg": (_sz, []),
     "pn_augment_resize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _f, _f, _vp]),
     "pn_train_set_precision": (_i, [_vp, _i]),
     "pn_train_ws_keep": (_i, [_vp, _i]),
@@ -244,6 +248,8 @@ def lib():
         raise PopnetError("pn_yolo_frame layout mismatch")
     if handle.pn_sizeof_augment_item() != C.sizeof(AugmentItem):
         raise PopnetError("pn_augment_item layout mismatch: C %d vs ctypes %d" % (handle.pn_sizeof_augment_item(), C.sizeof(AugmentItem)))
+    if handle.pn_sizeof_parse_cfg() != C.sizeof(ParseCfg):
+        raise PopnetError("pn_parse_cfg layout mismatch: C %d vs ctypes %d" % (handle.pn_sizeof_parse_cfg(), C.sizeof(ParseCfg)))
     _lib = handle
     return _lib
 

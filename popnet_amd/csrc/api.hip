@@ -151,6 +151,8 @@ int pn_preprocess(pn_ctx *ctx, const void *depth_dev, int depth_dtype, int B, in
     return PN_OK;
 }
 
+size_t pn_sizeof_parse_cfg(void) { return sizeof(pn_parse_cfg); }
+
 void pn_parse_cfg_default(pn_parse_cfg *cfg) {
     if (!cfg) return;
     cfg->thresh_heatmap = 0.1f;
@@ -166,6 +168,8 @@ void pn_parse_cfg_default(pn_parse_cfg *cfg) {
     cfg->cy = 320.62640380859375;
     cfg->depth_mean = 3.f;
     cfg->depth_std = 2.f;
+    cfg->z_readout = PN_Z_READOUT_HEAT_WEIGHTED;
+    for (int j = 0; j < PN_NUM_JOINTS; ++j) cfg->z_chn[j] = j;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Random training augmentation on the GPU: the image half of the reference's training transform
-//   Compose([Cvt2ndarray, Rotate(cx, cy), RenderDepth(cx, cy, max_ratio), Crop, Resize(S)])
-//   tpm/lib/datasets/data_augmentation_2d3d.py:411-448 (Rotate), :283-350 (RenderDepth), :94-128 (Crop), :497-522 (Resize)
+//   Compose([Cvt2ndarray, Rotate(cx, cy), RenderDepth(cx, cy, max_ratio), [Hflip,] Crop, Resize(S)])
+//   tpm/lib/datasets/data_augmentation_2d3d.py:411-448 (Rotate), :283-350 (RenderDepth), :452-493 (Hflip, the ITOP trainers), :94-128 (Crop),
+//   :497-522 (Resize)
 // followed by the clamp and the normalisation of KDH3D_Keypoints.__getitem__ (pn_preprocess's convention), as ONE launch per batch.
 // Every item carries its own geometry in a pn_augment_item record; all integer geometry (the int() truncations of RenderDepth and
 // Crop, numpy's clamping of slice ends) is decided on the host (popnet_amd/targets.py) -- the kernel never re-derives a truncation.
@@ -42,7 +43,8 @@ __device__ __forceinline__ float aug_rotated_pixel(const float *__restrict__ img
 
 // one pixel of the image Resize sees: (x, y) in the cropped render image
 __device__ __forceinline__ float aug_source_pixel(const float *__restrict__ img, int H, int W, const pn_augment_item &it, int x, int y) {
-    const int rx = x + it.crop_x0 + it.render_x, ry = y + it.crop_y0 + it.render_y;      // position in the rotated frame
+    const int cxr = x + it.crop_x0;                                                      // column of the render image Crop hands on
+    const int rx = (it.hflip ? it.render_w - 1 - cxr : cxr) + it.render_x, ry = y + it.crop_y0 + it.render_y;      // position in the rotated frame (Hflip: np.flip(axis=1) of the render image)
     if (rx < 0 || rx >= W || ry < 0 || ry >= H) return 0.f;                              // RenderDepth's zero image around the pasted frame
     return aug_rotated_pixel(img, H, W, it.m, rx, ry) * it.scale;
 }
@@ -90,6 +92,7 @@ int pn_augment_resize(pn_ctx *ctx, const float *composed_dev, const pn_augment_i
         for (int k = 0; k < 6; ++k) ok = ok && std::isfinite(it.m[k]) && std::fabs(it.m[k]) < 1.0e6;
         ok = ok && it.render_x > -65536 && it.render_x < 65536 && it.render_y > -65536 && it.render_y < 65536;
         ok = ok && it.crop_x0 >= 0 && it.crop_x0 < it.crop_x1 && it.crop_x1 <= it.render_w && it.crop_y0 >= 0 && it.crop_y0 < it.crop_y1 && it.crop_y1 <= it.render_h;
+        ok = ok && (it.hflip == 0 || it.hflip == 1);
         ok = ok && it.src_w == it.crop_x1 - it.crop_x0 && it.src_h == it.crop_y1 - it.crop_y0 && it.src_w >= 1 && it.src_h >= 1;
         if (!ok) return pn_set_error(ctx, PN_ERR_INVALID, "pn_augment_resize: item %d has inconsistent geometry", b);
         if (it.src_w == 2 * S && it.src_h == 2 * S)      // as pn_preprocess: cv::resize switches to INTER_AREA at exactly 2x decimation

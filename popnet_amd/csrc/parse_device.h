@@ -323,13 +323,27 @@ __device__ __forceinline__ int limb_score_pass(LimbLds<LF, N> &S, int &s_ncand, 
 // ---- per-joint read-out ----
 struct JointOut { double x2, y2, depth, X3, Y3, conf; };
 
-// One joint of one person: retrieve_depth_heat_weighted([int(x/f), int(y/f)], z*std+mean, heat, radius=1) on the joint's [h, w] heat and z maps,
-// the rescale to the original frame and the pinhole back-projection.  have == false (the person lacks the joint): (-1, -1, -1) and conf 0,
-// back-projected like any other value.
-__device__ __forceinline__ JointOut joint_readout(bool have, float peak_x, float peak_y, float peak_s, const float *__restrict__ hm,
-                                                  const float *__restrict__ zm, int h, int w, const pn_parse_cfg &cfg) {
+// Joint j of one person: its depth by the rule of cfg.z_readout, the rescale to the original frame and the pinhole back-projection.
+//   PN_Z_READOUT_HEAT_WEIGHTED  retrieve_depth_heat_weighted([int(x/f), int(y/f)], z*std+mean, heat, radius=1) on the joint's own [h, w] heat and z maps
+//   PN_Z_READOUT_CELL           z[z_chn[j]][int(y/f)][int(x/f)] * std + mean in float32 (evaluation_rtpose_light3d_itop.py:176-191); an index past the
+//                               last row / column (where the script raises IndexError) is clamped to the last cell: no other cell is read
+// heat_f / z_f: the frame's heat and pose-depth maps, channel-major [., h, w].  have == false (the person lacks the joint): (-1, -1, -1) and conf 0,
+// back-projected like any other value.  A negative fy (ITOP: Y = -(y - cy) z / f) needs no branch: IEEE division is sign-symmetric.
+__device__ __forceinline__ JointOut joint_readout(bool have, float peak_x, float peak_y, float peak_s, const float *__restrict__ heat_f,
+                                                  const float *__restrict__ z_f, int j, int h, int w, const pn_parse_cfg &cfg) {
     JointOut o = {-1.0, -1.0, -1.0, 0.0, 0.0, 0.0};
-    if (have) {
+    if (have && cfg.z_readout == PN_Z_READOUT_CELL) {
+        const double x = (double)peak_x, y = (double)peak_y, dsz = (double)cfg.downsample;
+        o.conf = (double)peak_s;
+        const int cx0 = min(max((int)(x / dsz), 0), w - 1), cy0 = min(max((int)(y / dsz), 0), h - 1);
+        const int zc = min(max(cfg.z_chn[j], 0), L_);      // checked on the host (pn_parse_check_cfg); the clamp keeps the load inside the map regardless
+        float dv = z_f[(size_t)zc * h * w + cy0 * w + cx0] * cfg.depth_std;      // posedepth *= depth_std; posedepth += depth_mean (float32)
+        dv = dv + cfg.depth_mean;
+        o.depth = (double)dv;
+        o.x2 = x / (double)cfg.input_size * (double)cfg.w_org;
+        o.y2 = y / (double)cfg.input_size * (double)cfg.h_org;
+    } else if (have) {
+        const float *__restrict__ hm = heat_f + (size_t)j * h * w, *__restrict__ zm = z_f + (size_t)j * h * w;
         const double x = (double)peak_x, y = (double)peak_y, dsz = (double)cfg.downsample;
         o.conf = (double)peak_s;
         const int cx0 = (int)(x / dsz), cy0 = (int)(y / dsz);

@@ -256,8 +256,7 @@ __global__ __launch_bounds__(256) void group_readout_kernel(const float *__restr
         const int r = __ffsll((long long)m) - 1;
         const int id = (int)rows[r][j];
         const int k = id - s_base[j];
-        const JointOut q = joint_readout(id >= 0, W.peak_x[j][max(k, 0)], W.peak_y[j][max(k, 0)], W.peak_s[j][max(k, 0)], heat_b + (size_t)j * hw,
-                                         z_b + (size_t)j * hw, h, w, cfg);
+        const JointOut q = joint_readout(id >= 0, W.peak_x[j][max(k, 0)], W.peak_y[j][max(k, 0)], W.peak_s[j][max(k, 0)], heat_b, z_b, j, h, w, cfg);
         const double x2 = q.x2, y2 = q.y2, depth = q.depth, X3 = q.X3, Y3 = q.Y3, conf = q.conf;
         F.joints_2d[o][j][0] = x2;
         F.joints_2d[o][j][1] = y2;

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void big_group_kernel(const float *__restrict_
             W.o_person_count[o] = (int)rows[(size_t)r * RW + J_ + 1];
         }
         const size_t k = (size_t)j * hw + max(id - s_base[j], 0);
-        const JointOut q = joint_readout(id >= 0, W.px[k], W.py[k], W.ps[k], heat + (size_t)j * hw, z + (size_t)j * hw, h, w, cfg);
+        const JointOut q = joint_readout(id >= 0, W.px[k], W.py[k], W.ps[k], heat, z, j, h, w, cfg);
         const double x2 = q.x2, y2 = q.y2, depth = q.depth, X3 = q.X3, Y3 = q.Y3, conf = q.conf;
         W.o_j2d[2 * (size_t)t + 0] = x2;
         W.o_j2d[2 * (size_t)t + 1] = y2;

@@ -63,6 +63,12 @@ inline int pn_parse_check_cfg(pn_ctx *ctx, const char *who, const pn_parse_cfg *
     if (pn_parse_factor_log2(cfg->downsample) < 0 || !pn_parse_pts_ok(cfg->num_intermed_pts))
         return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: downsample %d / num_intermed_pts %d: supported are downsample in {" PN_PARSE_FACTORS_TEXT "} and %d..%d intermediate points",
                             who, cfg->downsample, cfg->num_intermed_pts, PN_PARSE_MIN_PTS, PN_PARSE_MAX_PTS);
+    if (cfg->z_readout != PN_Z_READOUT_HEAT_WEIGHTED && cfg->z_readout != PN_Z_READOUT_CELL)
+        return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: z_readout %d is neither PN_Z_READOUT_HEAT_WEIGHTED nor PN_Z_READOUT_CELL", who, cfg->z_readout);
+    if (cfg->z_readout == PN_Z_READOUT_CELL)
+        for (int j = 0; j < J_; ++j)
+            if (cfg->z_chn[j] < 0 || cfg->z_chn[j] > L_)      // the pose-depth map has L + 1 channels
+                return pn_set_error(ctx, PN_ERR_INVALID, "%s: z_chn[%d] = %d is not a channel of the pose-depth map (0..%d)", who, j, cfg->z_chn[j], L_);
     return PN_OK;
 }
 

@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, profiles
 from .config import INTRINSICS, NUM_PARTS
 
 
@@ -67,8 +67,11 @@ ABLATION_KEYS = ("human_pred_set_3d_read_raw_depth", "human_pred_set_3d_perfect_
                  "human_gt_set_2d_visible")
 
 
-def pose_records_to_lists(recs, overflow=None, ablation=None):
-    """pn_pose_frame records -> the per-frame entries of human_pred_set_{2d,3d,visibility,part_conf} (float64 lists,
+def pose_records_to_lists(recs, overflow=None, ablation=None, profile=None):
+    """profile (popnet_amd.profiles, None = MP3DHP): a single-person profile (ITOP) names the lists as evaluation_rtpose_light3d_itop.py:294-298
+    does -- human_pred_set_2d, human_pred_set_3d, visibility_pred_set (all parsed persons of a frame, as in that script) -- see
+    _itop_pose_lists; the records themselves already carry the profile's read-out, rescale and back-projection (the engine's parse cfg).
+    pn_pose_frame records -> the per-frame entries of human_pred_set_{2d,3d,visibility,part_conf} (float64 lists,
     [-1, -1] / Z = -1 for joints a person does not have, exactly what the evaluation script appends).
     overflow: {frame index: result of utils.paf_to_pose.parse_paf_unbounded} for the frames whose record carries an overflow
     status (PoseEngine.predict_lists fills it); without it such a frame raises -- it is never truncated silently.
@@ -76,6 +79,13 @@ def pose_records_to_lists(recs, overflow=None, ablation=None):
     197-313) -- {"pred_raw": float64 [F, PN_MAX_PERSONS, 15, 3], "perfect_map" / "perfect_raw": float64 [F, Gmax, 15, 3], "gt_2d": per
     frame the labels' [n_g][15][2], "overflow_raw": {frame index: [P, 15, 3]} for the frames in `overflow`} -- adds ABLATION_KEYS:
     the raw arm follows the predicted persons, the perfect_* arms and human_gt_set_2d_visible the ground-truth persons."""
+    prof = profiles.get(profile)
+    if prof.single_person:
+        if ablation is not None:
+            raise _lib.PopnetError("the depth-ablation arms are the MP-3DHP script's; the %s profile has none" % prof.name)
+        full = pose_records_to_lists(recs, overflow)
+        return {"human_pred_set_2d": full["human_pred_set_2d"], "human_pred_set_3d": full["human_pred_set_3d"],
+                "visibility_pred_set": full["human_pred_set_visibility"]}
     out = {"human_pred_set_2d": [], "human_pred_set_3d": [], "human_pred_set_visibility": [], "human_pred_set_part_conf": []}
     if ablation is not None:
         if len(ablation["gt_2d"]) < len(recs) or any(len(ablation[k]) < len(recs) for k in ("pred_raw", "perfect_map", "perfect_raw")):
@@ -115,8 +125,28 @@ def pose_records_to_lists(recs, overflow=None, ablation=None):
     return out
 
 
-def yolo_records_to_lists(recs):
-    """pn_yolo_frame records -> human_pred_set_{2d,3d,part_conf} of evaluation_yolo_posenet_kdh3d_mpreal.py:182-247."""
+def yolo_records_to_lists(recs, profile=None):
+    """pn_yolo_frame records -> human_pred_set_{2d,3d,part_conf} of evaluation_yolo_posenet_kdh3d_mpreal.py:182-247.
+    A single-person profile (ITOP): human_pred_set_{2d,3d} of evaluation_yolo_posenet_itop.py:169-207 -- per frame ONE person, the first
+    detection of the record (build the YoloEngine with conf_threshold=0.1 and the profile, as that script parses), or, without a detection,
+    the script's placeholder: joints (-1, -1) and depth -1 as float64, rescaled and back-projected like any other value
+    (x = -1 / input_size * w_org, X = (x - cx) / f * -1, Y negated)."""
+    prof = profiles.get(profile)
+    if prof.single_person:
+        out = {"human_pred_set_2d": [], "human_pred_set_3d": []}
+        for fr in recs:
+            # bit 0 (more than PN_YOLO_MAX_DET survivors) truncates first-come in the reference's order: the first person, the only one
+            # this script keeps, is exact all the same (an untrained net at conf_threshold 0.1 sets it on every frame)
+            if int(fr["status"]) & ~1:
+                raise _lib.PopnetError("yolo record overflow (status=%d)" % int(fr["status"]))
+            if int(fr["n_det"]) > 0:
+                out["human_pred_set_2d"].append([np.asarray(fr["joints_2d"][0]).tolist()])
+                out["human_pred_set_3d"].append([np.asarray(fr["joints_3d"][0]).tolist()])
+            else:
+                j2, j3 = yolo_placeholder_person(prof)
+                out["human_pred_set_2d"].append([j2.tolist()])
+                out["human_pred_set_3d"].append([j3.tolist()])
+        return out
     out = {"human_pred_set_2d": [], "human_pred_set_3d": [], "human_pred_set_part_conf": []}
     for fr in recs:
         if int(fr["status"]):
@@ -126,6 +156,20 @@ def yolo_records_to_lists(recs):
         out["human_pred_set_3d"].append(np.asarray(fr["joints_3d"][:n]).tolist())
         out["human_pred_set_part_conf"].append(np.repeat(np.asarray(fr["bbox"][:n, 4:5], dtype=np.float64), NUM_PARTS, axis=1).tolist())
     return out
+
+
+def yolo_placeholder_person(profile, input_size=224):
+    """evaluation_yolo_posenet_itop.py:175-203 for a frame without a detection: np.ones * -1 joints and depths (float64) through the
+    script's rescale, pos_3d_from_2d_and_depth (common.py: (x - cx) / fx * Z) and the Y flip -- the profile's negative fy."""
+    prof = profiles.get(profile)
+    human = np.ones([NUM_PARTS, 2]) * (-1)
+    depth = np.ones(NUM_PARTS) * (-1)
+    human[:, 0] = human[:, 0] / input_size * prof.w_org
+    human[:, 1] = human[:, 1] / input_size * prof.h_org
+    k = prof.intrinsics
+    X = (human[:, 0] - k["cx"]) / k["fx"] * depth
+    Y = (human[:, 1] - k["cy"]) / k["fy"] * depth
+    return human, np.stack([X, Y, depth], axis=1)
 
 
 def run_sweep(engine, frames, batch_size=32, rank=0, world=1, drop_last=False, group=None, ablation=False):
@@ -231,12 +275,14 @@ def run_sweep_streaming(se, frames, batch_size=32, rank=0, world=1, drop_last=Fa
     return local.cpu().numpy().view(dtype).reshape(-1)
 
 
-def eval_data_from_records(recs, frames, ablation=None):
-    """The eval_data.json dictionary for a finished sweep (predictions from the records, ground truth from the labels).
+def eval_data_from_records(recs, frames, ablation=None, profile=None):
+    """profile: the dataset profile the records were made with (None = MP3DHP); it selects the keys of the profile's evaluation script.
+    The eval_data.json dictionary for a finished sweep (predictions from the records, ground truth from the labels).
     ablation: the arms run_sweep(..., ablation=True) returned next to the records -- all ten keys of the reference's ablation script."""
     if ablation is not None and recs.dtype != _lib.POSE_FRAME_DTYPE:
         raise _lib.PopnetError("the depth-ablation arms exist for the Open-Pose+ records only")
-    data = pose_records_to_lists(recs, ablation=ablation) if recs.dtype == _lib.POSE_FRAME_DTYPE else yolo_records_to_lists(recs)
+    data = (pose_records_to_lists(recs, ablation=ablation, profile=profile) if recs.dtype == _lib.POSE_FRAME_DTYPE
+            else yolo_records_to_lists(recs, profile=profile))
     g2, g3 = frames.ground_truth()
     data["human_gt_set_2d"], data["human_gt_set_3d"] = g2[:len(recs)], g3[:len(recs)]
     return data

@@ -130,6 +130,30 @@ def eval_human_dataset_2d_PCKh(humans_pred_set, humans_gt_set, head_id, neck_id,
     return _pck_summary(D, H, V.sum(axis=0))
 
 
+def eval_human_dataset_2d(humans_pred_set, humans_gt_set, num_joints=15, dist_th=10.0, iou_th=0.5, human_gt_set_visibility=None):
+    """evaluate/eval_pose_mp.py:6-66, the plain-threshold form the ITOP scripts call with dist_th = 0.02 * sqrt(w_org^2 + h_org^2)
+    -> (joint_avg_dist[J] in pixels, joint_KCP[J]).  A matched joint is a hit when its distance is < dist_th; the denominator is the
+    number of ground-truth persons, or, with a visibility set, the number of visible ground-truth joints."""
+    assert len(humans_gt_set) == len(humans_pred_set)
+    D, V, samples = [], [], 0
+    for i, (gt, pred) in enumerate(zip(humans_gt_set, humans_pred_set)):
+        samples += len(gt)
+        if len(gt) == 0:
+            continue
+        d = _match(pred, gt, pred, gt, iou_th, False)
+        if human_gt_set_visibility is not None:
+            vis = np.asarray(human_gt_set_visibility[i], dtype=np.float64)
+            d[vis == 0] = -1
+            V.append(vis)
+        D.append(d)
+    if not D:
+        return [float("nan")] * num_joints, [float("nan")] * num_joints
+    D = np.concatenate(D)
+    hits = (D >= 0) & (D < dist_th)
+    denom = np.concatenate(V).sum(axis=0) if human_gt_set_visibility is not None else float(samples)
+    return _pck_summary(D, hits, denom)
+
+
 def eval_human_dataset_3d(humans_pred_set_2d, humans_gt_set_2d, humans_pred_set_3d, humans_gt_set_3d, num_joints=15,
                           dist_th=0.1, iou_th=0.5, human_gt_set_visibility=None):
     """eval_pck.py:313-374 -> (joint_avg_dist[J] in metres, joint_KCP[J])."""

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, synth
+from . import _lib, profiles, synth
 from .config import DEPTH_MAX, DEPTH_MEAN, DEPTH_STD, INTRINSICS, default_cfg
 from .network._hipnet import _PREC
 from .network.rtpose_light3d import rtpose_light3d
@@ -25,8 +25,10 @@ from .utils.paf_to_pose import make_parse_cfg
 
 class PoseEngine:
     def __init__(self, precision="bf16", state_dict=None, device=None, max_batch=32, input_size=224,
-                 w_org=480, h_org=640, intrinsics=INTRINSICS, weight_seed=0, private_ctx=False, calib_gain=1.0, parse_config=None):
-        """private_ctx: give this engine its own pn_ctx (parse workspace), so that several engines can
+                 w_org=None, h_org=None, intrinsics=None, weight_seed=0, private_ctx=False, calib_gain=1.0, parse_config=None, profile=None):
+        """profile: the dataset profile (popnet_amd.profiles; None = MP3DHP) -- the depth clamp and normalisation of the pre-processing, the
+        frame size, intrinsics and joint depth read-out of the parse; w_org / h_org / intrinsics override the profile's.
+        private_ctx: give this engine its own pn_ctx (parse workspace), so that several engines can
         run concurrently on different HIP streams (bench.py pipelines consecutive batches that way).
         parse_config: a reference-style config namespace (TEST.THRESH_HEATMAP, TEST.THRESH_PAF, TEST.NUM_INTERMED_PTS_BETWEEN_KEYPOINTS,
         MODEL.DOWNSAMPLE, MODEL.NUM_KEYPOINTS) for the parse in place of default_cfg(); None = the defaults and the kernels built for them.
@@ -37,6 +39,7 @@ class PoseEngine:
             raise _lib.PopnetError("PoseEngine needs a GPU: the HIP path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_batch, self.S = int(max_batch), int(input_size)
+        self.profile = profiles.get(profile)
         self.model = rtpose_light3d(15, 14, 2, input_dim=1).eval()
         if state_dict is None:
             synth.load_synth_weights(self.model, seed=weight_seed)
@@ -47,7 +50,7 @@ class PoseEngine:
         self.ctx = _lib.Context(self.device.index) if private_ctx else _lib.Context.for_device(self.device.index)
         self.L = _lib.lib()
         self.cfg = make_parse_cfg(default_cfg() if parse_config is None else parse_config, input_size=self.S, w_org=w_org, h_org=h_org,
-                                  intrinsics=intrinsics, depth_mean=DEPTH_MEAN, depth_std=DEPTH_STD)
+                                  intrinsics=intrinsics, profile=self.profile)
         # a PRIVATE context's parse scratch is sized once for max_batch and never moves again (a captured graph keeps the
         # pointer).  The shared per-device context keeps growing on demand: fixing it here would make an unrelated later
         # call with a larger batch (utils.paf_to_pose.parse_paf_batch) fail depending on construction order
@@ -116,8 +119,8 @@ class PoseEngine:
             raise _lib.PopnetError("batch %d exceeds max_batch %d" % (B, self.max_batch))
         depth = depth.contiguous()
         self.ctx.check(self.L.pn_preprocess(self.ctx.handle, C.c_void_p(depth.data_ptr()), dt, B, H, W,
-                                            C.c_void_p(self.x.data_ptr()), self.S, float(DEPTH_MAX), float(DEPTH_MEAN),
-                                            float(DEPTH_STD), _lib.current_stream_ptr(self.device)), "pn_preprocess")
+                                            C.c_void_p(self.x.data_ptr()), self.S, float(self.profile.depth_max), float(self.profile.depth_mean),
+                                            float(self.profile.depth_std), _lib.current_stream_ptr(self.device)), "pn_preprocess")
         return B
 
     def forward(self, B):
@@ -135,7 +138,7 @@ class PoseEngine:
             raise _lib.PopnetError("batch %d exceeds max_batch %d" % (B, self.max_batch))
         depth = depth.contiguous()                                   # (a copy, if one is made, is stream-ordered like every torch allocation)
         dt = _lib.PN_DEPTH_F16 if depth.dtype == torch.float16 else _lib.PN_DEPTH_F32
-        return B, (C.c_void_p(depth.data_ptr()), dt, B, H, W, float(DEPTH_MAX), float(DEPTH_MEAN), float(DEPTH_STD))
+        return B, (C.c_void_p(depth.data_ptr()), dt, B, H, W, float(self.profile.depth_max), float(self.profile.depth_mean), float(self.profile.depth_std))
 
     def forward_frames(self, depth):
         """preprocess + forward as ONE call on the raw frames (pn_rtpose_forward_frames: the stem resizes / clamps / normalises its own
@@ -181,7 +184,7 @@ class PoseEngine:
         from .dataset import pose_records_to_lists
         from .utils.paf_to_pose import parse_paf_unbounded
         over = {i: parse_paf_unbounded(self.heat[i], self.paf[i], self.z[i], self.cfg) for i in range(len(recs)) if int(recs[i]["status"])}
-        return pose_records_to_lists(recs, over)
+        return pose_records_to_lists(recs, over, profile=self.profile)
 
     # ---- depth-ablation arms (evaluation_rtpose_light3d_kdh3d_mpreal_ablation.py:197-299) ----------
     def predict_ablation(self, depth, gt_2d, gmax=None):
@@ -289,14 +292,15 @@ class YoloEngine:
     tpm/evaluate/evaluation_yolo_posenet_kdh3d_mpreal.py:137-217 minus Python."""
 
     def __init__(self, precision="bf16", state_dict=None, device=None, max_batch=32, input_size=224,
-                 w_org=480, h_org=640, intrinsics=INTRINSICS, weight_seed=1, anchors=None,
-                 conf_threshold=0.5, nms_threshold=0.5, private_ctx=False):
+                 w_org=None, h_org=None, intrinsics=None, weight_seed=1, anchors=None,
+                 conf_threshold=0.5, nms_threshold=0.5, private_ctx=False, profile=None):
         from .config import YOLO_ANCHORS
         from .network.yolo_posenet import YoloPoseNet
         if not torch.cuda.is_available():
             raise _lib.PopnetError("YoloEngine needs a GPU: the HIP path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_batch, self.S = int(max_batch), int(input_size)
+        self.profile = profiles.get(profile)
         self.anchors = list(YOLO_ANCHORS if anchors is None else anchors)
         self.model = YoloPoseNet(15, input_dim=1, anchors=self.anchors).eval()
         if state_dict is None:
@@ -307,8 +311,7 @@ class YoloEngine:
         self.model.precision = precision
         self.ctx = _lib.Context(self.device.index) if private_ctx else _lib.Context.for_device(self.device.index)
         self.L = _lib.lib()
-        self.cfg = make_parse_cfg(default_cfg(), input_size=self.S, w_org=w_org, h_org=h_org, intrinsics=intrinsics,
-                                  depth_mean=DEPTH_MEAN, depth_std=DEPTH_STD)
+        self.cfg = make_parse_cfg(default_cfg(), input_size=self.S, w_org=w_org, h_org=h_org, intrinsics=intrinsics, profile=self.profile)
         self.conf_threshold, self.nms_threshold = float(conf_threshold), float(nms_threshold)
         flat = [float(v) for a in self.anchors for v in a]
         self._anchors_c = (C.c_float * len(flat))(*flat)
@@ -348,7 +351,7 @@ class YoloEngine:
         frames = self.frames if frames is None else frames
         h = self.S // 16
         self.ctx.check(self.L.pn_parse_yolo(self.ctx.handle, C.c_void_p(self.out.data_ptr()), B, h, h, self._anchors_c,
-                                            len(self.anchors), 15, self.S, self.S, float(DEPTH_MEAN), float(DEPTH_STD),
+                                            len(self.anchors), 15, self.S, self.S, float(self.profile.depth_mean), float(self.profile.depth_std),
                                             self.conf_threshold, self.nms_threshold, 0, C.byref(self.cfg),
                                             C.c_void_p(frames.data_ptr()), _lib.current_stream_ptr(self.device)),
                        "pn_parse_yolo")
@@ -548,14 +551,18 @@ class StreamingEngine:
     wire=True: what leaves the GPU per step is the compact pn_pose_wire form (6.2 KB instead of 33 KB per frame; PAF
     path only): `host_records()` then holds pn_pose_wire records, `records()` still the full pn_pose_frame ones.
 
-    Engine arguments (PoseEngine's parse_config among them) pass through **engine_kw to every slot's engine.
+    Engine arguments (PoseEngine's parse_config and the dataset `profile` among them) pass through **engine_kw to every slot's engine;
+    frame_hw=None takes the profile's frame size (640 x 480 for the default MP3DHP).
 
     Every engine gets its own context and its net is locked after the warm-up (pn_net_lock): nothing a captured graph
     points at (parse scratch, launch descriptors) can be reallocated or rewritten by a later eager call."""
 
-    def __init__(self, engine_cls=None, depth=3, frame_hw=(640, 480), frame_dtype=torch.float16, graph=True, pool=1,
+    def __init__(self, engine_cls=None, depth=3, frame_hw=None, frame_dtype=torch.float16, graph=True, pool=1,
                  wire=False, **engine_kw):
         engine_cls = PoseEngine if engine_cls is None else engine_cls
+        if frame_hw is None:
+            prof = profiles.get(engine_kw.get("profile"))
+            frame_hw = (prof.h_org, prof.w_org)
         self.depth = max(1, int(depth))
         self.pool = max(1, int(pool))
         engine_kw["private_ctx"] = True

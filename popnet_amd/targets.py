@@ -5,6 +5,9 @@ Host-side mirror of the reference's training dataset item, batched and on the de
   get_ground_truth              ...:318-401 (putGaussianMaps heatmap.py:20-36, putVecMaps paf.py:18-69, putJointZ posemap.py:83-106)
   Compose([Cvt2ndarray, Resize]) third_party_methods/lib/datasets/data_augmentation_2d3d.py:70-89,497-522
   Compose([Cvt2ndarray, Rotate, RenderDepth, Crop, Resize])   ...:411-448,283-350,94-128 -- the random training transform
+  Compose([Cvt2ndarray, Rotate(), RenderDepth(), Hflip(swap), Crop(), Resize])   ...:452-493 -- the ITOP trainers' transform; the single-person
+                                 batches without composition (itop_batch, itop_batch_yolo, ItopSet) mirror datasets_itop_rtpose.py / datasets_itop.py
+Dataset constants (depth clamp and normalisation, augmentation defaults) come from a `profile=` argument (popnet_amd/profiles.py, default MP3DHP).
 The arithmetic lives in csrc/targets.hip (pn_compose_depth, pn_rasterize_targets), csrc/augment.hip (pn_augment_resize) and
 csrc/api.hip (pn_preprocess); this module only owns tensors and the call order.  There is no CPU fallback: images must be device
 tensors.  The random transform's LABEL half (15 joints per person) and its integer geometry are host work, in numpy, mirroring the
@@ -17,7 +20,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, profiles
 from .config import DEPTH_MAX, DEPTH_MEAN, DEPTH_STD
 
 NUM_JOINTS, NUM_LIMBS = 15, 14
@@ -35,11 +38,14 @@ def _input_xy(input_size):
     return int(input_size), int(input_size)
 
 
-def target_cfg(input_size=224, stride=8, z_radius=2, sigma=7.0):
+def target_cfg(input_size=224, stride=8, z_radius=2, sigma=7.0, profile=None):
+    """profile (popnet_amd.profiles, None = MP3DHP): the depth clamp and normalisation of the z maps."""
+    prof = profiles.get(profile)
     cfg = _lib.TargetCfg()
     _lib.lib().pn_target_cfg_default(C.byref(cfg))
     cfg.input_x, cfg.input_y = _input_xy(input_size)
     cfg.stride, cfg.z_radius, cfg.sigma = int(stride), int(z_radius), float(sigma)
+    cfg.depth_max, cfg.depth_mean, cfg.depth_std = float(prof.depth_max), float(prof.depth_mean), float(prof.depth_std)
     return cfg
 
 
@@ -66,7 +72,7 @@ def compose_depth(fg_depth, fg_mask, n_src, bg, depth_max=DEPTH_MAX):
     return out
 
 
-def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, stride=8, z_radius=2, sigma=7.0):
+def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, stride=8, z_radius=2, sigma=7.0, profile=None):
     """get_ground_truth for a batch.  kp2d [B,P,15,2] float32 (network-input pixels), kp_z [B,P,15] float64 (metres), n_persons [B]
     int32, depth_resize [B,h,w] float32 -> (heat [B,16,h,w], paf [B,28,h,w], z [B,15,h,w], fg [B,15,h,w]) float32.
     input_size: an int, or (input_x, input_y) for a network input that is not square; h = input_y // stride, w = input_x // stride."""
@@ -87,7 +93,7 @@ def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, strid
     paf = torch.empty((B, 2 * NUM_LIMBS, gh, gw), dtype=torch.float32, device=dev)
     z = torch.empty((B, NUM_JOINTS, gh, gw), dtype=torch.float32, device=dev)
     fg = torch.empty((B, NUM_JOINTS, gh, gw), dtype=torch.float32, device=dev)
-    cfg = target_cfg(input_size, stride, z_radius, sigma)
+    cfg = target_cfg(input_size, stride, z_radius, sigma, profile)
     ctx = _ctx(dev)
     ctx.check(_lib.lib().pn_rasterize_targets(ctx.handle, C.c_void_p(kp2d.data_ptr()), C.c_void_p(kp_z.data_ptr()), C.c_void_p(n_persons.data_ptr()),
                                               B, P, C.c_void_p(depth_resize.data_ptr()), C.byref(cfg), C.c_void_p(heat.data_ptr()),
@@ -96,7 +102,9 @@ def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, strid
     return heat, paf, z, fg
 
 
-def yolo_target_cfg(input_size=224, stride_prior=16, anchors=((6., 3.), (12., 6.)), num_joints=NUM_JOINTS, noobject_scale=0.1, object_scale=1.0):
+def yolo_target_cfg(input_size=224, stride_prior=16, anchors=((6., 3.), (12., 6.)), num_joints=NUM_JOINTS, noobject_scale=0.1, object_scale=1.0,
+                    profile=None):
+    prof = profiles.get(profile)
     cfg = _lib.YoloTargetCfg()
     _lib.lib().pn_yolo_target_cfg_default(C.byref(cfg))
     if not 1 <= len(anchors) <= _lib.PN_YOLO_MAX_ANCHORS:
@@ -106,12 +114,12 @@ def yolo_target_cfg(input_size=224, stride_prior=16, anchors=((6., 3.), (12., 6.
     for a, (aw, ah) in enumerate(anchors):
         cfg.anchors[a][0], cfg.anchors[a][1] = float(aw), float(ah)
     cfg.noobject_scale, cfg.object_scale = float(noobject_scale), float(object_scale)
-    cfg.depth_mean, cfg.depth_std = float(DEPTH_MEAN), float(DEPTH_STD)
+    cfg.depth_mean, cfg.depth_std = float(prof.depth_mean), float(prof.depth_std)
     return cfg
 
 
 def prior_targets(boxes, kp2d, kp_z, pose_weight, n_persons, input_size=224, stride_prior=16, anchors=((6., 3.), (12., 6.)), noobject_scale=0.1,
-                  object_scale=1.0):
+                  object_scale=1.0, profile=None):
     """The YOLO training targets of a batch: build_prior_targets + bbox_ious (tpm/lib/datasets/datasets_kdh3d_mpaug.py:353-417,505-533, CR),
     fed like get_ground_truth feeds it (:556-585).  boxes [B,P,4] float64 (x0, y0, x1, y1 in network-input pixels, as Resize leaves
     ann['bbox']), kp2d [B,P,J,2] float32 (network-input pixels), kp_z [B,P,J] float64 (metres), pose_weight [B,P] float64, n_persons [B]
@@ -127,7 +135,7 @@ def prior_targets(boxes, kp2d, kp_z, pose_weight, n_persons, input_size=224, str
             or n_persons.shape != (B,) or B < 1):
         raise _lib.PopnetError("prior_targets: shape mismatch")
     dev = kp2d.device
-    cfg = yolo_target_cfg(input_size, stride_prior, anchors, J, noobject_scale, object_scale)
+    cfg = yolo_target_cfg(input_size, stride_prior, anchors, J, noobject_scale, object_scale, profile)
     A = len(anchors)
     g = int(input_size / stride_prior)
     boxes, kp2d, kp_z, pose_weight, n_persons = (t.contiguous() for t in (boxes, kp2d, kp_z, pose_weight, n_persons))
@@ -150,7 +158,7 @@ def _resize(frames, S, depth_max):
     return out[:, 0]
 
 
-def augmentation(rot, a, crops, H, W, cx, cy, input_size=224):
+def augmentation(rot, a, crops, H, W, cx, cy, input_size=224, hflip=False, swap_indices=None):
     """One item's random transform from explicit values: rot (degrees, Rotate), a (the ratio RenderDepth draws), crops = (left, right,
     top, bottom) fractions (Crop), for H x W frames with the intrinsics' principal point (cx, cy).  -> dict with the values, the
     forward rotation matrix (labels), the inverted one (image, for the kernel) and every integer the chain derives:
@@ -158,8 +166,13 @@ def augmentation(rot, a, crops, H, W, cx, cy, input_size=224):
       render_x/_y/_w/_h   the render image in the rotated frame (slice with numpy's clamping for a <= 1, zero image with the frame
                       pasted at (dy, dx) otherwise);   crop_bounds   (xmin, ymin, xmax, ymax) of Crop;   crop_x0.. the clamped slice
       src_w, src_h    the size Resize sees.
+    hflip: Hflip's coin came up (data_augmentation_2d3d.py:452-493, between RenderDepth and Crop): the render image is mirrored left to
+    right; swap_indices (the profile's get_swap_part_indices()) is then required -- the labels' left / right joints trade places.
     Nothing here touches the GPU.  A geometry the reference itself cannot run (the paste does not fit, an empty image) raises."""
     rot, a_drawn, crops = float(rot), float(a), tuple(float(c) for c in crops)
+    hflip = bool(hflip)
+    if hflip and (swap_indices is None or sorted(int(i) for i in swap_indices) != list(range(NUM_JOINTS))):
+        raise _lib.PopnetError("augmentation: hflip needs swap_indices, a permutation of the %d joints" % NUM_JOINTS)
     cx, cy, H, W = float(cx), float(cy), int(H), int(W)
     # getRotationMatrix2D: the centre is a Point2f; alpha, beta in double.  This and the inversion below are the product's own copy of
     # what tests/cv2_warp_reference.py restates; tests/test_augment_reference.py compares inv_mat with that restatement, and the
@@ -214,16 +227,19 @@ def augmentation(rot, a, crops, H, W, cx, cy, input_size=224):
     return dict(rot=rot, a=a_drawn, crops=crops, cx=cx, cy=cy, H=H, W=W, input_size=int(input_size), rot_mat=fwd, inv_mat=tuple(m),
                 render_corner=(new_xmin, new_ymin, new_xmax, new_ymax), render_a=a, render_x=render_x, render_y=render_y,
                 render_w=render_w, render_h=render_h, crop_bounds=(c_xmin, c_ymin, c_xmax, c_ymax), crop_x0=cx0, crop_y0=cy0,
-                crop_x1=cx1, crop_y1=cy1, src_w=cx1 - cx0, src_h=cy1 - cy0)
+                crop_x1=cx1, crop_y1=cy1, src_w=cx1 - cx0, src_h=cy1 - cy0, hflip=hflip,
+                swap_indices=[int(i) for i in swap_indices] if hflip else None)
 
 
-def draw_augmentation(H, W, cx, cy, min_ratio=0.7, max_ratio=1.7, max_crop=0.1, input_size=224):
+def draw_augmentation(H, W, cx, cy, min_ratio=0.7, max_ratio=1.7, max_crop=0.1, input_size=224, hflip=False, swap_indices=None):
     """Draws one item's transform from Python's `random` in the reference's order -- Rotate: uniform(-10, 10); RenderDepth:
-    uniform(min_ratio, max_ratio); Crop: four uniform(0, max_crop) for left, right, top, bottom -- and derives its geometry."""
+    uniform(min_ratio, max_ratio); with hflip (the ITOP trainers' Hflip) the coin uniform(0, 1) >= 0.5; Crop: four uniform(0, max_crop)
+    for left, right, top, bottom -- and derives its geometry.  Without hflip no coin is drawn: the six draws of the MP-3DHP chain."""
     rot = random.uniform(-10, 10)
     a = random.uniform(min_ratio, max_ratio)
+    flip = (random.uniform(0, 1) >= 0.5) if hflip else False
     crops = tuple(random.uniform(0, max_crop) for _ in range(4))
-    return augmentation(rot, a, crops, H, W, cx, cy, input_size)
+    return augmentation(rot, a, crops, H, W, cx, cy, input_size, hflip=flip, swap_indices=swap_indices if flip else None)
 
 
 class AugmentationBatch:
@@ -243,13 +259,19 @@ class AugmentationBatch:
             r.scale = float(np.float32(it["render_a"]))
             for k in ("render_x", "render_y", "render_w", "render_h", "crop_x0", "crop_y0", "crop_x1", "crop_y1", "src_w", "src_h"):
                 setattr(r, k, it[k])
+            r.hflip = 1 if it.get("hflip") else 0
 
     def __len__(self):
         return len(self.items)
 
-    def transform_labels(self, kp2d_org, kp3d, boxes=None):
+    def transform_labels(self, kp2d_org, kp3d, boxes=None, visible=None):
         """kp2d_org [B,P,15,2] float32 (original pixels), kp3d [B,P,15,3] float64, boxes [B,P,4] float64 (original pixels) or None, as
         host arrays -> (kp2d [B,P,15,2] float32 in network-input pixels, kp_z [B,P,15] float64, boxes [B,P,4] float64 or None).
+        visible [B,P,15] ('visible_joints') or None: when given, a fourth result, the array with Hflip's left / right swap applied.
+        Hflip (items whose coin came up), after RenderDepth and before Crop, the reference's rule as written: x' = -x + width with width
+        the render image's width (NOT width - 1: one pixel off the mirrored pixel centre), then the left / right swap of the joints and
+        of visible_joints, bbox = [-x1 + width, y0, -x0 + width, y1]; 3D X is not negated and the 3D joints are not swapped
+        (is_3d=False), so kp_z stays in the order of the labels.
         Rotate: homographic_transform of the float32 joints by the float64 3x3 (lib/utils/common.py:96-104), assigned back to float32;
         boxes are NOT rotated, as in the reference.  RenderDepth: minus its corner, z times the recomputed a (float64).  Crop: minus its
         corner.  Resize: times S / w, S / h of the item (float32 joints times a Python float; boxes in float64).  Padding slots are
@@ -257,6 +279,7 @@ class AugmentationBatch:
         kp = np.array(kp2d_org, dtype=np.float32)
         kz = np.array(np.asarray(kp3d)[..., 2], dtype=np.float64)
         bx = None if boxes is None else np.array(boxes, dtype=np.float64)
+        vs = None if visible is None else np.array(visible)
         if kp.shape[0] != len(self.items):
             raise _lib.PopnetError("AugmentationBatch: %d items for a batch of %d" % (len(self.items), kp.shape[0]))
         for b, it in enumerate(self.items):
@@ -271,6 +294,11 @@ class AugmentationBatch:
                 j[:, 0], j[:, 1] = trans[0, :] / trans[2, :], trans[1, :] / trans[2, :]
                 j[:, 0] -= ox
                 j[:, 1] -= oy
+                if it.get("hflip"):
+                    j[:, 0] = - j[:, 0] + it["render_w"]
+                    j[:] = j[it["swap_indices"], :]
+                    if vs is not None:
+                        vs[b, p] = vs[b, p][it["swap_indices"]]
                 j[:, 0] -= qx
                 j[:, 1] -= qy
                 j[:, 0] *= wr
@@ -279,20 +307,27 @@ class AugmentationBatch:
             if bx is not None:
                 bx[b, :, 0:4:2] -= ox
                 bx[b, :, 1:4:2] -= oy
+                if it.get("hflip"):
+                    xmin, xmax = -bx[b, :, 2] + it["render_w"], -bx[b, :, 0] + it["render_w"]
+                    bx[b, :, 0], bx[b, :, 2] = xmin, xmax
                 bx[b, :, 0:4:2] -= qx
                 bx[b, :, 1:4:2] -= qy
                 bx[b, :, 0:4:2] = bx[b, :, 0:4:2] * wr
                 bx[b, :, 1:4:2] = bx[b, :, 1:4:2] * hr
-        return kp, kz, bx
+        return (kp, kz, bx) if visible is None else (kp, kz, bx, vs)
 
 
-def augment_resize(frames, aug, input_size=224, depth_max=DEPTH_MAX, mean=0.0, std=1.0):
-    """Rotate -> RenderDepth -> Crop -> Resize -> clamp to [0, depth_max] -> (x - mean) / std of composed frames [B,H,W] float32 (device)
+def augment_resize(frames, aug, input_size=224, depth_max=None, mean=0.0, std=1.0, profile=None):
+    """depth_max=None: the clamp of the dataset profile (popnet_amd.profiles; None = MP3DHP, 6 m).  Items with Hflip set mirror their
+    render image inside the same launch.
+    Rotate -> RenderDepth -> [Hflip ->] Crop -> Resize -> clamp to [0, depth_max] -> (x - mean) / std of composed frames [B,H,W] float32 (device)
     with the per-item transforms of `aug` (AugmentationBatch): ONE launch for the batch (pn_augment_resize).  -> [B,1,S,S] float32.
     An item that Resize would decimate by exactly 2 in both axes is refused with a PopnetError naming it: cv2.resize(INTER_LINEAR)
     switches to INTER_AREA there, which is not built (as in pn_preprocess).  With the MP-3DHP geometry (480 x 512 frames, S = 224,
     a in [0.7, 1.7], crops up to 0.1) this cannot occur: a crop that is 448 wide needs a >= 0.93, which leaves at least 477 rows."""
     _lib.require_cuda_tensor(frames, "frames")
+    if depth_max is None:
+        depth_max = profiles.get(profile).depth_max
     if frames.dtype != torch.float32 or frames.dim() != 3:
         raise _lib.PopnetError("augment_resize: frames must be [B,H,W] float32")
     B, H, W = frames.shape
@@ -539,3 +574,137 @@ class MPAugTrainSet:
                     boxes[b, p, 1:4:2] = bb[1:4:2] * (float(input_size) / H)
                 pw[b, p] = float(ann["pose_weight"])
         return out + ((boxes, t(pw), aug) if augment else (t(boxes), t(pw)))
+
+
+# ---- single-person datasets without composition (ITOP) ---------------------------------------------------------------------------
+JOINT2BOX_MARGIN = 25      # datasets_itop.py: the prior box is the joints' bounding box grown by this many network-input pixels
+
+
+def _single_image(frames, aug, input_size, prof):
+    """The image half of ItopKeypoints.__getitem__ (datasets_itop_rtpose.py:213-223, datasets_itop.py:239-251): frames [B,H,W] float16 /
+    float32 (device) as stored, widened to float32 (Cvt2ndarray), through Resize or the random chain, clamped to [0, depth_max].
+    -> [B,S,S] float32, un-normalised."""
+    _lib.require_cuda_tensor(frames, "frames")
+    if frames.dim() != 3 or frames.dtype not in (torch.float16, torch.float32):
+        raise _lib.PopnetError("frames must be a [B,H,W] float16 / float32 tensor")
+    frames = frames.to(torch.float32).contiguous()
+    if aug is not None:
+        return augment_resize(frames, aug, input_size, prof.depth_max)[:, 0]
+    return _resize(frames, input_size, prof.depth_max)
+
+
+def _single_labels(frames, kp2d_org, kp3d, aug, input_size, boxes=None):
+    """The label half: Resize alone (float32 joints times a Python float) or the random chain's host transform.  -> host arrays
+    (kp2d [B,1,15,2] float32, kp_z [B,1,15] float64)."""
+    B, H, W = frames.shape
+    k2 = np.array(_host(kp2d_org), dtype=np.float32).reshape(B, 1, NUM_JOINTS, 2)
+    k3 = np.array(_host(kp3d), dtype=np.float64).reshape(B, 1, NUM_JOINTS, 3)
+    if aug is not None:
+        kp, kz, _ = aug.transform_labels(k2, k3)
+        return kp, kz
+    k2[..., 0] *= float(input_size) / W
+    k2[..., 1] *= float(input_size) / H
+    return k2, np.ascontiguousarray(k3[..., 2])
+
+
+def itop_batch(frames, kp2d_org, kp3d, input_size=224, stride=8, z_radius=2, aug=None, profile=None):
+    """A batch of Open-Pose+ training items of a single-person dataset as datasets_itop_rtpose.ItopKeypoints.__getitem__ builds them
+    (mpaug_batch minus the composition: the frames are used as they are).  frames [B,H,W] float16 / float32 (device), kp2d_org [B,15,2]
+    original pixels, kp3d [B,15,3] metres (host arrays or tensors; their transform is host work).  aug=None: Compose([Cvt2ndarray, Resize]);
+    aug (AugmentationBatch): Compose([Cvt2ndarray, Rotate(), RenderDepth(), Hflip(swap), Crop(), Resize]) -- the image through one
+    pn_augment_resize launch.  The maps follow the ITOP loader: joints are kept by the in-bounds test alone (remove_illegal_joint);
+    visible_joints does not gate them; the z maps clamp at the profile's depth_max (5 m).  get_ground_truth of that file mixes
+    self.joint_names / self.JOINT_NAMES and uses self.strideA / self.align_radius, which do not exist: with the names fixed and the unused
+    PoseAlign maps left out it is the kdh3d loader's get_ground_truth with depth_max = 5, which pn_rasterize_targets computes.
+    profile=None: ITOP.  Returns image [B,1,S,S] (normalised), heat, paf, z, fg."""
+    prof = profiles.ITOP if profile is None else profiles.get(profile)
+    img = _single_image(frames, aug, input_size, prof)
+    depth_resize = _resize(img, int(input_size / stride), 3.0e38)
+    kp, kz = _single_labels(frames, kp2d_org, kp3d, aug, input_size)
+    dev = img.device
+    n = torch.ones((img.shape[0],), dtype=torch.int32, device=dev)
+    heat, paf, z, fg = rasterize_targets(torch.from_numpy(kp).to(dev), torch.from_numpy(kz).to(dev), n, depth_resize, input_size, stride, z_radius,
+                                         profile=prof)
+    x = ((img - float(prof.depth_mean)) / float(prof.depth_std)).unsqueeze(1)
+    return x, heat, paf, z, fg
+
+
+def joints_box(kp2d, margin=JOINT2BOX_MARGIN):
+    """The prior box of the ITOP loader (datasets_itop.py:429-430): [min x - margin, min y - margin, max x + margin, max y + margin] over
+    ALL joints of the transformed labels.  The margin is added in float32 (a float32 extreme and a Python int: float32 under NumPy 2's
+    promotion rules, which is how the reference's line runs today); the box then enters the float64 object row."""
+    k = np.asarray(kp2d, dtype=np.float32)
+    lo, hi = k.min(axis=-2) - np.float32(margin), k.max(axis=-2) + np.float32(margin)
+    return np.concatenate([lo, hi], axis=-1).astype(np.float64)
+
+
+def itop_batch_yolo(frames, kp2d_org, kp3d, pose_weight=None, input_size=224, aug=None, profile=None):
+    """itop_batch for the YoloPoseNet trainer (datasets_itop.ItopKeypoints): the same image and the prior targets of its one person.  The box
+    is joints_box of the transformed joints (the loader never reads ann['bbox']); pose_weight [B] or None = 1.0 for everybody
+    (datasets_itop.py:425-428).  Returns image [B,1,S,S], prior_map, prior_mask_conf, prior_mask_coord, prior_weight_map."""
+    prof = profiles.ITOP if profile is None else profiles.get(profile)
+    img = _single_image(frames, aug, input_size, prof)
+    kp, kz = _single_labels(frames, kp2d_org, kp3d, aug, input_size)
+    B, dev = img.shape[0], img.device
+    pw = np.ones((B, 1), dtype=np.float64) if pose_weight is None else np.array(_host(pose_weight), dtype=np.float64).reshape(B, 1)
+    n = torch.ones((B,), dtype=torch.int32, device=dev)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    prior = prior_targets(t(joints_box(kp)), t(kp), t(kz), t(pw), n, input_size, profile=prof)
+    x = ((img - float(prof.depth_mean)) / float(prof.depth_std)).unsqueeze(1)
+    return (x,) + prior
+
+
+class ItopSet:
+    """The files of the ITOP side-view splits (datasets_itop_rtpose.py:171-178, datasets_itop.py:177-181): `annotations/ITOP_side_{train,test}
+    _labels.json` maps an image id to a list of persons ('2d_joints' [15][2], '3d_joints' [15][3], 'visible_joints' [15], optionally 'bbox'
+    and 'pose_weight'); the frame of id X is `<img_dir>/X.npy`, 240 x 320 float16 metres.  An 'intrinsics' entry is skipped.  `batch(indices)`
+    loads the frames and the FIRST person's labels (the dataset is single-person) for itop_batch / itop_batch_yolo."""
+
+    def __init__(self, img_dir, ann_file, device="cuda:0", profile=None):
+        import json
+        self.img_dir, self.device = img_dir, torch.device(device)
+        self.profile = profiles.ITOP if profile is None else profiles.get(profile)
+        self.anno_dic = json.load(open(ann_file, "r"))
+        self.ids = [k for k in self.anno_dic if k != "intrinsics"]
+
+    def __len__(self):
+        return len(self.ids)
+
+    def load(self, index):
+        import os
+        a = np.load(os.path.join(self.img_dir, self.ids[index] + ".npy"))
+        if a.ndim != 2:
+            raise _lib.PopnetError("%s: expected one [H, W] depth frame, got shape %s" % (self.ids[index], a.shape))
+        return a if a.dtype in (np.float16, np.float32) else a.astype(np.float32)
+
+    def ground_truth(self):
+        """(human_gt_set_2d, human_gt_set_3d) in frame order, as the evaluation scripts collect them."""
+        return ([[p["2d_joints"] for p in self.anno_dic[k]] for k in self.ids], [[p["3d_joints"] for p in self.anno_dic[k]] for k in self.ids])
+
+    def batches(self, indices, batch_size, drop_last=False):
+        """Yields (index list, host array [b, H, W]) like dataset.MP3DHPFrames.batches."""
+        indices = list(indices)
+        for s in range(0, len(indices), batch_size):
+            chunk = indices[s:s + batch_size]
+            if drop_last and len(chunk) < batch_size:
+                return
+            yield chunk, np.stack([self.load(i) for i in chunk])
+
+    def batch(self, indices, input_size=224, augment=False):
+        """-> (frames [B,H,W] device, kp2d_org [B,15,2] float32, kp3d [B,15,3] float64, visible [B,15], pose_weight [B] float64) -- host arrays
+        but the frames -- and, with augment=True, the batch's AugmentationBatch drawn with the profile's trainer defaults as the last element."""
+        frames = np.stack([self.load(i) for i in indices])
+        first = [self.anno_dic[self.ids[i]][0] for i in indices]
+        k2 = np.array([np.asarray(p["2d_joints"], dtype=np.float32).reshape(NUM_JOINTS, 2) for p in first])
+        k3 = np.array([np.asarray(p["3d_joints"], dtype=np.float64).reshape(NUM_JOINTS, 3) for p in first])
+        vis = np.array([np.asarray(p.get("visible_joints", [1] * NUM_JOINTS)).reshape(NUM_JOINTS) for p in first])
+        pw = np.array([float(p.get("pose_weight", 1.0)) for p in first], dtype=np.float64)
+        out = (torch.from_numpy(frames).to(self.device, non_blocking=True), k2, k3, vis, pw)
+        if not augment:
+            return out
+        H, W = frames.shape[1:]
+        a = self.profile.aug
+        cx, cy = self.profile.aug_centre(H, W)
+        items = [draw_augmentation(H, W, cx, cy, min_ratio=a["min_ratio"], max_ratio=a["max_ratio"], max_crop=a["max_crop"], input_size=input_size,
+                                   hflip=a["hflip"], swap_indices=self.profile.swap_indices) for _ in indices]
+        return out + (AugmentationBatch(items),)

@@ -24,9 +24,19 @@ paf_xy_coords_per_limb = np.arange(2 * len(LIMBS)).reshape(-1, 2)
 NUM_LIMBS = len(LIMBS)
 
 
-def make_parse_cfg(config=None, input_size=224, w_org=480, h_org=640, intrinsics=None, depth_mean=3.0, depth_std=2.0):
+def make_parse_cfg(config=None, input_size=224, w_org=None, h_org=None, intrinsics=None, depth_mean=None, depth_std=None, profile=None):
+    """pn_parse_cfg for a dataset profile (popnet_amd.profiles; default MP3DHP): frame size, intrinsics, depth normalisation, the joint
+    depth read-out rule and its channel table come from the profile; an explicit w_org / h_org / intrinsics / depth_mean / depth_std
+    argument overrides the profile's value."""
+    from .. import profiles
+    prof = profiles.get(profile)
+    w_org, h_org = prof.w_org if w_org is None else w_org, prof.h_org if h_org is None else h_org
+    intrinsics = prof.intrinsics if intrinsics is None else intrinsics
+    depth_mean, depth_std = prof.depth_mean if depth_mean is None else depth_mean, prof.depth_std if depth_std is None else depth_std
     cfg = _lib.ParseCfg()
     _lib.lib().pn_parse_cfg_default(C.byref(cfg))
+    cfg.z_readout = prof.z_readout
+    cfg.z_chn[:] = prof.z_chn
     if config is not None:
         cfg.thresh_heatmap = float(config.TEST.THRESH_HEATMAP)
         cfg.thresh_paf = float(config.TEST.THRESH_PAF)
