@@ -140,8 +140,13 @@ int pn_net_copy_activation(pn_net *net, const char *name, int B, float *dev_out,
  * pn_net_num_steps: the number of steps.  pn_net_step_info writes a JSON description of step k into out
  * (type stem / pool / conv / bblock, the kernel label, and per convolution its weight / BN prefixes, ks,
  * stride, act, buffers with channel offsets, input-channel map, fused tail or pool); k = -1 describes the
- * net (precision, input size, buffers as [H, W, C]).  PN_ERR_INVALID when cap is too small.             */
+ * net (precision, input size, buffers as [H, W, C]).  PN_ERR_INVALID when cap is too small.
+ * pn_net_forward_frames_partial: the same for the frames-in forward -- steps [0, nsteps) of pn_rtpose_forward_frames /
+ * pn_yolo_forward_frames (either net kind), with their argument and state checks and refusals in their order, then the two above
+ * (one full forward first, nsteps in range).  No output pointer is touched.  nsteps = 1 runs the stem that reads the raw frames.      */
 int pn_net_forward_partial(pn_net *net, const float *x_dev, int B, int nsteps, void *hip_stream);
+int pn_net_forward_frames_partial(pn_net *net, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max,
+                                  float depth_mean, float depth_std, int nsteps, void *hip_stream);
 int pn_net_num_steps(pn_net *net);
 int pn_net_step_info(pn_net *net, int k, char *out, size_t cap);
 /* The plan of one LEVEL of up to three independent convolutions that read the same H x W map, as pn_net_finalize would plan it, without a

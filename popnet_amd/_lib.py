@@ -124,6 +124,7 @@ _SIGNATURES = {
     "pn_net_read_activation": (_i, [_vp, C.c_char_p, _i, _vp, _sz, _vp]),
     "pn_net_copy_activation": (_i, [_vp, C.c_char_p, _i, _vp, _vp]),
     "pn_net_forward_partial": (_i, [_vp, _vp, _i, _i, _vp]),
+    "pn_net_forward_frames_partial": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _vp]),
     "pn_net_num_steps": (_i, [_vp]),
     "pn_net_step_info": (_i, [_vp, _i, C.c_char_p, _sz]),
     "pn_conv_level_plan_info": (_i, [_vp] + [_i] * 8 + [_vp] * 4 + [C.c_char_p, _sz]),

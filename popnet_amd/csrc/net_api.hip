@@ -33,9 +33,10 @@ int forward_entry(pn_net *n, int kind, bool pointers_ok, bool state = true) {
     return PN_OK;
 }
 
-// frames in: the 7x7 stem computes its input tile from the raw depth frames with pn_preprocess's arithmetic (preproc_pixel.h)
+// frames in: the 7x7 stem computes its input tile from the raw depth frames with pn_preprocess's arithmetic (preproc_pixel.h).
+// nsteps < 0: the whole step list (pn_*_forward_frames); otherwise steps [0, nsteps) under pn_net_forward_partial's two rules
 int forward_frames(pn_net *n, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max, float depth_mean, float depth_std,
-                   hipStream_t stream) {
+                   hipStream_t stream, int nsteps = -1, bool partial = false) {
     pn_ctx *ctx = n->ctx;
     if (!depth_dev || H < 2 || W < 2) return pn_set_error(ctx, PN_ERR_INVALID, "forward_frames: bad arguments");
     if (depth_dtype != PN_DEPTH_F16 && depth_dtype != PN_DEPTH_F32) return pn_set_error(ctx, PN_ERR_INVALID, "forward_frames: unknown depth dtype %d", depth_dtype);
@@ -45,13 +46,17 @@ int forward_frames(pn_net *n, const void *depth_dev, int depth_dtype, int B, int
     const int S = n->in_h;
     if (W == 2 * S && H == 2 * S)   // as pn_preprocess: cv::resize switches to INTER_AREA at exactly 2x decimation
         return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "forward_frames: %dx%d -> %d is an exact 2x decimation, where cv2.resize(INTER_LINEAR) runs INTER_AREA instead: not built", W, H, S);
+    if (partial) {
+        if (n->last_B < 0) return pn_set_error(ctx, PN_ERR_STATE, "pn_net_forward_frames_partial: run one full forward first");
+        if (nsteps < 0 || nsteps > (int)n->steps.size()) return pn_set_error(ctx, PN_ERR_INVALID, "nsteps %d outside [0, %zu]", nsteps, n->steps.size());
+    }
     PnFrameSrc fs;
     fs.frames = depth_dev; fs.dtype = depth_dtype; fs.H = H; fs.W = W;
     const double inv_x = (double)S / (double)W, inv_y = (double)S / (double)H;
     fs.scale_x = 1.0 / inv_x; fs.scale_y = 1.0 / inv_y;                    // as cv::resize computes them (pn_preprocess)
     fs.dmax = depth_max; fs.mean = depth_mean; fs.stdv = depth_std;
     n->frame_src = fs;
-    const int rc = run_forward(n, nullptr, B, stream);
+    const int rc = run_forward(n, nullptr, B, stream, nsteps);
     n->frame_src.frames = nullptr;
     return rc;
 }
@@ -220,6 +225,15 @@ int pn_net_forward_partial(pn_net *n, const float *x_dev, int B, int nsteps, voi
     if (n->last_B < 0) return pn_set_error(n->ctx, PN_ERR_STATE, "pn_net_forward_partial: run one full forward first");
     if (nsteps < 0 || nsteps > (int)n->steps.size()) return pn_set_error(n->ctx, PN_ERR_INVALID, "nsteps %d outside [0, %zu]", nsteps, n->steps.size());
     return run_forward(n, x_dev, B, (hipStream_t)hip_stream, nsteps);
+}
+
+// steps [0, nsteps) of the frames-in forward: pn_*_forward_frames' checks in their order, then pn_net_forward_partial's; either net kind, and the
+// output pointers of the last full forward stay as they are
+int pn_net_forward_frames_partial(pn_net *n, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max, float depth_mean,
+                                  float depth_std, int nsteps, void *hip_stream) {
+    if (!n) return PN_ERR_INVALID;
+    if (n->kind != PN_NET_RTPOSE_LIGHT3D && n->kind != PN_NET_YOLO_POSENET) return pn_set_error(n->ctx, PN_ERR_INVALID, "not an rtpose_light3d or a YoloPoseNet net");
+    return forward_frames(n, depth_dev, depth_dtype, B, H, W, depth_max, depth_mean, depth_std, (hipStream_t)hip_stream, nsteps, true);
 }
 
 int pn_net_num_steps(pn_net *n) {

@@ -1075,7 +1075,10 @@ def test_engine_other_frame_sizes_and_dtypes(gpu, shape, dtype):
 def test_frames_in_forward_equals_preprocess_plus_forward(gpu, prec, shape, dtype):
     """pn_rtpose_forward_frames / pn_yolo_forward_frames (the stem computes its input tile from the raw frames with pn_preprocess's
     arithmetic) give the SAME maps, bit for bit, as pn_preprocess + pn_*_forward, for f16 and f32 frames of three sizes; the fp32
-    parity net refuses the call (it keeps the two-call form)."""
+    parity net refuses the call (it keeps the two-call form).  These are three decimating, finite frames into the 224 net with the
+    MP-3DHP constants, where no stem block is ragged and only the final maps are compared; tests/test_gpu_preproc_edges.py runs the
+    frames-in stems by themselves (pn_net_forward_frames_partial) and the whole forward on up-sampled, one-axis-2x, two-pixel and
+    non-finite frames, at net sizes with ragged stem and pool blocks, with ITOP's and a third set of constants."""
     import ctypes as C
     from popnet_amd import _lib
     from popnet_amd.pipeline import PoseEngine, YoloEngine

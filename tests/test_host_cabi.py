@@ -33,6 +33,8 @@ def test_library_loads_and_exports_every_declared_symbol():
         assert hasattr(handle, s), "libpopnet_hip.so does not export %s" % s
     # every symbol the Python binding uses is declared in the header too
     assert set(_lib.declared_symbols()) <= set(syms)
+    # the test / diagnostic entries of the nets are declared, bound and exported; additions do not bump the ABI version
+    assert {"pn_net_forward_partial", "pn_net_forward_frames_partial", "pn_net_num_steps", "pn_net_step_info"} <= set(syms) & set(_lib.declared_symbols())
     assert handle.pn_abi_version() == 1
 
 
