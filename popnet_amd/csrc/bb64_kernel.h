@@ -43,6 +43,8 @@
 // pn_conv_row_channel(tile, row, 4) so that a lane's 16 accumulators are 16 consecutive channels.
 // bb64s_kernel.h is this kernel (HV = 1) handing out column segments instead of tiles and carrying the intermediate's two overlap rows down a segment;
 // net_run.hip chooses between the two per launch.
+// bb64_common.h holds what the two kernels share, each piece described at its code: the LDS layout, the weight-loader stream, the image-piece DMA, the
+// ticket sign-off, the fragment reads, the k-step-outer MFMA loop and the output epilogue.
 #pragma once
 #include "bb64_common.h"
 
@@ -55,16 +57,10 @@
 // waves and 55 % more LDS bytes per k-step (both halves read every B fragment) cost the clock what they save in cycles.  Kept as a switch.
 template <int HV>
 __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProblem P) {
-    typedef __bf16 T;
-    constexpr int CT = 4 / HV, NCW = 4 * HV, NP = CT / 2, PT1 = 5, PT2 = 4, KK = 9, BQ = 6;
+    constexpr int CT = 4 / HV, NCW = 4 * HV, NP = CT / 2, PT1 = 5, PT2 = 4, BQ = BB_BQ;
     constexpr bool SPLIT = HV == 1;                      // conv2 without padding tiles (below)
     constexpr bool XCH = HV == 1;                        // last phase of each convolution pixel tile outer, epilogues among its MFMAs
     constexpr int NKO = XCH ? 16 : 18;                   // k-steps that run k-step outer
-    // Epilogue instructions (VALU / SALU / LDS write or store) placed behind each MFMA of a last phase.  Chosen from the cross-compiled instruction
-    // stream, not tuned on a GPU: conv1 has 28 MFMAs after its first finished tile for four epilogues of about 45 instructions, conv2 16 for three of
-    // about 58; with a smaller number the compiler leaves the rest in one lump at the end of the phase.  An MFMA hides only two VALU, so these
-    // regions are VALU-bound either way.
-    constexpr int FILL1 = 7, FILL2 = 11;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -73,7 +69,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
     const int W = P.W, H = P.H;
 
     // ticket slots: pixel column 31 of row 0 of the intermediate image's first quarter plane is never written (MC <= 30) nor read (x + kx <= 29)
-    volatile int *s_tile = reinterpret_cast<volatile int *>(smem + BB_OFF_MID + 31 * 32);
+    volatile int *s_tile = reinterpret_cast<volatile int *>(smem + BB_OFF_TICKET);
     const bool dyn = P.tickets != nullptr;
     // tile k + 1 of this workgroup, as every wave sees it at the start of tile k (static schedule: t + gridDim.x)
     auto next_tile = [&](int t, int k) -> int { return dyn ? __builtin_amdgcn_readfirstlane(s_tile[(k + 1) & 3]) : t + (int)gridDim.x; };
@@ -94,45 +90,23 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
         int t = blockIdx.x;
         if (t >= P.ntiles) return;
         if (lw < 2) {
-            // ---- weight loaders: each fetches half (two 1 KB instructions) of both k-steps of a phase ----
-            // Ring of 6 slots, k-step k in slot k % 6; the compute waves read the fragments of k-step k during k - 1.  In phase q
-            // (k-steps 2q, 2q + 1) the loaders issue k-step 2q + 4 and then 2q + 5 into the slots phase q - 1 has just released;
-            // 2q + 4 is read in phase q + 1 and must have landed by the barrier that ends phase q (vmcnt leaves only the two
-            // newer instructions = 2q + 5 in flight), 2q + 5 is read in phase q + 2 and gets a phase of slack.
+            // ---- weight loaders ----
             const char *wsrc = (const char *)P.wpack + lw * 2048;
-            auto dma_a = [&](int kstep) {                        // this wave's half of a k-step of the periodic 36-step stream
-                pn_glds16_s<0>(wsrc + (size_t)kstep * BB_ASLOT, lane16, (unsigned)(BB_OFF_A + (kstep % BB_NSLOT) * BB_ASLOT) + (unsigned)__builtin_amdgcn_readfirstlane(lw * 2048));
-                pn_glds16_s<0>(wsrc + (size_t)kstep * BB_ASLOT + 1024, lane16, (unsigned)(BB_OFF_A + (kstep % BB_NSLOT) * BB_ASLOT + 1024) + (unsigned)__builtin_amdgcn_readfirstlane(lw * 2048));
-            };
-            dma_a(0); dma_a(1); dma_a(2); dma_a(3);             // phases 0 and 1
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-            asm volatile("s_barrier" ::: "memory");              // (the compute waves have read k-step 0's fragments)
+            auto dma_a = [&](int kstep) { bb_dma_a(wsrc, lane16, lw, kstep); };
+            bb_weights_prologue(dma_a);
             for (int k = 0; t < P.ntiles; ++k) {
                 const int tnx = next_tile_raw(t, k);
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 18; ++p) {                   // phase p = k-steps 2p, 2p + 1 of the tile's 36
-                    dma_a((2 * p + 4) % 36);
-                    dma_a((2 * p + 5) % 36);
-                    asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-                    if (p == 8) asm volatile("s_barrier" ::: "memory");          // the compute waves publish the intermediate image
-                }
-                asm volatile("s_barrier" ::: "memory");                             // end of tile
+                bb_weights_tile(dma_a);
                 t = __builtin_amdgcn_readfirstlane(tnx);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             return;
         }
         // ---- image loaders: wave 6 / 7 fetches pieces 0..23 / 24..47 of the NEXT tile's input image, two per phase ----
-        auto dma_in = [&](int tt, int buf, int n) {            // piece n = (quarter n / 12, halo row n % 12): 32 pixels x 32 B
+        auto dma_in = [&](int tt, int buf, int n) {            // piece n of tile tt
             int b, oy0, ox0, R, Wc;
             tile_geom(tt, b, oy0, ox0, R, Wc);
-            const int qu = n / 12, row = n % 12;
-            const int px = lane >> 1;
-            const int iy = oy0 - 2 + row, ix = ox0 - 2 + px;
-            const size_t frame_b = ((size_t)b * H * W * P.in_cs + P.in_coff) * 2;
-            const bool inb = px < Wc + 4 && (unsigned)ix < (unsigned)W && (unsigned)iy < (unsigned)H;
-            const unsigned off = inb ? (unsigned)((iy * W + ix) * P.in_cs * 2 + qu * 32 + (lane & 1) * 16) : P.in_zero_off - (unsigned)frame_b;
-            pn_glds16_s<0>((const char *)P.in + frame_b, off, (unsigned)__builtin_amdgcn_readfirstlane(buf * BB_IN + qu * BB_INQ + row * 1024));
+            bb_dma_in(P, H, W, lane, b, oy0, ox0, Wc, buf, n);
         };
         const int n0 = (lw - 2) * 24;
         const bool ticketer = dyn && lw == 2 && lane == 0;      // this lane fetches the tickets: tile k + 2 during tile k
@@ -155,8 +129,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             const int tnx = next_tile(t, k);
             const int tn = tnx < P.ntiles ? tnx : t;             // past the last tile: a harmless refetch into the idle image
             // a workgroup on its LAST tile has no use for another ticket: it signs off instead (looked at after the end-of-tile wait, ten microseconds
-            // later: the kernel's end does not wait for an atomic's round trip).  The workgroup that signs off last knows every claim has been made and
-            // leaves both counters at zero for the next launch (graph replay).
+            // later: the kernel's end does not wait for an atomic's round trip)
             int signed_off = -1;
             if (ticketer) {
                 if (tnx < P.ntiles) ticket = claim();
@@ -171,10 +144,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           // end of tile: the next image is complete (and the ticket is back)
             if (ticketer) {
                 s_tile[(k + 2) & 3] = ticket;
-                if (signed_off == (int)gridDim.x - 1) {
-                    __hip_atomic_store(P.tickets, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(P.tickets + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                bb_sign_off(P.tickets, signed_off, (int)gridDim.x);
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             cur ^= 1;
@@ -243,10 +213,6 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
             ba2[pt] = ba2base + (s < nout ? (r * 32 + x) * 32 : 0);
         }
         f32x4 acc[CT][PT1];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int pt = 0; pt < PT1; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // ---------------- the two epilogues, one pixel tile each, branch-free (a branch would end the scheduling region they are placed in) ----------------
         // (r, x) of a slot come back out of its image address
         const bool border = oy0 == 0 || ox0 == 0 || oy0 + R >= H || ox0 + Wc >= W;        // wave-uniform
@@ -276,63 +242,16 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
         const int resw = inb + q * BB_INQ + (2 * 32 + 2) * 32 + 16 * pc(0);
         __amdgpu_buffer_rsrc_t orsrc;
         auto epi2 = [&](int pt) {
-            const int nct = SPLIT && pt == 3 ? 2 : CT, np = nct / 2;
-            const int pix = ba2[pt] - ba2base, r = pix >> 10, x = (pix >> 5) & 31;
-            const bool valid = out_tile(pt) * 16 + cc < nout;
-            u32x4 rr[NP], o[NP];
-            rr[0] = *reinterpret_cast<const u32x4 *>(smem + resw + pix);
-            if (np == 2) rr[NP - 1] = *reinterpret_cast<const u32x4 *>(smem + ((resw + pix) ^ 16));
-#pragma unroll
-            for (int ct = 0; ct < nct; ++ct) {
-                const unsigned ra = rr[ct >> 1][2 * (ct & 1)], rb = rr[ct >> 1][2 * (ct & 1) + 1];
-                // a bf16 is the upper half of its float: residual channels by shift / mask, no conversion instruction
-                f32x2 lo = {acc[ct][pt][0] + b2[4 * ct + 0] + __builtin_bit_cast(float, ra << 16),
-                            acc[ct][pt][1] + b2[4 * ct + 1] + __builtin_bit_cast(float, ra & 0xffff0000u)};
-                f32x2 hi = {acc[ct][pt][2] + b2[4 * ct + 2] + __builtin_bit_cast(float, rb << 16),
-                            acc[ct][pt][3] + b2[4 * ct + 3] + __builtin_bit_cast(float, rb & 0xffff0000u)};
-                o[ct >> 1][2 * (ct & 1)] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2)));
-                o[ct >> 1][2 * (ct & 1) + 1] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2)));
-            }
-            // out-of-range offset for the unused slots: the store is issued unconditionally and dropped by the hardware
-            unsigned vin = (unsigned)(((oy0 + r) * W + ox0 + x) * P.out_cs * 2 + 32 * q);
-            asm volatile("" : "+v"(vin));                  // computed for every slot: the compiler otherwise branches round the multiply
-            const unsigned voff = valid ? vin : 0x80000000u;
-#pragma unroll
-            for (int k = 0; k < np; ++k) __builtin_amdgcn_raw_buffer_store_b128(o[k], orsrc, voff + 16u * (unsigned)pc(k), 0, 0);
+            bb_epi2<CT, SPLIT>(smem, acc, b2, pt, ba2[pt] - ba2base, out_tile(pt) * 16 + cc < nout, resw, orsrc, oy0, ox0, W, P.out_cs, q, pc);
         };
         // (aq[0] holds k-step 0's weight fragments: read in the prologue / prefetched by the previous tile's last phase)
         // ---------------- conv1: 18 k-steps on the input image ----------------
-#define BB_TAPOFF(tap) ((((tap) / 3) * 32 + ((tap) % 3)) * 32)
-#define BB_A(k, ct) (*reinterpret_cast<const bf16x8 *>(smem + ((ct) < 2 ? aaddr0 : aaddr1) + ((k) % BB_NSLOT) * BB_ASLOT + ((ct) & 1) * 1024))                    /* weight fragment of k-step k of the tile's 36 */
-#define BB_KOFF1(ks) (((ks) / KK) * 2 * BB_INQ + BB_TAPOFF((ks) % KK))
-#define BB_B1(n) (*reinterpret_cast<const bf16x8 *>(smem + ba1[bb_item_pt(n, PT1, XCH)] + BB_KOFF1(bb_item_ks(n, PT1, XCH))))         /* B fragment of item n */
-#pragma unroll
-        for (int j = 0; j < BQ - 1; ++j) bq[j] = BB_B1(j);
-#pragma clang loop unroll(full)
-        for (int ph = 0; ph < NKO; ++ph) {
-            __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT1; ++pt) {
-                const int j = ph * PT1 + pt, jr = j + BQ - 1;
-                if (pt < CT) aq[(ph + 1) & 1][pt] = BB_A(ph + 1, pt);
-                if (jr < 18 * PT1) bq[jr % BQ] = BB_B1(jr);
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
-                if (pt < CT && jr < 18 * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                else if (pt < CT || jr < 18 * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // one barrier per two k-steps (no lgkmcnt wait: the ring slots refilled after it were last read a phase ago, the
-            // images are stable)
-            if (ph & 1) asm volatile("s_barrier" ::: "memory");
-        }
+        bb_kouter<PT1, NKO, 0, BB_INQ, false>(smem, aaddr0, aaddr1, ba1, acc, aq, bq);
 #pragma unroll
         for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4 *>(b1 + 4 * i) = *reinterpret_cast<const f32x4 *>(smem + biasaddr + 16 * pct(i));
         if constexpr (XCH) {
             // last phase, pixel tile outer (bb_item_*): the intermediate epilogue of a finished tile is issued among the MFMAs of the tiles after it
-            // (FILL1 VALU / SALU / ds_write per MFMA); only the last tile's epilogue is exposed.  aq[0] = k-step 16, aq[1] = k-step 17, read here.
+            // (BB_FILL1 VALU / SALU / ds_write per MFMA); only the last tile's epilogue is exposed.  aq[0] = k-step 16, aq[1] = k-step 17, read here.
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) aq[1][ct] = BB_A(17, ct);
@@ -353,7 +272,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x206, FILL1, 0);
+                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x206, BB_FILL1, 0);
                 }
                 if (m == 2 * PT1 - 2) __builtin_amdgcn_sched_group_barrier(0x100, CT, 0);
             }
@@ -366,35 +285,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         // ---------------- conv2: 18 k-steps on the intermediate image ----------------
-#define BB_KOFF2(ks) (((ks) / KK) * 2 * BB_MIDQ + BB_TAPOFF((ks) % KK))
-#define BB_B2(n) (*reinterpret_cast<const bf16x8 *>(smem + ba2[bb_item_pt(n, PT2, XCH)] + BB_KOFF2(bb_item_ks(n, PT2, XCH))))
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < BQ - 1; ++j) bq[j] = BB_B2(j);
-#pragma clang loop unroll(full)
-        for (int p2 = 0; p2 < NKO; ++p2) {
-            const int ph = 18 + p2;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT2; ++pt) {
-                const int j = p2 * PT2 + pt, jr = j + BQ - 1;
-                if (pt < CT) aq[(ph + 1) & 1][pt] = BB_A(ph + 1, pt);
-                if (jr < 18 * PT2) bq[jr % BQ] = BB_B2(jr);
-                const int nct = SPLIT && pt == 3 ? 2 : CT;           // the half tile: slots 0, 1
-#pragma unroll
-                for (int ct = 0; ct < nct; ++ct)
-                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
-                if (pt < CT && jr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                else if (pt < CT || jr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (SPLIT && pt == 3) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                else __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (ph & 1) asm volatile("s_barrier" ::: "memory");
-        }
+        bb_kouter<PT2, NKO, 18, BB_MIDQ, SPLIT>(smem, aaddr0, aaddr1, ba2, acc, aq, bq);
 #pragma unroll
         for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4 *>(b2 + 4 * i) = *reinterpret_cast<const f32x4 *>(smem + biasaddr + 1024 + 16 * pct(i));
         orsrc = __builtin_amdgcn_make_buffer_rsrc((char *)P.out + ((size_t)b * H * W * P.out_cs + P.out_coff) * 2, 0, (int)((size_t)H * W * P.out_cs * 2), 0x00020000);
@@ -422,7 +313,7 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
 #pragma unroll
                 for (int ct = 0; ct < nct; ++ct) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x146, FILL2, 0);
+                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x146, BB_FILL2, 0);
                 }
                 if (m == 2 * PT2 - 2) __builtin_amdgcn_sched_group_barrier(0x100, CT, 0);
             }
@@ -437,12 +328,6 @@ __global__ __launch_bounds__((4 * HV + 4) * 64, 1) void bb64_kernel(const BBProb
         cur ^= 1;
         t = __builtin_amdgcn_readfirstlane(tnx);
     }
-#undef BB_A
-#undef BB_B1
-#undef BB_B2
-#undef BB_KOFF1
-#undef BB_KOFF2
-#undef BB_TAPOFF
 }
 
 static int bb64_launch(pn_ctx *ctx, const BBProblem &P, int num_cus, hipStream_t stream) {

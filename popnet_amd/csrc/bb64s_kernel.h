@@ -1,5 +1,6 @@
 // Fused ResNet BasicBlock(64), bf16, walking COLUMN SEGMENTS top-down (the "strip kernel"): bb64_kernel<1> (bb64_kernel.h: LDS images, weight ring,
-// loader-wave roles, barrier cadence, epilogues -- read that header first) without most of its conv1 recompute.
+// loader-wave roles, barrier cadence, epilogues -- read that header first; bb64_common.h: the code the two kernels share) without most of its conv1
+// recompute.
 //
 // bb64_kernel evaluates conv1 on the 10 x 30 intermediate halo of every 8 x 28 output tile: 20 MFMAs per k-step and compute wave where conv2 takes 14.
 // Rows 0 and 1 of that halo are rows 8 and 9 of the tile above.  Here a workgroup takes SEGMENTS of consecutive row tiles of one column instead of
@@ -11,7 +12,7 @@
 //     (pixel columns 0..29 of the four quarter planes: 480 x 16 B through registers; columns 30, 31 hold the biases and the ticket slot), and conv1
 //     covers rows 2..9 only: 8 x 30 = 240 pixels = 15 pixel tiles, PT1 = 4, 16 MFMAs per k-step and wave.  The copy is complete before the loaders
 //     reach the first barrier of the tile; conv1 writes rows 8, 9 in its last phase and conv2 reads rows 0, 1 after the "publish" barrier;
-//   * conv2, the residual and the stores are bb64_kernel's.  The tile loop holds two unrolled conv1 bodies behind a wave-uniform branch and ONE conv2 body;
+//   * conv2, the residual and the stores are bb64_kernel's (the k-step-outer loop and the output epilogue through bb64_common.h).  The tile loop holds two unrolled conv1 bodies behind a wave-uniform branch and ONE conv2 body;
 //   * the first segment of a workgroup is its position; where there are more segments than workgroups the further ones come through the ticket counter
 //     (claimed during a segment's first tile, published at that tile's end, looked at from its last tile on), with bb64_kernel's sign-off: the workgroup
 //     that signs off last leaves both counters at zero.
@@ -22,8 +23,8 @@
 #include "bb64_common.h"
 
 __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) {
-    constexpr int CT = 4, NCW = 4, NP = 2, PT2 = 4, KK = 9, BQ = 6, NKO = 16;
-    constexpr int FILL1 = 7, FILL2 = 11;                 // as bb64_kernel: epilogue instructions behind each MFMA of a last phase
+    constexpr int CT = 4, NCW = 4, NP = 2, PT2 = 4, BQ = BB_BQ, NKO = 16;
+    constexpr bool SPLIT = true, XCH = true;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
     const int nseg = P.nseg, grid = (int)gridDim.x;
 
     // ticket slot (as bb64_kernel's): pixel column 31 of row 0 of the intermediate image's first quarter plane is never written nor read as pixels
-    volatile int *s_next = reinterpret_cast<volatile int *>(smem + BB_OFF_MID + 31 * 32);
+    volatile int *s_next = reinterpret_cast<volatile int *>(smem + BB_OFF_TICKET);
     const bool dyn = P.tickets != nullptr;
     // the segment after `seg` of this workgroup; the slot is valid from the end of the segment's first tile on, and is looked at in its last tile (>= second)
     auto next_seg_raw = [&](int seg) -> int { return dyn ? s_next[0] : seg + grid; };
@@ -58,25 +59,13 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
         const int lw = wave - NCW;
         const unsigned lane16 = (unsigned)lane * 16u;
         if (lw < 2) {
-            // ---- weight loaders: bb64_kernel's (the 36-step stream does not depend on the conv1 body) ----
+            // ---- weight loaders (the 36-step stream does not depend on the conv1 body) ----
             const char *wsrc = (const char *)P.wpack + lw * 2048;
-            auto dma_a = [&](int kstep) {
-                pn_glds16_s<0>(wsrc + (size_t)kstep * BB_ASLOT, lane16, (unsigned)(BB_OFF_A + (kstep % BB_NSLOT) * BB_ASLOT) + (unsigned)__builtin_amdgcn_readfirstlane(lw * 2048));
-                pn_glds16_s<0>(wsrc + (size_t)kstep * BB_ASLOT + 1024, lane16, (unsigned)(BB_OFF_A + (kstep % BB_NSLOT) * BB_ASLOT + 1024) + (unsigned)__builtin_amdgcn_readfirstlane(lw * 2048));
-            };
-            dma_a(0); dma_a(1); dma_a(2); dma_a(3);
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-            asm volatile("s_barrier" ::: "memory");
+            auto dma_a = [&](int kstep) { bb_dma_a(wsrc, lane16, lw, kstep); };
+            bb_weights_prologue(dma_a);
             while (seg < nseg) {
                 const int snx = next_seg_raw(seg);
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 18; ++p) {
-                    dma_a((2 * p + 4) % 36);
-                    dma_a((2 * p + 5) % 36);
-                    asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-                    if (p == 8) asm volatile("s_barrier" ::: "memory");
-                }
-                asm volatile("s_barrier" ::: "memory");                             // end of tile
+                bb_weights_tile(dma_a);
                 if (++j == slen) {
                     seg = __builtin_amdgcn_readfirstlane(snx);
                     j = 0;
@@ -87,15 +76,7 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
             return;
         }
         // ---- image loaders: the next tile's input image (all 12 rows: the four shared ones were read a tile ago), the carry, the tickets ----
-        auto dma_in = [&](int b, int oy0, int ox0, int Wc, int buf, int n) {            // piece n = (quarter n / 12, halo row n % 12): 32 pixels x 32 B
-            const int qu = n / 12, row = n % 12;
-            const int px = lane >> 1;
-            const int iy = oy0 - 2 + row, ix = ox0 - 2 + px;
-            const size_t frame_b = ((size_t)b * H * W * P.in_cs + P.in_coff) * 2;
-            const bool inb = px < Wc + 4 && (unsigned)ix < (unsigned)W && (unsigned)iy < (unsigned)H;
-            const unsigned off = inb ? (unsigned)((iy * W + ix) * P.in_cs * 2 + qu * 32 + (lane & 1) * 16) : P.in_zero_off - (unsigned)frame_b;
-            pn_glds16_s<0>((const char *)P.in + frame_b, off, (unsigned)__builtin_amdgcn_readfirstlane(buf * BB_IN + qu * BB_INQ + row * 1024));
-        };
+        auto dma_in = [&](int b, int oy0, int ox0, int Wc, int buf, int n) { bb_dma_in(P, H, W, lane, b, oy0, ox0, Wc, buf, n); };
         const int n0 = (lw - 2) * 24;
         const bool ticketer = dyn && lw == 2 && lane == 0;
         int ticket = 0;
@@ -151,10 +132,7 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           // end of tile: the next image is complete (and the atomic is back)
             if (ticketer) {
                 if (j == 0) s_next[0] = ticket;
-                if (signed_off == grid - 1) {
-                    __hip_atomic_store(P.tickets, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(P.tickets + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                bb_sign_off(P.tickets, signed_off, grid);
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             cur ^= 1;
@@ -208,10 +186,6 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
         f32x4 acc[CT][5];
         const bool border = oy0 == 0 || ox0 == 0 || oy0 + R >= H || ox0 + Wc >= W;        // wave-uniform
         const int midw = BB_OFF_MID + q * BB_MIDQ + 16 * pc(0);
-#define BB_TAPOFF(tap) ((((tap) / 3) * 32 + ((tap) % 3)) * 32)
-#define BB_A(k, ct) (*reinterpret_cast<const bf16x8 *>(smem + ((ct) < 2 ? aaddr0 : aaddr1) + ((k) % BB_NSLOT) * BB_ASLOT + ((ct) & 1) * 1024))                    /* weight fragment of k-step k of the tile's 36 */
-#define BB_KOFF1(ks) (((ks) / KK) * 2 * BB_INQ + BB_TAPOFF((ks) % KK))
-#define BB_B1(n) (*reinterpret_cast<const bf16x8 *>(smem + ba1[bb_item_pt(n, PT1, true)] + BB_KOFF1(bb_item_ks(n, PT1, true))))         /* B fragment of item n */
         // ---------------- conv1: 18 k-steps on the input image, intermediate rows ROW0..9 in PT1 pixel tiles per wave ----------------
         // (aq[0] holds k-step 0's weight fragments: read in the prologue / prefetched by the previous tile's last phase)
         auto conv1 = [&](auto pt1c) __attribute__((always_inline)) {
@@ -225,10 +199,6 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
                 const int r = (int)((fc + (float)sb) * inv_mc), x = s - r * MC;
                 ba1[pt] = ba1base + (s < nmid ? ((r + ROW0) * 32 + x) * 32 : dumppix);
             }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int pt = 0; pt < PT1; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
             // intermediate: bias + ReLU -> bf16 -> LDS image (zero outside the map = conv2's padding); (r, x) of a slot come back out of its image address
             auto epi1 = [&](int pt) {
                 const int pix = ba1[pt] - ba1base, r = pix >> 10, x = (pix >> 5) & 31;
@@ -246,26 +216,7 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
                 *reinterpret_cast<u32x4 *>(smem + dsta) = o[0];
                 *reinterpret_cast<u32x4 *>(smem + (dsta ^ 16)) = o[1];
             };
-#pragma unroll
-            for (int n = 0; n < BQ - 1; ++n) bq[n] = BB_B1(n);
-#pragma clang loop unroll(full)
-            for (int ph = 0; ph < NKO; ++ph) {
-                __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(full)
-                for (int pt = 0; pt < PT1; ++pt) {
-                    const int n = ph * PT1 + pt, nr = n + BQ - 1;
-                    if (pt < CT) aq[(ph + 1) & 1][pt] = BB_A(ph + 1, pt);
-                    if (nr < 18 * PT1) bq[nr % BQ] = BB_B1(nr);
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct)
-                        acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[n % BQ], acc[ct][pt], 0, 0, 0);
-                    if (pt < CT && nr < 18 * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    else if (pt < CT || nr < 18 * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (ph & 1) asm volatile("s_barrier" ::: "memory");      // one barrier per two k-steps
-            }
+            bb_kouter<PT1, NKO, 0, BB_INQ, false>(smem, aaddr0, aaddr1, ba1, acc, aq, bq);
 #pragma unroll
             for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4 *>(b1 + 4 * i) = *reinterpret_cast<const f32x4 *>(smem + biasaddr + 16 * pct(i));
             // last phase, pixel tile outer (bb_item_*): the epilogue of a finished tile among the MFMAs of the tiles after it; the last tile's is exposed
@@ -289,7 +240,7 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x206, FILL1, 0);
+                    if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x206, BB_FILL1, 0);
                 }
                 if (m == 2 * PT1 - 2) __builtin_amdgcn_sched_group_barrier(0x100, CT, 0);
             }
@@ -305,58 +256,9 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
         const int resw = inb + q * BB_INQ + (2 * 32 + 2) * 32 + 16 * pc(0);
         __amdgpu_buffer_rsrc_t orsrc;
         auto epi2 = [&](int pt) {
-            const int nct = pt == 3 ? 2 : CT, np = nct / 2;
-            const int pix = ba2[pt] - ba2base, r = pix >> 10, x = (pix >> 5) & 31;
-            const bool valid = out_tile(pt) * 16 + cc < nout;
-            u32x4 rr[NP], o[NP];
-            rr[0] = *reinterpret_cast<const u32x4 *>(smem + resw + pix);
-            if (np == 2) rr[NP - 1] = *reinterpret_cast<const u32x4 *>(smem + ((resw + pix) ^ 16));
-#pragma unroll
-            for (int ct = 0; ct < nct; ++ct) {
-                const unsigned ra = rr[ct >> 1][2 * (ct & 1)], rb = rr[ct >> 1][2 * (ct & 1) + 1];
-                f32x2 lo = {acc[ct][pt][0] + b2[4 * ct + 0] + __builtin_bit_cast(float, ra << 16),
-                            acc[ct][pt][1] + b2[4 * ct + 1] + __builtin_bit_cast(float, ra & 0xffff0000u)};
-                f32x2 hi = {acc[ct][pt][2] + b2[4 * ct + 2] + __builtin_bit_cast(float, rb << 16),
-                            acc[ct][pt][3] + b2[4 * ct + 3] + __builtin_bit_cast(float, rb & 0xffff0000u)};
-                o[ct >> 1][2 * (ct & 1)] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2)));
-                o[ct >> 1][2 * (ct & 1) + 1] = bb_relu_pk(__builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2)));
-            }
-            // out-of-range offset for the unused slots: the store is issued unconditionally and dropped by the hardware
-            unsigned vin = (unsigned)(((oy0 + r) * W + ox0 + x) * P.out_cs * 2 + 32 * q);
-            asm volatile("" : "+v"(vin));
-            const unsigned voff = valid ? vin : 0x80000000u;
-#pragma unroll
-            for (int k = 0; k < np; ++k) __builtin_amdgcn_raw_buffer_store_b128(o[k], orsrc, voff + 16u * (unsigned)pc(k), 0, 0);
+            bb_epi2<CT, SPLIT>(smem, acc, b2, pt, ba2[pt] - ba2base, out_tile(pt) * 16 + cc < nout, resw, orsrc, oy0, ox0, W, P.out_cs, q, pc);
         };
-#define BB_KOFF2(ks) (((ks) / KK) * 2 * BB_MIDQ + BB_TAPOFF((ks) % KK))
-#define BB_B2(n) (*reinterpret_cast<const bf16x8 *>(smem + ba2[bb_item_pt(n, PT2, true)] + BB_KOFF2(bb_item_ks(n, PT2, true))))
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int n = 0; n < BQ - 1; ++n) bq[n] = BB_B2(n);
-#pragma clang loop unroll(full)
-        for (int p2 = 0; p2 < NKO; ++p2) {
-            const int ph = 18 + p2;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT2; ++pt) {
-                const int n = p2 * PT2 + pt, nr = n + BQ - 1;
-                if (pt < CT) aq[(ph + 1) & 1][pt] = BB_A(ph + 1, pt);
-                if (nr < 18 * PT2) bq[nr % BQ] = BB_B2(nr);
-                const int nct = pt == 3 ? 2 : CT;           // the half tile: slots 0, 1
-#pragma unroll
-                for (int ct = 0; ct < nct; ++ct)
-                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[n % BQ], acc[ct][pt], 0, 0, 0);
-                if (pt < CT && nr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                else if (pt < CT || nr < 18 * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (pt == 3) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                else __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (ph & 1) asm volatile("s_barrier" ::: "memory");
-        }
+        bb_kouter<PT2, NKO, 18, BB_MIDQ, SPLIT>(smem, aaddr0, aaddr1, ba2, acc, aq, bq);
 #pragma unroll
         for (int i = 0; i < CT; ++i) *reinterpret_cast<f32x4 *>(b2 + 4 * i) = *reinterpret_cast<const f32x4 *>(smem + biasaddr + 1024 + 16 * pct(i));
         orsrc = __builtin_amdgcn_make_buffer_rsrc((char *)P.out + ((size_t)b * H * W * P.out_cs + P.out_coff) * 2, 0, (int)((size_t)H * W * P.out_cs * 2), 0x00020000);
@@ -383,7 +285,7 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
 #pragma unroll
             for (int ct = 0; ct < nct; ++ct) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x146, FILL2, 0);
+                if (m >= 3) __builtin_amdgcn_sched_group_barrier(0x146, BB_FILL2, 0);
             }
             if (m == 2 * PT2 - 2) __builtin_amdgcn_sched_group_barrier(0x100, CT, 0);
         }
@@ -398,12 +300,6 @@ __global__ __launch_bounds__(512, 1) void bb64s_strip_kernel(const BBProblem P) 
             seg_geom(seg, sb_, sox0, sWc, sty0, slen);
         }
     }
-#undef BB_A
-#undef BB_B1
-#undef BB_B2
-#undef BB_KOFF1
-#undef BB_KOFF2
-#undef BB_TAPOFF
 }
 
 static int bb64s_launch(pn_ctx *ctx, const BBProblem &P, int num_cus, hipStream_t stream) {
