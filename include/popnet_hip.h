@@ -49,7 +49,11 @@ enum pn_net_kind {
     PN_NET_A2J = 2              /* "Yolo-A2J" second stage: A2J_model  third_party_methods/A2J_experiments/model.py:145-186, resnet.py:61-164 */
 };
 
-enum pn_depth_dtype { PN_DEPTH_F16 = 0, PN_DEPTH_F32 = 1 };
+enum pn_depth_dtype {
+    PN_DEPTH_F16 = 0,
+    PN_DEPTH_F32 = 1,
+    PN_DEPTH_NET = 2   /* the ablation entries only: the buffer is the network input [B,1,S,S] f32, clamped and normalised */
+};
 
 typedef struct pn_ctx pn_ctx;
 typedef struct pn_net pn_net;
@@ -351,7 +355,11 @@ size_t pn_sizeof_pose_wire(void);
  *   pn_depth_probe           raw[y, x] of frame b for n points pts_dev int32 [n][3] = (frame, y, x) -> out_dev float [n].  The second-pass
  *                            entry (frames whose record overflowed are re-parsed without capacities and read their raw depth here) and a
  *                            test handle for the pixel arithmetic.  A point outside the batch or the S x S frame is PN_ERR_INVALID, never
- *                            clamped: the points are checked on the host first, so this call waits for the stream.                       */
+ *                            clamped: the points are checked on the host first, so this call waits for the stream.
+ * depth_dtype = PN_DEPTH_NET (all three): depth_dev is the network input itself, [B,1,S,S] f32 already clamped and normalised, as the
+ * scripts that compose or augment their frames hold it (evaluation_rtpose_light3d_kdh3d_mpaug_ablation.py:206-207; there is no raw frame
+ * to re-derive it from): raw[y, x] = fl32(fl32(depth_dev[b][y][x] * depth_std) + depth_mean).  H == W == S is required, else
+ * PN_ERR_INVALID before any launch; depth_max is ignored and the 2x refusal does not apply (nothing is resized).                   */
 int pn_ablation_pred_raw(pn_ctx *ctx, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max,
                          const pn_parse_cfg *cfg, const pn_pose_frame *frames_dev, double *out_dev, void *hip_stream);
 int pn_ablation_perfect_2d(pn_ctx *ctx, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max,
@@ -385,6 +393,12 @@ int pn_compose_depth(pn_ctx *ctx, const void *fg_depth_dev, const unsigned char 
 int pn_rasterize_targets(pn_ctx *ctx, const float *kp2d_dev, const double *kp_z_dev, const int *n_persons_dev, int B, int Pmax,
                          const float *depth_resize_dev, const pn_target_cfg *cfg, float *heat_dev, float *paf_dev,
                          float *z_dev, float *fg_dev, void *hip_stream);
+/* The background swap of the single-person loader (tpm/lib/datasets/datasets_kdh3d_rtpose.py:227-234, bg_aug):
+ * out = fg_mask > 0 ? fg_depth : bg per pixel -- no z-buffer and no 2 * depth_max cap, so a foreground pixel beyond the cap survives
+ * (pn_compose_depth with one source would cut it).  fg_depth, bg [B,H,W] f16 / f32 metres (depth_dtype), fg_mask [B,H,W] uint8, out
+ * [B,H,W] f32; B <= 65535; asynchronous on hip_stream, one launch, like pn_compose_depth.                                          */
+int pn_compose_bg(pn_ctx *ctx, const void *fg_depth_dev, const unsigned char *fg_mask_dev, const void *bg_dev, int depth_dtype,
+                  int B, int H, int W, float *out_dev, void *hip_stream);
 
 /* ---- random training augmentation ---------------------------------------------------------------------
  * The image half of the reference's training transform Compose([Cvt2ndarray, Rotate(cx, cy), RenderDepth(cx, cy, max_ratio), Crop,

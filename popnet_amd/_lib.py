@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("POPNET_LIB_PATH") or os.path.join(_HERE, "libpopnet_h
 PN_OK = 0
 PN_PREC_F32, PN_PREC_BF16, PN_PREC_BF16X3 = 0, 1, 2
 PN_NET_RTPOSE_LIGHT3D, PN_NET_YOLO_POSENET, PN_NET_A2J = 0, 1, 2
-PN_DEPTH_F16, PN_DEPTH_F32 = 0, 1
+PN_DEPTH_F16, PN_DEPTH_F32, PN_DEPTH_NET = 0, 1, 2
 
 PN_NUM_JOINTS = 15
 PN_NUM_LIMBS = 14
@@ -140,6 +140,7 @@ _SIGNATURES = {
     "pn_parse_paf_wire": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(ParseCfg), _vp, _vp, _vp]),
     "pn_target_cfg_default": (None, [C.POINTER(TargetCfg)]),
     "pn_compose_depth": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "pn_compose_bg": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "pn_rasterize_targets": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(TargetCfg), _vp, _vp, _vp, _vp, _vp]),
     "pn_sizeof_augment_item": (_sz, []),
     "pn_sizeof_parse_cfg": (_sz, []),

@@ -31,6 +31,19 @@ __device__ __forceinline__ void back_project(double x2, double y2, double d, con
     out3[2] = d;
 }
 
+// PN_DEPTH_NET: the buffer IS the network input [B,1,S,S] float32 (H == W == S), already clamped and normalised -- the scripts that compose
+// or augment their frames have no raw frame to re-derive a pixel from (evaluation_rtpose_light3d_kdh3d_mpaug_ablation.py:206-207).  The tag
+// type selects the overload below in the same three kernels; the un-normalisation is the same two roundings.
+struct NetIn { float v; };
+
+__device__ __forceinline__ float raw_pixel(const NetIn *__restrict__ img, int H, int W, int dy, int dx, double, double, float, float mean, float stdv) {
+#pragma clang fp contract(off)
+    float v = img[(size_t)dy * W + dx].v;
+    v = v * stdv;
+    v = v + mean;
+    return v;
+}
+
 // grid = B, block = 256: thread t -> (person, joint) rows of one record
 template <typename TIN>
 __global__ __launch_bounds__(256) void ablation_pred_raw_kernel(const TIN *__restrict__ depth, int H, int W, double scale_x, double scale_y,
@@ -116,8 +129,13 @@ int check_frames(pn_ctx *ctx, const char *who, const void *depth_dev, int depth_
     if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
     if ((B > 0 && !depth_dev) || B < 0 || H < 2 || W < 2 || S < 1 || (size_t)S * S > 0x7fffffffu || B > 65535)
         return pn_set_error(ctx, PN_ERR_INVALID, "%s: bad arguments", who);
-    if (depth_dtype != PN_DEPTH_F16 && depth_dtype != PN_DEPTH_F32)
+    if (depth_dtype != PN_DEPTH_F16 && depth_dtype != PN_DEPTH_F32 && depth_dtype != PN_DEPTH_NET)
         return pn_set_error(ctx, PN_ERR_INVALID, "%s: unknown depth dtype %d", who, depth_dtype);
+    if (depth_dtype == PN_DEPTH_NET) {   // nothing is resized: the 2x refusal below does not apply
+        if (H != S || W != S)
+            return pn_set_error(ctx, PN_ERR_INVALID, "%s: a network input (PN_DEPTH_NET) is %dx%d, the buffer is %dx%d", who, S, S, W, H);
+        return PN_OK;
+    }
     if (W == 2 * S && H == 2 * S)   // as pn_preprocess: the pixel would be INTER_AREA's, which is not built
         return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: %dx%d -> %d is an exact 2x decimation, where cv2.resize(INTER_LINEAR) runs INTER_AREA instead: not built", who, W, H, S);
     return PN_OK;
@@ -135,6 +153,8 @@ int check_cfg(pn_ctx *ctx, const char *who, const pn_parse_cfg *cfg) {
     do {                                                                                                            \
         if (depth_dtype == PN_DEPTH_F16)                                                                            \
             hipLaunchKernelGGL(kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16 *)depth_dev, __VA_ARGS__);  \
+        else if (depth_dtype == PN_DEPTH_NET)                                                                       \
+            hipLaunchKernelGGL(kernel<NetIn>, grid, dim3(256), 0, s, (const NetIn *)depth_dev, __VA_ARGS__);        \
         else                                                                                                        \
             hipLaunchKernelGGL(kernel<float>, grid, dim3(256), 0, s, (const float *)depth_dev, __VA_ARGS__);        \
     } while (0)

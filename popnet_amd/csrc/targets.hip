@@ -31,6 +31,16 @@ __global__ void compose_depth_kernel(const T *__restrict__ fg_depth, const unsig
     out[(size_t)b * HW + i] = (float)v;
 }
 
+// single-person background swap (datasets_kdh3d_rtpose.py:227-234): image * mask + bg * (1 - mask) with a 0 / 1 mask is a select
+template <typename T>
+__global__ void compose_bg_kernel(const T *__restrict__ fg_depth, const unsigned char *__restrict__ fg_mask, const T *__restrict__ bg, size_t HW,
+                                  float *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= HW) return;
+    const size_t o = (size_t)blockIdx.y * HW + i;
+    out[o] = fg_mask[o] > 0 ? (float)fg_depth[o] : (float)bg[o];
+}
+
 // inside the network input?  remove_illegal_joint (:308-316)
 __device__ __forceinline__ bool t_inb(const float *kp, int input_x, int input_y) {
     return !(kp[0] >= (float)input_x || kp[0] < 0.f || kp[1] >= (float)input_y || kp[1] < 0.f);
@@ -149,6 +159,25 @@ int pn_compose_depth(pn_ctx *ctx, const void *fg_depth_dev, const unsigned char 
         hipLaunchKernelGGL(compose_depth_kernel<float>, grid, block, 0, s, (const float *)fg_depth_dev, fg_mask_dev, n_src_dev, (const float *)bg_dev, S, HW, (double)depth_max, out_dev);
     else
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_compose_depth: unknown depth dtype %d", depth_dtype);
+    PN_HIP_CHECK(ctx, hipGetLastError());
+    return PN_OK;
+}
+
+int pn_compose_bg(pn_ctx *ctx, const void *fg_depth_dev, const unsigned char *fg_mask_dev, const void *bg_dev, int depth_dtype, int B, int H, int W,
+                  float *out_dev, void *hip_stream) {
+    if (!ctx) return PN_ERR_INVALID;
+    if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
+    if (!fg_depth_dev || !fg_mask_dev || !bg_dev || !out_dev || B < 1 || B > 65535 || H < 1 || W < 1)
+        return pn_set_error(ctx, PN_ERR_INVALID, "pn_compose_bg: bad arguments");
+    if (depth_dtype != PN_DEPTH_F16 && depth_dtype != PN_DEPTH_F32)
+        return pn_set_error(ctx, PN_ERR_INVALID, "pn_compose_bg: unknown depth dtype %d", depth_dtype);
+    const size_t HW = (size_t)H * W;
+    dim3 grid((unsigned)((HW + 255) / 256), (unsigned)B), block(256);
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (depth_dtype == PN_DEPTH_F16)
+        hipLaunchKernelGGL(compose_bg_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)fg_depth_dev, fg_mask_dev, (const _Float16 *)bg_dev, HW, out_dev);
+    else
+        hipLaunchKernelGGL(compose_bg_kernel<float>, grid, block, 0, s, (const float *)fg_depth_dev, fg_mask_dev, (const float *)bg_dev, HW, out_dev);
     PN_HIP_CHECK(ctx, hipGetLastError());
     return PN_OK;
 }

@@ -158,15 +158,55 @@ def yolo_records_to_lists(recs, profile=None):
     return out
 
 
-def yolo_placeholder_person(profile, input_size=224):
+def kdh3d_pose_lists(lists, first_person=False):
+    """pose_records_to_lists(...) of the MP-3DHP profile (with or without ablation=) -> the lists of the composed and single-person KDH3D
+    scripts (evaluation_rtpose_light3d_kdh3d_mpaug_ablation.py:397-410, ..._kdh3d_ablation.py:400-410): the visibility list is named
+    `visibility_pred_set` and there is no part confidence.  first_person: the single-person scripts keep only the first parsed person of a
+    frame (..._kdh3d_ablation.py:198-201) -- in the 2D / 3D / visibility lists and in the raw-depth arm that follows the predicted persons;
+    the perfect_2d arms follow the ground-truth persons and keep theirs.  A frame without a person stays an empty list."""
+    cut = (lambda per_frame: [f[:1] for f in per_frame]) if first_person else (lambda per_frame: per_frame)
+    out = {"human_pred_set_2d": cut(lists["human_pred_set_2d"]), "human_pred_set_3d": cut(lists["human_pred_set_3d"]),
+           "visibility_pred_set": cut(lists["human_pred_set_visibility"])}
+    if "human_pred_set_3d_read_raw_depth" in lists:
+        out["human_pred_set_3d_read_raw_depth"] = cut(lists["human_pred_set_3d_read_raw_depth"])
+        for k in ABLATION_KEYS[1:]:
+            out[k] = lists[k]
+    return out
+
+
+def yolo_kdh3d_lists(recs, first_person=False, profile=None, input_size=224, w_org=None, h_org=None, intrinsics=None):
+    """pn_yolo_frame records -> human_pred_set_{2d,3d} of the Yolo-Pose+ scripts of the composed and single-person KDH3D sets.
+    first_person=False (evaluation_yolo_posenet_kdh3d_mpaug.py:185-225; engine with conf_threshold=0.5, nms_threshold=0.5): every person of
+    a frame.  first_person=True (evaluation_yolo_posenet_kdh3d.py:189-233; engine with conf_threshold=0.1): the first one.  Either way a
+    frame without a detection gets the scripts' placeholder person (yolo_placeholder_person), never an empty list.  w_org / h_org /
+    intrinsics: the engine's overrides of the profile's, for the placeholder's rescale and back-projection."""
+    prof = profiles.get(profile)
+    out = {"human_pred_set_2d": [], "human_pred_set_3d": []}
+    for fr in recs:
+        # bit 0 truncates first-come in the reference's order, so the first person is exact all the same (see yolo_records_to_lists)
+        if int(fr["status"]) & (~1 if first_person else ~0):
+            raise _lib.PopnetError("yolo record overflow (status=%d)" % int(fr["status"]))
+        n = min(int(fr["n_det"]), 1) if first_person else int(fr["n_det"])
+        if n > 0:
+            out["human_pred_set_2d"].append(np.asarray(fr["joints_2d"][:n]).tolist())
+            out["human_pred_set_3d"].append(np.asarray(fr["joints_3d"][:n]).tolist())
+        else:
+            j2, j3 = yolo_placeholder_person(prof, input_size, w_org, h_org, intrinsics)
+            out["human_pred_set_2d"].append([j2.tolist()])
+            out["human_pred_set_3d"].append([j3.tolist()])
+    return out
+
+
+def yolo_placeholder_person(profile, input_size=224, w_org=None, h_org=None, intrinsics=None):
     """evaluation_yolo_posenet_itop.py:175-203 for a frame without a detection: np.ones * -1 joints and depths (float64) through the
-    script's rescale, pos_3d_from_2d_and_depth (common.py: (x - cx) / fx * Z) and the Y flip -- the profile's negative fy."""
+    script's rescale, pos_3d_from_2d_and_depth (common.py: (x - cx) / fx * Z) and the Y flip -- the profile's negative fy.
+    w_org / h_org / intrinsics override the profile's, as the engines' arguments of those names do."""
     prof = profiles.get(profile)
     human = np.ones([NUM_PARTS, 2]) * (-1)
     depth = np.ones(NUM_PARTS) * (-1)
-    human[:, 0] = human[:, 0] / input_size * prof.w_org
-    human[:, 1] = human[:, 1] / input_size * prof.h_org
-    k = prof.intrinsics
+    human[:, 0] = human[:, 0] / input_size * (prof.w_org if w_org is None else w_org)
+    human[:, 1] = human[:, 1] / input_size * (prof.h_org if h_org is None else h_org)
+    k = prof.intrinsics if intrinsics is None else intrinsics
     X = (human[:, 0] - k["cx"]) / k["fx"] * depth
     Y = (human[:, 1] - k["cy"]) / k["fy"] * depth
     return human, np.stack([X, Y, depth], axis=1)

@@ -140,6 +140,37 @@ class PoseEngine:
         dt = _lib.PN_DEPTH_F16 if depth.dtype == torch.float16 else _lib.PN_DEPTH_F32
         return B, (C.c_void_p(depth.data_ptr()), dt, B, H, W, float(self.profile.depth_max), float(self.profile.depth_mean), float(self.profile.depth_std))
 
+    def _inputs_args(self, x):
+        """_frames_args for the third input kind of the ablation entries (PN_DEPTH_NET): x [B,1,S,S] float32, the network input itself.
+        -> (B, the entry's frame arguments, the contiguous tensor they point into)."""
+        _lib.require_cuda_tensor(x, "x")
+        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (1, self.S, self.S):
+            raise _lib.PopnetError("a network input must be a [B,1,%d,%d] float32 tensor, got %s %s" % (self.S, self.S, tuple(x.shape), x.dtype))
+        B = x.shape[0]
+        if B > self.max_batch:
+            raise _lib.PopnetError("batch %d exceeds max_batch %d" % (B, self.max_batch))
+        x = x.contiguous()      # handed back: the pointer in the arguments is into THIS tensor, which the caller keeps until the launch
+        return B, (C.c_void_p(x.data_ptr()), _lib.PN_DEPTH_NET, B, self.S, self.S, float(self.profile.depth_max), float(self.profile.depth_mean),
+                   float(self.profile.depth_std)), x
+
+    def _depth_args(self, depth):
+        """(B, the entry's frame arguments, the contiguous tensor they point into) of raw frames [B,H,W] or of a network input [B,1,S,S]."""
+        if isinstance(depth, torch.Tensor) and depth.dim() == 4:
+            return self._inputs_args(depth)
+        depth = depth.contiguous() if isinstance(depth, torch.Tensor) else depth      # (_frames_args points into what it is given once contiguous)
+        B, args = self._frames_args(depth)
+        return B, args, depth
+
+    def predict_inputs(self, x, frames=None, wire=None):
+        """predict() on an already clamped and normalised network input x [B,1,S,S] float32 (device) -- what the scripts that compose or
+        augment their frames feed the net (targets.augment_resize, KDH3DSingleSet.inputs).  In every precision x is copied into self.x
+        and forward(B) runs: the fused frames-in stem resizes raw frames and has nothing to do here.  No sync."""
+        B, _, x = self._inputs_args(x)
+        self.x[:B].copy_(x)
+        self.forward(B)
+        self.parse(B, frames, wire)
+        return (self.frames if frames is None else frames)[:B]
+
     def forward_frames(self, depth):
         """preprocess + forward as ONE call on the raw frames (pn_rtpose_forward_frames: the stem resizes / clamps / normalises its own
         input tile; bit-identical maps, the pre-processed tensor is never written).  The fp32 parity mode keeps the two calls."""
@@ -201,8 +232,10 @@ class PoseEngine:
 
     def ablation_arms(self, depth, recs, gt_2d, gmax=None):
         """The two launches behind predict_ablation: pn_ablation_pred_raw on the device records `recs` and pn_ablation_perfect_2d on the
-        pose-depth maps in self.z, both reading the raw frames `depth` the records and maps came from.  -> (pred_raw, perfect_map, perfect_raw)."""
-        B, args = self._frames_args(depth)
+        pose-depth maps in self.z, both reading the raw frames `depth` the records and maps came from.  -> (pred_raw, perfect_map, perfect_raw).
+        depth may also be the network input itself, [B,1,S,S] float32 as predict_inputs took it (PN_DEPTH_NET): the raw depth is then
+        that tensor un-normalised, as in the scripts that have no raw frame (evaluation_rtpose_light3d_kdh3d_mpaug_ablation.py:206-207)."""
+        B, args, depth = self._depth_args(depth)
         if len(gt_2d) != B or recs.shape[0] != B:
             raise _lib.PopnetError("ablation_arms: %d frames, %d records, ground truth for %d" % (B, recs.shape[0], len(gt_2d)))
         J = _lib.PN_NUM_JOINTS
@@ -217,7 +250,6 @@ class PoseEngine:
                 if a.shape != (len(g), J, 2):
                     raise _lib.PopnetError("ablation_arms: ground truth of frame %d has shape %s, expected [n][%d][2]" % (b, a.shape, J))
                 gt[b, :len(g)] = a
-        depth = depth.contiguous()
         recs = recs.contiguous()
         d = self.device
         gt_dev = torch.from_numpy(gt).to(d, non_blocking=True)
@@ -237,10 +269,10 @@ class PoseEngine:
 
     def depth_probe(self, depth, points):
         """The un-normalised network input ("raw depth" of the evaluation script) at `points` [n][3] = (frame, y, x) of the S x S frames the
-        engine derives from depth [B,H,W]: float32 [n] (host).  A point outside the batch or the frame raises."""
-        B, args = self._frames_args(depth)
+        engine derives from depth [B,H,W], or of a network input [B,1,S,S] (see ablation_arms): float32 [n] (host).  A point outside the
+        batch or the frame raises."""
+        B, args, depth = self._depth_args(depth)
         pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 3)
-        depth = depth.contiguous()
         pts_dev = torch.from_numpy(pts).to(self.device)
         out = torch.empty((len(pts),), device=self.device, dtype=torch.float32)
         self.ctx.check(self.L.pn_depth_probe(self.ctx.handle, C.c_void_p(depth.data_ptr()), *args[1:5], self.S, *args[5:8],
@@ -252,7 +284,8 @@ class PoseEngine:
         """The eval_data.json lists of one batch with the four ablation keys (dataset.pose_records_to_lists(..., ablation=...)): recs (numpy
         records) and the three arms (numpy or device) as predict_ablation returned them for depth / gt_2d, the batch's maps still in
         self.heat / self.paf / self.z.  A frame whose record overflowed is parsed again without capacities, as in lists_from_records; its raw
-        arm then comes from pn_depth_probe at the re-parsed joints and the reference's float64 back-projection."""
+        arm then comes from pn_depth_probe at the re-parsed joints and the reference's float64 back-projection.  depth: raw frames or the
+        network input, as in ablation_arms."""
         from .dataset import pose_records_to_lists
         from .utils.paf_to_pose import parse_paf_unbounded
         tonp = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
@@ -334,6 +367,15 @@ class YoloEngine:
                                                                    _lib.current_stream_ptr(self.device)), "pn_yolo_forward")
 
     _frames_args = PoseEngine._frames_args
+    _inputs_args = PoseEngine._inputs_args
+
+    def predict_inputs(self, x, frames=None):
+        """predict() on an already clamped and normalised network input x [B,1,S,S] float32 (device); see PoseEngine.predict_inputs."""
+        B, _, x = self._inputs_args(x)
+        self.x[:B].copy_(x)
+        self.forward(B)
+        self.parse(B, frames)
+        return (self.frames if frames is None else frames)[:B]
 
     def forward_frames(self, depth):
         """preprocess + forward as one call on the raw frames (pn_yolo_forward_frames); fp32 keeps the two calls."""

@@ -72,6 +72,28 @@ def compose_depth(fg_depth, fg_mask, n_src, bg, depth_max=DEPTH_MAX):
     return out
 
 
+def compose_bg(fg_depth, fg_mask, bg):
+    """The single-person loader's background swap (datasets_kdh3d_rtpose.py:227-234): fg_mask > 0 ? fg_depth : bg per pixel, with no
+    z-buffer and no 2 * depth_max cap (compose_depth with one source cuts a foreground pixel beyond the cap; this keeps it).
+    fg_depth, bg [B,H,W] float16 / float32 metres (same dtype), fg_mask [B,H,W] uint8 -> [B,H,W] float32."""
+    for t, n in ((fg_depth, "fg_depth"), (fg_mask, "fg_mask"), (bg, "bg")):
+        _lib.require_cuda_tensor(t, n)
+    if fg_depth.dtype not in (torch.float16, torch.float32) or bg.dtype != fg_depth.dtype:
+        raise _lib.PopnetError("compose_bg: fg_depth / bg must both be float16 or float32")
+    if fg_mask.dtype != torch.uint8:
+        raise _lib.PopnetError("compose_bg: fg_mask must be uint8")
+    if fg_depth.dim() != 3 or fg_mask.shape != fg_depth.shape or bg.shape != fg_depth.shape:
+        raise _lib.PopnetError("compose_bg: shape mismatch")
+    B, H, W = fg_depth.shape
+    fg_depth, fg_mask, bg = fg_depth.contiguous(), fg_mask.contiguous(), bg.contiguous()
+    out = torch.empty((B, H, W), dtype=torch.float32, device=fg_depth.device)
+    ctx = _ctx(fg_depth.device)
+    dt = _lib.PN_DEPTH_F16 if fg_depth.dtype == torch.float16 else _lib.PN_DEPTH_F32
+    ctx.check(_lib.lib().pn_compose_bg(ctx.handle, C.c_void_p(fg_depth.data_ptr()), C.c_void_p(fg_mask.data_ptr()), C.c_void_p(bg.data_ptr()), dt,
+                                       B, H, W, C.c_void_p(out.data_ptr()), _lib.current_stream_ptr(fg_depth.device)), "pn_compose_bg")
+    return out
+
+
 def rasterize_targets(kp2d, kp_z, n_persons, depth_resize, input_size=224, stride=8, z_radius=2, sigma=7.0, profile=None):
     """get_ground_truth for a batch.  kp2d [B,P,15,2] float32 (network-input pixels), kp_z [B,P,15] float64 (metres), n_persons [B]
     int32, depth_resize [B,h,w] float32 -> (heat [B,16,h,w], paf [B,28,h,w], z [B,15,h,w], fg [B,15,h,w]) float32.
@@ -168,8 +190,10 @@ def augmentation(rot, a, crops, H, W, cx, cy, input_size=224, hflip=False, swap_
       src_w, src_h    the size Resize sees.
     hflip: Hflip's coin came up (data_augmentation_2d3d.py:452-493, between RenderDepth and Crop): the render image is mirrored left to
     right; swap_indices (the profile's get_swap_part_indices()) is then required -- the labels' left / right joints trade places.
+    crops=None: the chain has no Crop (the composed test set's Compose([Cvt2ndarray, Rotate, RenderDepth, Resize]),
+    evaluation_rtpose_light3d_kdh3d_mpaug_ablation.py:118-123): Resize reads the whole render image, crop_bounds = (0, 0, render_w, render_h).
     Nothing here touches the GPU.  A geometry the reference itself cannot run (the paste does not fit, an empty image) raises."""
-    rot, a_drawn, crops = float(rot), float(a), tuple(float(c) for c in crops)
+    rot, a_drawn, crops = float(rot), float(a), None if crops is None else tuple(float(c) for c in crops)
     hflip = bool(hflip)
     if hflip and (swap_indices is None or sorted(int(i) for i in swap_indices) != list(range(NUM_JOINTS))):
         raise _lib.PopnetError("augmentation: hflip needs swap_indices, a permutation of the %d joints" % NUM_JOINTS)
@@ -217,12 +241,18 @@ def augmentation(rot, a, crops, H, W, cx, cy, input_size=224, hflip=False, swap_
         render_x, render_y = -dx, -dy
     if render_w < 1 or render_h < 1:
         raise _lib.PopnetError("augmentation: RenderDepth with a = %r leaves an empty image" % a_drawn)
-    # Crop (:102-118) on the render image
-    c_xmin, c_ymin = int(min(crops[0] * render_w, render_w)), int(min(crops[2] * render_h, render_h))
-    c_xmax, c_ymax = int(max(render_w - 1 - crops[1] * render_w, 0)), int(max(render_h - 1 - crops[3] * render_h, 0))
-    cy0, cy1, _ = slice(c_ymin, c_ymax).indices(render_h)
-    cx0, cx1, _ = slice(c_xmin, c_xmax).indices(render_w)
-    if cx1 - cx0 < 1 or cy1 - cy0 < 1:
+    if crops is None:
+        # no Crop in the chain (the evaluation scripts' Compose): Resize sees the whole render image.  Zero fractions are NOT this: Crop's
+        # xmax = w - 1 still drops the last row and column
+        c_xmin, c_ymin, c_xmax, c_ymax = 0, 0, render_w, render_h
+        cx0, cy0, cx1, cy1 = 0, 0, render_w, render_h
+    else:
+        # Crop (:102-118) on the render image
+        c_xmin, c_ymin = int(min(crops[0] * render_w, render_w)), int(min(crops[2] * render_h, render_h))
+        c_xmax, c_ymax = int(max(render_w - 1 - crops[1] * render_w, 0)), int(max(render_h - 1 - crops[3] * render_h, 0))
+        cy0, cy1, _ = slice(c_ymin, c_ymax).indices(render_h)
+        cx0, cx1, _ = slice(c_xmin, c_xmax).indices(render_w)
+    if crops is not None and (cx1 - cx0 < 1 or cy1 - cy0 < 1):      # (without Crop the source is the render image, checked above)
         raise _lib.PopnetError("augmentation: Crop %r leaves an empty image" % (crops,))
     return dict(rot=rot, a=a_drawn, crops=crops, cx=cx, cy=cy, H=H, W=W, input_size=int(input_size), rot_mat=fwd, inv_mat=tuple(m),
                 render_corner=(new_xmin, new_ymin, new_xmax, new_ymax), render_a=a, render_x=render_x, render_y=render_y,
@@ -231,14 +261,15 @@ def augmentation(rot, a, crops, H, W, cx, cy, input_size=224, hflip=False, swap_
                 swap_indices=[int(i) for i in swap_indices] if hflip else None)
 
 
-def draw_augmentation(H, W, cx, cy, min_ratio=0.7, max_ratio=1.7, max_crop=0.1, input_size=224, hflip=False, swap_indices=None):
+def draw_augmentation(H, W, cx, cy, min_ratio=0.7, max_ratio=1.7, max_crop=0.1, input_size=224, hflip=False, swap_indices=None, crop=True):
     """Draws one item's transform from Python's `random` in the reference's order -- Rotate: uniform(-10, 10); RenderDepth:
     uniform(min_ratio, max_ratio); with hflip (the ITOP trainers' Hflip) the coin uniform(0, 1) >= 0.5; Crop: four uniform(0, max_crop)
-    for left, right, top, bottom -- and derives its geometry.  Without hflip no coin is drawn: the six draws of the MP-3DHP chain."""
+    for left, right, top, bottom -- and derives its geometry.  Without hflip no coin is drawn: the six draws of the MP-3DHP chain.
+    crop=False: the chain without Crop (augmentation(crops=None)); its four draws are not made, the others are, in the same order."""
     rot = random.uniform(-10, 10)
     a = random.uniform(min_ratio, max_ratio)
     flip = (random.uniform(0, 1) >= 0.5) if hflip else False
-    crops = tuple(random.uniform(0, max_crop) for _ in range(4))
+    crops = tuple(random.uniform(0, max_crop) for _ in range(4)) if crop else None
     return augmentation(rot, a, crops, H, W, cx, cy, input_size, hflip=flip, swap_indices=swap_indices if flip else None)
 
 
@@ -315,6 +346,20 @@ class AugmentationBatch:
                 bx[b, :, 0:4:2] = bx[b, :, 0:4:2] * wr
                 bx[b, :, 1:4:2] = bx[b, :, 1:4:2] * hr
         return (kp, kz, bx) if visible is None else (kp, kz, bx, vs)
+
+
+def composed_ground_truth(kp2d, kp3d, kp_z, n_persons, w_org, h_org, input_size=224):
+    """The ground truth the composed-test-set scripts collect per frame (evaluation_rtpose_light3d_kdh3d_mpaug_ablation.py:176-189) from
+    transform_labels' results: kp2d [B,P,15,2] float32 (network-input pixels) scaled back with `*= w_org / input_size`, `*= h_org /
+    input_size` on the float32 array, and the labels' 3D joints kp3d [B,P,15,3] with the depth RenderDepth scaled (kp_z [B,P,15]; X and
+    Y stay as labelled).  -> (human_gt_set_2d, human_gt_set_3d): per frame a list of its n_persons[b] persons' [15][2] / [15][3] lists."""
+    kp = np.array(kp2d, dtype=np.float32)
+    kp[..., 0] *= (w_org / input_size)
+    kp[..., 1] *= (h_org / input_size)
+    k3 = np.array(kp3d, dtype=np.float64)
+    k3[..., 2] = np.asarray(kp_z, dtype=np.float64)
+    n = [int(v) for v in _host(n_persons)]
+    return [kp[b, :n[b]].tolist() for b in range(len(n))], [k3[b, :n[b]].tolist() for b in range(len(n))]
 
 
 def augment_resize(frames, aug, input_size=224, depth_max=None, mean=0.0, std=1.0, profile=None):
@@ -450,6 +495,18 @@ class MPAugSampler:
             return self._arrays(picks) + (AugmentationBatch(items),)
         return self._arrays(picks)
 
+    def test_batch(self, batch_size, dataset_len, **aug_args):
+        """The draws of generate_test_batch (datasets_kdh3d_rtpose_mpaug.py:431-476): per item the index FIRST
+        (random.randint(0, dataset_len - 1)), then its source draws, then its augmentation draws (draw_augmentation(**aug_args); the
+        evaluation scripts' chain has no Crop: pass crop=False).  -> (indices [B] int64, src, n_src, bg, AugmentationBatch)."""
+        indices, picks, items = [], [], []
+        for _ in range(int(batch_size)):
+            index = random.randint(0, int(dataset_len) - 1)
+            indices.append(index)
+            picks.append(self.sources(index))
+            items.append(draw_augmentation(**aug_args))
+        return (np.array(indices, dtype=np.int64),) + self._arrays(picks) + (AugmentationBatch(items),)
+
     def _arrays(self, picks):
         src = np.full((len(picks), self.max_sources, 2), -1, dtype=np.int64)
         for r, (s, _) in enumerate(picks):
@@ -506,23 +563,37 @@ class MPAugTrainSet:
             self._hw = tuple(np.load(os.path.join(self.bg_dir, self.bg[0]["file_name"]), mmap_mode="r").shape)
         return self._hw
 
-    def batch(self, indices, with_boxes=False, input_size=224, augment=False, max_aug_ratio=1.7):
+    def batch(self, indices, with_boxes=False, input_size=224, augment=False, max_aug_ratio=1.7, crop=True):
         """with_boxes: also return boxes [B,P,4] float64 (ann['bbox'] scaled by Resize to input_size, in float64 like
         data_augmentation_2d3d.py:497-522) and pose_weight [B,P] float64 (ann['pose_weight']) -- the YoloPoseNet trainer's extra inputs.
         augment: draw the random training transform of every item (Rotate / RenderDepth(max_ratio=max_aug_ratio) / Crop about the
         `intrinsics` cx, cy of the first annotation file, interleaved with the source draws like the reference's __getitem__) and
         append the batch's AugmentationBatch as the LAST element, for mpaug_batch(..., aug=) / mpaug_batch_yolo(..., aug=).  The
         labels then stay on the host (kp2d_org, kp3d and boxes as numpy arrays: their transform is host work) and boxes stay in
-        ORIGINAL pixels, because the transform's offsets come before its scale."""
-        import os
+        ORIGINAL pixels, because the transform's offsets come before its scale.  crop=False: the chain without Crop (draw_augmentation)."""
         if augment:
             cx, cy = self._principal_point()
             H0, W0 = self._frame_size()
             src, n_src, bg_id, aug = self.sampler.batch(indices, augment=True, H=H0, W=W0, cx=cx, cy=cy, max_ratio=float(max_aug_ratio),
-                                                        input_size=input_size)
+                                                        input_size=input_size, crop=crop)
         else:
-            src, n_src, bg_id = self.sampler.batch(indices)
-        B, S = len(indices), self.max_sources
+            src, n_src, bg_id, aug = self.sampler.batch(indices) + (None,)
+        return self._load(src, n_src, bg_id, aug, with_boxes, input_size)
+
+    def test_batch(self, batch_size, input_size=224, max_aug_ratio=1.7, with_boxes=False):
+        """A batch of the composed TEST set as generate_test_batch draws it (datasets_kdh3d_rtpose_mpaug.py:415-488): random indices, each
+        followed by its source draws and the two draws of the evaluation scripts' chain Rotate / RenderDepth(max_ratio=max_aug_ratio) /
+        Resize -- no Crop.  Returns what batch(augment=True) returns (labels on the host, the AugmentationBatch last)."""
+        cx, cy = self._principal_point()
+        H0, W0 = self._frame_size()
+        _, src, n_src, bg_id, aug = self.sampler.test_batch(batch_size, len(self), H=H0, W=W0, cx=cx, cy=cy, max_ratio=float(max_aug_ratio),
+                                                            input_size=input_size, crop=False)
+        return self._load(src, n_src, bg_id, aug, with_boxes, input_size)
+
+    def _load(self, src, n_src, bg_id, aug, with_boxes, input_size):
+        import os
+        augment = aug is not None
+        B, S = len(n_src), self.max_sources
         frames, masks, bgs, persons = [], [], [], []
         for b in range(B):
             fr, mk, pp = [], [], []
@@ -708,3 +779,61 @@ class ItopSet:
         items = [draw_augmentation(H, W, cx, cy, min_ratio=a["min_ratio"], max_ratio=a["max_ratio"], max_crop=a["max_crop"], input_size=input_size,
                                    hflip=a["hflip"], swap_indices=self.profile.swap_indices) for _ in indices]
         return out + (AugmentationBatch(items),)
+
+
+class KDH3DSingleSet:
+    """The files of the single-person KDH3D sets (`val`, and `test_bgaug` with bg_aug=True) as datasets_kdh3d_rtpose.KDH3D_Keypoints reads them
+    (:161-180, :222-234): one annotation file (image id -> list of persons; an 'intrinsics' entry is skipped), the frame of id X is
+    `<img_dir>/X`.  bg_aug: the frame's foreground (`<seg_dir>/X`, > 0) is pasted over background index % n_bg of bg_file's list, which is
+    shuffled once at construction (random.shuffle, as the reference does) -- compose_bg, not the z-buffer composition.
+    `inputs(indices)` returns the network input [B,1,S,S] (device): Resize, the clamp and the normalisation of __getitem__ in one
+    pn_preprocess launch."""
+
+    def __init__(self, img_dir, ann_file, bg_aug=False, bg_file=None, bg_dir=None, seg_dir=None, device="cuda:0", profile=None, shuffle=True):
+        import json
+        self.img_dir, self.bg_dir, self.seg_dir, self.device = img_dir, bg_dir, seg_dir, torch.device(device)
+        self.profile = profiles.get(profile)
+        self.anno_dic = json.load(open(ann_file, "r"))
+        self.ids = [k for k in self.anno_dic if k != "intrinsics"]
+        self.bg_aug = bool(bg_aug)
+        self.bg = []
+        if self.bg_aug:
+            if not (bg_file and bg_dir and seg_dir):
+                raise _lib.PopnetError("KDH3DSingleSet(bg_aug=True) needs bg_file, bg_dir and seg_dir")
+            self.bg = list(json.load(open(bg_file, "r")).values())
+            if shuffle:
+                random.shuffle(self.bg)
+
+    def __len__(self):
+        return len(self.ids)
+
+    def ground_truth(self, indices=None):
+        """(human_gt_set_2d, human_gt_set_3d) of the frames `indices` (None = all), as the evaluation scripts collect them (:164-171)."""
+        ids = self.ids if indices is None else [self.ids[i] for i in indices]
+        return ([[p["2d_joints"] for p in self.anno_dic[k]] for k in ids], [[p["3d_joints"] for p in self.anno_dic[k]] for k in ids])
+
+    def frames(self, indices):
+        """-> [B,H,W] float32 (device): the stored frames, with the background swapped in when bg_aug."""
+        import os
+        dev = self.device
+        fg = np.stack([np.load(os.path.join(self.img_dir, self.ids[i])) for i in indices])
+        dt = np.float16 if fg.dtype == np.float16 else np.float32
+        if not self.bg_aug:
+            return torch.from_numpy(fg.astype(dt)).to(dev).to(torch.float32)
+        mask = np.stack([np.asarray(np.load(os.path.join(self.seg_dir, self.ids[i]))) > 0 for i in indices]).astype(np.uint8)
+        bg = np.stack([np.load(os.path.join(self.bg_dir, self.bg[i % len(self.bg)]["file_name"])) for i in indices])
+        if bg.dtype != np.float16:
+            dt = np.float32
+        return compose_bg(torch.from_numpy(fg.astype(dt)).to(dev), torch.from_numpy(mask).to(dev), torch.from_numpy(bg.astype(dt)).to(dev))
+
+    def inputs(self, indices, input_size=224, frames=None):
+        """frames: what frames(indices) returned, when the caller has it already."""
+        frames = self.frames(indices) if frames is None else frames
+        B, H, W = frames.shape
+        out = torch.empty((B, 1, int(input_size), int(input_size)), dtype=torch.float32, device=frames.device)
+        p = self.profile
+        ctx = _ctx(frames.device)
+        ctx.check(_lib.lib().pn_preprocess(ctx.handle, C.c_void_p(frames.data_ptr()), _lib.PN_DEPTH_F32, B, H, W, C.c_void_p(out.data_ptr()),
+                                           int(input_size), float(p.depth_max), float(p.depth_mean), float(p.depth_std),
+                                           _lib.current_stream_ptr(frames.device)), "pn_preprocess")
+        return out
