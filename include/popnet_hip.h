@@ -746,6 +746,43 @@ int pn_a2j_predict(pn_net *net, const void *frames_dev, int depth_dtype, int F, 
                    const pn_a2j_cfg *cfg, const float *anchors_dev, float *crops_dev, int32_t *flags_dev, float *votes_dev,
                    pn_a2j_record *records_dev, void *hip_stream);
 
+/* ---- A2J training crops: the crop-level augmentation of the A2J trainers (csrc/a2j_traincrop.hip) ------------------------------
+ * dataPreprocess + transform of third_party_methods/A2J_experiments/itop_train_64.py:208-295, train_a2j_base.py:236-317 and
+ * train_a2j_bgaug_new.py:251-338 as ONE launch for n crops: the box region of a frame, (pasted into the zero image of the raw box,)
+ * cv2.resize(INTER_NEAREST) to crop_w x crop_h, float32, (the ITOP depth window,) (v - mean) / std and, when `warp` is set,
+ * cv2.warpAffine(INTER_LINEAR, constant border 0) of that NORMALISED crop onto crop_w x crop_h with the item's rotation and scale about
+ * the crop centre -- bit for bit what numpy and OpenCV 4.2's scalar float32 paths give (agreement with a live cv2 build is unverified, as
+ * for pn_augment_resize).  The shape of pn_augment_resize: one record per crop, every integer of the geometry and every scalar decided on
+ * the host (popnet_amd/a2j_crops.py), the records checked here and uploaded in stream order; the kernel never re-derives a truncation.
+ *   warp == 0   one source pixel per output pixel (augment=False: the reference does not call transform at all)
+ *   warp == 1   the four warpAffine taps; each tap is one pixel of the normalised crop, a tap outside the crop reads 0 (NOT normalised
+ *               zero depth); m is the INVERTED matrix as warpAffine holds it, the convention of pn_augment_item.m
+ *   one tap     INTER_NEAREST index min(floor(d * (1 / (dsize / ssize))), ssize - 1) in double; padded: the paste loop's strict
+ *               start < i < end test and its int(i - start) index, in float32; the frame's pixel as float32; window: v >= hi -> fill,
+ *               then v <= lo -> fill, then (v - sub) * scale (a NaN fails both comparisons and stays NaN); (v - mean) / std
+ * sh < 1 or sw < 1 is the empty image on which cv2.resize raises: the crop is zeros and flags_dev[row] (may be NULL) is 1, else 0.
+ * mean / std / crop_w / crop_h come from cfg; its other fields are not read.  frames_dev [F, H, W] f16 / f32.  items_host holds the n
+ * records; items_dev has room for n (the caller's buffer, nothing is allocated); out_dev [n, 1, crop_h, crop_w] f32.  No synchronisation;
+ * items_host stays untouched until the stream has passed the call.  Refusals (PN_ERR_INVALID, the text names the item; nothing is copied
+ * or launched): inconsistent geometry, a non-finite matrix or scalar, a matrix outside |m0|, |m1|, |m3|, |m4| <= 64 and |m2|, |m5| <= 2^19 (the
+ * fixed-point products then fit an int for every crop size; a crop-centre rotation at scales from 1/64 up lies far inside), n > 65535, a crop side
+ * over 4096, std == 0.  n == 0 is PN_OK.  */
+typedef struct pn_a2j_crop_item {
+    double m[6];                       /* warp: the inverted 2x3 matrix (destination pixel -> pixel of the normalised crop), row major   */
+    int frame;                         /* index into frames_dev                                                                           */
+    int cy0, cx0, ih, iw;              /* the clipped region depth[cy0 : cy0 + ih, cx0 : cx0 + iw] (Python's slice rules applied): inside
+                                          the frame                                                                                       */
+    int sh, sw;                        /* the image cv2.resize reads: ih x iw, or the padded image int(y1 - y0) x int(x1 - x0)            */
+    int padded;                        /* 1: the region is pasted into the zero image sh x sw                                             */
+    float start1, start2, end1, end2;  /* the paste loop's bounds (rows: 1, columns: 2), read when padded                                 */
+    int window;                        /* 1: the ITOP depth window                                                                        */
+    float hi, lo, fill, sub, scale;    /* centre depth +- depth_thres, the centre depth (twice), float32(RandomScale); read when window   */
+    int warp;                          /* 1: transform() follows (augment=True)                                                           */
+} pn_a2j_crop_item;
+size_t pn_sizeof_a2j_crop_item(void);
+int pn_a2j_train_crop(pn_ctx *ctx, const void *frames_dev, int depth_dtype, int F, int H, int W, const pn_a2j_crop_item *items_host,
+                      pn_a2j_crop_item *items_dev, int n, const pn_a2j_cfg *cfg, float *out_dev, int32_t *flags_dev, void *hip_stream);
+
 /* ---- legacy plug-in ABI: the SWIG module `pafprocess` -----------------------------------------
  * Same seven symbols, same argument meaning and the same (non re-entrant, global-state)
  * semantics as tpm/lib/pafprocess/pafprocess.h:53-59, COCO-18 topology (pafprocess.h:6-24).

@@ -54,6 +54,14 @@ class AugmentItem(C.Structure):
                 ("src_w", C.c_int), ("src_h", C.c_int), ("hflip", C.c_int)]
 
 
+class A2JCropItem(C.Structure):
+    """pn_a2j_crop_item"""
+    _fields_ = [("m", C.c_double * 6), ("frame", C.c_int), ("cy0", C.c_int), ("cx0", C.c_int), ("ih", C.c_int), ("iw", C.c_int),
+                ("sh", C.c_int), ("sw", C.c_int), ("padded", C.c_int), ("start1", C.c_float), ("start2", C.c_float), ("end1", C.c_float),
+                ("end2", C.c_float), ("window", C.c_int), ("hi", C.c_float), ("lo", C.c_float), ("fill", C.c_float), ("sub", C.c_float),
+                ("scale", C.c_float), ("warp", C.c_int)]
+
+
 class NmsOpt(C.Structure):
     """pn_nms_opt"""
     _fields_ = [("upsample", C.c_int), ("refine_center", C.c_int), ("gaussian_filt", C.c_int)]
@@ -211,6 +219,8 @@ _SIGNATURES = {
     "pn_a2j_head_shape": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "pn_a2j_vote": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn_a2j_predict": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_sizeof_a2j_crop_item": (_sz, []),
+    "pn_a2j_train_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "pn_debug_cubic_coeffs": (None, [_f, C.POINTER(C.c_float)]),
     "process_paf": (_i, [_i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "get_num_humans": (_i, []),
@@ -250,6 +260,8 @@ def lib():
         raise PopnetError("pn_yolo_frame layout mismatch")
     if handle.pn_sizeof_augment_item() != C.sizeof(AugmentItem):
         raise PopnetError("pn_augment_item layout mismatch: C %d vs ctypes %d" % (handle.pn_sizeof_augment_item(), C.sizeof(AugmentItem)))
+    if handle.pn_sizeof_a2j_crop_item() != C.sizeof(A2JCropItem):
+        raise PopnetError("pn_a2j_crop_item layout mismatch: C %d vs ctypes %d" % (handle.pn_sizeof_a2j_crop_item(), C.sizeof(A2JCropItem)))
     if handle.pn_sizeof_parse_cfg() != C.sizeof(ParseCfg):
         raise PopnetError("pn_parse_cfg layout mismatch: C %d vs ctypes %d" % (handle.pn_sizeof_parse_cfg(), C.sizeof(ParseCfg)))
     _lib = handle

@@ -447,7 +447,7 @@ class A2JEngine:
         self.anchors = torch.from_numpy(shift([self.crop_h // 16, self.crop_w // 16], 16, generate_anchors())).float().to(d)
         self.x = torch.empty((self.max_batch, 1, self.crop_h, self.crop_w), device=d, dtype=torch.float32)
         self.last_flags = None
-        self.votes = torch.empty((self.max_batch, 15, 3), device=d, dtype=torch.float32)
+        self._votes = torch.empty((self.max_batch, 15, 3), device=d, dtype=torch.float32)
 
     @property
     def net(self):
@@ -476,6 +476,43 @@ class A2JEngine:
                                           _lib.current_stream_ptr(self.device)), "pn_a2j_crop")
         return out, flags
 
+    def train_crops(self, frames, items):
+        """The trainers' crop-level augmentation (pn_a2j_train_crop): frames [F, H, W] float16 / float32 and the pn_a2j_crop_item records of
+        popnet_amd.a2j_crops.itop_items / box_items -> ([n, 1, crop_h, crop_w] float32, [n] int32 flags: 1 where the reference would
+        raise, the crop is zeros).  One launch, no sync; mean / std are self.cfg's.  The records are copied to the device in stream order
+        and must stay untouched until the stream has passed the call: the engine holds on to `items` until its next train_crops, so
+        a caller may drop or rebind them at once, but must not write into them before a synchronise."""
+        frames, dt = self._frames(frames)
+        n = len(items)
+        self._items_host = items
+        out = torch.empty((n, 1, self.crop_h, self.crop_w), device=self.device, dtype=torch.float32)
+        flags = torch.zeros((n,), device=self.device, dtype=torch.int32)
+        items_dev = torch.empty((max(n, 1) * C.sizeof(_lib.A2JCropItem),), device=self.device, dtype=torch.uint8)      # the call uploads the records it has checked
+        self.ctx.check(self.L.pn_a2j_train_crop(self.ctx.handle, C.c_void_p(frames.data_ptr()), dt, frames.shape[0], frames.shape[1], frames.shape[2],
+                                                C.cast(items, C.c_void_p), C.c_void_p(items_dev.data_ptr()), n, C.byref(self.cfg), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(flags.data_ptr()), _lib.current_stream_ptr(self.device)), "pn_a2j_train_crop")
+        return out, flags
+
+    def votes(self, crops):
+        """crops [n, 1, crop_h, crop_w] float32 (device) -> [n, 15, 3] float32 (y, x, z) in crop pixels: pn_a2j_forward and pn_a2j_vote in
+        chunks of max_batch, no map back to a frame (post_process of the eval-mode module; no sync)."""
+        _lib.require_cuda_tensor(crops, "crops")
+        if crops.dim() != 4 or tuple(crops.shape[1:]) != (1, self.crop_h, self.crop_w) or crops.dtype != torch.float32:
+            raise _lib.PopnetError("crops must be a [n, 1, %d, %d] float32 tensor, got %s %s" % (self.crop_h, self.crop_w, tuple(crops.shape), crops.dtype))
+        crops = crops.contiguous()
+        n = crops.shape[0]
+        out = torch.empty((n, 15, 3), device=self.device, dtype=torch.float32)
+        net = self.net
+        prec = self.model._net[1][1]
+        stream = _lib.current_stream_ptr(self.device)
+        for i in range(0, n, self.max_batch):
+            m = min(self.max_batch, n - i)
+            ptrs = [C.c_void_p() for _ in range(3)]
+            self.ctx.check(self.L.pn_a2j_forward(net, C.c_void_p(crops[i:].data_ptr()), m, *(C.byref(p) for p in ptrs), stream), "pn_a2j_forward")
+            self.ctx.check(self.L.pn_a2j_vote(self.ctx.handle, ptrs[0], ptrs[1], ptrs[2], prec, m, self.crop_h // 16, self.crop_w // 16, 16, 15,
+                                              C.c_void_p(self.anchors.data_ptr()), C.c_void_p(out[i:].data_ptr()), None, None, None, stream), "pn_a2j_vote")
+        return out
+
     def predict(self, frames, boxes):
         """-> device uint8 tensor [n, sizeof(pn_a2j_record)], the rows in chunks of max_batch (no sync).  self.last_flags: device int32 [n],
         1 where the reference would raise on the row's box (zero crop, see crops())."""
@@ -491,7 +528,7 @@ class A2JEngine:
             self.ctx.check(self.L.pn_a2j_predict(
                 net, C.c_void_p(frames.data_ptr()), dt, frames.shape[0], frames.shape[1], frames.shape[2], C.c_void_p(rows[i:].data_ptr()), m,
                 C.byref(self.cfg), C.c_void_p(self.anchors.data_ptr()), C.c_void_p(self.x.data_ptr()), C.c_void_p(flags[i:].data_ptr()),
-                C.c_void_p(self.votes.data_ptr()), C.c_void_p(recs[i:].data_ptr()), _lib.current_stream_ptr(self.device)), "pn_a2j_predict")
+                C.c_void_p(self._votes.data_ptr()), C.c_void_p(recs[i:].data_ptr()), _lib.current_stream_ptr(self.device)), "pn_a2j_predict")
         return recs
 
     def predict_host(self, frames, boxes):
@@ -502,6 +539,17 @@ class A2JEngine:
         human_pred_set_2d / _3d / part_conf lists (a2j_test_pred_box_new.py:397-421)."""
         recs = self.predict_host(frames, boxes)
         return lists_from_a2j_records(recs, frames.shape[0] if n_frames is None else n_frames)
+
+
+def a2j_set_votes(engine, batch_fn, n, batch_size):
+    """The test loop of the A2J trainers (itop_train_64.py:417-424): items 0 .. n - 1 in order, batch_fn(indices) -> (frames, records, labels)
+    (ItopA2JSet.batch / KDH3DSingleSet.crop_batch) -> engine.train_crops -> engine.votes.  -> [n, 15, 3] float32 host array (y, x, z)."""
+    out = []
+    for s in range(0, n, batch_size):
+        frames, items, _ = batch_fn(list(range(s, min(s + batch_size, n))))
+        crops, _ = engine.train_crops(frames, items)
+        out.append(engine.votes(crops))
+    return torch.cat(out).cpu().numpy() if out else np.zeros((0, 15, 3), np.float32)
 
 
 def lists_from_a2j_records(recs, n_frames):

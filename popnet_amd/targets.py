@@ -14,13 +14,12 @@ tensors.  The random transform's LABEL half (15 joints per person) and its integ
 reference operation for operation so that every dtype rounds the same way.
 """
 import ctypes as C
-import math
 import random
 
 import numpy as np
 import torch
 
-from . import _lib, profiles
+from . import _lib, a2j_crops, profiles, warp_affine
 from .config import DEPTH_MAX, DEPTH_MEAN, DEPTH_STD
 
 NUM_JOINTS, NUM_LIMBS = 15, 14
@@ -198,25 +197,12 @@ def augmentation(rot, a, crops, H, W, cx, cy, input_size=224, hflip=False, swap_
     if hflip and (swap_indices is None or sorted(int(i) for i in swap_indices) != list(range(NUM_JOINTS))):
         raise _lib.PopnetError("augmentation: hflip needs swap_indices, a permutation of the %d joints" % NUM_JOINTS)
     cx, cy, H, W = float(cx), float(cy), int(H), int(W)
-    # getRotationMatrix2D: the centre is a Point2f; alpha, beta in double.  This and the inversion below are the product's own copy of
-    # what tests/cv2_warp_reference.py restates; tests/test_augment_reference.py compares inv_mat with that restatement, and the
-    # exact-rational derivation of tests/test_cv2_warp_kat.py pins the restatement -- through that equality it guards this copy too.
-    fcx, fcy = float(np.float32(cx)), float(np.float32(cy))
-    ang = rot * (math.pi / 180)
-    alpha, beta = math.cos(ang) * 1.0, math.sin(ang) * 1.0
-    fwd = np.array([[alpha, beta, (1 - alpha) * fcx - beta * fcy], [-beta, alpha, beta * fcx + (1 - alpha) * fcy]], dtype=np.float64)
-    # warpAffine's inversion, in its operation order (imgwarp.cpp)
-    m = [float(v) for v in fwd.reshape(6)]
-    D = m[0] * m[4] - m[1] * m[3]
-    D = 1.0 / D if D != 0 else 0.0
-    A11, A22 = m[4] * D, m[0] * D
-    m[0] = A11
-    m[1] *= -D
-    m[3] *= -D
-    m[4] = A22
-    b1 = -m[0] * m[2] - m[1] * m[5]
-    b2 = -m[3] * m[2] - m[4] * m[5]
-    m[2], m[5] = b1, b2
+    # getRotationMatrix2D: the centre is a Point2f; alpha, beta in double.  This and the inversion below (warp_affine.py, shared with A2J's
+    # crop-level warp) are the product's own copy of what tests/cv2_warp_reference.py restates; tests/test_augment_reference.py compares
+    # inv_mat with that restatement, and the exact-rational derivation of tests/test_cv2_warp_kat.py pins the restatement -- through that
+    # equality it guards this copy too.
+    fwd = warp_affine.rotation_matrix((cx, cy), rot, 1.0)
+    m = warp_affine.invert_affine(fwd)      # warpAffine's inversion, in its operation order (imgwarp.cpp)
     # RenderDepth (data_augmentation_2d3d.py:303-335)
     xmin, ymin, xmax, ymax = float(0), float(0), float(W), float(H)
     new_xmin, new_ymin = int(a_drawn * (xmin - cx) + cx), int(a_drawn * (ymin - cy) + cy)
@@ -781,20 +767,52 @@ class ItopSet:
         return out + (AugmentationBatch(items),)
 
 
+class ItopA2JSet(ItopSet):
+    """The ITOP side-view split as the A2J trainer reads it (A2J_experiments/itop_train_64.py:88-185): the frames and labels of ItopSet plus
+    `center_{train,test}.txt`, one line `u v depth` per frame.  keypoints [N,15,3] float32 are the FIRST person's '3d_joints' (the script's
+    keypointsUVD: u, v, depth), lefttop / rightbottom the boxes of a2j_crops.itop_boxes.
+    A line containing `invalid` drops THAT FRAME from the set.  (The reference compacts the centre list only, which silently pairs every
+    later frame and label with the wrong centre.)
+    `batch(indices, draws)` -> (frames [B,H,W] device, pn_a2j_crop_item records, labels [B,15,3] float32 host) for A2JEngine.train_crops."""
+
+    def __init__(self, img_dir, ann_file, centre_file, device="cuda:0"):
+        super().__init__(img_dir, ann_file, device=device)
+        self.centres, kept, n = a2j_crops.read_centres(centre_file)
+        if n != len(self.ids):
+            raise _lib.PopnetError("%s has %d lines (invalid ones included), %s has %d frames" % (centre_file, n, ann_file, len(self.ids)))
+        self.ids = [self.ids[i] for i in kept]
+        self.keypoints = np.asarray([self.anno_dic[k][0]["3d_joints"] for k in self.ids], dtype=np.float32).reshape(-1, NUM_JOINTS, 3)
+        self.lefttop, self.rightbottom = a2j_crops.itop_boxes(self.centres)
+
+    def batch(self, indices, draws=None, crop=288):
+        """draws: one A2JCropSampler.draw() per item (augment=True) or None (augment=False)."""
+        frames = np.stack([self.load(i) for i in indices])
+        items, labels = a2j_crops.itop_items(list(indices), self.centres, self.lefttop, self.rightbottom, self.keypoints, frames.shape[1:], draws=draws,
+                                             crop_w=crop, crop_h=crop)
+        return torch.from_numpy(frames).to(self.device, non_blocking=True), items, labels
+
+
 class KDH3DSingleSet:
     """The files of the single-person KDH3D sets (`val`, and `test_bgaug` with bg_aug=True) as datasets_kdh3d_rtpose.KDH3D_Keypoints reads them
     (:161-180, :222-234): one annotation file (image id -> list of persons; an 'intrinsics' entry is skipped), the frame of id X is
     `<img_dir>/X`.  bg_aug: the frame's foreground (`<seg_dir>/X`, > 0) is pasted over background index % n_bg of bg_file's list, which is
     shuffled once at construction (random.shuffle, as the reference does) -- compose_bg, not the z-buffer composition.
     `inputs(indices)` returns the network input [B,1,S,S] (device): Resize, the clamp and the normalisation of __getitem__ in one
-    pn_preprocess launch."""
+    pn_preprocess launch.
+    boxes=True: the arrays the A2J trainers build at import (A2J_experiments/train_a2j_base.py:70-103) from the FIRST person of every frame --
+    bndbox [N,4], keypoints_2d [N,15,2], keypoints_3d [N,15,3] float32 -- for `crop_batch`."""
 
-    def __init__(self, img_dir, ann_file, bg_aug=False, bg_file=None, bg_dir=None, seg_dir=None, device="cuda:0", profile=None, shuffle=True):
+    def __init__(self, img_dir, ann_file, bg_aug=False, bg_file=None, bg_dir=None, seg_dir=None, device="cuda:0", profile=None, shuffle=True, boxes=False):
         import json
         self.img_dir, self.bg_dir, self.seg_dir, self.device = img_dir, bg_dir, seg_dir, torch.device(device)
         self.profile = profiles.get(profile)
         self.anno_dic = json.load(open(ann_file, "r"))
         self.ids = [k for k in self.anno_dic if k != "intrinsics"]
+        if boxes:
+            first = [self.anno_dic[k][0] for k in self.ids]
+            self.bndbox = np.asarray([p["bbox"] for p in first], dtype=np.float32).reshape(-1, 4)
+            self.keypoints_2d = np.asarray([p["2d_joints"] for p in first], dtype=np.float32).reshape(-1, NUM_JOINTS, 2)
+            self.keypoints_3d = np.asarray([p["3d_joints"] for p in first], dtype=np.float32).reshape(-1, NUM_JOINTS, 3)
         self.bg_aug = bool(bg_aug)
         self.bg = []
         if self.bg_aug:
@@ -825,6 +843,17 @@ class KDH3DSingleSet:
         if bg.dtype != np.float16:
             dt = np.float32
         return compose_bg(torch.from_numpy(fg.astype(dt)).to(dev), torch.from_numpy(mask).to(dev), torch.from_numpy(bg.astype(dt)).to(dev))
+
+    def crop_batch(self, indices, draws=None, crop=288, img_wh=None):
+        """boxes=True sets only: the A2J trainers' item (train_a2j_base.py / train_a2j_bgaug_new.py dataPreprocess) -> (frames [B,H,W] float32
+        device -- with the background swapped in when bg_aug --, pn_a2j_crop_item records, labels [B,15,3] float32 host) for
+        A2JEngine.train_crops.  draws: one A2JCropSampler('box').draw() per item (augment=True) or None."""
+        if not hasattr(self, "bndbox"):
+            raise _lib.PopnetError("KDH3DSingleSet.crop_batch needs boxes=True at construction")
+        frames = self.frames(indices)
+        items, labels = a2j_crops.box_items(list(indices), self.bndbox, self.keypoints_2d, self.keypoints_3d, frames.shape[1:], draws=draws,
+                                            crop_w=crop, crop_h=crop, img_wh=img_wh)
+        return frames, items, labels
 
     def inputs(self, indices, input_size=224, frames=None):
         """frames: what frames(indices) returned, when the caller has it already."""
