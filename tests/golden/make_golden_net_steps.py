@@ -5,10 +5,12 @@ finalize, before any forward, pn_net_step_info is dumped for k = -1 .. n - 1.  T
 
   every entry of test_gpu_layers.CONFIGS with its environment (the two reference-default topologies included),
   every case of test_gpu_layer_shapes.CASES, POPNET_MAX_BATCH honoured as network/_hipnet.py::_compile honours it,
-  the A2J nets at the sizes and precisions tests/test_gpu_a2j.py compiles.
+  the A2J nets tests/test_gpu_a2j.py compiles: the rows of tests/a2j_plan_cases.py, each at its max_batch.
 
 The recorded file was written on an MI355X (--device 0) by the last commit whose pn_net_finalize needed a device; a context without a device
-(--device -1, the default) must reproduce it: the step list is decided on the host (tests/test_net_steps.py).  A convolution's "cin_map" is
+(--device -1, the default) must reproduce it: the step list is decided on the host (tests/test_net_steps.py).  The A2J rows added with
+tests/a2j_plan_cases.py were written without a device, the older entries reproduced byte for byte beside them; tests/test_gpu_a2j.py compares the
+kernel labels of the deployed plans as a device compiles them with the device-less list.  A convolution's "cin_map" is
 stored as [length, sha256 of its decimal text], which keeps the file small.  The lists of nets are those of the GPU test modules themselves, imported
 here (they import without a GPU), so this recipe and tests/test_net_steps.py follow them and depend on their importing.
 
@@ -32,16 +34,17 @@ for _p in (ROOT, TESTS):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 import a2j_cases as AC  # noqa: E402
+import a2j_plan_cases as APC  # noqa: E402
 import plan_cases as PC  # noqa: E402
 import test_gpu_layers as GL  # noqa: E402
 import test_gpu_layer_shapes as GS  # noqa: E402
 from popnet_amd import _lib  # noqa: E402
 
 OUT = os.path.join(HERE, "net_steps.json.gz")
-# tests/test_gpu_a2j.py: the two fixture shapes, and the two wider pitch classes of test_dilated_steps_at_the_wider_pitch_classes (its parametrize list is
-# not importable: keep the two in step).  Not covered: the nets the engines of that file compile for themselves (A2JEngine at 288 x 288, max_batch 2 = the
-# LARGE plan; YoloA2JEngine at crop 96).
-A2J_SHAPES = [AC.SMALL, AC.LARGE, (64, 480, 1), (64, 992, 1)]
+# tests/test_gpu_a2j.py compiles the rows of tests/a2j_plan_cases.py and nothing else: (H, W, B run, max_batch compiled, precision) of each row -- the
+# fixture shapes, the wider pitch classes, the plans the engines deploy (288 x 288 at max_batch 32 / 16 / 2) and the census's additions.  Not covered:
+# YoloA2JEngine at crop 96, whose instance keys tests/test_a2j_plan_cases.py shows to be among the compared ones.
+A2J_SHAPES = [(H, W, B, mb, prec) for _, prec, H, W, B, mb, _ in APC.CASES]
 PREC = {"fp32": _lib.PN_PREC_F32, "bf16": _lib.PN_PREC_BF16, "bf16x3": _lib.PN_PREC_BF16X3}
 _CIN_MAP = re.compile(r'"cin_map": \[([^\]]*)\]')
 
@@ -53,9 +56,8 @@ def nets():
         env = dict(env)
         mb = max(B, int(env.pop("POPNET_MAX_BATCH", "0")))
         out.append((id_, kind, prec, mb, H, W, default, env))
-    for H, W, B in A2J_SHAPES:
-        for prec in ("bf16", "fp32"):
-            out.append(("a2j_%dx%d_b%d_%s" % (H, W, B, prec), "a2j", prec, B, H, W, False, {}))
+    for H, W, B, mb, prec in A2J_SHAPES:
+        out.append((APC.case_id(prec, H, W, B, mb), "a2j", prec, mb, H, W, False, {}))
     assert len({n[0] for n in out}) == len(out)
     return out
 
@@ -129,6 +131,22 @@ def step_texts(ctx, h):
         assert rc == 0, (k, rc, last_error(ctx))
         out.append(short_cin_map(buf.value.decode()))
     return out
+
+
+def a2j_steps(ctx, prec, max_batch, H, W):
+    """The steps of one A2J net as pn_net_step_info gives them (parsed, cin_map kept): what tests/a2j_plan_cases.py's instance keys are read from."""
+    L = _lib.lib()
+    h = compile_net(ctx, ("a2j", "a2j", prec, max_batch, H, W, False, {}))
+    try:
+        buf = C.create_string_buffer(1 << 16)
+        out = []
+        for k in range(L.pn_net_num_steps(h)):
+            rc = L.pn_net_step_info(h, k, buf, len(buf))
+            assert rc == 0, (k, rc, last_error(ctx))
+            out.append(json.loads(buf.value.decode()))
+        return out
+    finally:
+        L.pn_net_destroy(h)
 
 
 def net_steps(ctx, net):

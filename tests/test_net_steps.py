@@ -57,7 +57,7 @@ def _first_difference(got, want):
 
 
 def test_the_recorded_file_covers_every_net(recorded):
-    assert len(NETS) == 26 + 89 + 8 and set(recorded) == set(BY_ID)
+    assert len(NETS) == 26 + 89 + 26 and set(recorded) == set(BY_ID)          # A2J: the 26 rows of tests/a2j_plan_cases.py (8 before the deployed plans)
     assert set(MK.GPU_IDS) <= set(BY_ID)
 
 
