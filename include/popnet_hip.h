@@ -688,7 +688,7 @@ void pn_debug_cubic_coeffs(float x, float *out4);
  * [-1, -1, -1, -1, 0] for a frame without a detection), A2J regresses 15 joints per box crop.
  * A net of kind PN_NET_A2J (pn_net_create(ctx, PN_NET_A2J, 15, 16, 1)) takes the reference's A2J_model state dict ("Backbone.model.*",
  * "regressionModel.*", "classificationModel.*", "DepthRegressionModel.*"; Backbone.model.fc.* and *.num_batches_tracked are accepted and
- * ignored) and any input size that is a multiple of 16, in PN_PREC_F32 or PN_PREC_BF16 (PN_PREC_BF16X3: PN_ERR_UNSUPPORTED).  The three
+ * ignored) and any input size that is a multiple of 16, in any of the three precisions (PN_PREC_BF16X3: every map, the heads included, is a [hi | lo] plane pair).  The three
  * identical input channels of ResNetBackBone.forward (model.py:155-156) are one channel with the 7x7 weights summed over Cin in double.
  * layer4's blocks 1 and 2 run conv2 at dilation 2 (resnet.py:112,145): pn_net_step_info reports "dil": 2 for those steps only.
  * In PN_PREC_F32 the convolutions of this net accumulate in blocks (the 32 products of a k-step are summed from zero, then added to the running
@@ -724,7 +724,7 @@ int pn_a2j_crop(pn_ctx *ctx, const void *frames_dev, int depth_dtype, int F, int
                 const pn_a2j_cfg *cfg, float *out_dev, int32_t *flags_dev, void *hip_stream);
 /* A2J_model.forward (model.py:179-186) on crops_dev [B, 1, in_h, in_w] f32.  The head maps stay on the device as the last convolutions
  * left them: NHWC [B, h, w, 16 x 15] (classification, depth) and [B, h, w, 16 x 15 x 2] (regression), h = in_h / 16, bf16 or f32 by the
- * net's precision (pn_a2j_head_shape).  The pointers stay valid until the net is destroyed; the next forward overwrites the maps. */
+ * net's precision (pn_a2j_head_shape; PN_PREC_BF16X3: a pixel's row is the bf16 planes [hi | lo], the value hi + lo).  The pointers stay valid until the net is destroyed; the next forward overwrites the maps. */
 int pn_a2j_forward(pn_net *net, const float *crops_dev, int B, const void **cls_dev, const void **reg_dev, const void **dep_dev,
                    void *hip_stream);
 int pn_a2j_head_shape(pn_net *net, int *h, int *w, int *precision);
@@ -732,7 +732,8 @@ int pn_a2j_head_shape(pn_net *net, int *h, int *w, int *precision);
  * P_z = sum w dep -- max-subtracted softmax and sums in fp32, one block per (crop, joint), one launch.  anchors_dev [K][2] f32 (y, x) is
  * shift([h, w], stride, generate_anchors()) (anchor.py:7-42) computed by the caller in the reference's own arithmetic: anchor k belongs to
  * cell k / A, column (k / A) / h, row (k / A) % h (W-major, as the reference's permute(0, 3, 2, 1)).
- * h > 0: the heads are the NHWC maps of pn_a2j_forward (precision = the net's), read in place.  h == 0: the heads are f32 tensors in the
+ * h > 0: the heads are the NHWC maps of pn_a2j_forward (precision = the net's), read in place.  PN_PREC_BF16X3: a value is hi + lo added in
+ * fp32 (exact); one block per crop reads the plane pairs in 16-byte pieces (A x P a multiple of 8).  h == 0 (f32 only): the heads are f32 tensors in the
  * reference's layout [B, K, P] / [B, K, P, 2] (K = w: pass the anchor count as w).  A = anchors per cell, P = joints.
  * votes_dev [B, P, 3] f32 (y, x, z), may be NULL when records are wanted only.
  * rows_dev / cfg / records_dev (all or none): the map back to the frame (a2j_test_pred_box_new.py:373-421) in the same launch, in the

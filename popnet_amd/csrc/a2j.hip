@@ -2,7 +2,7 @@
 //
 // Replaces (third_party_methods/A2J_experiments/):
 //   dataPreprocess                 a2j_test_pred_box_new.py:268-313   -> a2j_crop_kernel
-//   post_process.forward           anchor.py:57-82                    -> a2j_vote_kernel
+//   post_process.forward           anchor.py:57-82                    -> a2j_vote_kernel (f32 / bf16 heads), a2j_vote_x3_kernel ([hi | lo] heads of a bf16x3 net)
 //   main(), result -> frame lists  a2j_test_pred_box_new.py:373-421   -> a2j_vote_kernel's epilogue
 // The network itself (A2J_model, model.py:145-186) is a pn_net of kind PN_NET_A2J (net.hip::build_a2j).
 #include <hip/hip_fp16.h>
@@ -103,6 +103,28 @@ __device__ __forceinline__ float ld(const void *p, size_t i, int bf16) {
     return __uint_as_float((unsigned)((const unsigned short *)p)[i] << 16);
 }
 
+// The end of a vote, one thread per (crop b, joint p): t = (sum e, sum e (anchor_y + reg_y), sum e (anchor_x + reg_x), sum e dep) -> the voted joint and,
+// with records, its map back to the frame
+__device__ __forceinline__ void vote_finish(const VoteArgs &a, int b, int p, const float *t) {
+    const int P = a.P;
+    const float vy = t[1] / t[0], vx = t[2] / t[0], vz = t[3] / t[0];
+    if (a.votes) {
+        float *o = a.votes + ((size_t)b * P + p) * 3;
+        o[0] = vy; o[1] = vx; o[2] = vz;
+    }
+    if (a.recs && p < PN_NUM_JOINTS) {      // a2j_test_pred_box_new.py:373-394, float32 as numpy computes it
+        const float *r = a.rows + (size_t)b * 6;
+        const float x = __fadd_rn(__fdiv_rn(__fmul_rn(vx, __fsub_rn(r[3], r[1])), a.crop_w), r[1]);
+        const float y = __fadd_rn(__fdiv_rn(__fmul_rn(vy, __fsub_rn(r[4], r[2])), a.crop_h), r[2]);
+        pn_a2j_record &R = a.recs[b];
+        R.joint[p][0] = x; R.joint[p][1] = y;
+        R.joint[p][2] = __fdiv_rn(__fmul_rn(__fsub_rn(x, a.cx), vz), a.fx);
+        R.joint[p][3] = __fdiv_rn(__fmul_rn(__fsub_rn(y, a.cy), vz), a.fy);
+        R.joint[p][4] = vz;
+        if (p == 0) { R.conf = r[5]; R.frame = (int32_t)r[0]; }
+    }
+}
+
 // blockDim 256, grid (P, B).  Anchor k of the reference's order lives in head row (k / A -> cell (column x = cell / h, row y = cell % h)), anchor k % A.
 __global__ __launch_bounds__(256) void a2j_vote_kernel(VoteArgs a) {
     const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -145,22 +167,112 @@ __global__ __launch_bounds__(256) void a2j_vote_kernel(VoteArgs a) {
     float t[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) t[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-    const float vy = t[1] / t[0], vx = t[2] / t[0], vz = t[3] / t[0];
-    if (a.votes) {
-        float *o = a.votes + ((size_t)b * P + p) * 3;
-        o[0] = vy; o[1] = vx; o[2] = vz;
+    vote_finish(a, b, p, t);
+}
+
+// ---- bf16x3 heads: the vote on [hi | lo] plane pairs ----------------------------------------------------------------------------------
+// A head row (one map cell of one crop) is [hi: A * P (x 2) values | lo: the same], bf16; a value is (float)hi + (float)lo, exact in fp32 (|lo| is at
+// most half a bf16 ulp of hi, so the sum has 16 significant bits).  One block per crop; a group of TPG = A * P / 8 threads walks the cells, thread t of a
+// group owning the same 8 (anchor, joint) slots 8 t .. 8 t + 7 of every cell it visits: per cell it loads 16 B of cls.hi, 16 B of cls.lo, the same of
+// dep and 2 x 32 B of reg -- the group's loads of a plane are one contiguous run, hi and lo runs back to back.  Pass 1: per-slot maxima in registers,
+// reduced per joint through LDS.  Pass 2: e = expf(c - max) and the four sums per slot in registers, reduced per joint in a fixed order (groups, then
+// the A anchors of the joint).  Softmax and sums are fp32 as in a2j_vote_kernel; only the summation order differs.
+constexpr int VX3_THREADS = 512;
+
+__device__ __forceinline__ void ld8_pair(const unsigned short *hi, int split, float *v) {
+    const uint4 h = *reinterpret_cast<const uint4 *>(hi), l = *reinterpret_cast<const uint4 *>(hi + split);
+    const unsigned hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = __uint_as_float(hw[i] << 16) + __uint_as_float(lw[i] << 16);
+        v[2 * i + 1] = __uint_as_float(hw[i] & 0xffff0000u) + __uint_as_float(lw[i] & 0xffff0000u);
     }
-    if (a.recs && p < PN_NUM_JOINTS) {      // a2j_test_pred_box_new.py:373-394, float32 as numpy computes it
-        const float *r = a.rows + (size_t)b * 6;
-        const float x = __fadd_rn(__fdiv_rn(__fmul_rn(vx, __fsub_rn(r[3], r[1])), a.crop_w), r[1]);
-        const float y = __fadd_rn(__fdiv_rn(__fmul_rn(vy, __fsub_rn(r[4], r[2])), a.crop_h), r[2]);
-        pn_a2j_record &R = a.recs[b];
-        R.joint[p][0] = x; R.joint[p][1] = y;
-        R.joint[p][2] = __fdiv_rn(__fmul_rn(__fsub_rn(x, a.cx), vz), a.fx);
-        R.joint[p][3] = __fdiv_rn(__fmul_rn(__fsub_rn(y, a.cy), vz), a.fy);
-        R.joint[p][4] = vz;
-        if (p == 0) { R.conf = r[5]; R.frame = (int32_t)r[0]; }
+}
+
+// blockDim VX3_THREADS, grid (B), dynamic LDS (NG * TPG * 8 + P) floats; (A * P) % 8 == 0 and TPG <= VX3_THREADS (pn_a2j_vote checks both)
+__global__ __launch_bounds__(VX3_THREADS) void a2j_vote_x3_kernel(VoteArgs a) {
+    extern __shared__ float vsm[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int A = a.A, P = a.P, AP = A * P, h = a.h, w = a.w, cells = h * w;
+    const int TPG = AP / 8, NG = VX3_THREADS / TPG;
+    const int g = tid / TPG, t = tid - g * TPG, e0 = 8 * t;
+    const bool on = g < NG;                                  // the threads behind the last whole group only take part in the barriers
+    float *red = vsm, *smax = vsm + NG * AP;                 // red[group][slot], smax[joint]
+    const unsigned short *cls = (const unsigned short *)a.cls + (size_t)b * cells * 2 * AP + e0;
+    const unsigned short *dep = (const unsigned short *)a.dep + (size_t)b * cells * 2 * AP + e0;
+    const unsigned short *reg = (const unsigned short *)a.reg + (size_t)b * cells * 4 * AP + 2 * e0;
+    // pass 1: max of the logits of every slot this thread owns
+    float m[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
+    if (on)
+        for (int cell = g; cell < cells; cell += NG) {
+            float c[8];
+            ld8_pair(cls + (size_t)cell * 2 * AP, AP, c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], c[j]);
+        }
+    if (on) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[g * AP + e0 + j] = m[j];
     }
+    __syncthreads();
+    if (tid < P) {
+        float mm = -INFINITY;
+        for (int gg = 0; gg < NG; ++gg)
+            for (int an = 0; an < A; ++an) mm = fmaxf(mm, red[gg * AP + an * P + tid]);
+        smax[tid] = mm;
+    }
+    __syncthreads();
+    // pass 2: sum e, sum e (anchor + reg), sum e dep per slot
+    float s[4][8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[i][j] = 0.f;
+    if (on) {
+        float mj[8];
+        int anj[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { anj[j] = (e0 + j) / P; mj[j] = smax[(e0 + j) - anj[j] * P]; }
+        for (int cell = g; cell < cells; cell += NG) {
+            const int y = cell / w, x = cell - y * w;
+            const float *an0 = a.anchors + (size_t)(x * h + y) * A * 2;      // the reference's order: cells column by column
+            float c[8], d[8], r[16];
+            ld8_pair(cls + (size_t)cell * 2 * AP, AP, c);
+            ld8_pair(dep + (size_t)cell * 2 * AP, AP, d);
+            ld8_pair(reg + (size_t)cell * 4 * AP, 2 * AP, r);
+            ld8_pair(reg + (size_t)cell * 4 * AP + 8, 2 * AP, r + 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float e = expf(c[j] - mj[j]);
+                s[0][j] += e;
+                s[1][j] += e * (an0[2 * anj[j]] + r[2 * j]);
+                s[2][j] += e * (an0[2 * anj[j] + 1] + r[2 * j + 1]);
+                s[3][j] += e * d[j];
+            }
+        }
+    }
+    float tsum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        __syncthreads();                                     // red is free again
+        if (on) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red[g * AP + e0 + j] = s[i][j];
+        }
+        __syncthreads();
+        if (tid < P) {
+            float acc = 0.f;
+            for (int an = 0; an < A; ++an) {
+                float ga = 0.f;
+                for (int gg = 0; gg < NG; ++gg) ga += red[gg * AP + an * P + tid];
+                acc += ga;
+            }
+            tsum[i] = acc;
+        }
+    }
+    if (tid < P) vote_finish(a, b, tid, tsum);
 }
 
 }  // namespace
@@ -201,7 +313,7 @@ int pn_a2j_vote(pn_ctx *ctx, const void *cls_dev, const void *reg_dev, const voi
     if (!ctx) return PN_ERR_INVALID;
     if (!cls_dev || !reg_dev || !dep_dev || !anchors_dev || B < 0 || h < 0 || w < 1 || A < 1 || P < 1 || (!votes_dev && !records_dev))
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_vote: bad arguments");
-    if (precision != PN_PREC_F32 && precision != PN_PREC_BF16) return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_vote: heads are f32 or bf16");
+    if (precision != PN_PREC_F32 && precision != PN_PREC_BF16 && precision != PN_PREC_BF16X3) return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_vote: heads are f32, bf16 or bf16x3");
     if (h == 0 && precision != PN_PREC_F32) return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_vote: the [B, K, P] entry takes f32 tensors");
     if (records_dev && (!rows_dev || !cfg || P != PN_NUM_JOINTS)) return pn_set_error(ctx, PN_ERR_INVALID, "pn_a2j_vote: records need the box rows, a configuration and %d joints", PN_NUM_JOINTS);
     const long K = h ? (long)h * w * A : (long)w;
@@ -212,7 +324,15 @@ int pn_a2j_vote(pn_ctx *ctx, const void *cls_dev, const void *reg_dev, const voi
     a.bf16 = precision == PN_PREC_BF16; a.B = B; a.h = h; a.w = w; a.A = A; a.P = P; a.K = (int)K;
     a.crop_w = cfg ? (float)cfg->crop_w : 1.f; a.crop_h = cfg ? (float)cfg->crop_h : 1.f;
     a.fx = cfg ? (float)cfg->fx : 1.f; a.fy = cfg ? (float)cfg->fy : 1.f; a.cx = cfg ? (float)cfg->cx : 0.f; a.cy = cfg ? (float)cfg->cy : 0.f;
-    hipLaunchKernelGGL(a2j_vote_kernel, dim3(P, B), dim3(256), 0, (hipStream_t)hip_stream, a);
+    if (precision == PN_PREC_BF16X3) {
+        // 16-byte pieces of a plane, a group of A * P / 8 threads per cell, one thread per joint at the end
+        if ((A * P) % 8 || A * P / 8 > VX3_THREADS || P > VX3_THREADS)
+            return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "pn_a2j_vote: bf16x3 head rows of %d x %d values (A x P must be a multiple of 8, at most %d; P at most %d)", A, P, 8 * VX3_THREADS, VX3_THREADS);
+        const int groups = VX3_THREADS / (A * P / 8);
+        hipLaunchKernelGGL(a2j_vote_x3_kernel, dim3(B), dim3(VX3_THREADS), ((size_t)groups * A * P + P) * sizeof(float), (hipStream_t)hip_stream, a);
+    } else {
+        hipLaunchKernelGGL(a2j_vote_kernel, dim3(P, B), dim3(256), 0, (hipStream_t)hip_stream, a);
+    }
     PN_HIP_CHECK(ctx, hipGetLastError());
     return PN_OK;
 }

@@ -381,17 +381,18 @@ int build_yolo(pn_net *n) {
 // strided downsample; layer4 at stride 1 with conv2 of its blocks 1 and 2 at dilation 2 / padding 2, block 0 not dilated: resnet.py:112,142-145), output
 // stride 16, and three heads of 4 x (3x3 conv + bias + BN + ReLU) + a 3x3 output conv with bias: classification on layer3's map, regression and depth on
 // layer4's.  The head maps stay NHWC [B, h, w, 16 anchors x 15 joints (x 2)] in the buffers "cls" / "reg" / "dep": pn_a2j_vote reads them there.
-// Backbone.model.fc.* is never executed (model.py:158-167) and is skipped at load.
+// Backbone.model.fc.* is never executed (model.py:158-167) and is skipped at load.  bf16x3: every buffer a [hi | lo] plane pair like the other nets'; the
+// head maps' planes (240 / 480 channels) are no multiple of 64, which is legal because nothing convolves them (pn_a2j_vote reads them as hi + lo).
 int build_a2j(pn_net *n) {
     const int H = n->in_h, W = n->in_w;
     if (H % 16 || W % 16 || H < 16 || W < 16) return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "input size must be a multiple of 16");
-    if (n->x3) return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "the A2J net is built for fp32 and bf16 (bf16x3: its 64 -> 256 and 240 / 480-channel tensors are not laid out as plane pairs)");
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H16 = H / 16, W16 = W / 16;
     n->out_h = H16; n->out_w = W16;
     const int A1 = new_buf(n, H2, W2, 64), X0 = new_buf(n, H4, W4, 64);
     if (int rc = add_stem(n, A1, "Backbone.model.conv1", "Backbone.model.bn1", 3)) return rc;
     Levels levels;
-    if (n->prec == PN_PREC_BF16 && !n->sw.no_stempool) n->steps.back().stem_pool_buf = X0;     // conv1 - bn1 - relu - maxpool as one launch, as build_yolo
+    // conv1 - bn1 - relu - maxpool as one launch, as build_yolo; bf16x3 keeps the two launches (the fused kernel stores one plane)
+    if (n->prec == PN_PREC_BF16 && !n->x3 && !n->sw.no_stempool) n->steps.back().stem_pool_buf = X0;
     else levels.pool(1, A1, X0, 64, 0);
     int cur = X0, ch = H4, cw = W4;
     const int nblocks[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512}, strides[4] = {1, 2, 2, 1}, dils[4] = {1, 1, 1, 2};
@@ -452,7 +453,8 @@ int compile_net(pn_net *n) {
     for (auto &b : n->bufs) {
         b.bytes = (size_t)n->max_batch * b.H * b.W * b.C * n->esize();
         if (const size_t bytes = b.bytes + 2048; bytes >= ((size_t)1 << 32))     // + zero page; the kernels address a buffer with 32-bit byte offsets (zero page, epilogue stores)
-            return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "activation buffer %dx%dx%d x batch %d = %zu B exceeds the 4 GiB the kernels' 32-bit offsets address; lower max_batch", b.H, b.W, b.C, n->max_batch, bytes);
+            return pn_set_error(n->ctx, PN_ERR_UNSUPPORTED, "activation buffer %dx%dx%d%s x batch %d = %zu B exceeds the 4 GiB the kernels' 32-bit offsets address; lower max_batch", b.H, b.W, b.C,
+                                n->x3 ? " (bf16x3: hi and lo planes)" : "", n->max_batch, bytes);
     }
     for (size_t i = 0; i < n->bufs.size(); ++i) {     // every buffer by number (pn_net_step_info's buffer indices), for per-layer checks
         const std::string nm = "buf" + std::to_string(i);

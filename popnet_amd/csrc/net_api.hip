@@ -149,7 +149,7 @@ int pn_a2j_head_shape(pn_net *n, int *h, int *w, int *precision) {
     if (n->kind != PN_NET_A2J || !n->finalized) return pn_set_error(n->ctx, PN_ERR_STATE, "not a finalized A2J net");
     if (h) *h = n->out_h;
     if (w) *w = n->out_w;
-    if (precision) *precision = n->prec;
+    if (precision) *precision = n->x3 ? PN_PREC_BF16X3 : n->prec;      // bf16x3: the head rows are [hi | lo] pairs
     return PN_OK;
 }
 
@@ -166,7 +166,7 @@ int pn_a2j_predict(pn_net *n, const void *frames_dev, int depth_dtype, int F, in
     if (int rc = pn_a2j_crop(ctx, frames_dev, depth_dtype, F, H, W, rows_dev, nrows, cfg, crops_dev, flags_dev, hip_stream)) return rc;
     const void *cls = nullptr, *reg = nullptr, *dep = nullptr;
     if (int rc = pn_a2j_forward(n, crops_dev, nrows, &cls, &reg, &dep, hip_stream)) return rc;
-    return pn_a2j_vote(ctx, cls, reg, dep, n->prec, nrows, n->out_h, n->out_w, 16, n->num_parts, anchors_dev, votes_dev, rows_dev, cfg, records_dev, hip_stream);
+    return pn_a2j_vote(ctx, cls, reg, dep, n->x3 ? PN_PREC_BF16X3 : n->prec, nrows, n->out_h, n->out_w, 16, n->num_parts, anchors_dev, votes_dev, rows_dev, cfg, records_dev, hip_stream);
 }
 
 int pn_rtpose_forward_frames(pn_net *n, const void *depth_dev, int depth_dtype, int B, int H, int W, float depth_max, float depth_mean, float depth_std,

@@ -419,8 +419,6 @@ class A2JEngine:
         from .network.a2j import A2J_model, A2JCfg, A2J_RECORD_DTYPE, generate_anchors, shift
         if not torch.cuda.is_available():
             raise _lib.PopnetError("A2JEngine needs a GPU: the HIP path has no CPU fallback")
-        if str(precision).lower() == "bf16x3":
-            raise _lib.PopnetError("A2JEngine: precision is 'fp32' or 'bf16'")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_batch = int(max_batch)
         self.crop_h, self.crop_w = (int(crop), int(crop)) if np.isscalar(crop) else (int(crop[0]), int(crop[1]))

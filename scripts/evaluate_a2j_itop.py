@@ -34,7 +34,7 @@ def main(argv=None):
     ap.add_argument("--result-file", default="result_itop64.txt")
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--crop", type=int, default=288)
-    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"))
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16", "bf16x3"))
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--test-augment", type=int, choices=(0, 1), default=0)
     ap.add_argument("--reference-error", type=int, choices=(0, 1), default=0)

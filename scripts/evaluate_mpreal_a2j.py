@@ -7,7 +7,7 @@ time: --net (only ``yolo`` makes the boxes), --pipeline and --gpus 1 are accepte
 here; --gpus above 1 and --ablation (Open-Pose+ only) are refused with the reason.
 
     python scripts/evaluate_mpreal_a2j.py --annotations labels.json --image-dir depth_maps --weight best_pose.pth \
-        --a2j-weight net_47.pth --output-dir out [--precision fp32|bf16] [--batch-size 32] [--drop-last]
+        --a2j-weight net_47.pth --output-dir out [--precision fp32|bf16|bf16x3] [--batch-size 32] [--drop-last]
 """
 import argparse
 import json
@@ -36,7 +36,7 @@ def main(argv=None):
     ap.add_argument("--weight", required=True, help="YoloPoseNet checkpoint (state_dict, 'module.'-prefixed or not)")
     ap.add_argument("--a2j-weight", required=True, help="A2J_model checkpoint (the reference's 410 keys)")
     ap.add_argument("--output-dir", required=True)
-    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"])
     ap.add_argument("--crop", type=int, default=288)
     ap.add_argument("--drop-last", action="store_true")
     ap.add_argument("--no-metrics", action="store_true")
