@@ -589,6 +589,37 @@ int pn_a2j_loss(pn_ctx *ctx, const float *cls_dev, const float *reg_dev, const f
 int pn_adam(pn_ctx *ctx, float *param_dev, const float *grad_dev, float *exp_avg_dev, float *exp_avg_sq_dev, size_t n, double lr,
             double beta1, double beta2, double eps, double weight_decay, int t, double grad_scale, void *hip_stream);
 
+/* ---- 1x1 training convolutions in split bf16 (csrc/conv1x1_x3.hip, conv1x1_x3_kernels.h) -----------------------------------------
+ * The 1x1, stride-1, pad-0 convolutions of a ResNet bottleneck (conv1, conv3, the stride-1 downsample) on the bf16 matrix cores, for
+ * A2JTrainEngine(precision="bf16x3").  Entries of their own: pn_conv2d_forward / _dgrad / _wgrad keep running every 1x1 call on the fp32
+ * kernels whatever pn_train_set_precision says, and these do not read that switch.  Tensors are fp32 NCHW with HW = H W pixels per map:
+ *   pn_conv1x1_x3_forward   y[n, co, p] (+)= bias[co] + sum_ci x[n, ci, p] w[co, ci]            (bias_dev may be NULL)
+ *   pn_conv1x1_x3_dgrad     dx[n, ci, p] (+)= sum_co dy[n, co, p] w[co, ci]                     (the forward kernel on the transposed pack)
+ *   pn_conv1x1_x3_wgrad     dw[co, ci] = sum_{n, p} dy[n, co, p] x[n, ci, p]; dbias[co] = sum dy (dbias_dev may be NULL; pn_conv2d_wgrad's
+ *                           double-precision channel reduction)
+ * Arithmetic: BOTH operands are split, hi = RNE_bf16(v), lo = RNE_bf16(fp32(v - hi)), and every block of 32 k is three
+ * v_mfma_f32_16x16x32_bf16 into one fp32 accumulator: a_hi b_hi + a_hi b_lo + a_lo b_hi, no lo * lo term.  The bias is added once to the
+ * accumulator; with accumulate != 0 the previous output is added after it.  k runs in order (chunks of 32 channels; for the weight gradient
+ * chunks of 32 pixels that never straddle two images, in slices whose partial sums a second launch adds in slice order): the summation
+ * order depends on the shape alone, a repeated call gives the same bits, no float atomics.  Any N, Cin, HW, Cout >= 1 (k tails, ragged
+ * channel blocks and pixel tiles are masked in the kernels; the weight gradient uses 16-byte loads only when HW % 4 == 0 and both
+ * tensors are 16-byte aligned, element loads otherwise and at the ragged end of an image); N, Cin, HW, Cout < 1 or a NULL tensor is
+ * PN_ERR_INVALID before any launch.  The [hi | lo] weight pack and its transpose live in the pack cache (pn_train_pack_cache;
+ * pn_train_pack_refresh rebuilds them, pn_adam / pn_sgd_nesterov mark them stale); with the cache off they are packed on every call.
+ *   pn_conv1x1_x3_plan_info  the launch code's own plan of one call as JSON, launching nothing; works on pn_create(-1).  which =
+ *                           PN_PLAN_FORWARD / PN_PLAN_DGRAD / PN_PLAN_WGRAD.  Fields: kernel (label; "split": true -- no shape is kept on
+ *                           the fp32 kernels), BM / BN / BK (block tile: A rows, B rows, k), grid, lds; forward / dgrad: M, K (output and
+ *                           reduced channels), P = N HW, chunks; wgrad: slices, per_slice (pixels, a multiple of 32: chunk padding counted),
+ *                           per_slice_chunks, chunks, chunks_per_image, aligned (the label says <vec> / <scalar>; for 16-byte aligned
+ *                           tensors), csl (the bias gradient's slices). */
+int pn_conv1x1_x3_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int N, int Cin, int HW,
+                          int Cout, int accumulate, void *hip_stream);
+int pn_conv1x1_x3_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int HW, int Cout,
+                        int accumulate, void *hip_stream);
+int pn_conv1x1_x3_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float *dw_dev, float *dbias_dev, int N, int Cin, int HW,
+                        int Cout, void *hip_stream);
+int pn_conv1x1_x3_plan_info(pn_ctx *ctx, int which, int N, int Cin, int HW, int Cout, char *out, size_t cap);
+
 /* ---- training step on NHWC [hi | lo] bf16 planes (round 6; csrc/trainx.hip) -------------------------------------------------
  * One object runs forward + loss + backward of rtpose_light3d(15, 14, 2, input_dim = 1) in train mode for ONE batch shape:
  * the per-batch body of tpm/train_rtpose_light3d_kdh3d_mpaug.py:160-180 (CR) up to (not including) optimizer.step(), i.e.

@@ -179,6 +179,10 @@ _SIGNATURES = {
     "pn_conv2d_wgrad_dil": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "pn_a2j_loss": (_i, [_vp, _vp, _vp, _vp] + [_i] * 5 + [_vp, _vp, _f] + [_vp] * 6),
     "pn_adam": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _d, _d, _d, _d, _d, _i, _d, _vp]),
+    "pn_conv1x1_x3_forward": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "pn_conv1x1_x3_dgrad": (_i, [_vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "pn_conv1x1_x3_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 4 + [_vp]),
+    "pn_conv1x1_x3_plan_info": (_i, [_vp] + [_i] * 5 + [C.c_char_p, _sz]),
     "pn_yolo_target_cfg_default": (None, [C.POINTER(YoloTargetCfg)]),
     "pn_build_prior_targets": (_i, [_vp] * 6 + [_i, _i, C.POINTER(YoloTargetCfg)] + [_vp] * 5),
     "pn_trainer_create": (_vp, [_vp]),

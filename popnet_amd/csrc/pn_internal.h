@@ -27,7 +27,7 @@ struct pn_ctx {
     // pn_train_pack_cache: the packed (transposed / rotated / split) weights of the 3x3 training convolutions live in persistent buffers keyed by
     // (weight pointer, shape, flip, precision) and are all refreshed by ONE launch per step (pn_train_pack_refresh) instead of one launch per
     // convolution call (train.hip)
-    struct PackEntry { const float *w; int Cout, Cin, flip, x3; void *buf; size_t bytes; bool fresh; };
+    struct PackEntry { const float *w; int Cout, Cin, flip, x3; void *buf; size_t bytes; bool fresh; };      // x3: 0 = fp32 3x3, 1 = split 3x3, 2 = split 1x1 (conv1x1_x3.hip: rows Cout over k Cin, flip = transposed)
     bool train_pack_cache = false;
     std::vector<PackEntry> train_packs;
     void *train_pack_table = nullptr;      // device copy of the descriptor table
@@ -96,6 +96,9 @@ __host__ __device__ inline int pn_limb_dst(int l) {
     return t[l];
 }
 int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)
+// train.hip, for conv1x1_x3.hip: the pack cache's lookup (t_pack_get; x3 = 2 keys the 1x1 split packs) and pn_conv2d_wgrad's bias gradient
+int pn_train_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, int x3, size_t bytes, hipStream_t s, void **buf, bool *fresh);
+void pn_train_dbias(hipStream_t s, const float *dy_dev, float *dbias_dev, int N, int Cout, int HW, int csl, double *part);
 const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned *grid_x, unsigned *grid_y);     // train_yolo.hip: kernel label and grid of pn_conv2d_dgrad_strided
 
 #define PN_HIP_CHECK(ctx, expr)                                                              \

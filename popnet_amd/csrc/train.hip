@@ -734,7 +734,8 @@ int pn_train_pack_refresh(pn_ctx *ctx, void *hip_stream) {
         unsigned blocks = 0;
         for (size_t i = 0; i < n; ++i) {
             const auto &e = ctx->train_packs[i];
-            const size_t items = e.x3 ? (size_t)((e.Cin + 31) / 32) * 9 * e.Cout * 32 : (size_t)9 * e.Cin * e.Cout;
+            const size_t items = e.x3 == 2 ? (size_t)((e.Cin + 31) / 32) * e.Cout * 32          // conv1x1_x3.hip's packs
+                                 : e.x3 ? (size_t)((e.Cin + 31) / 32) * 9 * e.Cout * 32 : (size_t)9 * e.Cin * e.Cout;
             host[i] = TPackDesc{e.w, e.buf, e.Cout, e.Cin, e.flip, e.x3, blocks, 0u};
             blocks += (unsigned)((items + 255) / 256);
         }
@@ -934,6 +935,17 @@ int pn_conv2d_wgrad_dil(pn_ctx *ctx, const float *x_dev, const float *dy_dev, fl
 }
 
 }   // extern "C"
+// ---- what conv1x1_x3.hip shares with the entries above (internal, not part of the C ABI) -----------------------------------------------
+int pn_train_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, int x3, size_t bytes, hipStream_t s, void **buf, bool *fresh) {
+    return t_pack_get(ctx, w, Cout, Cin, flip, x3, bytes, s, buf, fresh);
+}
+
+// dbias[co] = sum dy over (n, pixel): pn_conv2d_wgrad's bias gradient -- chan_reduce_kernel<2> in double over csl slices into part, then sums_finish_kernel
+void pn_train_dbias(hipStream_t s, const float *dy_dev, float *dbias_dev, int N, int Cout, int HW, int csl, double *part) {
+    t_chan_reduce<2>(s, nullptr, dy_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, N, Cout, HW, csl, part);
+    hipLaunchKernelGGL(sums_finish_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(64), 0, s, (const double *)part, Cout, csl, dbias_dev, nullptr, nullptr);
+}
+
 // ---- the planes training engine's stem (trainx.hip; internal, not part of the C ABI) --------------------------------------------------
 // model0.conv1 (rtpose_light3d.py:144: 7x7 / 2, Cin = 1) with its output / its output gradient as a planes tensor (TConv::pl): the kernels,
 // grids, slices and summation order of pn_conv2d_forward / pn_conv2d_wgrad's generic path, without the NCHW f32 hand-over tensor.

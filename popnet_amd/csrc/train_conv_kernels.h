@@ -420,16 +420,30 @@ __global__ void wpack3_x3_kernel(const float *__restrict__ w, __bf16 *__restrict
     wpx[plane + i] = (__bf16)(v - (float)h);
 }
 
-// Every cached pack of a context refreshed by ONE launch (pn_train_pack_refresh): the block finds its descriptor (<= ~70 entries, scanned by
+// Every cached pack of a context refreshed by ONE launch (pn_train_pack_refresh): the block finds its descriptor (<= ~130 entries, bisected by
 // every thread: uniform) and runs wpack3_kernel's / wpack3_x3_kernel's element arithmetic on it -- the same values as the per-call packs.
 struct TPackDesc { const float *w; void *dst; int Cout, Cin, flip, x3; unsigned first_block, pad; };
 __global__ void wpack_all_kernel(const TPackDesc *__restrict__ tab, int n) {
-    int e = 0;
-    while (e + 1 < n && blockIdx.x >= tab[e + 1].first_block) ++e;
+    int e = 0, hi = n - 1;          // the last entry whose first block is <= this one (first_block ascends strictly); A2J's bf16x3 step has ~130 entries: bisect
+    while (e < hi) {
+        const int mid = (e + hi + 1) >> 1;
+        if (blockIdx.x >= tab[mid].first_block) e = mid;
+        else hi = mid - 1;
+    }
     const TPackDesc d = tab[e];
     const size_t i = (size_t)(blockIdx.x - d.first_block) * blockDim.x + threadIdx.x;
     const int Cout = d.Cout, Cin = d.Cin;
-    if (d.x3) {
+    if (d.x3 == 2) {                 // the 1x1 split pack (conv1x1_wpack_x3_kernel: rows M = d.Cout over K = d.Cin, flip = transposed source)
+        const size_t plane = (size_t)((Cin + 31) / 32) * Cout * 32;
+        if (i >= plane) return;
+        const int k = (int)((i >> 5) / Cout) * 32 + (int)(i & 31), m = (int)((i >> 5) % Cout);
+        float v = 0.f;
+        if (k < Cin) v = d.flip ? d.w[(size_t)k * Cout + m] : d.w[(size_t)m * Cin + k];
+        const __bf16 h = (__bf16)v;
+        __bf16 *wp = (__bf16 *)d.dst;
+        wp[i] = h;
+        wp[plane + i] = (__bf16)(v - (float)h);
+    } else if (d.x3) {
         const int chunks = (Cin + 31) / 32;
         const size_t plane = (size_t)chunks * 9 * Cout * 32;
         if (i >= plane) return;

@@ -5,7 +5,7 @@ Host-side mirror of the per-batch body of the reference trainer
   third_party_methods/A2J_experiments/model.py:145-186, resnet.py      the module in train mode (ResNet-50, layer4.1 / layer4.2 conv2 dilated)
   third_party_methods/A2J_experiments/anchor.py:84-154                 the loss
   torch.optim.Adam(lr 0.00035, weight_decay 1e-4)                      the trainer's optimiser
-on the fp32 NCHW primitives of csrc/train.hip (convolutions -- the dilated ones included --, BatchNorm), csrc/train_yolo.hip (strided data
+on the NCHW primitives of csrc/train.hip (fp32; in precision="bf16x3" the split-bf16 3x3 kernels and csrc/conv1x1_x3.hip) (convolutions -- the dilated ones included --, BatchNorm), csrc/train_yolo.hip (strided data
 gradient, max pooling) and csrc/train_a2j.hip (pn_a2j_loss on the raw NCHW head maps, pn_adam).  popnet_amd.train.TrainEngine supplies the flat
 parameter / gradient buffers, the per-layer plumbing, the data-parallel exchange and the checkpoint format; this class adds A2J's call order.
 
@@ -47,18 +47,29 @@ def crop_labels(bbox, joints_2d, joints_3d, frame_shape=(512, 480), crop_w=288, 
 
 
 class A2JTrainEngine(TrainEngine):
-    """state_dict: reference-format (optionally `module.`-prefixed) A2J_model(num_classes) checkpoint."""
+    """state_dict: reference-format (optionally `module.`-prefixed) A2J_model(num_classes) checkpoint.
+
+    precision (reported by engine.precision): "fp32", the default -- every product an exact fp32 FMA chain -- or "bf16x3": the split-bf16
+    matrix-core kernels (both operands hi + lo bf16, three MFMAs per product block, fp32 accumulators) wherever they exist:
+      * every 3x3 stride-1 undilated convolution with Cin >= 32 (most bottleneck conv2, the 15 head convolutions), through the base
+        engine's "bf16x3-nchw" mode (tconv3_tile_x3* / tconv3_wgrad_x3*);
+      * the 34 stride-1 1x1 convolutions (conv1 / conv3 of the 16 bottlenecks, the downsample of layer1.0 and layer4.0), forward, data
+        and weight gradient, through pn_conv1x1_x3_forward / _dgrad / _wgrad.
+    Still fp32 in "bf16x3": the two stride-2 downsample convolutions, the two stride-2 3x3, the two dilated 3x3 (layer4.1 / layer4.2
+    conv2), the 7x7 stem, BatchNorm, pooling, the loss and Adam.  Parameters, gradients, optimiser state and checkpoints are fp32 in
+    both modes."""
 
     _carry_prefix = "Backbone.model.fc."
     num_anchors = 16
 
     def __init__(self, state_dict, device="cuda:0", lr=0.00035, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, spatial_factor=0.5, reg_loss_factor=3,
                  num_classes=15, process_group=None, world_size=1, precision="fp32"):
-        if precision != "fp32":
-            raise ValueError("A2JTrainEngine computes in fp32 only, got precision %r" % (precision,))
+        if precision not in ("fp32", "bf16x3"):
+            raise ValueError("A2JTrainEngine: precision must be 'fp32' or 'bf16x3', got %r" % (precision,))
         super().__init__(state_dict, device=device, lr=lr, momentum=0.0, weight_decay=weight_decay, process_group=process_group, world_size=world_size,
-                         precision="fp32-nchw")
-        self.precision = "fp32"
+                         precision=precision + "-nchw")
+        self.precision = precision
+        self._x3 = precision == "bf16x3"
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.spatial_factor, self.reg_loss_factor, self.num_classes = float(spatial_factor), float(reg_loss_factor), int(num_classes)
         A, P = self.num_anchors, self.num_classes
@@ -87,6 +98,15 @@ class A2JTrainEngine(TrainEngine):
 
     # ---- convolutions with a dilation ----
     def _conv(self, name, x, ks, stride=1, pad=0, dil=1):
+        if self._x3 and ks == 1 and stride == 1 and pad == 0:
+            w = self.p[name + ".weight"]
+            N, Cin, H, W = x.shape
+            Cout = w.shape[0]
+            y = self._buf("c:" + name, (N, Cout, H, W))
+            self._check(self.L.pn_conv1x1_x3_forward(self.ctx.handle, self._ptr(x), self._ptr(w), self._ptr(self.p.get(name + ".bias")), self._ptr(y), N, Cin, H * W,
+                                                     Cout, 0, self._s()), "pn_conv1x1_x3_forward")
+            self.A["x:" + name] = x
+            return y
         if dil == 1:
             return super()._conv(name, x, ks, stride, pad)
         w = self.p[name + ".weight"]
@@ -99,6 +119,20 @@ class A2JTrainEngine(TrainEngine):
         return y
 
     def _conv_bwd(self, name, dy, ks, stride=1, pad=0, dx=None, accumulate=False, need_dx=True, dil=1):
+        if self._x3 and ks == 1 and stride == 1 and pad == 0:
+            x = self.A["x:" + name]
+            w = self.p[name + ".weight"]
+            N, Cin, H, W = x.shape
+            Cout = w.shape[0]
+            self._check(self.L.pn_conv1x1_x3_wgrad(self.ctx.handle, self._ptr(x), self._ptr(dy), self._ptr(self.g[name + ".weight"]), self._ptr(self.g.get(name + ".bias")),
+                                                   N, Cin, H * W, Cout, self._s()), "pn_conv1x1_x3_wgrad")
+            if not need_dx:
+                return None
+            if dx is None:
+                dx = self._buf("dx:" + name, x.shape)
+            self._check(self.L.pn_conv1x1_x3_dgrad(self.ctx.handle, self._ptr(dy), self._ptr(w), self._ptr(dx), N, Cin, H * W, Cout, 1 if accumulate else 0, self._s()),
+                        "pn_conv1x1_x3_dgrad")
+            return dx
         if dil == 1:
             return super()._conv_bwd(name, dy, ks, stride, pad, dx=dx, accumulate=accumulate, need_dx=need_dx)
         x = self.A["x:" + name]
@@ -246,6 +280,21 @@ class A2JTrainEngine(TrainEngine):
         terms = self.forward_backward(img, label)
         self.apply()
         return terms
+
+    def conv1x1_shapes(self, H, W):
+        """[(name, Cin, HW, Cout)] of the stride-1 1x1 convolutions of one step on H x W crops: the calls precision="bf16x3" sends to
+        pn_conv1x1_x3_forward / _dgrad / _wgrad (conv1, conv3 and a stride-1 downsample of every bottleneck)."""
+        out = []
+        h, w = -(-H // 4), -(-W // 4)
+        for layer, stride, _ in LAYERS:
+            for i, p in enumerate(self._block_names(layer)):
+                st = stride if i == 0 else 1
+                ho, wo = -(-h // st), -(-w // st)
+                for n, hw in ((".conv1", h * w), (".conv3", ho * wo)) + (((".downsample.0", h * w),) if st == 1 and (p + ".downsample.0.weight") in self.p else ()):
+                    wt = self.p[p + n + ".weight"]
+                    out.append((p + n, wt.shape[1], hw, wt.shape[0]))
+                h, w = ho, wo
+        return out
 
     def flops_per_step(self, N, H, W):
         """Algorithmic FLOPs of one step (2 per multiply-add): every convolution's forward and weight gradient, and the data gradient of every

@@ -56,6 +56,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=35)
     ap.add_argument("--crop", type=int, default=288)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32",
+                    help="the training step's arithmetic (A2JTrainEngine): exact fp32, or split bf16 on the matrix cores for the stride-1 1x1 and 3x3 convolutions")
     ap.add_argument("--weight", default=None, help="start from this local checkpoint instead of the module's initial state")
     ap.add_argument("--lr", "--learning-rate", type=float, default=0.00035)
     ap.add_argument("--weight-decay", "--wd", type=float, default=1e-4)
@@ -99,7 +101,7 @@ def main(argv=None):
     if args.weight:
         module.load_state_dict(torch.load(args.weight, map_location="cpu"))
     eng = A2JTrainEngine.from_module(module, device=dev, lr=args.lr, weight_decay=args.weight_decay, spatial_factor=SPATIAL_FACTOR,
-                                     reg_loss_factor=REG_LOSS_FACTOR, world_size=world)
+                                     reg_loss_factor=REG_LOSS_FACTOR, world_size=world, precision=args.precision)
     per_rank = args.batch_size // world
     infer = A2JEngine(precision="fp32", state_dict=module.state_dict(), device=dev, max_batch=per_rank, crop=args.crop)
     infer.cfg.mean, infer.cfg.std = float(np.load(args.mean_file).reshape(-1)[-1]), float(np.load(args.std_file).reshape(-1)[-1])      # mean[-1], std[-1]

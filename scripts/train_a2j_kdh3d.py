@@ -66,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=None, help="default 35, 100 with --bg-aug 1")
     ap.add_argument("--crop", type=int, default=288)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32",
+                    help="the training step's arithmetic (A2JTrainEngine): exact fp32, or split bf16 on the matrix cores for the stride-1 1x1 and 3x3 convolutions")
     ap.add_argument("--weight", default=None, help="start from this local checkpoint instead of the module's initial state")
     ap.add_argument("--lr", "--learning-rate", type=float, default=0.00035)
     ap.add_argument("--weight-decay", "--wd", type=float, default=1e-4)
@@ -113,7 +115,7 @@ def main(argv=None):
     if args.weight:
         module.load_state_dict(torch.load(args.weight, map_location="cpu"))
     eng = A2JTrainEngine.from_module(module, device=dev, lr=args.lr, weight_decay=args.weight_decay, spatial_factor=SPATIAL_FACTOR,
-                                     reg_loss_factor=REG_LOSS_FACTOR, world_size=world)
+                                     reg_loss_factor=REG_LOSS_FACTOR, world_size=world, precision=args.precision)
     per_rank = args.batch_size // world
     infer = A2JEngine(precision="fp32", state_dict=module.state_dict(), device=dev, max_batch=per_rank, crop=args.crop)      # mean 3, std 2, img 480 x 512
     intrinsics = dict(fx=infer.cfg.fx, fy=infer.cfg.fy, cx=infer.cfg.cx, cy=infer.cfg.cy)

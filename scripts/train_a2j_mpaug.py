@@ -54,6 +54,8 @@ def main(argv=None):
     ap.add_argument("--num-classes", type=int, default=15)
     ap.add_argument("--print-freq", type=int, default=10)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--precision", choices=("fp32", "bf16x3"), default="fp32",
+                    help="the training step's arithmetic (A2JTrainEngine): exact fp32, or split bf16 on the matrix cores for the stride-1 1x1 and 3x3 convolutions")
     ap.add_argument("--weight", default=None, help="start from this local checkpoint instead of the module's initial state")
     ap.add_argument("--augment", type=int, choices=(0, 1), default=1, help="1: random Rotate / RenderDepth on the training batches (the reference's preprocess)")
     ap.add_argument("--max-aug-ratio", type=float, default=1.7, help="RenderDepth's max_ratio")
@@ -80,7 +82,7 @@ def main(argv=None):
     if args.weight:
         module.load_state_dict(torch.load(args.weight, map_location="cpu"))
     eng = A2JTrainEngine.from_module(module, device=dev, lr=args.lr, weight_decay=args.weight_decay, spatial_factor=args.spatial_factor,
-                                     reg_loss_factor=args.reg_loss_factor)
+                                     reg_loss_factor=args.reg_loss_factor, precision=args.precision)
     module = module.to(dev).eval()
     module.precision = "fp32"
     cropper = A2JEngine(precision="fp32", state_dict=module.state_dict(), device=dev, max_batch=1, crop=args.crop, img_wh=(S, S))      # its crops() only: pn_a2j_crop
