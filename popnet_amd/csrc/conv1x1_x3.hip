@@ -2,7 +2,7 @@
 // pn_conv1x1_x3_plan_info (contract: include/popnet_hip.h; kernels and arithmetic: conv1x1_x3_kernels.h).  Entries of their OWN: the
 // pn_conv2d_* entries keep sending every 1x1 call to the fp32 kernels whatever the precision, and only A2JTrainEngine(precision="bf16x3")
 // calls these.  One planner per role decides kernel, grid and slices; the launch code and pn_conv1x1_x3_plan_info both call it.
-// Weight packs ([hi | lo], and the transpose for the data gradient) live in the context's pack cache under the key x3 = 2
+// Weight packs ([hi | lo], and the transpose for the data gradient) live in the context's pack cache under the kind PN_PACK_C1_X3
 // (pn_train_pack_refresh rebuilds them in its one launch, pn_adam / pn_sgd_nesterov mark them stale); with the cache off they are packed
 // per call into the training scratch.
 #include <cstdio>
@@ -27,7 +27,7 @@ static bool c1_plan_gemm(int N, int K, int HW, int M, C1Plan *p) {
     p->grid[1] = (unsigned)((M + C1_BM - 1) / C1_BM);
     p->grid[2] = 1;
     p->chunks = (K + C1_BK - 1) / C1_BK;
-    return p->grid[1] <= 65535 && (long)p->grid[0] * p->grid[1] <= 0x7fffffffL;          // (c1_logical_block computes the block count in an int)
+    return p->grid[1] <= 65535 && (long)p->grid[0] * p->grid[1] <= 0x7fffffffL;          // (t_logical_block computes the block count in an int)
 }
 
 // weight gradient: enough slices of whole 32-pixel chunks to fill the chip, at least C1_MIN_CHUNKS chunks each (the second launch reads every
@@ -61,11 +61,10 @@ static int c1_gemm(pn_ctx *ctx, const char *who, const float *x, const float *w,
                    int accumulate, hipStream_t s) {
     C1Plan plan;
     if (!c1_plan_gemm(N, K, HW, M, &plan)) return pn_set_error(ctx, PN_ERR_INVALID, "%s: size out of range", who);
-    const size_t plane = (size_t)plan.chunks * M * 32;
     void *wp = nullptr;
     bool fresh = false;
-    if (int rc = pn_train_pack_get(ctx, w, M, K, flip, 2, 2 * plane * sizeof(__bf16), s, &wp, &fresh)) return rc;
-    if (!fresh) hipLaunchKernelGGL(conv1x1_wpack_x3_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, w, (__bf16 *)wp, M, K, flip);
+    if (int rc = pn_train_pack_get(ctx, w, M, K, flip, PN_PACK_C1_X3, s, &wp, &fresh)) return rc;
+    if (!fresh) hipLaunchKernelGGL(conv1x1_wpack_x3_kernel, dim3(t_pack_blocks(PN_PACK_C1_X3, M, K)), dim3(256), 0, s, w, (__bf16 *)wp, M, K, flip);
     C1Gemm c;
     c.x = x; c.wp = (const __bf16 *)wp; c.bias = bias; c.y = y;
     c.N = N; c.K = K; c.HW = HW; c.M = M; c.accumulate = accumulate; c.P = N * HW;
@@ -74,15 +73,11 @@ static int c1_gemm(pn_ctx *ctx, const char *who, const float *x, const float *w,
     return PN_OK;
 }
 
-#define C1_CTX_CHECK                                                                                        \
-    if (!ctx) return PN_ERR_INVALID;                                                                        \
-    if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
-
 extern "C" {
 
 int pn_conv1x1_x3_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int N, int Cin, int HW, int Cout,
                           int accumulate, void *hip_stream) {
-    C1_CTX_CHECK
+    PN_CTX_CHECK
     if (!x_dev || !w_dev || !y_dev || N < 1 || Cin < 1 || HW < 1 || Cout < 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv1x1_x3_forward: bad arguments");
     return c1_gemm(ctx, "pn_conv1x1_x3_forward", x_dev, w_dev, bias_dev, y_dev, N, Cin, HW, Cout, 0, accumulate, (hipStream_t)hip_stream);
@@ -90,7 +85,7 @@ int pn_conv1x1_x3_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, c
 
 int pn_conv1x1_x3_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int HW, int Cout, int accumulate,
                         void *hip_stream) {
-    C1_CTX_CHECK
+    PN_CTX_CHECK
     if (!dy_dev || !w_dev || !dx_dev || N < 1 || Cin < 1 || HW < 1 || Cout < 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv1x1_x3_dgrad: bad arguments");
     return c1_gemm(ctx, "pn_conv1x1_x3_dgrad", dy_dev, w_dev, nullptr, dx_dev, N, Cout, HW, Cin, 1, accumulate, (hipStream_t)hip_stream);
@@ -98,7 +93,7 @@ int pn_conv1x1_x3_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, fl
 
 int pn_conv1x1_x3_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float *dw_dev, float *dbias_dev, int N, int Cin, int HW, int Cout,
                         void *hip_stream) {
-    C1_CTX_CHECK
+    PN_CTX_CHECK
     if (!x_dev || !dy_dev || !dw_dev || N < 1 || Cin < 1 || HW < 1 || Cout < 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv1x1_x3_wgrad: bad arguments");
     C1Plan plan;
@@ -116,7 +111,7 @@ int pn_conv1x1_x3_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, fl
     // 16-byte loads only where every whole group of a row is aligned: HW % 4 == 0 AND both tensors 16-byte aligned
     if (plan.aligned && ((((size_t)x_dev) | ((size_t)dy_dev)) & 15) == 0) hipLaunchKernelGGL(conv1x1_wgrad_x3_kernel<true>, grid, dim3(256), 0, s, c);
     else hipLaunchKernelGGL(conv1x1_wgrad_x3_kernel<false>, grid, dim3(256), 0, s, c);
-    hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, s, (const float *)ws, dw_dev, wn, plan.slices);
+    pn_train_wgrad_reduce(s, (const float *)ws, dw_dev, wn, plan.slices);       // (wn <= INT_MAX: c1_plan_wgrad)
     if (dbias_dev) pn_train_dbias(s, dy_dev, dbias_dev, N, Cout, HW, plan.csl, (double *)((char *)ws + part_off));
     PN_HIP_CHECK(ctx, hipGetLastError());
     return PN_OK;

@@ -3,8 +3,10 @@
 //   forward        y[n][co][p]  = sum_ci w[co][ci] x[n][ci][p]        A = weight pack [co][ci],     B = x as [pixel][ci]   (k-strided in memory)
 //   data gradient  dx[n][ci][p] = sum_co w[co][ci] dy[n][co][p]       A = TRANSPOSED pack [ci][co], B = dy as [pixel][co]  (the same kernel)
 //   weight grad.   dw[co][ci]   = sum_np dy[n][co][p] x[n][ci][p]     A = dy rows [co][pixel],      B = x rows [ci][pixel] (both k-contiguous)
-// Arithmetic, as the 3x3 x3 kernels (train_conv_kernels.h): every fp32 value v is split hi = bf16(v), lo = bf16(v - hi) (round to nearest
-// even) and a product block is three v_mfma_f32_16x16x32_bf16 into ONE fp32 accumulator, a_hi b_hi + a_hi b_lo + a_lo b_hi; no lo * lo.
+// Arithmetic, as the 3x3 x3 kernels (train_conv_kernels.h) and through the same functions (train_conv_common.h: t_split8, t_mfma_x3): every fp32
+// value v is split hi = bf16(v), lo = bf16(v - hi) (round to nearest even) and a product block is three v_mfma_f32_16x16x32_bf16 into ONE fp32
+// accumulator, a_hi b_hi + a_hi b_lo + a_lo b_hi; no lo * lo.  The block order is t_logical_block's, decoded with the sharing dimension fastest (the
+// channel blocks of one pixel tile; the blocks of one slice); the weight-gradient slices are added by train.hip's reduction (pn_train_wgrad_reduce).
 // LDS: both operands as [row][32 k] bf16 rows of 80 bytes (16-byte fragment reads and 16-byte staging writes are conflict-free at that
 // pitch), one hi and one lo plane each: 2 x 64 x 80 + 2 x 128 x 80 = 30 KB, static.  The next chunk's global loads are issued before the
 // MFMAs of the current one and land in registers (no second LDS buffer: several blocks per CU hide the two barriers).
@@ -13,11 +15,7 @@
 // kernel, so the 16 lanes of a group store 64 contiguous bytes of one output row.
 // The summation order is fixed by the shape alone (chunks in order, slices in order): repeated calls give identical bits; no atomics.
 #pragma once
-#include <hip/hip_runtime.h>
-
-typedef __bf16 c1_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float c1_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned c1_u32x4 __attribute__((ext_vector_type(4)));
+#include "train_conv_common.h"
 
 #define C1_BM 64                         // A rows per block
 #define C1_BN 128                        // B rows per block
@@ -42,70 +40,38 @@ struct C1Wgrad {         // partial[slice][co][ci] = sum over the slice's pixel 
     int cpi, total, per;                 // 32-pixel chunks per image (the last one ragged: a chunk never straddles two images), chunks in all, chunks per slice
 };
 
-__device__ __forceinline__ void c1_split8(const float (&v)[8], c1_bf16x8 &hi, c1_bf16x8 &lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        hi[j] = h;
-        lo[j] = (__bf16)(v[j] - (float)h);
-    }
-}
-
-// The reuse-aware block order of train_conv_kernels.h (t_logical_block): workgroups are dealt round-robin over the 8 XCDs in linear-id order
-// and every XCD has its own L2, so the hardware id is mapped to a logical id of which each XCD owns one contiguous range; the kernels decode
-// it with the sharing dimension fastest (the channel blocks of one pixel tile; the blocks of one slice).  Which block computes which tile
-// changes, nothing else.
-__device__ __forceinline__ int c1_logical_block() {
-    const int nb = (int)(gridDim.x * gridDim.y * gridDim.z);
-    const int L = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-    const int xcd = L & 7, idx = L >> 3, qq = nb >> 3, rr = nb & 7;
-    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-}
-
 // one chunk of 32 k from the staged planes
-__device__ __forceinline__ void c1_mma_chunk(const unsigned char *sm, int wave, int q, int r, c1_f32x4 (&acc)[4][2]) {
+__device__ __forceinline__ void c1_mma_chunk(const unsigned char *sm, int wave, int q, int r, t_f32x4 (&acc)[4][2]) {
     const unsigned char *Ah = sm, *Al = sm + C1_A_BYTES, *Bh = sm + 2 * C1_A_BYTES, *Bl = Bh + C1_B_BYTES;
-    c1_bf16x8 bh[2], bl[2];
+    t_bf16x8 bh[2], bl[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int off = (32 * wave + 16 * n + r) * C1_PITCH + 16 * q;
-        bh[n] = *(const c1_bf16x8 *)(Bh + off);
-        bl[n] = *(const c1_bf16x8 *)(Bl + off);
+        bh[n] = *(const t_bf16x8 *)(Bh + off);
+        bl[n] = *(const t_bf16x8 *)(Bl + off);
     }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         const int off = (16 * m + r) * C1_PITCH + 16 * q;
-        const c1_bf16x8 ah = *(const c1_bf16x8 *)(Ah + off), al = *(const c1_bf16x8 *)(Al + off);
+        const t_bf16x8 ah = *(const t_bf16x8 *)(Ah + off), al = *(const t_bf16x8 *)(Al + off);
 #pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
-        }
+        for (int n = 0; n < 2; ++n) t_mfma_x3(acc[m][n], ah, al, bh[n], bl[n]);
     }
 }
 
-// The [hi | lo] pack of w [Cout][Cin]: flip = 0: rows M = Cout over K = Cin (forward); flip = 1: the transpose, rows M = Cin over K = Cout
-// (data gradient).  pn_train_pack_refresh's wpack_all_kernel repeats this element arithmetic for the cached packs (key x3 = 2).
+// PN_PACK_C1_X3, per call: the [hi | lo] pack of w [Cout][Cin] -- flip = 0: rows M = Cout over K = Cin (forward); flip = 1: the transpose, rows
+// M = Cin over K = Cout (data gradient)
 __global__ void conv1x1_wpack_x3_kernel(const float *__restrict__ w, __bf16 *__restrict__ wp, int M, int K, int flip) {
-    const size_t plane = (size_t)((K + 31) / 32) * M * 32;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= plane) return;
-    const int k = (int)((i >> 5) / M) * 32 + (int)(i & 31), m = (int)((i >> 5) % M);
-    float v = 0.f;
-    if (k < K) v = flip ? w[(size_t)k * M + m] : w[(size_t)m * K + k];
-    const __bf16 h = (__bf16)v;
-    wp[i] = h;
-    wp[plane + i] = (__bf16)(v - (float)h);
+    t_pack_element<PN_PACK_C1_X3>(w, wp, M, K, flip, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void conv1x1_x3_kernel(C1Gemm c) {
     __shared__ __attribute__((aligned(16))) unsigned char sm[C1_LDS];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
-    const int lg = c1_logical_block();
+    const int lg = t_logical_block();
     const int p0 = (lg / (int)gridDim.y) * C1_BN, m0 = (lg % (int)gridDim.y) * C1_BM;          // (p0 < P <= INT_MAX - 128: the entry checks)
     const int chunks = (c.K + 31) / 32;
-    const size_t plane = (size_t)chunks * c.M * 32;
+    const size_t plane = t_pack_elems(PN_PACK_C1_X3, c.M, c.K);
     // staging roles.  B: this wave stages channels 8 wave .. + 7 of the chunk for pixels lane and lane + 64 (the lanes of a load are 64
     // consecutive pixels of one channel row); A: thread t copies 16 bytes (8 k) of pack row t / 4, both planes.
     long xoff[2];
@@ -118,13 +84,13 @@ __global__ __launch_bounds__(256) void conv1x1_x3_kernel(C1Gemm c) {
     const int arow = t >> 2, aseg = t & 3;
     const bool aok = m0 + arow < c.M;
     float xv[2][8];
-    c1_u32x4 wv[2];
-    const c1_u32x4 zero4 = {0u, 0u, 0u, 0u};
-    c1_f32x4 acc[4][2];
+    t_u32x4 wv[2];
+    const t_u32x4 zero4 = {0u, 0u, 0u, 0u};
+    t_f32x4 acc[4][2];
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = c1_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < 2; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
 
 #define C1_LOAD_CHUNK(ch)                                                                                                   \
     {                                                                                                                       \
@@ -133,22 +99,22 @@ __global__ __launch_bounds__(256) void conv1x1_x3_kernel(C1Gemm c) {
             _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                                   \
                 xv[i][j] = (xoff[i] >= 0 && ci0 + j < c.K) ? c.x[xoff[i] + (size_t)(ci0 + j) * c.HW] : 0.f;                 \
         const __bf16 *src = c.wp + ((size_t)(ch) * c.M + m0 + arow) * 32 + 8 * aseg;                                        \
-        wv[0] = aok ? *(const c1_u32x4 *)src : zero4;                                                                       \
-        wv[1] = aok ? *(const c1_u32x4 *)(src + plane) : zero4;                                                             \
+        wv[0] = aok ? *(const t_u32x4 *)src : zero4;                                                                       \
+        wv[1] = aok ? *(const t_u32x4 *)(src + plane) : zero4;                                                             \
     }
 
     C1_LOAD_CHUNK(0)
     for (int ch = 0; ch < chunks; ++ch) {
         __syncthreads();                 // the previous chunk's fragment reads are done
-        *(c1_u32x4 *)(sm + arow * C1_PITCH + 16 * aseg) = wv[0];
-        *(c1_u32x4 *)(sm + C1_A_BYTES + arow * C1_PITCH + 16 * aseg) = wv[1];
+        *(t_u32x4 *)(sm + arow * C1_PITCH + 16 * aseg) = wv[0];
+        *(t_u32x4 *)(sm + C1_A_BYTES + arow * C1_PITCH + 16 * aseg) = wv[1];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            c1_bf16x8 hi, lo;
-            c1_split8(xv[i], hi, lo);
+            t_bf16x8 hi, lo;
+            t_split8(xv[i], 0xffu, hi, lo);
             const int off = (lane + 64 * i) * C1_PITCH + 16 * wave;
-            *(c1_bf16x8 *)(sm + 2 * C1_A_BYTES + off) = hi;
-            *(c1_bf16x8 *)(sm + 2 * C1_A_BYTES + C1_B_BYTES + off) = lo;
+            *(t_bf16x8 *)(sm + 2 * C1_A_BYTES + off) = hi;
+            *(t_bf16x8 *)(sm + 2 * C1_A_BYTES + C1_B_BYTES + off) = lo;
         }
         __syncthreads();
         if (ch + 1 < chunks) C1_LOAD_CHUNK(ch + 1)
@@ -182,7 +148,7 @@ __global__ __launch_bounds__(256) void conv1x1_x3_kernel(C1Gemm c) {
 template <bool VEC>
 __device__ __forceinline__ void c1_load8(const float *__restrict__ p, bool row_ok, int rem, float (&v)[8]) {
     if (VEC && row_ok && rem >= 8) {
-        const c1_f32x4 a = *(const c1_f32x4 *)p, b = *(const c1_f32x4 *)(p + 4);
+        const t_f32x4 a = *(const t_f32x4 *)p, b = *(const t_f32x4 *)(p + 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
     } else {
@@ -195,18 +161,18 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void conv1x1_wgrad_x3_kernel(C1Wgrad c) {
     __shared__ __attribute__((aligned(16))) unsigned char sm[C1_LDS];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
-    const int lg = c1_logical_block(), slice = lg / (int)(gridDim.x * gridDim.y);
+    const int lg = t_logical_block(), slice = lg / (int)(gridDim.x * gridDim.y);
     const int n0 = (lg % (int)gridDim.x) * C1_BN, m0 = ((lg / (int)gridDim.x) % (int)gridDim.y) * C1_BM;          // ci block, co block
     const int k_begin = slice * c.per, k_end = min(c.total, k_begin + c.per);
     // staging: thread t splits pixels 8 (t % 4) .. + 7 of the chunk for dy row t / 4 and x rows t / 4, t / 4 + 64
     const int row = t >> 2, seg = t & 3;
     const bool aok = m0 + row < c.Cout, bok0 = n0 + row < c.Cin, bok1 = n0 + 64 + row < c.Cin;
     float av[8], bv[2][8];
-    c1_f32x4 acc[4][2];
+    t_f32x4 acc[4][2];
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = c1_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < 2; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
 
 #define C1_LOAD_CHUNK(kc)                                                                                                   \
     {                                                                                                                       \
@@ -219,16 +185,16 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_x3_kernel(C1Wgrad c) {
     if (k_begin < k_end) C1_LOAD_CHUNK(k_begin)
     for (int kc = k_begin; kc < k_end; ++kc) {
         __syncthreads();
-        c1_bf16x8 hi, lo;
-        c1_split8(av, hi, lo);
-        *(c1_bf16x8 *)(sm + row * C1_PITCH + 16 * seg) = hi;
-        *(c1_bf16x8 *)(sm + C1_A_BYTES + row * C1_PITCH + 16 * seg) = lo;
+        t_bf16x8 hi, lo;
+        t_split8(av, 0xffu, hi, lo);
+        *(t_bf16x8 *)(sm + row * C1_PITCH + 16 * seg) = hi;
+        *(t_bf16x8 *)(sm + C1_A_BYTES + row * C1_PITCH + 16 * seg) = lo;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            c1_split8(bv[i], hi, lo);
+            t_split8(bv[i], 0xffu, hi, lo);
             const int off = (row + 64 * i) * C1_PITCH + 16 * seg;
-            *(c1_bf16x8 *)(sm + 2 * C1_A_BYTES + off) = hi;
-            *(c1_bf16x8 *)(sm + 2 * C1_A_BYTES + C1_B_BYTES + off) = lo;
+            *(t_bf16x8 *)(sm + 2 * C1_A_BYTES + off) = hi;
+            *(t_bf16x8 *)(sm + 2 * C1_A_BYTES + C1_B_BYTES + off) = lo;
         }
         __syncthreads();
         if (kc + 1 < k_end) C1_LOAD_CHUNK(kc + 1)
@@ -249,21 +215,4 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_x3_kernel(C1Wgrad c) {
                 if (co < c.Cout) out[(size_t)co * c.Cin + ci] = acc[m][n][i];
             }
     }
-}
-
-// dw[i] = the slices' partial sums added in slice order
-__global__ void conv1x1_wgrad_reduce_kernel(const float *__restrict__ partial, float *__restrict__ dw, size_t wn, int slices) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= wn) return;
-    float s = 0.f;
-    int sl = 0;
-    for (; sl + 8 <= slices; sl += 8) {              // eight loads in flight, added in slice order
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = partial[(size_t)(sl + j) * wn + i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += v[j];
-    }
-    for (; sl < slices; ++sl) s += partial[(size_t)sl * wn + i];
-    dw[i] = s;
 }

@@ -7,6 +7,9 @@
 #include <vector>
 #include "../../include/popnet_hip.h"
 
+// What a cached / per-call weight pack of the NCHW training convolutions holds; the formats are defined in train_conv_common.h (t_pack_element)
+enum PnPackKind { PN_PACK_TILE3 = 0, PN_PACK_TILE3_X3 = 1, PN_PACK_C1_X3 = 2 };     // fp32 3x3, split-bf16 3x3, split-bf16 1x1 (conv1x1_x3.hip)
+
 struct pn_ctx {
     int device = 0;
     std::string err;
@@ -27,7 +30,7 @@ struct pn_ctx {
     // pn_train_pack_cache: the packed (transposed / rotated / split) weights of the 3x3 training convolutions live in persistent buffers keyed by
     // (weight pointer, shape, flip, precision) and are all refreshed by ONE launch per step (pn_train_pack_refresh) instead of one launch per
     // convolution call (train.hip)
-    struct PackEntry { const float *w; int Cout, Cin, flip, x3; void *buf; size_t bytes; bool fresh; };      // x3: 0 = fp32 3x3, 1 = split 3x3, 2 = split 1x1 (conv1x1_x3.hip: rows Cout over k Cin, flip = transposed)
+    struct PackEntry { const float *w; int Cout, Cin, flip; PnPackKind kind; void *buf; size_t bytes; bool fresh; };      // (PN_PACK_C1_X3: rows Cout over k Cin, flip = transposed)
     bool train_pack_cache = false;
     std::vector<PackEntry> train_packs;
     void *train_pack_table = nullptr;      // device copy of the descriptor table
@@ -96,8 +99,10 @@ __host__ __device__ inline int pn_limb_dst(int l) {
     return t[l];
 }
 int pn_train_ws(pn_ctx *ctx, size_t bytes, void **out);     // train.hip: the training scratch of the context (grown on demand, stream-ordered reuse)
-// train.hip, for conv1x1_x3.hip: the pack cache's lookup (t_pack_get; x3 = 2 keys the 1x1 split packs) and pn_conv2d_wgrad's bias gradient
-int pn_train_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, int x3, size_t bytes, hipStream_t s, void **buf, bool *fresh);
+// train.hip, for conv1x1_x3.hip: the pack cache's lookup (the buffer is sized by t_pack_bytes), pn_conv2d_wgrad's slice-order reduction of
+// partial weight gradients (wn <= INT_MAX elements per slice) and its bias gradient
+int pn_train_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, PnPackKind kind, hipStream_t s, void **buf, bool *fresh);
+void pn_train_wgrad_reduce(hipStream_t s, const float *partial, float *dw_dev, size_t wn, int slices);
 void pn_train_dbias(hipStream_t s, const float *dy_dev, float *dbias_dev, int N, int Cout, int HW, int csl, double *part);
 const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned *grid_x, unsigned *grid_y);     // train_yolo.hip: kernel label and grid of pn_conv2d_dgrad_strided
 
@@ -108,6 +113,11 @@ const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned
             return pn_set_error((ctx), PN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,           \
                                 hipGetErrorString(_e), __FILE__, __LINE__);                  \
     } while (0)
+
+// first statement of every extern "C" entry that launches: a context, and one that holds a device
+#define PN_CTX_CHECK                                                                                        \
+    if (!ctx) return PN_ERR_INVALID;                                                                        \
+    if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: every launch site keeps one of these (a static
 // per kernel instantiation) and opts in once per device it launches on (a process-wide flag left a second GPU unconfigured).

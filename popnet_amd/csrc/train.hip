@@ -4,7 +4,8 @@
 //   conv forward / data gradient / weight gradient   implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains), or split-bf16 MFMA
 //       nn.Conv2d of tpm/lib/network/rtpose_light3d.py:31-40,144-146,232-246 and its autograd
 //       kernels: train_conv_kernels.h (forward, data gradient, weight packs, the planes engine's stem forward),
-//                train_wgrad_kernels.h (weight gradient and its slice reduction, the planes engine's stem weight gradient)
+//                train_wgrad_kernels.h (weight gradient and its slice reduction, the planes engine's stem weight gradient),
+//                train_conv_common.h (what those two share with conv1x1_x3_kernels.h, and the weight-pack formats)
 //   train-mode BatchNorm2d (+ residual add + ReLU / LeakyReLU(0.1)) forward and backward      rtpose_light3d.py:52-70,147,244
 //   AvgPool2d(3, 2, 1) forward / backward                                                     rtpose_light3d.py:152,158
 //   sigmoid heads + rtpose_light3d_loss_fgweight forward and gradient                         rtpose_light3d.py:335-337, losses.py:65-106
@@ -20,13 +21,14 @@
 #include "train_wgrad_kernels.h"
 
 static int t_ws(pn_ctx *ctx, size_t bytes, void **out);
-// The pack buffer of (w, shape, flip, precision): the context's scratch when the cache is off (packed by the caller on every call), else
-// the cached entry -- *fresh tells the caller whether this step's refresh has already filled it.
-static int t_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, int x3, size_t bytes, hipStream_t s, void **buf, bool *fresh) {
+// The pack buffer of (w, shape, flip, kind), t_pack_bytes large: the context's scratch when the cache is off (packed by the caller on every call),
+// else the cached entry -- *fresh tells the caller whether this step's refresh has already filled it.
+static int t_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, PnPackKind kind, hipStream_t s, void **buf, bool *fresh) {
     *fresh = false;
+    const size_t bytes = t_pack_bytes(kind, Cout, Cin);
     if (!ctx->train_pack_cache) return t_ws(ctx, bytes, buf);
     for (auto &e : ctx->train_packs)
-        if (e.w == w && e.Cout == Cout && e.Cin == Cin && e.flip == flip && e.x3 == x3) {
+        if (e.w == w && e.Cout == Cout && e.Cin == Cin && e.flip == flip && e.kind == kind) {
             *buf = e.buf; *fresh = e.fresh; e.fresh = true;           // (a stale entry is packed by the caller right now)
             return PN_OK;
         }
@@ -35,7 +37,7 @@ static int t_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, 
     if (cap != hipStreamCaptureStatusNone)
         return pn_set_error(ctx, PN_ERR_STATE, "pn_train_pack_cache: a convolution met weights that were never packed while the stream is capturing (run one eager step first)");
     pn_ctx::PackEntry e;
-    e.w = w; e.Cout = Cout; e.Cin = Cin; e.flip = flip; e.x3 = x3; e.bytes = bytes; e.fresh = true; e.buf = nullptr;
+    e.w = w; e.Cout = Cout; e.Cin = Cin; e.flip = flip; e.kind = kind; e.bytes = bytes; e.fresh = true; e.buf = nullptr;
     PN_HIP_CHECK(ctx, hipMalloc(&e.buf, bytes));
     ctx->train_packs.push_back(e);
     *buf = e.buf;
@@ -665,21 +667,20 @@ static int t_conv_desc(pn_ctx *ctx, TConv *c, const char *who, int N, int Cin, i
 // (flip: the data gradient's rotated, transposed weights -- the packing IS the rotation; the pack's shape is c's own Cout x Cin), then halo tiles.
 static int t_launch_tile3(pn_ctx *ctx, const TTilePlan &plan, const TConv &c, const float *w_dev, int flip, hipStream_t s) {
     const TTile &g = plan.g;
-    const size_t wn = (size_t)c.Cout * c.Cin * 9;
-    const size_t wx = (size_t)((c.Cin + 31) / 32) * 9 * c.Cout * 32;        // elements per plane of the split-bf16 pack
+    const PnPackKind kind = plan.kernel == TK_TILE ? PN_PACK_TILE3 : PN_PACK_TILE3_X3;
     void *ws = nullptr;
     bool fresh = false;
     int rc;
     if ((rc = t_tile_lds_ok(ctx)) != PN_OK) return rc;
     const dim3 grid((unsigned)(c.N * g.tiles_x * g.tiles_y), (unsigned)((c.Cout + 63) / 64));
+    if ((rc = t_pack_get(ctx, w_dev, c.Cout, c.Cin, flip, kind, s, &ws, &fresh)) != PN_OK) return rc;
+    const dim3 pack_grid(t_pack_blocks(kind, c.Cout, c.Cin));
     if (plan.kernel == TK_TILE) {
-        if ((rc = t_pack_get(ctx, w_dev, c.Cout, c.Cin, flip, 0, wn * sizeof(float), s, &ws, &fresh)) != PN_OK) return rc;
-        if (!fresh) hipLaunchKernelGGL(wpack3_kernel, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, s, w_dev, (float *)ws, c.Cout, c.Cin, flip);
+        if (!fresh) hipLaunchKernelGGL(wpack3_kernel, pack_grid, dim3(256), 0, s, w_dev, (float *)ws, c.Cout, c.Cin, flip);
         const size_t lds = (size_t)(144 * TT_AP + 16 * g.CHP) * sizeof(float);
         hipLaunchKernelGGL(tconv3_tile_kernel, grid, dim3(256), lds, s, c, g, (const float *)ws);
     } else {
-        if ((rc = t_pack_get(ctx, w_dev, c.Cout, c.Cin, flip, 1, 4 * wx, s, &ws, &fresh)) != PN_OK) return rc;
-        if (!fresh) hipLaunchKernelGGL(wpack3_x3_kernel, dim3((unsigned)((wx + 255) / 256)), dim3(256), 0, s, w_dev, (__bf16 *)ws, c.Cout, c.Cin, flip);
+        if (!fresh) hipLaunchKernelGGL(wpack3_x3_kernel, pack_grid, dim3(256), 0, s, w_dev, (__bf16 *)ws, c.Cout, c.Cin, flip);
         if (plan.kernel == TK_TILE_X3W) {
             const size_t ldsw2 = (size_t)2 * TXW2_A_BYTES + (size_t)2 * g.HR * g.HC * TXW2_PITCH;
             hipLaunchKernelGGL(tconv3_tile_x3w_kernel, grid, dim3(256), ldsw2, s, c, g, (const __bf16 *)ws);
@@ -692,20 +693,16 @@ static int t_launch_tile3(pn_ctx *ctx, const TTilePlan &plan, const TConv &c, co
     return PN_OK;
 }
 
-#define T_CTX_CHECK(name)                                                                                   \
-    if (!ctx) return PN_ERR_INVALID;                                                                        \
-    if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
-
 extern "C" {
 
 int pn_train_ws_keep(pn_ctx *ctx, int keep) {
-    T_CTX_CHECK("pn_train_ws_keep")
+    PN_CTX_CHECK
     ctx->train_ws_keep = keep != 0;
     return PN_OK;
 }
 
 int pn_train_pack_cache(pn_ctx *ctx, int enable) {
-    T_CTX_CHECK("pn_train_pack_cache")
+    PN_CTX_CHECK
     if (!enable && ctx->train_pack_cache) {
         PN_HIP_CHECK(ctx, hipDeviceSynchronize());
         for (auto &e : ctx->train_packs) (void)hipFree(e.buf);
@@ -720,7 +717,7 @@ int pn_train_pack_cache(pn_ctx *ctx, int enable) {
 }
 
 int pn_train_pack_refresh(pn_ctx *ctx, void *hip_stream) {
-    T_CTX_CHECK("pn_train_pack_refresh")
+    PN_CTX_CHECK
     if (!ctx->train_pack_cache || ctx->train_packs.empty()) return PN_OK;
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t n = ctx->train_packs.size();
@@ -734,14 +731,12 @@ int pn_train_pack_refresh(pn_ctx *ctx, void *hip_stream) {
         unsigned blocks = 0;
         for (size_t i = 0; i < n; ++i) {
             const auto &e = ctx->train_packs[i];
-            const size_t items = e.x3 == 2 ? (size_t)((e.Cin + 31) / 32) * e.Cout * 32          // conv1x1_x3.hip's packs
-                                 : e.x3 ? (size_t)((e.Cin + 31) / 32) * 9 * e.Cout * 32 : (size_t)9 * e.Cin * e.Cout;
-            host[i] = TPackDesc{e.w, e.buf, e.Cout, e.Cin, e.flip, e.x3, blocks, 0u};
-            blocks += (unsigned)((items + 255) / 256);
+            host[i] = TPackDesc{e.w, e.buf, e.Cout, e.Cin, e.flip, e.kind, blocks, 0u};
+            blocks += t_pack_blocks(e.kind, e.Cout, e.Cin);
         }
         PN_HIP_CHECK(ctx, hipStreamSynchronize(s));
         // The table is APPEND-ONLY in a fixed-capacity block: a captured step graph bakes (table pointer, entry count, grid) into its
-        // wpack_all_kernel node, and an eager step of another resolution after capture() adds (w, Cout, Cin, flip, x3) keys.  Entries
+        // wpack_all_kernel node, and an eager step of another resolution after capture() adds (w, Cout, Cin, flip, kind) keys.  Entries
         // 0 .. n_old - 1 keep their bytes and their block offsets, so the replayed node stays valid (the table used to be
         // freed and reallocated here -- a replay then read freed memory).  Beyond the capacity the old block is retired, not freed,
         // while a graph may point at it (pn_train_ws_keep), exactly like train_ws.
@@ -776,7 +771,7 @@ int pn_train_set_precision(pn_ctx *ctx, int precision) {
 
 int pn_conv2d_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int N, int Cin, int H, int W,
                       int Cout, int ks, int stride, int pad, int accumulate, void *hip_stream) {
-    T_CTX_CHECK("pn_conv2d_forward")
+    PN_CTX_CHECK
     if (!x_dev || !w_dev || !y_dev || N < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || stride < 1 || pad < 0 || (ks != 1 && ks != 3 && ks != 7))
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_forward: bad arguments (kernel sizes 1, 3, 7)");
     TConv c;
@@ -795,7 +790,7 @@ int pn_conv2d_forward(pn_ctx *ctx, const float *x_dev, const float *w_dev, const
 
 int pn_conv2d_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int H, int W, int Cout, int ks, int pad,
                     int accumulate, void *hip_stream) {
-    T_CTX_CHECK("pn_conv2d_dgrad")
+    PN_CTX_CHECK
     if (!dy_dev || !w_dev || !dx_dev || (ks != 1 && ks != 3 && ks != 7) || pad > ks - 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_dgrad: bad arguments (stride 1 only)");
     const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
@@ -819,7 +814,7 @@ int pn_conv2d_dgrad(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float 
 
 int pn_conv2d_wgrad(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float *dw_dev, float *dbias_dev, int N, int Cin, int H, int W, int Cout,
                     int ks, int stride, int pad, void *hip_stream) {
-    T_CTX_CHECK("pn_conv2d_wgrad")
+    PN_CTX_CHECK
     if (!x_dev || !dy_dev || !dw_dev || N < 1 || (ks != 1 && ks != 3 && ks != 7) || stride < 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_wgrad: bad arguments");
     TConv c;
@@ -878,7 +873,7 @@ static int t_dil_desc(pn_ctx *ctx, TConv *c, const char *who, int N, int Cin, in
 
 int pn_conv2d_forward_dil(pn_ctx *ctx, const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int N, int Cin, int H, int W,
                           int Cout, int ks, int stride, int pad, int dil, int accumulate, void *hip_stream) {
-    T_CTX_CHECK("pn_conv2d_forward_dil")
+    PN_CTX_CHECK
     if (!x_dev || !w_dev || !y_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_forward_dil: null tensor");
     TConv c;
     c.x = x_dev; c.w = w_dev; c.bias = bias_dev; c.y = y_dev;
@@ -892,7 +887,7 @@ int pn_conv2d_forward_dil(pn_ctx *ctx, const float *x_dev, const float *w_dev, c
 
 int pn_conv2d_dgrad_dil(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int H, int W, int Cout, int ks, int pad,
                         int dil, int accumulate, void *hip_stream) {
-    T_CTX_CHECK("pn_conv2d_dgrad_dil")
+    PN_CTX_CHECK
     if (!dy_dev || !w_dev || !dx_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_dgrad_dil: null tensor");
     TConv f;        // the forward convolution this is the gradient of: range checks and the shape of dy
     if (int rc = t_dil_desc(ctx, &f, "pn_conv2d_dgrad_dil", N, Cin, H, W, Cout, ks, 1, pad, dil, accumulate)) return rc;
@@ -907,7 +902,7 @@ int pn_conv2d_dgrad_dil(pn_ctx *ctx, const float *dy_dev, const float *w_dev, fl
 
 int pn_conv2d_wgrad_dil(pn_ctx *ctx, const float *x_dev, const float *dy_dev, float *dw_dev, float *dbias_dev, int N, int Cin, int H, int W, int Cout,
                         int ks, int stride, int pad, int dil, void *hip_stream) {
-    T_CTX_CHECK("pn_conv2d_wgrad_dil")
+    PN_CTX_CHECK
     if (!x_dev || !dy_dev || !dw_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_wgrad_dil: null tensor");
     TConv c;
     c.x = x_dev; c.w = nullptr; c.bias = nullptr; c.y = (float *)dy_dev;
@@ -936,9 +931,11 @@ int pn_conv2d_wgrad_dil(pn_ctx *ctx, const float *x_dev, const float *dy_dev, fl
 
 }   // extern "C"
 // ---- what conv1x1_x3.hip shares with the entries above (internal, not part of the C ABI) -----------------------------------------------
-int pn_train_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, int x3, size_t bytes, hipStream_t s, void **buf, bool *fresh) {
-    return t_pack_get(ctx, w, Cout, Cin, flip, x3, bytes, s, buf, fresh);
+int pn_train_pack_get(pn_ctx *ctx, const float *w, int Cout, int Cin, int flip, PnPackKind kind, hipStream_t s, void **buf, bool *fresh) {
+    return t_pack_get(ctx, w, Cout, Cin, flip, kind, s, buf, fresh);
 }
+
+void pn_train_wgrad_reduce(hipStream_t s, const float *partial, float *dw_dev, size_t wn, int slices) { t_wgrad_reduce(s, partial, dw_dev, wn, slices); }
 
 // dbias[co] = sum dy over (n, pixel): pn_conv2d_wgrad's bias gradient -- chan_reduce_kernel<2> in double over csl slices into part, then sums_finish_kernel
 void pn_train_dbias(hipStream_t s, const float *dy_dev, float *dbias_dev, int N, int Cout, int HW, int csl, double *part) {
@@ -960,7 +957,7 @@ static int t_stem_conv(pn_ctx *ctx, TConv *c, const float *x_dev, void *planes, 
 
 int pn_stem_forward_planes(pn_ctx *ctx, const float *x_dev, const float *w_dev, void *y_planes, int cs, int split, int f32, int N, int Cin, int H, int W, int Cout,
                            int ks, int stride, int pad, int gather, hipStream_t s) {
-    T_CTX_CHECK("pn_stem_forward_planes")
+    PN_CTX_CHECK
     TConv c;
     if (int rc = t_stem_conv(ctx, &c, x_dev, y_planes, cs, split, N, Cin, H, W, Cout, ks, stride, pad)) return rc;
     if (!w_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_stem_forward_planes: no weights");
@@ -985,7 +982,7 @@ int pn_stem_forward_planes(pn_ctx *ctx, const float *x_dev, const float *w_dev, 
 
 int pn_stem_wgrad_planes(pn_ctx *ctx, const float *x_dev, const void *dy_planes, int cs, int split, int f32, const PnStemBn *bn, float *dw_dev, int N, int Cin, int H,
                          int W, int Cout, int ks, int stride, int pad, int depth, hipStream_t s) {
-    T_CTX_CHECK("pn_stem_wgrad_planes")
+    PN_CTX_CHECK
     TConv c;
     if (int rc = t_stem_conv(ctx, &c, x_dev, (void *)dy_planes, cs, split, N, Cin, H, W, Cout, ks, stride, pad)) return rc;
     if (!dw_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_stem_wgrad_planes: no output");
@@ -1025,7 +1022,7 @@ extern "C" {
 int pn_bn_train_forward(pn_ctx *ctx, const float *x_dev, const float *gamma_dev, const float *beta_dev, const float *res_dev, float *y_dev,
                         float *save_mean_dev, float *save_invstd_dev, float *running_mean_dev, float *running_var_dev, float momentum, float eps,
                         int act, int N, int C, int HW, void *hip_stream) {
-    T_CTX_CHECK("pn_bn_train_forward")
+    PN_CTX_CHECK
     if (!x_dev || !gamma_dev || !beta_dev || !y_dev || !save_mean_dev || !save_invstd_dev || N < 1 || C < 1 || HW < 1 || (long)N * HW < 2)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_forward: bad arguments");
     if ((long)N * C > 65535) return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_forward: N * C out of range");        // (grid.y of the apply kernel) refused before anything is launched
@@ -1050,7 +1047,7 @@ int pn_bn_train_forward(pn_ctx *ctx, const float *x_dev, const float *gamma_dev,
 int pn_bn_train_backward(pn_ctx *ctx, const float *x_dev, const float *dy_dev, const float *out_dev, const float *gamma_dev, const float *beta_dev,
                          const float *save_mean_dev, const float *save_invstd_dev, int act, int N, int C, int HW, float *dx_dev, float *dgamma_dev, float *dbeta_dev,
                          float *dres_dev, int dres_accumulate, void *hip_stream) {
-    T_CTX_CHECK("pn_bn_train_backward")
+    PN_CTX_CHECK
     if (!x_dev || !dy_dev || !gamma_dev || !save_mean_dev || !save_invstd_dev || !dx_dev || !dgamma_dev || !dbeta_dev || (act != PN_ACT_NONE && !out_dev && !beta_dev))
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_bn_train_backward: bad arguments (an activation needs out, or beta to recompute its mask)");
     if (N < 1 || C < 1 || HW < 1 || (long)N * C > 65535)        // (grid.y of the apply kernel) refused before anything is launched
@@ -1075,7 +1072,7 @@ int pn_bn_train_backward(pn_ctx *ctx, const float *x_dev, const float *dy_dev, c
 }
 
 int pn_avgpool3s2_forward(pn_ctx *ctx, const float *x_dev, float *y_dev, int planes, int H, int W, void *hip_stream) {
-    T_CTX_CHECK("pn_avgpool3s2_forward")
+    PN_CTX_CHECK
     if (!x_dev || !y_dev || planes < 1 || H < 1 || W < 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_avgpool3s2_forward: bad arguments");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const size_t total = (size_t)planes * Ho * Wo;
@@ -1085,7 +1082,7 @@ int pn_avgpool3s2_forward(pn_ctx *ctx, const float *x_dev, float *y_dev, int pla
 }
 
 int pn_avgpool3s2_backward(pn_ctx *ctx, const float *dy_dev, float *dx_dev, int planes, int H, int W, void *hip_stream) {
-    T_CTX_CHECK("pn_avgpool3s2_backward")
+    PN_CTX_CHECK
     if (!dy_dev || !dx_dev || planes < 1 || H < 1 || W < 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_avgpool3s2_backward: bad arguments");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const size_t total = (size_t)planes * H * W;
@@ -1096,7 +1093,7 @@ int pn_avgpool3s2_backward(pn_ctx *ctx, const float *dy_dev, float *dx_dev, int 
 
 int pn_head_forward(pn_ctx *ctx, const float *v_dev, const float *target_dev, const float *fg_dev, int kind, int N, int C, int HW, float *s_dev,
                     float *out_dev, int out_ld, float *loss_dev, void *hip_stream) {
-    T_CTX_CHECK("pn_head_forward")
+    PN_CTX_CHECK
     if (!v_dev || !target_dev || !s_dev || !out_dev || !loss_dev || out_ld < C || N < 1) return pn_set_error(ctx, PN_ERR_INVALID, "pn_head_forward: bad arguments");
     const size_t total = (size_t)N * C * HW;
     const unsigned nb = (unsigned)((total + 255) / 256);
@@ -1112,7 +1109,7 @@ int pn_head_forward(pn_ctx *ctx, const float *v_dev, const float *target_dev, co
 
 int pn_head_backward(pn_ctx *ctx, const float *s_dev, const float *target_dev, const float *fg_dev, const float *dextra_dev, int dextra_ld, int kind,
                      int N, int C, int HW, float *dv_dev, void *hip_stream) {
-    T_CTX_CHECK("pn_head_backward")
+    PN_CTX_CHECK
     if (!s_dev || !target_dev || !dv_dev || (dextra_dev && dextra_ld < C)) return pn_set_error(ctx, PN_ERR_INVALID, "pn_head_backward: bad arguments");
     const size_t total = (size_t)N * C * HW;
     hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, s_dev, target_dev, fg_dev, dextra_dev,
@@ -1122,7 +1119,7 @@ int pn_head_backward(pn_ctx *ctx, const float *s_dev, const float *target_dev, c
 }
 
 int pn_slice_copy(pn_ctx *ctx, const float *src_dev, int src_ld, float *dst_dev, int dst_ld, int N, int C, int HW, int accumulate, void *hip_stream) {
-    T_CTX_CHECK("pn_slice_copy")
+    PN_CTX_CHECK
     if (!src_dev || !dst_dev || src_ld < C || dst_ld < C) return pn_set_error(ctx, PN_ERR_INVALID, "pn_slice_copy: bad arguments");
     const size_t total = (size_t)N * C * HW;
     hipLaunchKernelGGL(slice_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, src_dev, src_ld, dst_dev, dst_ld, C, HW,
@@ -1133,7 +1130,7 @@ int pn_slice_copy(pn_ctx *ctx, const float *src_dev, int src_ld, float *dst_dev,
 
 int pn_sgd_nesterov(pn_ctx *ctx, float *param_dev, const float *grad_dev, float *momentum_buf_dev, size_t n, float lr, float momentum, float weight_decay,
                     int first_step, float grad_scale, void *hip_stream) {
-    T_CTX_CHECK("pn_sgd_nesterov")
+    PN_CTX_CHECK
     if (!param_dev || !grad_dev || !momentum_buf_dev) return pn_set_error(ctx, PN_ERR_INVALID, "pn_sgd_nesterov: bad arguments");
     if (n == 0) return PN_OK;
     for (auto &e : ctx->train_packs) e.fresh = false;         // the weights move: cached packs are stale until the next pn_train_pack_refresh (or per-call pack)

@@ -3,13 +3,12 @@
 //   tconv3_tile_kernel             3x3 stride 1 on halo tiles, fp32 MFMA
 //   tconv3_tile_x3 / _x3w_kernel   the same tiles on split-bf16 MFMA ("bf16x3"): 128 / 256 pixel slots per block
 //   tstem_fwd_kernel               the planes engine's 7x7 / 2 single-channel stem (trainx.hip)
-//   wpack3 / wpack3_x3 / wpack_all / wflip   weight packs of the kernels above
-// The launches, the geometry functions and the planners are in train.hip.
+//   wpack3 / wpack3_x3 / wpack_all / wflip   weight packs of the kernels above (the pack formats themselves: train_conv_common.h)
+// What the kernels share is written once: t_tile_epilogue (all four NCHW epilogues), t_tile_block / t_tile_slot / t_halo_off (the tile kernels'
+// decodes), TXRows80 / TXRowsSwz + t_x3_load_w / t_x3_store_w / t_x3_next_w / t_x3_stage_halo (the two split-bf16 tile kernels, which differ in
+// their LDS address function and their pixel-tile count).  The launches, the geometry functions and the planners are in train.hip.
 #pragma once
-#include "pn_internal.h"
-
-
-typedef float t_f32x4 __attribute__((ext_vector_type(4)));
+#include "train_conv_common.h"
 
 struct TConv {
     const float *x;      // [N, Cin, H, W]
@@ -26,9 +25,6 @@ struct TConv {
     int pl_cs = 0, pl_split = 0;
     int dil = 1;         // tap spacing; read by the DIL instantiations of tconv_fwd_kernel / tconv_wgrad_kernel only (pn_conv2d_*_dil)
 };
-typedef __attribute__((ext_vector_type(8))) __bf16 t_bf8;
-typedef __attribute__((ext_vector_type(4))) __bf16 t_bf4;
-typedef __attribute__((ext_vector_type(2))) float t_f32x2;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Forward (and, with flipped weights, the stride-1 data gradient): D[cout][pixel] = sum_k W[cout][k] * X[k][pixel],
@@ -40,30 +36,51 @@ typedef __attribute__((ext_vector_type(2))) float t_f32x2;
 #define TC_AP 80      // LDS pitches: 4 k rows x 16 lanes of an MFMA operand read fall on 64 different banks
 #define TC_BP 144
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Reuse-aware block order (round 5).  The dispatcher deals the workgroups of a launch round-robin over the 8 XCDs in linear-id order
-// (x fastest) and every XCD has its own 4 MB L2.  With the plain (tile, cout block) / (ci block, cout block, slice) grids the blocks
-// that read the SAME operand tile -- the cout blocks of one input tile in the forward / data-gradient kernels, the (ci, cout) blocks of
-// one pixel slice in the weight gradient -- sat on different XCDs or ran a whole grid apart in time: every operand tile crossed the
-// fabric once per sharer (a 256 -> 256 weight gradient staged 444 MB for 51 MB of tensors).  t_logical_block() maps the hardware id to
-// a LOGICAL id such that each XCD owns one contiguous range of logical ids (a bijection, the conv kernels' remap of net.hip); the
-// kernels decode the logical id with the sharing dimension fastest, so sharers run at the same time behind the same L2.  Which block
-// computes which tile changes, nothing else: results are bit-identical.
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int t_logical_block() {
-    const int nb = (int)(gridDim.x * gridDim.y * gridDim.z);
-    const int L = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-    const int xcd = L & 7, idx = L >> 3, qq = nb >> 3, rr = nb & 7;
-    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+// The bias of this lane's sixteen couts co0 + 16 m + 4 q + i (element i of MFMA tile m), gathered once (round 5: `v += c.bias[co]` inside the store loop
+// compiled to load, s_waitcnt vmcnt(0), add -- sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler
+// had sunk to their uses)
+__device__ __forceinline__ void t_bias16(const TConv &c, int co0, int q, float (&bv)[16]) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
+        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
+    }
+    T_PIN16(bv);
 }
-// Sixteen loaded values pinned in registers at this point of the program: every one of their loads has been issued before the first is
-// waited for.  Without it the compiler sinks each load to its single use (legal: the addresses are provably distinct from the stores in
-// between) and waits for it there -- a dependent memory round trip per element.
-#define T_PIN16(a) do { _Pragma("unroll") for (int _k = 0; _k < 16; ++_k) asm volatile("" : "+v"((a)[_k])); } while (0)
-// forward-type grids (tiles, cout blocks): the cout blocks of a tile are neighbours in logical order
-#define T_DECODE_TILE_CB(tile, cb) const int _lg = t_logical_block(), cb = _lg % (int)gridDim.y, tile = _lg / (int)gridDim.y
-// weight-gradient grids (column blocks, cout blocks, slices): a slice's blocks are one contiguous logical range
-#define T_DECODE_XYZ(bx, by, bz) const int _lg = t_logical_block(), bx = _lg % (int)gridDim.x, by = (_lg / (int)gridDim.x) % (int)gridDim.y, bz = _lg / (int)(gridDim.x * gridDim.y)
+// NCHW epilogue of the forward kernels: acc[m][n][i] is cout co0 + 16 m + 4 q + i of the lane's pixel slot n; slot(n, pok) returns the address of that pixel
+// in cout plane 0 of y (any valid address when the slot is unused: pok = 0).  y (+)= bias + acc; the accumulate form first gathers all sixteen old values of
+// a slot (independent loads in flight), then adds and stores.
+template <int NT, class Slot>
+__device__ __forceinline__ void t_tile_epilogue(const TConv &c, int HoWo, int co0, int q, const t_f32x4 (&acc)[4][NT], Slot slot) {
+    float bv[16];
+    t_bias16(c, co0, q, bv);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        int pok;
+        float *yb = slot(n, pok);
+        float old[16];
+        if (c.accumulate) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int co = co0 + 16 * m + 4 * q + i;
+                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
+                }
+            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int co = co0 + 16 * m + 4 * q + i;
+                float v = acc[m][n][i];
+                v += bv[4 * m + i];
+                if (c.accumulate) v += old[4 * m + i];
+                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
+            }
+    }
+}
 
 // DIL: the taps are c.dil pixels apart (A2J's layer4.1 / layer4.2 conv2, third_party_methods/A2J_experiments/resnet.py:112,145) -- the gather address
 // changes, the k order and the MFMA order do not.  DIL = false is the kernel as it always was.
@@ -143,70 +160,46 @@ __global__ __launch_bounds__(256) void tconv_fwd_kernel(TConv c) {
                 for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
         }
     }
-    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
-    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
-    float bv[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
-        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
+    // epilogue: lane holds couts 16m + 4q + i of pixel 32 wave + 16 n + r
+    if (!PL) {
+        t_tile_epilogue<2>(c, HoWo, co0, q, acc, [&](int n, int &pok) {
+            const int p = p0 + 32 * wave + 16 * n + r;
+            pok = (int)(p < c.P);
+            const int pc = p & -pok, img = pc / HoWo, rem = pc - img * HoWo;
+            return c.y + (size_t)img * c.Cout * HoWo + rem;
+        });
+        return;
     }
-    T_PIN16(bv);
-    // epilogue: lane holds couts 16m + 4q + i of pixel 32 wave + 16 n + r; the accumulate form first gathers all old values
-    // (32 independent loads in flight), then adds and stores
+    // planes: this lane's four consecutive couts of a 16-cout tile are one 8-byte (bf16 hi, lo) / 16-byte (f32) store
+    float bv[16];
+    t_bias16(c, co0, q, bv);
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int p = p0 + 32 * wave + 16 * n + r;
         const int pok = (int)(p < c.P);
         const int pc = p & -pok;
-        if (PL) {       // planes: this lane's four consecutive couts of a 16-cout tile are one 8-byte (bf16 hi, lo) / 16-byte (f32) store
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int co = co0 + 16 * m + 4 * q;
-                float v[4];
+        for (int m = 0; m < 4; ++m) {
+            const int co = co0 + 16 * m + 4 * q;
+            float v[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = acc[m][n][i] + bv[4 * m + i];
-                if (!pok || co >= c.Cout) continue;
-                if (PL == 2) {
-                    *reinterpret_cast<t_f32x4 *>((float *)c.pl + (size_t)pc * c.pl_cs + co) = t_f32x4{v[0], v[1], v[2], v[3]};
-                } else {
-                    t_bf4 h, l;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const __bf16 hi = (__bf16)v[i];
-                        h[i] = hi;
-                        l[i] = (__bf16)(v[i] - (float)hi);
-                    }
-                    __bf16 *o = (__bf16 *)c.pl + (size_t)pc * c.pl_cs + co;
-                    *reinterpret_cast<t_bf4 *>(o) = h;
-                    *reinterpret_cast<t_bf4 *>(o + c.pl_split) = l;
-                }
-            }
-            continue;
-        }
-        const int img = pc / HoWo, rem = pc - img * HoWo;
-        float *yb = c.y + (size_t)img * c.Cout * HoWo + rem;
-        float old[16];
-        if (c.accumulate) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
+            for (int i = 0; i < 4; ++i) v[i] = acc[m][n][i] + bv[4 * m + i];
+            if (!pok || co >= c.Cout) continue;
+            if (PL == 2) {
+                *reinterpret_cast<t_f32x4 *>((float *)c.pl + (size_t)pc * c.pl_cs + co) = t_f32x4{v[0], v[1], v[2], v[3]};
+            } else {
+                t_bf4 h, l;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int co = co0 + 16 * m + 4 * q + i;
-                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
+                    const __bf16 hi = (__bf16)v[i];
+                    h[i] = hi;
+                    l[i] = (__bf16)(v[i] - (float)hi);
                 }
-            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int co = co0 + 16 * m + 4 * q + i;
-                float v = acc[m][n][i];
-                v += bv[4 * m + i];
-                if (c.accumulate) v += old[4 * m + i];
-                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
+                __bf16 *o = (__bf16 *)c.pl + (size_t)pc * c.pl_cs + co;
+                *reinterpret_cast<t_bf4 *>(o) = h;
+                *reinterpret_cast<t_bf4 *>(o + c.pl_split) = l;
             }
+        }
     }
 }
 
@@ -228,12 +221,39 @@ struct TTile {
 #define TT_AP 80
 #define TT_MAXNI 2
 
-// wp[tap][ci][co] = flip ? W[co_w = ci][ci_w = co][8 - tap] : W[co][ci][tap]   (flip: the data gradient's transposed, rotated weights)
+// The block's tile (b = tile index of the grid, image-major): image, top-left output pixel, first cout
+struct TBlock { int img, y0, x0, co0; };
+__device__ __forceinline__ TBlock t_tile_block(const TTile &g, int b, int cblk) {
+    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y;
+    return TBlock{b / (g.tiles_x * g.tiles_y), ty * g.R, tx * g.TW, cblk * 64};
+}
+// Pixel slot sl of the tile (an MFMA column; row-major, TW slots per row): hpix = the halo pixel of its top-left tap, opix = its pixel in the output plane;
+// a slot beyond the tile or the map reads halo pixel 0 and has opix = -1
+__device__ __forceinline__ void t_tile_slot(const TConv &c, const TTile &g, const TBlock &k, int sl, int &hpix, int &opix) {
+    const int ry = sl / g.TW, rx = sl - ry * g.TW;
+    const bool ok = ry < g.R && k.y0 + ry < c.Ho && k.x0 + rx < c.Wo;
+    hpix = ok ? ry * g.HC + rx : 0;
+    opix = ok ? (k.y0 + ry) * c.Wo + k.x0 + rx : -1;
+}
+// Halo element e (row-major, HC per row): its offset inside an input plane, or -1 = zero padding / beyond the halo tile
+__device__ __forceinline__ int t_halo_off(const TConv &c, const TTile &g, const TBlock &k, int e) {
+    const int hy = e / g.HC, hx = e - hy * g.HC;
+    const int iy = k.y0 - c.pad + hy, ix = k.x0 - c.pad + hx;
+    return (e < g.HR * g.HC && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
+}
+// the tile kernels' epilogue: slot n is pixel opix[n] of image k.img (opix < 0: unused)
+template <int NT>
+__device__ __forceinline__ void t_tile_epilogue(const TConv &c, const TBlock &k, int q, const t_f32x4 (&acc)[4][NT], const int (&opix)[NT]) {
+    const int HoWo = c.Ho * c.Wo;
+    t_tile_epilogue<NT>(c, HoWo, k.co0, q, acc, [&](int n, int &pok) {
+        pok = (int)(opix[n] >= 0);
+        return c.y + (size_t)k.img * c.Cout * HoWo + (opix[n] & -pok);
+    });
+}
+
+// PN_PACK_TILE3 (flip: the data gradient's transposed, rotated weights), per call
 __global__ void wpack3_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int flip) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 9 * Cin * Cout) return;
-    const int co = i % Cout, ci = (i / Cout) % Cin, tap = i / (Cout * Cin);
-    wp[i] = flip ? w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : w[((size_t)co * Cin + ci) * 9 + tap];
+    t_pack_element<PN_PACK_TILE3>(w, wp, Cout, Cin, flip, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ __launch_bounds__(256, 2) void tconv3_tile_kernel(TConv c, TTile g, const float *__restrict__ wp) {
@@ -242,31 +262,21 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_kernel(TConv c, TTile g, c
     float *Hs = t_smem + 144 * TT_AP;         // [16][CHP]         halo tile of 16 input channels
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
     T_DECODE_TILE_CB(b, cblk);
-    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y, img = b / (g.tiles_x * g.tiles_y);
-    const int y0 = ty * g.R, x0 = tx * g.TW, co0 = cblk * 64;
-    const int HW = c.H * c.W, HoWo = c.Ho * c.Wo;
+    const TBlock k = t_tile_block(g, b, cblk);
+    const int co0 = k.co0, HW = c.H * c.W;
     // this lane's two pixel slots (MFMA columns)
     int hb[2], opix[2];
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int sl = 32 * wave + 16 * n + r;
-        const int ry = sl / g.TW, rx = sl - ry * g.TW;
-        const bool ok = ry < g.R && y0 + ry < c.Ho && x0 + rx < c.Wo;
-        hb[n] = ok ? ry * g.HC + rx : 0;
-        opix[n] = ok ? (y0 + ry) * c.Wo + x0 + rx : -1;
-    }
+    for (int n = 0; n < 2; ++n) t_tile_slot(c, g, k, 32 * wave + 16 * n + r, hb[n], opix[n]);
     // halo elements this thread stages for every channel: offset inside the image plane (or -1 = zero padding)
     int hoff[TT_MAXNI], hdst[TT_MAXNI];
 #pragma unroll
     for (int i = 0; i < TT_MAXNI; ++i) {
         const int e = t + 256 * i;
-        const int hy = e / g.HC, hx = e - hy * g.HC;
-        const int iy = y0 - c.pad + hy, ix = x0 - c.pad + hx;
-        const bool in = e < g.HR * g.HC;
-        hdst[i] = in ? e : -1;
-        hoff[i] = (in && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
+        hdst[i] = e < g.HR * g.HC ? e : -1;
+        hoff[i] = t_halo_off(c, g, k, e);
     }
-    const float *xb = c.x + (size_t)img * c.Cin * HW;
+    const float *xb = c.x + (size_t)k.img * c.Cin * HW;
     const int a_co = t & 63, a_r0 = t >> 6;
     const bool a_ok = co0 + a_co < c.Cout;
     const float *wa = wp + (a_ok ? co0 + a_co : 0);
@@ -342,41 +352,7 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_kernel(TConv c, TTile g, c
             }
         }
     }
-    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
-    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
-    float bv[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
-        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
-    }
-    T_PIN16(bv);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int pok = (int)(opix[n] >= 0);
-        float *yb = c.y + (size_t)img * c.Cout * HoWo + (opix[n] & -pok);
-        float old[16];
-        if (c.accumulate) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int co = co0 + 16 * m + 4 * q + i;
-                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
-                }
-            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int co = co0 + 16 * m + 4 * q + i;
-                float v = acc[m][n][i];
-                v += bv[4 * m + i];
-                if (c.accumulate) v += old[4 * m + i];
-                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
-            }
-    }
+    t_tile_epilogue<2>(c, k, q, acc, opix);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -387,42 +363,32 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_kernel(TConv c, TTile g, c
 // matrix-pipe time for fp32-class results.  Chunks of 32 input channels; LDS images are [row][32 channels] bf16 with an
 // 80-byte pitch (16-byte fragment reads and 16-byte staging writes both conflict-free); the weight slice is staged one
 // kernel row (3 taps) at a time.
+// Two kernels: tconv3_tile_x3_kernel (64 couts x 128 pixel slots per block, rows at the 80-byte pitch) and the wide tconv3_tile_x3w_kernel
+// (64 couts x 256 slots, swizzled 64-byte rows).  They share the staging below and differ through the row-address functor and the tile count.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef __bf16 t_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned t_u32x4 __attribute__((ext_vector_type(4)));
 #define TX_PITCH 80                     // bytes per [32 x bf16] row
 #define TX_A_BYTES (3 * 64 * TX_PITCH)  // one plane of the weight slice of one kernel row
+#define TXW2_PITCH 64                   // the wide kernel's
+#define TXW2_A_BYTES (3 * 64 * TXW2_PITCH)
+// LDS byte address of 16-byte segment seg (8 channels) of row `row`, as a functor passed by value
+struct TXRows80 {
+    __device__ __forceinline__ int operator()(int row, int seg) const { return row * TX_PITCH + 16 * seg; }
+};
+// 64-byte pitch with the segment XOR-swizzled by (row >> 2) & 3: sixteen consecutive rows x one segment cover sixteen different 16-byte bank groups, for the
+// staging stores and for both operands' fragment reads
+struct TXRowsSwz {
+    __device__ __forceinline__ int operator()(int row, int seg) const { return row * TXW2_PITCH + 16 * (seg ^ ((row >> 2) & 3)); }
+};
 
-__device__ __forceinline__ void t_split8(const float (&v)[8], unsigned okmask, t_bf16x8 &hi, t_bf16x8 &lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float x = (okmask >> j) & 1u ? v[j] : 0.f;
-        const __bf16 h = (__bf16)x;
-        hi[j] = h;
-        lo[j] = (__bf16)(x - (float)h);
-    }
-}
-
-// Weights of the split-bf16 kernel, packed once per launch in the LDS image's own order: wpx[plane][chunk of 32 ci][tap][cout][32 ci]
-// bf16 (plane 0 = hi, 1 = lo; channels beyond Cin are zero), so that staging a kernel row is six 16-byte copies per thread instead
-// of 24 dword loads + the split arithmetic per thread.  flip as in wpack3_kernel (the data gradient's rotated, transposed weights).
+// PN_PACK_TILE3_X3, per call: the weights in the LDS image's own order, so that staging a kernel row is six 16-byte copies per thread instead of 24 dword
+// loads + the split arithmetic per thread
 __global__ void wpack3_x3_kernel(const float *__restrict__ w, __bf16 *__restrict__ wpx, int Cout, int Cin, int flip) {
-    const int chunks = (Cin + 31) / 32;
-    const size_t plane = (size_t)chunks * 9 * Cout * 32;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= plane) return;
-    const int ch = (int)(i & 31), co = (int)((i >> 5) % Cout), tap = (int)(((i >> 5) / Cout) % 9), chunk = (int)((i >> 5) / Cout / 9);
-    const int ci = chunk * 32 + ch;
-    float v = 0.f;
-    if (ci < Cin) v = flip ? w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : w[((size_t)co * Cin + ci) * 9 + tap];
-    const __bf16 h = (__bf16)v;
-    wpx[i] = h;
-    wpx[plane + i] = (__bf16)(v - (float)h);
+    t_pack_element<PN_PACK_TILE3_X3>(w, wpx, Cout, Cin, flip, (size_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // Every cached pack of a context refreshed by ONE launch (pn_train_pack_refresh): the block finds its descriptor (<= ~130 entries, bisected by
-// every thread: uniform) and runs wpack3_kernel's / wpack3_x3_kernel's element arithmetic on it -- the same values as the per-call packs.
-struct TPackDesc { const float *w; void *dst; int Cout, Cin, flip, x3; unsigned first_block, pad; };
+// every thread: uniform) and writes its 256 elements of that pack -- t_pack_element, as the per-call pack kernels.
+struct TPackDesc { const float *w; void *dst; int Cout, Cin, flip; PnPackKind kind; unsigned first_block, pad; };
 __global__ void wpack_all_kernel(const TPackDesc *__restrict__ tab, int n) {
     int e = 0, hi = n - 1;          // the last entry whose first block is <= this one (first_block ascends strictly); A2J's bf16x3 step has ~130 entries: bisect
     while (e < hi) {
@@ -432,34 +398,78 @@ __global__ void wpack_all_kernel(const TPackDesc *__restrict__ tab, int n) {
     }
     const TPackDesc d = tab[e];
     const size_t i = (size_t)(blockIdx.x - d.first_block) * blockDim.x + threadIdx.x;
-    const int Cout = d.Cout, Cin = d.Cin;
-    if (d.x3 == 2) {                 // the 1x1 split pack (conv1x1_wpack_x3_kernel: rows M = d.Cout over K = d.Cin, flip = transposed source)
-        const size_t plane = (size_t)((Cin + 31) / 32) * Cout * 32;
-        if (i >= plane) return;
-        const int k = (int)((i >> 5) / Cout) * 32 + (int)(i & 31), m = (int)((i >> 5) % Cout);
-        float v = 0.f;
-        if (k < Cin) v = d.flip ? d.w[(size_t)k * Cout + m] : d.w[(size_t)m * Cin + k];
-        const __bf16 h = (__bf16)v;
-        __bf16 *wp = (__bf16 *)d.dst;
-        wp[i] = h;
-        wp[plane + i] = (__bf16)(v - (float)h);
-    } else if (d.x3) {
-        const int chunks = (Cin + 31) / 32;
-        const size_t plane = (size_t)chunks * 9 * Cout * 32;
-        if (i >= plane) return;
-        const int ch = (int)(i & 31), co = (int)((i >> 5) % Cout), tap = (int)(((i >> 5) / Cout) % 9), chunk = (int)((i >> 5) / Cout / 9);
-        const int ci = chunk * 32 + ch;
-        float v = 0.f;
-        if (ci < Cin) v = d.flip ? d.w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : d.w[((size_t)co * Cin + ci) * 9 + tap];
-        const __bf16 h = (__bf16)v;
-        __bf16 *wpx = (__bf16 *)d.dst;
-        wpx[i] = h;
-        wpx[plane + i] = (__bf16)(v - (float)h);
-    } else {
-        if (i >= (size_t)9 * Cin * Cout) return;
-        const int co = (int)(i % Cout), ci = (int)((i / Cout) % Cin), tap = (int)(i / ((size_t)Cout * Cin));
-        ((float *)d.dst)[i] = d.flip ? d.w[((size_t)ci * Cout + co) * 9 + (8 - tap)] : d.w[((size_t)co * Cin + ci) * 9 + tap];
+    switch (d.kind) {
+    case PN_PACK_C1_X3: t_pack_element<PN_PACK_C1_X3>(d.w, d.dst, d.Cout, d.Cin, d.flip, i); break;
+    case PN_PACK_TILE3_X3: t_pack_element<PN_PACK_TILE3_X3>(d.w, d.dst, d.Cout, d.Cin, d.flip, i); break;
+    default: t_pack_element<PN_PACK_TILE3>(d.w, d.dst, d.Cout, d.Cin, d.flip, i);
     }
+}
+
+// Weight staging role of a thread: per kernel row 3 taps x 64 couts x 4 segments of 8 channels x 2 planes = 1536 16-byte pieces, 6 per thread
+struct TXPiece { int pl, kx, co, seg; };
+__device__ __forceinline__ TXPiece t_x3_piece(int t, int j) {
+    const int piece = t + 256 * j;                    // < 1536: plane, kx, cout, segment
+    const int pl = piece / 768, rem = piece - pl * 768;
+    return TXPiece{pl, rem >> 8, (rem >> 2) & 63, rem & 3};
+}
+// the thread's pieces of (chunk wc0 / 32, kernel row wky), from the packed planes into registers
+__device__ __forceinline__ void t_x3_load_w(const TConv &c, const __bf16 *__restrict__ wpx, int co0, int t, int wc0, int wky, t_u32x4 (&wv)[6]) {
+    const size_t wplane = t_pack_elems(PN_PACK_TILE3_X3, c.Cout, c.Cin);
+    const __bf16 *wrow = wpx + ((size_t)(wc0 >> 5) * 9 + wky * 3) * c.Cout * 32;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const TXPiece p = t_x3_piece(t, j);
+        const int ok = (int)(co0 + p.co < c.Cout);
+        const size_t off = ((size_t)p.pl * wplane + ((size_t)p.kx * c.Cout + (size_t)((co0 + p.co) & -ok)) * 32 + p.seg * 8);
+        wv[j] = *reinterpret_cast<const t_u32x4 *>(wrow + off);       // (rows beyond Cout read row 0: zeroed when the piece is stored -- a select here would wait for the load)
+    }
+}
+// ... and from the registers into the slice [3 taps][64 couts][32 ch] of each plane: straight 16-byte copies
+template <class Rows>
+__device__ __forceinline__ void t_x3_store_w(const TConv &c, int co0, int t, const t_u32x4 (&wv)[6], unsigned char *As_hi, unsigned char *As_lo, Rows rows) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const TXPiece p = t_x3_piece(t, j);
+        *reinterpret_cast<t_u32x4 *>((p.pl ? As_lo : As_hi) + rows(p.kx * 64 + p.co, p.seg)) = co0 + p.co < c.Cout ? wv[j] : t_u32x4{0u, 0u, 0u, 0u};
+    }
+}
+// The weights are fetched one (chunk, kernel row) step AHEAD (round 5): the loads of the step after (c0, ky) are in flight under this step's MFMAs instead
+// of in front of them -- three of a chunk's five exposed memory round trips gone.  ONE call site, always taken (past the last step: the current slice again,
+// unused): two conditional sites merged the loaded registers through copies that waited for the loads right there.
+__device__ __forceinline__ void t_x3_next_w(const TConv &c, const __bf16 *__restrict__ wpx, int co0, int t, int c0, int ky, t_u32x4 (&wv)[6]) {
+    const int nc0 = ky == 2 ? c0 + 32 : c0, nky = ky == 2 ? 0 : ky + 1;
+    const bool more = nc0 < c.Cin;
+    t_x3_load_w(c, wpx, co0, t, more ? nc0 : c0, more ? nky : ky, wv);
+}
+// Halo staging role: a wave stages channels cbase = c0 + 8 wave .. + 7 (cmask: those below Cin) of halo pixels lane + 64 i.  Pixels i = I0 .. I1 - 1: all
+// loads first, then -- SYNC: behind the barrier after which the previous chunk's last kernel row has been consumed -- split + two 16-byte stores per pixel.
+template <int I0, int I1, bool SYNC, class Rows, int NH>
+__device__ __forceinline__ void t_x3_stage_halo(const float *__restrict__ xb, int HW, int nhalo, const int (&hoff)[NH], int cbase, unsigned cmask, int lane,
+                                                int wave, unsigned char *Hs_hi, unsigned char *Hs_lo, Rows rows) {
+    float hv[I1 - I0][8];
+#pragma unroll
+    for (int i = I0; i < I1; ++i) {
+        const int okp = (int)(hoff[i] >= 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) hv[i - I0][j] = xb[((cbase + j) * HW + hoff[i]) & -(okp & (int)((cmask >> j) & 1u))];
+    }
+    if (SYNC) __syncthreads();
+#pragma unroll
+    for (int i = I0; i < I1; ++i) {
+        const int e = lane + 64 * i;
+        if (e < nhalo) {
+            t_bf16x8 hi, lo;
+            t_split8(hv[i - I0], hoff[i] >= 0 ? cmask : 0u, hi, lo);
+            *reinterpret_cast<t_bf16x8 *>(Hs_hi + rows(e, wave)) = hi;
+            *reinterpret_cast<t_bf16x8 *>(Hs_lo + rows(e, wave)) = lo;
+        }
+    }
+}
+__device__ __forceinline__ unsigned t_x3_chan_mask(const TConv &c, int cbase) {
+    unsigned cmask = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cmask |= (unsigned)(cbase + j < c.Cin) << j;
+    return cmask;
 }
 
 __global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g, const __bf16 *__restrict__ wpx) {
@@ -469,31 +479,20 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g
     unsigned char *Hs_lo = Hs_hi + g.HR * g.HC * TX_PITCH;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
     T_DECODE_TILE_CB(b, cblk);
-    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y, img = b / (g.tiles_x * g.tiles_y);
-    const int y0 = ty * g.R, x0 = tx * g.TW, co0 = cblk * 64;
-    const int HW = c.H * c.W, HoWo = c.Ho * c.Wo, nhalo = g.HR * g.HC;
-    int hb[2], opix[2];
+    const TBlock k = t_tile_block(g, b, cblk);
+    const int co0 = k.co0, HW = c.H * c.W, nhalo = g.HR * g.HC;
+    const TXRows80 rows;
+    int hb[2], opix[2];                         // LDS byte offset of the slot's top-left tap (this lane's segment q), output pixel (or -1)
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-        const int sl = 32 * wave + 16 * n + r;
-        const int ry = sl / g.TW, rx = sl - ry * g.TW;
-        const bool ok = ry < g.R && y0 + ry < c.Ho && x0 + rx < c.Wo;
-        hb[n] = (ok ? ry * g.HC + rx : 0) * TX_PITCH + 16 * q;
-        opix[n] = ok ? (y0 + ry) * c.Wo + x0 + rx : -1;
+        t_tile_slot(c, g, k, 32 * wave + 16 * n + r, hb[n], opix[n]);
+        hb[n] = rows(hb[n], q);
     }
-    // halo staging role: this wave stages channels 8 wave .. 8 wave + 7 of halo pixels lane + 64 i
     constexpr int NH = 5;               // ceil(320 / 64): halo tiles have at most (2 + 2) x (64 + 2) = 264 pixels
     int hoff[NH];
 #pragma unroll
-    for (int i = 0; i < NH; ++i) {
-        const int e = lane + 64 * i;
-        const int hy = e / g.HC, hx = e - hy * g.HC;
-        const int iy = y0 - c.pad + hy, ix = x0 - c.pad + hx;
-        hoff[i] = (e < nhalo && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
-    }
-    const float *xb = c.x + (size_t)img * c.Cin * HW;
-    // weight staging role: per kernel row 3 taps x 64 couts x 4 segments of 8 channels x 2 planes = 1536 16-byte pieces, 6 per thread
-    const size_t wplane = (size_t)((c.Cin + 31) / 32) * 9 * c.Cout * 32;
+    for (int i = 0; i < NH; ++i) hoff[i] = t_halo_off(c, g, k, lane + 64 * i);
+    const float *xb = c.x + (size_t)k.img * c.Cin * HW;
 
     t_f32x4 acc[4][2];
 #pragma unroll
@@ -502,61 +501,16 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g
         for (int n = 0; n < 2; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
 
     t_u32x4 wv[6];                                     // the NEXT (chunk, kernel row) step's weight pieces of this thread
-    auto load_w = [&](int wc0, int wky) {
-        const __bf16 *wrow = wpx + ((size_t)(wc0 >> 5) * 9 + wky * 3) * c.Cout * 32;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int piece = t + 256 * j;                    // < 1536: plane, kx, cout, segment
-            const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
-            const int ok = (int)(co0 + co < c.Cout);
-            const size_t off = ((size_t)pl * wplane + ((size_t)kx * c.Cout + (size_t)((co0 + co) & -ok)) * 32 + seg * 8);
-            wv[j] = *reinterpret_cast<const t_u32x4 *>(wrow + off);       // (rows beyond Cout read row 0: zeroed when the piece is stored -- a select here would wait for the load)
-        }
-    };
-    load_w(0, 0);
+    t_x3_load_w(c, wpx, co0, t, 0, 0, wv);
 
     for (int c0 = 0; c0 < c.Cin; c0 += 32) {
         const int cbase = c0 + 8 * wave;
-        unsigned cmask = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) cmask |= (unsigned)(cbase + j < c.Cin) << j;
-        // ---- halo tile of 32 channels (all loads first, then split + 16-byte stores) ----
-        float hv[NH][8];
-#pragma unroll
-        for (int i = 0; i < NH; ++i) {
-            const int okp = (int)(hoff[i] >= 0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) hv[i][j] = xb[((cbase + j) * HW + hoff[i]) & -(okp & (int)((cmask >> j) & 1u))];
-        }
-        __syncthreads();                              // the previous chunk's last kernel row has been consumed
-#pragma unroll
-        for (int i = 0; i < NH; ++i) {
-            const int e = lane + 64 * i;
-            if (e < nhalo) {
-                t_bf16x8 hi, lo;
-                t_split8(hv[i], hoff[i] >= 0 ? cmask : 0u, hi, lo);
-                *reinterpret_cast<t_bf16x8 *>(Hs_hi + e * TX_PITCH + 16 * wave) = hi;
-                *reinterpret_cast<t_bf16x8 *>(Hs_lo + e * TX_PITCH + 16 * wave) = lo;
-            }
-        }
+        t_x3_stage_halo<0, NH, true>(xb, HW, nhalo, hoff, cbase, t_x3_chan_mask(c, cbase), lane, wave, Hs_hi, Hs_lo, rows);
         for (int ky = 0; ky < 3; ++ky) {
-            // ---- weight slice of kernel row ky: [3 taps][64 couts][32 ch], straight 16-byte copies of the packed planes; fetched one
-            // (chunk, kernel row) step AHEAD (round 5): the loads of the next step are in flight under this step's MFMAs instead of in
-            // front of them -- three of a chunk's five exposed memory round trips gone ----
             if (ky) __syncthreads();                  // the previous kernel row's fragments have been read
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int piece = t + 256 * j;
-                const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
-                *reinterpret_cast<t_u32x4 *>((pl ? As_lo : As_hi) + (kx * 64 + co) * TX_PITCH + 16 * seg) = co0 + co < c.Cout ? wv[j] : t_u32x4{0u, 0u, 0u, 0u};
-            }
+            t_x3_store_w(c, co0, t, wv, As_hi, As_lo, rows);
             __syncthreads();
-            {   // ONE call site, always taken (past the last step: the current slice again, unused): two conditional sites merged the loaded
-                // registers through copies that waited for the loads right here
-                const int nc0 = ky == 2 ? c0 + 32 : c0, nky = ky == 2 ? 0 : ky + 1;
-                const bool more = nc0 < c.Cin;
-                load_w(more ? nc0 : c0, more ? nky : ky);
-            }
+            t_x3_next_w(c, wpx, co0, t, c0, ky, wv);
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const int toff = (ky * g.HC + kx) * TX_PITCH;
@@ -568,65 +522,21 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3_kernel(TConv c, TTile g
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const int ao = (kx * 64 + 16 * m + r) * TX_PITCH + 16 * q;
+                    const int ao = rows(kx * 64 + 16 * m + r, q);
                     const t_bf16x8 ah = *reinterpret_cast<const t_bf16x8 *>(As_hi + ao);
                     const t_bf16x8 al = *reinterpret_cast<const t_bf16x8 *>(As_lo + ao);
 #pragma unroll
-                    for (int n = 0; n < 2; ++n) {
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
-                    }
+                    for (int n = 0; n < 2; ++n) t_mfma_x3(acc[m][n], ah, al, bh[n], bl[n]);
                 }
             }
         }
     }
-    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
-    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
-    float bv[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
-        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
-    }
-    T_PIN16(bv);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int pok = (int)(opix[n] >= 0);
-        float *yb = c.y + (size_t)img * c.Cout * HoWo + (opix[n] & -pok);
-        float old[16];
-        if (c.accumulate) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int co = co0 + 16 * m + 4 * q + i;
-                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
-                }
-            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int co = co0 + 16 * m + 4 * q + i;
-                float v = acc[m][n][i];
-                v += bv[4 * m + i];
-                if (c.accumulate) v += old[4 * m + i];
-                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
-            }
-    }
+    t_tile_epilogue<2>(c, k, q, acc, opix);
 }
 
 // Wide variant: 64 couts x 256 pixel slots per block, a wave owns 64 couts x 64 pixels (4 x 4 MFMA tiles): per tap 8 + 8 fragment
 // reads feed 48 MFMAs (the 128-slot kernel above: 8 + 4 for 24) and a block's packed weight slice -- the larger part of its
-// vector-memory bytes -- serves twice the pixels.  LDS images at a 64-byte pitch with the 16-byte segment XOR-swizzled by
-// (row >> 2) & 3: sixteen consecutive rows x one segment cover sixteen different 16-byte bank groups, for the staging stores and
-// for both operands' fragment reads, and two blocks still fit a CU (76 KB).
-#define TXW2_PITCH 64
-#define TXW2_A_BYTES (3 * 64 * TXW2_PITCH)
-__device__ __forceinline__ int t_swz(int row, int seg) { return row * TXW2_PITCH + 16 * (seg ^ ((row >> 2) & 3)); }
-
+// vector-memory bytes -- serves twice the pixels.  LDS images at TXRowsSwz's swizzled 64-byte pitch: two blocks still fit a CU (76 KB).
 __global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile g, const __bf16 *__restrict__ wpx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char t_smem8[];
     unsigned char *As_hi = t_smem8, *As_lo = t_smem8 + TXW2_A_BYTES;
@@ -634,29 +544,17 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile 
     unsigned char *Hs_lo = Hs_hi + g.HR * g.HC * TXW2_PITCH;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, r = lane & 15;
     T_DECODE_TILE_CB(b, cblk);
-    const int tx = b % g.tiles_x, ty = (b / g.tiles_x) % g.tiles_y, img = b / (g.tiles_x * g.tiles_y);
-    const int y0 = ty * g.R, x0 = tx * g.TW, co0 = cblk * 64;
-    const int HW = c.H * c.W, HoWo = c.Ho * c.Wo, nhalo = g.HR * g.HC;
+    const TBlock k = t_tile_block(g, b, cblk);
+    const int co0 = k.co0, HW = c.H * c.W, nhalo = g.HR * g.HC;
+    const TXRowsSwz rows;
     int hbp[4], opix[4];                        // halo pixel of the slot's top-left tap, output pixel (or -1)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int sl = 64 * wave + 16 * n + r;
-        const int ry = sl / g.TW, rx = sl - ry * g.TW;
-        const bool ok = ry < g.R && y0 + ry < c.Ho && x0 + rx < c.Wo;
-        hbp[n] = ok ? ry * g.HC + rx : 0;
-        opix[n] = ok ? (y0 + ry) * c.Wo + x0 + rx : -1;
-    }
+    for (int n = 0; n < 4; ++n) t_tile_slot(c, g, k, 64 * wave + 16 * n + r, hbp[n], opix[n]);
     constexpr int NH = 7;                       // halo tiles have at most 400 pixels (t_tile_geometry_x3w)
     int hoff[NH];
 #pragma unroll
-    for (int i = 0; i < NH; ++i) {
-        const int e = lane + 64 * i;
-        const int hy = e / g.HC, hx = e - hy * g.HC;
-        const int iy = y0 - c.pad + hy, ix = x0 - c.pad + hx;
-        hoff[i] = (e < nhalo && iy >= 0 && iy < c.H && ix >= 0 && ix < c.W) ? iy * c.W + ix : -1;
-    }
-    const float *xb = c.x + (size_t)img * c.Cin * HW;
-    const size_t wplane = (size_t)((c.Cin + 31) / 32) * 9 * c.Cout * 32;
+    for (int i = 0; i < NH; ++i) hoff[i] = t_halo_off(c, g, k, lane + 64 * i);
+    const float *xb = c.x + (size_t)k.img * c.Cin * HW;
 
     t_f32x4 acc[4][4];
 #pragma unroll
@@ -665,122 +563,41 @@ __global__ __launch_bounds__(256, 2) void tconv3_tile_x3w_kernel(TConv c, TTile 
         for (int n = 0; n < 4; ++n) acc[m][n] = t_f32x4{0.f, 0.f, 0.f, 0.f};
 
     t_u32x4 wv[6];                                     // the NEXT (chunk, kernel row) step's weight pieces of this thread
-    auto load_w = [&](int wc0, int wky) {
-        const __bf16 *wrow = wpx + ((size_t)(wc0 >> 5) * 9 + wky * 3) * c.Cout * 32;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int piece = t + 256 * j;
-            const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
-            const int ok = (int)(co0 + co < c.Cout);
-            const size_t off = ((size_t)pl * wplane + ((size_t)kx * c.Cout + (size_t)((co0 + co) & -ok)) * 32 + seg * 8);
-            wv[j] = *reinterpret_cast<const t_u32x4 *>(wrow + off);       // (rows beyond Cout read row 0: zeroed when the piece is stored -- a select here would wait for the load)
-        }
-    };
-    load_w(0, 0);
+    t_x3_load_w(c, wpx, co0, t, 0, 0, wv);
 
     for (int c0 = 0; c0 < c.Cin; c0 += 32) {
         const int cbase = c0 + 8 * wave;
-        unsigned cmask = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) cmask |= (unsigned)(cbase + j < c.Cin) << j;
+        const unsigned cmask = t_x3_chan_mask(c, cbase);
         // halo of 32 channels, in two halves of the pixel range (56 prefetch registers would not fit next to 64 accumulators)
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            constexpr int I0[2] = {0, 4}, I1[2] = {4, NH};
-            float hv[4][8];
-#pragma unroll
-            for (int i = I0[half]; i < I1[half]; ++i) {
-                const int okp = (int)(hoff[i] >= 0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    hv[i - I0[half]][j] = xb[((cbase + j) * HW + hoff[i]) & -(okp & (int)((cmask >> j) & 1u))];
-            }
-            if (half == 0) __syncthreads();       // the previous chunk's last kernel row has been consumed
-#pragma unroll
-            for (int i = I0[half]; i < I1[half]; ++i) {
-                const int e = lane + 64 * i;
-                if (e < nhalo) {
-                    t_bf16x8 hi, lo;
-                    t_split8(hv[i - I0[half]], hoff[i] >= 0 ? cmask : 0u, hi, lo);
-                    *reinterpret_cast<t_bf16x8 *>(Hs_hi + t_swz(e, wave)) = hi;
-                    *reinterpret_cast<t_bf16x8 *>(Hs_lo + t_swz(e, wave)) = lo;
-                }
-            }
-        }
+        t_x3_stage_halo<0, 4, true>(xb, HW, nhalo, hoff, cbase, cmask, lane, wave, Hs_hi, Hs_lo, rows);
+        t_x3_stage_halo<4, NH, false>(xb, HW, nhalo, hoff, cbase, cmask, lane, wave, Hs_hi, Hs_lo, rows);
 #pragma unroll 1
         for (int ky = 0; ky < 3; ++ky) {
             if (ky) __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int piece = t + 256 * j;
-                const int pl = piece / 768, rem = piece - pl * 768, kx = rem >> 8, co = (rem >> 2) & 63, seg = rem & 3;
-                *reinterpret_cast<t_u32x4 *>((pl ? As_lo : As_hi) + t_swz(kx * 64 + co, seg)) = co0 + co < c.Cout ? wv[j] : t_u32x4{0u, 0u, 0u, 0u};
-            }
+            t_x3_store_w(c, co0, t, wv, As_hi, As_lo, rows);
             __syncthreads();
-            {   // the next step's weights, in flight under this step's MFMAs (see tconv3_tile_x3_kernel)
-                const int nc0 = ky == 2 ? c0 + 32 : c0, nky = ky == 2 ? 0 : ky + 1;
-                const bool more = nc0 < c.Cin;
-                load_w(more ? nc0 : c0, more ? nky : ky);
-            }
+            t_x3_next_w(c, wpx, co0, t, c0, ky, wv);
 #pragma unroll 1
             for (int kx = 0; kx < 3; ++kx) {          // not unrolled: with three taps' fragments hoisted the kernel spills (124 B / lane)
                 t_bf16x8 bh[4], bl[4];
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
-                    const int o = t_swz(hbp[n] + ky * g.HC + kx, q);
+                    const int o = rows(hbp[n] + ky * g.HC + kx, q);
                     bh[n] = *reinterpret_cast<const t_bf16x8 *>(Hs_hi + o);
                     bl[n] = *reinterpret_cast<const t_bf16x8 *>(Hs_lo + o);
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const int ao = t_swz(kx * 64 + 16 * m + r, q);
+                    const int ao = rows(kx * 64 + 16 * m + r, q);
                     const t_bf16x8 ah = *reinterpret_cast<const t_bf16x8 *>(As_hi + ao);
                     const t_bf16x8 al = *reinterpret_cast<const t_bf16x8 *>(As_lo + ao);
 #pragma unroll
-                    for (int n = 0; n < 4; ++n) {
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[n], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[n], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[n], acc[m][n], 0, 0, 0);
-                    }
+                    for (int n = 0; n < 4; ++n) t_mfma_x3(acc[m][n], ah, al, bh[n], bl[n]);
                 }
             }
         }
     }
-    // bias of this lane's sixteen couts, gathered once (round 5: `v += c.bias[co]` inside the store loop compiled to load, s_waitcnt vmcnt(0), add --
-    // sixteen dependent round trips per pixel tile, as did the accumulate form's old values, which the compiler had sunk to their uses)
-    float bv[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int co = co0 + 16 * (k >> 2) + 4 * q + (k & 3);
-        bv[k] = c.bias ? c.bias[co < c.Cout ? co : 0] : 0.f;
-    }
-    T_PIN16(bv);
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int pok = (int)(opix[n] >= 0);
-        float *yb = c.y + (size_t)img * c.Cout * HoWo + (opix[n] & -pok);
-        float old[16];
-        if (c.accumulate) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int co = co0 + 16 * m + 4 * q + i;
-                    old[4 * m + i] = yb[(co * HoWo) & -(int)(co < c.Cout)];
-                }
-            T_PIN16(old);                               // all sixteen loads issued, THEN used (see T_PIN16)
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int co = co0 + 16 * m + 4 * q + i;
-                float v = acc[m][n][i];
-                v += bv[4 * m + i];
-                if (c.accumulate) v += old[4 * m + i];
-                if (pok && co < c.Cout) yb[(size_t)co * HoWo] = v;
-            }
-    }
+    t_tile_epilogue<4>(c, k, q, acc, opix);
 }
 
 // Weights for the data gradient: Wt[ci][(co, ky', kx')] = W[co][ci][KS-1-ky'][KS-1-kx']
@@ -874,7 +691,7 @@ __global__ __launch_bounds__(256) void tstem_fwd_kernel(TConv c, int tiles_x, in
 #pragma unroll
                 for (int j = 0; j < 4; ++j) *reinterpret_cast<t_f32x4 *>(o + 4 * j) = t_f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
             } else {
-                t_bf8 h[2], l[2];
+                t_bf16x8 h[2], l[2];
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
                     const __bf16 hi = (__bf16)v[j];
@@ -882,10 +699,10 @@ __global__ __launch_bounds__(256) void tstem_fwd_kernel(TConv c, int tiles_x, in
                     l[j >> 3][j & 7] = (__bf16)(v[j] - (float)hi);
                 }
                 __bf16 *o = (__bf16 *)c.pl + p * c.pl_cs + 16 * q;
-                *reinterpret_cast<t_bf8 *>(o) = h[0];
-                *reinterpret_cast<t_bf8 *>(o + 8) = h[1];
-                *reinterpret_cast<t_bf8 *>(o + c.pl_split) = l[0];
-                *reinterpret_cast<t_bf8 *>(o + c.pl_split + 8) = l[1];
+                *reinterpret_cast<t_bf16x8 *>(o) = h[0];
+                *reinterpret_cast<t_bf16x8 *>(o + 8) = h[1];
+                *reinterpret_cast<t_bf16x8 *>(o + c.pl_split) = l[0];
+                *reinterpret_cast<t_bf16x8 *>(o + c.pl_split + 8) = l[1];
             }
         }
     }

@@ -275,15 +275,11 @@ const char *pn_dgrad_strided_plan(int N, int Cin, int H, int W, int ks, unsigned
     return ks == 3 ? "dgrad_strided_kernel<3>" : "dgrad_strided_kernel<1>";
 }
 
-#define Y_CTX_CHECK                                                                                         \
-    if (!ctx) return PN_ERR_INVALID;                                                                        \
-    if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
-
 extern "C" {
 
 int pn_conv2d_dgrad_strided(pn_ctx *ctx, const float *dy_dev, const float *w_dev, float *dx_dev, int N, int Cin, int H, int W, int Cout, int ks, int stride,
                             int pad, int accumulate, void *hip_stream) {
-    Y_CTX_CHECK
+    PN_CTX_CHECK
     if (!dy_dev || !w_dev || !dx_dev || (ks != 1 && ks != 3) || stride < 1 || pad < 0 || pad > ks - 1 || N < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_conv2d_dgrad_strided: bad arguments (kernel 1 or 3, stride >= 1, 0 <= pad < kernel)");
     const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
@@ -308,7 +304,7 @@ static int y_pool_geom(int H, int W, int k, int stride, int pad, int *Ho, int *W
 }
 
 int pn_maxpool_forward(pn_ctx *ctx, const float *x_dev, float *y_dev, int *idx_dev, int planes, int H, int W, int k, int stride, int pad, void *hip_stream) {
-    Y_CTX_CHECK
+    PN_CTX_CHECK
     int Ho, Wo;
     if (!x_dev || !y_dev || !idx_dev || planes < 1 || !y_pool_geom(H, W, k, stride, pad, &Ho, &Wo))
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_maxpool_forward: bad arguments");
@@ -319,7 +315,7 @@ int pn_maxpool_forward(pn_ctx *ctx, const float *x_dev, float *y_dev, int *idx_d
 }
 
 int pn_maxpool_backward(pn_ctx *ctx, const float *dy_dev, const int *idx_dev, float *dx_dev, int planes, int H, int W, int k, int stride, int pad, void *hip_stream) {
-    Y_CTX_CHECK
+    PN_CTX_CHECK
     int Ho, Wo;
     if (!dy_dev || !idx_dev || !dx_dev || planes < 1 || !y_pool_geom(H, W, k, stride, pad, &Ho, &Wo))
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_maxpool_backward: bad arguments");
@@ -331,7 +327,7 @@ int pn_maxpool_backward(pn_ctx *ctx, const float *dy_dev, const int *idx_dev, fl
 
 int pn_yolo_loss(pn_ctx *ctx, const float *v_dev, const float *prior_map_dev, const float *mask_conf_dev, const float *mask_coord_dev, const float *weight_map_dev,
                  int N, int A, int J, int h, int w, float *out_dev, float *terms_dev, float *dv_dev, void *hip_stream) {
-    Y_CTX_CHECK
+    PN_CTX_CHECK
     if (!v_dev || !prior_map_dev || !mask_conf_dev || !mask_coord_dev || !out_dev || !terms_dev || !dv_dev || N < 1 || A < 1 || J < 1 || h < 1 || w < 1)
         return pn_set_error(ctx, PN_ERR_INVALID, "pn_yolo_loss: bad arguments");
     YoloLossArgs a;
@@ -366,7 +362,7 @@ void pn_yolo_target_cfg_default(pn_yolo_target_cfg *cfg) {
 int pn_build_prior_targets(pn_ctx *ctx, const double *boxes_dev, const float *kp2d_dev, const double *kp_z_dev, const double *pose_weight_dev,
                            const int *n_persons_dev, int B, int Pmax, const pn_yolo_target_cfg *cfg, float *prior_map_dev, float *mask_conf_dev,
                            float *mask_coord_dev, float *weight_map_dev, void *hip_stream) {
-    Y_CTX_CHECK
+    PN_CTX_CHECK
     if (!cfg || !n_persons_dev || !prior_map_dev || !mask_conf_dev || !mask_coord_dev || !weight_map_dev || B < 1 || Pmax < 0 ||
         (Pmax > 0 && (!boxes_dev || !kp2d_dev || !kp_z_dev || !pose_weight_dev)) || cfg->stride_prior < 1 || cfg->num_joints < 1 ||
         cfg->num_anchors < 1 || cfg->num_anchors > PN_YOLO_MAX_ANCHORS || cfg->input_x < cfg->stride_prior || cfg->input_y < cfg->stride_prior)
