@@ -7,7 +7,7 @@
 // bb64s_strip_kernel are pinned to what they were (profiles/bb64_shared_ab.txt).  The compute-wave prologue, the per-tile set-up, the intermediate
 // epilogue and the pixel-tile-outer last phases are still written out in both kernels: every way of sharing them that was tried changed those streams.
 #pragma once
-#include "conv3_kernel.h"
+#include "conv_common.h"
 
 
 // LDS images are QUARTER-major: [4 quarters of 16 channels][row][32 px][32 B].  A lane's 16-B B fragment (8 channels) is

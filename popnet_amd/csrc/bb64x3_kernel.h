@@ -24,7 +24,7 @@
 // Weight pack (net.hip::add_bblock): [conv 2][W_hi, W_lo][18 k-steps = (half, tap)][4 cout tiles][64 lanes][8 bf16], rows permuted with
 // pn_conv_row_channel(tile, row, 4) so that a lane's 16 accumulators are 16 consecutive channels.
 #pragma once
-#include "conv3_kernel.h"
+#include "conv_common.h"
 
 #define BX_ROWS 6
 #define BX_INQ (10 * 32 * 32)                 // one 16-channel quarter of one plane of the input image

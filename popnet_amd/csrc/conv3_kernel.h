@@ -1,7 +1,7 @@
 // bf16 3x3 / 1x1 stride-1 "same" convolution on the CDNA4 matrix cores, high-occupancy variant.
 //
-// Same math, weight packing and epilogue contract as conv_mfma_kernel.h (which stays the generic
-// kernel: fp32 parity mode, stride 2, odd shapes); this one is what the bf16 perf path runs for
+// Same math and weight packing as conv_mfma_kernel.h (which stays the generic kernel: fp32 parity
+// mode, stride 2, odd shapes), same block set-up and epilogues (conv_common.h); this one is what the bf16 perf path runs for
 // every stride-1 layer whose map splits into <= 30-column strips.  It replaces the same reference
 // code (tpm/lib/network/rtpose_light3d.py:24-72,222-246,335-350; yolo_posenet.py:101-126;
 // resnet.py:27-56).  What differs, and why (profiles/README.md, round-1 timeline stamps):
@@ -22,35 +22,17 @@
 //   * Weights: global -> VGPR fragments through a 3-slot queue (2 k-steps ahead is enough at 4
 //     waves per SIMD).
 #pragma once
-#include "conv_mfma_kernel.h"
+#include "conv_common.h"
 
 constexpr int PN_CONV3_OCC = 4;             // waves per SIMD of the 4-row kernels
 // (output tiles with the nt store hint, experiment v21: faster alone, slower in the network, where the next layer re-reads them; removed)
-constexpr int PN_CONV3_FAST_EPILOGUE = 2;   // wave-uniform fast epilogue: 0 never, 1 every instantiation, 2 the 128-cout blocks only (profiles/README.md v23)
 // (the piece-major and quarter-major LDS halo layouts of earlier rounds were measured and removed: profiles/README.md v16, profiles/r05_notes.txt)
-
-// LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS [lds_dst, lds_dst + 1024).
-// M0 is written in the same statement that uses it (the compiler does not preserve it around asm).
-__device__ __forceinline__ void pn_glds16(gcptr src, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-}
-
-// LDS-DMA, scalar base + 32-bit lane offset: no 64-bit address registers, the per-step pointer bump is scalar.
-template <int IMM>
-__device__ __forceinline__ void pn_glds16_s(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(IMM) : "memory");
-}
 
 // PT = pixel tiles of 16 per wave: 7 (112 pixels = 4 rows of a 28-column strip, 56 accumulator VGPRs, 4 waves / SIMD) or
 // 14 (224 pixels = 8 rows, 112 accumulator VGPRs, 2 waves / SIMD: half the weight bytes per MFMA, for Cin = 64 layers
 // on large maps, whose 224-pixel tiles otherwise stream their whole weight slice twice).
 // RPG = output rows per wave group kept in the halo image: 4 for 24..30-column strips (4 x 28 = 112 pixels), 8 for
 // narrow maps (8 x 14 = 112: the 14x14 layers of YoloPoseNet), 8 as well for PT = 14.
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;   // native vector: storable through address-space pointers
 
 // TAIL: the instantiation whose blocks run a second 1x1 convolution on their 128-channel output tile instead of storing it
 // (ConvProblem::tail_w; its own instantiation so that the plain kernel's register allocation is untouched: with both epilogues
@@ -75,12 +57,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     if ((int)blockIdx.x >= P.nblocks) return;
-    int bx;
-    {   // XCD-aware remap, see conv_mfma_kernel.h
-        const int nb = P.nblocks, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int qq = nb >> 3, rr = nb & 7;
-        bx = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-    }
+    const int bx = pn_xcd_block(blockIdx.x, P.nblocks);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,44 +65,31 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
     const int c = lane & 15, q = lane >> 4;
 
     const int cb = bx % P.cout_blocks;
-    const int tt = bx / P.cout_blocks;
-    const int tile = tt % P.tiles_per_img;
-    const int b = tt / P.tiles_per_img;
-    const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+    const int Wo = P.Wo;
+    PnTile tl = pn_tile_decode(bx / P.cout_blocks, P.tiles_per_img, P.tiles_x, P.R, P.Wt, P.Ho, Wo);
     // TAIL == 2 (fused average pool): the block computes the (2 * 3 + 1) x (2 * 7 + 1) patch of the 1x1 convolution's output that its 3 x 7
     // pooled pixels need, origin one row / column before the first window (rows and columns outside the map: zero-page input,
     // masked out of the window sums); neighbouring blocks recompute the shared row and column
-    const int oy0 = TAIL == 2 ? ty * 6 - 1 : ty * P.R, ox0 = TAIL == 2 ? tx * 14 - 1 : tx * P.Wt;
-    const int R = TAIL == 2 ? 7 : min(P.R, P.Ho - oy0);
-    const int Wo = P.Wo;
-    const int Wc = TAIL == 2 ? 15 : min(P.Wt, Wo - ox0);
-    const int npix = R * Wc;
+    if (TAIL == 2) tl.oy0 = tl.ty * 6 - 1, tl.ox0 = tl.tx * 14 - 1, tl.R = 7, tl.Wc = 15, tl.npix = 7 * 15, tl.inv_wc = 1.0f / 15.0f;
+    const int b = tl.b, ty = tl.ty, tx = tl.tx, oy0 = tl.oy0, ox0 = tl.ox0, Wc = tl.Wc, npix = tl.npix;
     const int HC = Wc + KS - 1;
     const int iy0 = oy0 - PAD, ix0 = ox0 - PAD;
-    const float inv_wc = 1.0f / (float)Wc;
+    const float inv_wc = tl.inv_wc;
     const int nchunks = P.cin_chunks;
     const int in_wrap = P.in_wrap;
 
     // ---- weight stream: scalar base per cout tile + lane offset; first NA-1 k-steps in flight ----
     const int ctile0 = (cb * WC + wc) * CT;
-    // buffer loads: one resource for the whole pack, scalar fragment offset, 32-bit lane offset -- no vector ALU
-    // work and no 64-bit address registers per k-step (the flat form cost 2 v_lshl_add_u64 + 6 VGPRs)
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(P.wpack), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = pn_weight_rsrc(P.wpack);
     unsigned wbase[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) wbase[ct] = (unsigned)__builtin_amdgcn_readfirstlane((ctile0 + ct) * P.ksteps * FRAGB);
+    pn_weight_bases<CT>(ctile0, P.ksteps, FRAGB, wbase);
     const unsigned wlane = (unsigned)lane * 16u;
     auto load_w = [&](unsigned soff) -> Frag {
         const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, soff, 0);
         return __builtin_bit_cast(Frag, r);
     };
     Frag aq[NA][CT];
-#pragma unroll
-    for (int d = 0; d < NA - 1; ++d)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) aq[d][ct] = load_w(wbase[ct] + d * FRAGB);
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) wbase[ct] += (NA - 1) * FRAGB;
+    pn_weight_prime<CT, NA>(FRAGB, wbase, aq, load_w);
 
     // ---- halo DMA: instruction n = wave * NGW + j fills rows (2i, 2i+1) of piece plane pc ----
     constexpr int NGW = (NG + NW - 1) / NW;
@@ -167,8 +131,8 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
     for (int pt = 0; pt < PT; ++pt) {
         int slot = (wp * PT + pt) * 16 + c;
         int s = slot < npix ? slot : 0;
-        int ry = (int)(((float)s + 0.5f) * inv_wc);
-        int rx = s - ry * Wc;
+        int ry, rx;
+        pn_slot_pixel(s, inv_wc, Wc, ry, rx);
         baddr[pt] = q * 16 + (ry * PITCH + rx) * 64;
     }
     f32x4 acc[CT][PT];
@@ -255,11 +219,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         constexpr int LC = CT * 4;
         const int cw = wc * (CT * 16) + LC * q;
         float bias[LC];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const f32x4 b4 = *reinterpret_cast<const PN_GLOBAL f32x4 *>((const PN_GLOBAL float *)P.bias + cw + 4 * ct);
-            bias[4 * ct + 0] = b4[0]; bias[4 * ct + 1] = b4[1]; bias[4 * ct + 2] = b4[2]; bias[4 * ct + 3] = b4[3];
-        }
+        pn_load_bias<LC>(P.bias, cw, bias);
         const int act = P.act;
         // bf16x3 (round 5): the convolution's value is parked as its two planes hi = bf16(v), lo = bf16(v - hi) -- what the unfused launch stores --
         // the lo tile PARK bytes behind the hi tile; the window sums add (float)hi + (float)lo per tap like pool_kernel<.., SPLIT> and the pooled
@@ -267,28 +227,7 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         constexpr int PARK = 4 * PT * 1024;
         const int tsplit = P.tail_split;
         __syncthreads();                                 // every wave is done reading the halo image: its space becomes the parked tile
-        auto park = [&](auto actc) {
-            constexpr int ACT = decltype(actc)::value;
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT; ++pt) {
-                T ov[LC], ol[LC];
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float v = acc[ct][pt][i] + bias[4 * ct + i];
-                        if (ACT == PN_ACT_RELU) v = v > 0.f ? v : 0.f;
-                        else if (ACT == PN_ACT_LEAKY) v = v > 0.f ? v : v * 0.1f;
-                        ov[4 * ct + i] = (T)v;
-                        ol[4 * ct + i] = (T)(v - (float)ov[4 * ct + i]);
-                    }
-                *reinterpret_cast<u32x4 *>(smem + ((wc * PT + pt) * 64 + lane) * 16) = *reinterpret_cast<u32x4 *>(ov);
-                if (tsplit) *reinterpret_cast<u32x4 *>(smem + PARK + ((wc * PT + pt) * 64 + lane) * 16) = *reinterpret_cast<u32x4 *>(ol);
-            }
-        };
-        if (act == PN_ACT_RELU) park(std::integral_constant<int, PN_ACT_RELU>{});
-        else if (act == PN_ACT_LEAKY) park(std::integral_constant<int, PN_ACT_LEAKY>{});
-        else park(std::integral_constant<int, PN_ACT_NONE>{});
+        pn_with_act<false>(act, [&](auto actc) { pn_park_tile<decltype(actc)::value, true, CT, PT>(acc, bias, smem, wc, lane, tsplit ? PARK : 0); });
         __syncthreads();
         const int Hp = (P.Ho - 1) / 2 + 1, Wp = (Wo - 1) / 2 + 1;          // pooled map
         PN_GLOBAL T *pout = (PN_GLOBAL T *)P.tail_out + P.tail_out_coff;
@@ -339,35 +278,12 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
             constexpr int LC = CT * 4;
             const int cw = wc * (CT * 16) + LC * q;
             float bias[LC];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                const f32x4 b4 = *reinterpret_cast<const PN_GLOBAL f32x4 *>((const PN_GLOBAL float *)P.bias + cw + 4 * ct);
-                bias[4 * ct + 0] = b4[0]; bias[4 * ct + 1] = b4[1]; bias[4 * ct + 2] = b4[2]; bias[4 * ct + 3] = b4[3];
-            }
+            pn_load_bias<LC>(P.bias, cw, bias);
             const int act = P.act;
             __syncthreads();                             // every wave is done reading the halo image: its space becomes the fragment image
             // (compile-time activation, as in the epilogues below: the run-time pn_activate switch, unrolled over 56 values, made this
             // instantiation 100 KB of code -- more than the instruction cache -- and the launch 10 us slower)
-            auto park = [&](auto actc) {
-                constexpr int ACT = decltype(actc)::value;
-#pragma clang loop unroll(full)
-                for (int pt = 0; pt < PT; ++pt) {
-                    T ov[LC];
-#pragma unroll
-                    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float v = acc[ct][pt][i] + bias[4 * ct + i];
-                            if (ACT == PN_ACT_RELU) v = v > 0.f ? v : 0.f;
-                            else if (ACT == PN_ACT_LEAKY) v = v > 0.f ? v : v * 0.1f;
-                            ov[4 * ct + i] = (T)v;
-                        }
-                    *reinterpret_cast<u32x4 *>(smem + ((wc * PT + pt) * 64 + lane) * 16) = *reinterpret_cast<u32x4 *>(ov);
-                }
-            };
-            if (act == PN_ACT_RELU) park(std::integral_constant<int, PN_ACT_RELU>{});
-            else if (act == PN_ACT_LEAKY) park(std::integral_constant<int, PN_ACT_LEAKY>{});
-            else park(std::integral_constant<int, PN_ACT_NONE>{});           // net.hip::fuse_1x1_tails admits these three only
+            pn_with_act<false>(act, [&](auto actc) { pn_park_tile<decltype(actc)::value, false, CT, PT>(acc, bias, smem, wc, lane, 0); });           // net.hip::fuse_1x1_tails admits RELU / LEAKY / NONE only
             __syncthreads();
             const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(P.tail_w), 0, 2 * 4 * 1024, 0x00020000);
             unsigned tlane = (unsigned)lane * 16u;
@@ -394,7 +310,8 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
                 }
                 const int slot = pt * 16 + c;
                 if (slot < npix) {
-                    const int ry = (int)(((float)slot + 0.5f) * inv_wc), rx = slot - ry * Wc;
+                    int ry, rx;
+                    pn_slot_pixel(slot, inv_wc, Wc, ry, rx);
                     const size_t opix = (size_t)(b * Ho + oy0 + ry) * Wo + ox0 + rx;
                     // a lane holds channels 8q .. 8q + 7 of its pixel: one 16-byte NHWC store (8 bytes when only the first four
                     // exist: 28 PAF channels); element-wise 2-byte stores into 384-byte pixel lines cost more than the whole tail
@@ -430,151 +347,41 @@ __device__ __forceinline__ void conv3_body(const ConvProblem &P) {
         }
     }
 
-    // ---- epilogue: identical contract to conv_mfma_kernel.h (permuted cout rows, direct stores) ----
+    // ---- epilogue (conv_common.h; permuted cout rows, direct stores) ----
     constexpr int LC = CT * 4;
-    const int cw = (cb * WC + wc) * (CT * 16) + LC * q;
+    const int wave_c0 = (cb * WC + wc) * (CT * 16);
+    const int cw = wave_c0 + LC * q;
     const int cout = P.cout, act = P.act;
     float bias[LC];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const f32x4 b4 = *reinterpret_cast<const PN_GLOBAL f32x4 *>((const PN_GLOBAL float *)P.bias + cw + 4 * ct);
-        bias[4 * ct + 0] = b4[0]; bias[4 * ct + 1] = b4[1]; bias[4 * ct + 2] = b4[2]; bias[4 * ct + 3] = b4[3];
-    }
-    const bool full = cw + LC <= cout;
-    const PN_GLOBAL T *res_base = P.res ? (const PN_GLOBAL T *)P.res + P.res_coff + cw : nullptr;
-    PN_GLOBAL T *out_base = P.out ? (PN_GLOBAL T *)P.out + P.out_coff + cw : nullptr;
+    pn_load_bias<LC>(P.bias, cw, bias);
     PN_GLOBAL float *nchw = (PN_GLOBAL float *)P.out_nchw;
     const int res_cs = P.res_cs, out_cs = P.out_cs, Ho = P.Ho, naf = P.yolo_naf;
     const int split = P.split, res_split = P.res_split;
     const int pix0 = (b * Ho + oy0) * Wo + ox0;
-    auto finish = [&](auto actc) {
-        constexpr int ACT = decltype(actc)::value;
-#pragma clang loop unroll(full)                          // a rolled loop would index acc[] dynamically = scratch memory
-        for (int pt = 0; pt < PT; ++pt) {
-            const int slot = (wp * PT + pt) * 16 + c;
-            if (slot >= npix || cw >= cout) continue;
-            const int ry = (int)(((float)slot + 0.5f) * inv_wc);
-            const int rx = slot - ry * Wc;
-            const int opix = pix0 + ry * Wo + rx;
-            float v[LC];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[4 * ct + i] = acc[ct][pt][i] + bias[4 * ct + i];
-            for (int pl = 0; pl < (res_base ? (res_split ? 2 : 1) : 0); ++pl) {      // bf16x3: residual = hi plane + lo plane
-                const PN_GLOBAL T *rp = res_base + (unsigned)(opix * res_cs + pl * res_split);
-                if (full) {
-                    T rv[LC];
-                    *reinterpret_cast<u32x4 *>(rv) = *reinterpret_cast<const PN_GLOBAL u32x4 *>(rp);
-#pragma unroll
-                    for (int k = 0; k < LC; ++k) v[k] += (float)rv[k];
-                } else {
-                    for (int k = 0; k < LC; ++k)
-                        if (cw + k < cout) v[k] += (float)rp[k];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < LC; ++k) {
-                if (ACT == PN_ACT_NONE) {}
-                else if (ACT == PN_ACT_RELU) v[k] = v[k] > 0.f ? v[k] : 0.f;
-                else if (ACT == PN_ACT_LEAKY) v[k] = v[k] > 0.f ? v[k] : v[k] * 0.1f;
-                else v[k] = pn_activate(v[k], act, cw + k, naf);
-            }
-            if (out_base) {
-                // bf16x3: two planes [hi | lo] `split` channels apart, hi = bf16(v), lo = bf16(v - hi)
-                for (int pl = 0; pl < (split ? 2 : 1); ++pl) {
-                    PN_GLOBAL T *op = out_base + (unsigned)(opix * out_cs + pl * split);
-                    T ov[LC];
-#pragma unroll
-                    for (int k = 0; k < LC; ++k) {
-                        const T hi = (T)v[k];
-                        ov[k] = pl == 1 ? (T)(v[k] - (float)hi) : hi;
-                    }
-                    if (full) {
-                        *reinterpret_cast<PN_GLOBAL u32x4 *>(op) = *reinterpret_cast<u32x4 *>(ov);
-                    } else {
-                        for (int k = 0; k < LC; ++k)
-                            if (cw + k < cout) op[k] = ov[k];
-                    }
-                }
-            }
-            if (nchw) {
-                const size_t hw = (size_t)Ho * Wo;
-                PN_GLOBAL float *np = nchw + ((size_t)b * cout + cw) * hw + (size_t)(oy0 + ry) * Wo + (ox0 + rx);
-                for (int k = 0; k < LC; ++k)
-                    if (cw + k < cout) np[(size_t)k * hw] = v[k];
-            }
-        }
-    };
-#define PN3_PIXOF(ba) ((unsigned)(ba) >> 6)
-    // Fast path, chosen per WAVE (every condition is wave-uniform, so no exec-mask branching): all 32 couts of the wave
-    // exist, NHWC output only, a compile-time activation.  The pixel of a slot is recovered from its LDS read address
-    // (baddr = q*16 + (ry*32 + rx)*64) instead of being divided out again; same arithmetic on the values as `finish`,
-    // so the results are bit-identical (tests: conv3 == generic kernel).
-    const int wave_c0 = (cb * WC + wc) * (CT * 16);
-    const bool fast = (PN_CONV3_FAST_EPILOGUE == 1 || (PN_CONV3_FAST_EPILOGUE == 2 && WC == 4)) &&
-                      wave_c0 + CT * 16 <= cout && P.out && !nchw && !split && !res_split && (act == PN_ACT_RELU || act == PN_ACT_LEAKY || act == PN_ACT_NONE);
-    auto finish_fast = [&](auto actc, auto resc) {
-        constexpr int ACT = decltype(actc)::value;
-        constexpr bool RES = decltype(resc)::value;
-        PN_GLOBAL T *ob = (PN_GLOBAL T *)P.out + P.out_coff + wave_c0;
-        const PN_GLOBAL T *rb = (const PN_GLOBAL T *)P.res + P.res_coff + wave_c0;
-        const unsigned lane_c = (unsigned)(LC * q);
-        int ba[PT];                                       // opaque copies: keep the pixel arithmetic HERE (hoisted above the K loop it only adds spills)
-#pragma clang loop unroll(full)
-        for (int pt = 0; pt < PT; ++pt) { ba[pt] = baddr[pt]; asm volatile("" : "+v"(ba[pt])); }
-        u32x4 rq[PT];
-        if (RES) {
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT; ++pt) {
-                const unsigned t = PN3_PIXOF(ba[pt]);
-                const unsigned opix = (unsigned)pix0 + (t >> 5) * (unsigned)Wo + (t & 31u);
-                rq[pt] = *reinterpret_cast<const PN_GLOBAL u32x4 *>(rb + (opix * (unsigned)res_cs + lane_c));
-            }
-        }
-#pragma clang loop unroll(full)
-        for (int pt = 0; pt < PT; ++pt) {
-            const int slot = (wp * PT + pt) * 16 + c;
-            const unsigned t = PN3_PIXOF(ba[pt]);
-            const unsigned opix = (unsigned)pix0 + (t >> 5) * (unsigned)Wo + (t & 31u);
-            float v[LC];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[4 * ct + i] = acc[ct][pt][i] + bias[4 * ct + i];
-            if (RES) {
-                T rv[LC];
-                *reinterpret_cast<u32x4 *>(rv) = rq[pt];
-#pragma unroll
-                for (int k = 0; k < LC; ++k) v[k] += (float)rv[k];
-            }
-#pragma unroll
-            for (int k = 0; k < LC; ++k) {
-                if (ACT == PN_ACT_RELU) v[k] = v[k] > 0.f ? v[k] : 0.f;
-                else if (ACT == PN_ACT_LEAKY) v[k] = v[k] > 0.f ? v[k] : v[k] * 0.1f;
-            }
-            T ov[LC];
-#pragma unroll
-            for (int k = 0; k < LC; ++k) ov[k] = (T)v[k];
-            if (slot < npix) *reinterpret_cast<PN_GLOBAL u32x4 *>(ob + (opix * (unsigned)out_cs + lane_c)) = *reinterpret_cast<u32x4 *>(ov);
-        }
-    };
+    // Fast path of the 128-cout blocks (WC == 4; on the narrower blocks it measured slower: profiles/README.md v23), chosen per wave: all 32 couts
+    // of the wave exist, NHWC output only, no split planes, a compile-time activation.  baddr = q*16 + (ry*32 + rx)*64.
+    const bool fast = WC == 4 && wave_c0 + CT * 16 <= cout && P.out && !nchw && !split && !res_split &&
+                      (act == PN_ACT_RELU || act == PN_ACT_LEAKY || act == PN_ACT_NONE);
     if (fast) {
-        if (P.res) {
-            if (act == PN_ACT_RELU) finish_fast(std::integral_constant<int, PN_ACT_RELU>{}, std::true_type{});
-            else if (act == PN_ACT_LEAKY) finish_fast(std::integral_constant<int, PN_ACT_LEAKY>{}, std::true_type{});
-            else finish_fast(std::integral_constant<int, PN_ACT_NONE>{}, std::true_type{});
-        } else {
-            if (act == PN_ACT_RELU) finish_fast(std::integral_constant<int, PN_ACT_RELU>{}, std::false_type{});
-            else if (act == PN_ACT_LEAKY) finish_fast(std::integral_constant<int, PN_ACT_LEAKY>{}, std::false_type{});
-            else finish_fast(std::integral_constant<int, PN_ACT_NONE>{}, std::false_type{});
-        }
+        pn_with_act<false>(act, P.res != nullptr, [&](auto actc, auto resc) {
+            int ba[PT];                                       // opaque copies: keep the pixel arithmetic HERE (hoisted above the K loop it only adds spills)
+#pragma clang loop unroll(full)
+            for (int pt = 0; pt < PT; ++pt) { ba[pt] = baddr[pt]; asm volatile("" : "+v"(ba[pt])); }
+            pn_conv_epilogue_fast<decltype(actc)::value, decltype(resc)::value, true, T, CT, PT>(
+                acc, bias, ba, [](int a) { return (unsigned)a >> 6; }, wp * PT * 16 + c, npix, (unsigned)pix0, (unsigned)Wo,
+                (PN_GLOBAL T *)P.out + P.out_coff + wave_c0, (const PN_GLOBAL T *)P.res + P.res_coff + wave_c0, (unsigned)(LC * q),
+                (unsigned)res_cs, 0, (unsigned)out_cs, 0, act, cw, naf);
+        });
         return;
     }
-    if (act == PN_ACT_RELU) finish(std::integral_constant<int, PN_ACT_RELU>{});
-    else if (act == PN_ACT_LEAKY) finish(std::integral_constant<int, PN_ACT_LEAKY>{});
-    else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{});
-    else finish(std::integral_constant<int, -1>{});
+    const PN_GLOBAL T *res_base = P.res ? (const PN_GLOBAL T *)P.res + P.res_coff + cw : nullptr;
+    PN_GLOBAL T *out_base = P.out ? (PN_GLOBAL T *)P.out + P.out_coff + cw : nullptr;
+    int slot0 = wp * PT * 16 + c;
+    asm volatile("" : "+v"(slot0));                           // opaque, like ba[] above: merged with the K loop's address set-up the pixel arithmetic is live across the loop (spills)
+    pn_with_act<true>(act, [&](auto actc) {
+        pn_conv_epilogue<decltype(actc)::value, T, CT, PT>(acc, bias, slot0, npix, inv_wc, Wc, cw, cout, act, naf, res_base, res_cs, res_split,
+                                                           out_base, out_cs, split, nchw, b, Ho, Wo, oy0, ox0, pix0);
+    });
 }
 
 template <int KS, int WC, int WP, int NBUF, int PT, int RPG = PT * 4 / 7, int TAIL = 0>

@@ -1,6 +1,6 @@
 // bf16 3x3 stride-1 "same" convolution on the CDNA4 matrix cores, third generation: BOTH operands through LDS.
 //
-// Same math and epilogue contract as conv3_kernel.h / conv_mfma_kernel.h (it replaces the same reference code:
+// Same math as conv3_kernel.h / conv_mfma_kernel.h; block order, tile decode and epilogues are conv_common.h's (it replaces the same reference code:
 // tpm/lib/network/rtpose_light3d.py:24-72,222-246; yolo_posenet.py:101-126; resnet.py:27-56) for the layers that
 // dominate the conv time: 3x3, Cin >= 128, >= 64 couts, maps that split into <= 30-column strips.
 //
@@ -25,7 +25,7 @@
 // is 8 KB contiguous, each DMA instruction copies 1 KB of consecutive bytes.
 // k order: (32-channel half hh, tap) -- identical to conv3's (chunk, half, tap).
 #pragma once
-#include "conv3_kernel.h"
+#include "conv_common.h"
 
 #define PN4_ASLOT 8192                  // one k-step of weight fragments: 8 cout tiles x 1 KB
 constexpr int PN4_RING = 3;             // weight ring slots: the slot of a k-step is an immediate offset
@@ -43,12 +43,7 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     if (block_x >= P.nblocks) return;
-    int bx;
-    {   // XCD-aware remap, see conv_mfma_kernel.h
-        const int nb = P.nblocks, xcd = block_x & 7, idx = block_x >> 3;
-        const int qq = nb >> 3, rr = nb & 7;
-        bx = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-    }
+    const int bx = pn_xcd_block(block_x, P.nblocks);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -61,17 +56,12 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
     const int sid_raw = pair * 2 + wp;
     const bool strip_ok = sid_raw < nstrips;             // an odd strip count leaves the last block half empty
     const int sid = strip_ok ? sid_raw : nstrips - 1;
-    const int tile = sid % P.tiles_per_img;
-    const int b = sid / P.tiles_per_img;
-    const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-    const int oy0 = ty * P.R, ox0 = tx * P.Wt;
-    const int R = min(P.R, P.Ho - oy0);
     const int Wo = P.Wo;
-    const int Wc = min(P.Wt, Wo - ox0);
-    const int npix = R * Wc;
+    const PnTile tl = pn_tile_decode(sid, P.tiles_per_img, P.tiles_x, P.R, P.Wt, P.Ho, Wo);      // this wave's strip
+    const int b = tl.b, oy0 = tl.oy0, ox0 = tl.ox0, Wc = tl.Wc, npix = tl.npix;
     const int HC = Wc + KS - 1;
     const int iy0 = oy0 - 1, ix0 = ox0 - 1;
-    const float inv_wc = 1.0f / (float)Wc;
+    const float inv_wc = tl.inv_wc;
     const int nchunks = P.cin_chunks;
 
     // ---- weight ring: wave w fetches cout tiles 2w, 2w+1 of every k-step (2 x 1 KB of consecutive bytes) ----
@@ -120,8 +110,8 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
     for (int pt = 0; pt < PT; ++pt) {
         const int slot = pt * 16 + c;
         const int s = slot < npix ? slot : 0;
-        const int ry = (int)(((float)s + 0.5f) * inv_wc);
-        const int rx = s - ry * Wc;
+        int ry, rx;
+        pn_slot_pixel(s, inv_wc, Wc, ry, rx);
         baddr[pt] = PN4_ARING + wp * PN4_BSTRIP + (q >> 1) * PN4_BQUART + (q & 1) * 16 + (ry * PITCH + rx) * 32;
     }
     const int aaddr = wc * 4096 + lane * 16;
@@ -196,117 +186,35 @@ __device__ __forceinline__ void conv4_body(const ConvProblem &P, const int block
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the surplus prefetches must not land in LDS after this block has exited
     if (!active || !strip_ok) return;
 
-    // ---- epilogue: a lane holds 16 CONSECUTIVE couts of each of its pixels (net.hip packs the rows with
-    // pn_conv_row_channel(tile, row, 4)): bias + residual + activation + two 16-B NHWC stores per pixel tile; the four
+    // ---- epilogue (conv_common.h): a lane holds 16 CONSECUTIVE couts of each of its pixels (net.hip packs the rows with
+    // pn_conv_row_channel(tile, row, 4)): bias + residual + activation + two 16-B NHWC stores per pixel tile and plane; the four
     // lane quarters cover one whole 128-B line of the pixel ----
     constexpr int LC = CT * 4;
     const int wave_c0 = (cb * 2 + wc) * 64;
     const int cw = wave_c0 + LC * q;
-    const int cout = P.cout, act = P.act;
+    const int cout = P.cout, act = P.act, naf = P.yolo_naf;
     float bias[LC];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const f32x4 b4 = *reinterpret_cast<const PN_GLOBAL f32x4 *>((const PN_GLOBAL float *)P.bias + cw + 4 * ct);
-        bias[4 * ct + 0] = b4[0]; bias[4 * ct + 1] = b4[1]; bias[4 * ct + 2] = b4[2]; bias[4 * ct + 3] = b4[3];
-    }
+    pn_load_bias<LC>(P.bias, cw, bias);
     const int res_cs = P.res_cs, out_cs = P.out_cs, Ho = P.Ho;
     const int split = P.split, res_split = P.res_split;
-    const unsigned pix0 = (unsigned)((b * Ho + oy0) * Wo + ox0);
-    const bool full = wave_c0 + 64 <= cout && P.out && !P.out_nchw;
-    if (full) {
-        PN_GLOBAL T *ob = (PN_GLOBAL T *)P.out + P.out_coff + cw;
-        const PN_GLOBAL T *rb = P.res ? (const PN_GLOBAL T *)P.res + P.res_coff + cw : nullptr;
-        auto finish = [&](auto actc, auto resc) {
-            constexpr int ACT = decltype(actc)::value;
-            constexpr bool RES = decltype(resc)::value;
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT; ++pt) {
-                const int slot = pt * 16 + c;
-                const unsigned t = (unsigned)(baddr[pt] - PN4_ARING - wp * PN4_BSTRIP - (q >> 1) * PN4_BQUART) >> 5;     // ry * 32 + rx
-                const unsigned opix = PITCH == 32 ? pix0 + (t >> 5) * (unsigned)Wo + (t & 31u) : pix0 + (t / (unsigned)PITCH) * (unsigned)Wo + (t % (unsigned)PITCH);
-                float v[LC];
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[4 * ct + i] = acc[ct][pt][i] + bias[4 * ct + i];
-                if (RES) {
-                    for (int pl = 0; pl < (res_split ? 2 : 1); ++pl) {       // bf16x3: residual = hi plane + lo plane
-                        T rv[LC];
-                        const PN_GLOBAL u32x4 *rp = reinterpret_cast<const PN_GLOBAL u32x4 *>(rb + (opix * (unsigned)res_cs + (unsigned)(pl * res_split)));
-                        reinterpret_cast<u32x4 *>(rv)[0] = rp[0];
-                        reinterpret_cast<u32x4 *>(rv)[1] = rp[1];
-#pragma unroll
-                        for (int k = 0; k < LC; ++k) v[k] += (float)rv[k];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < LC; ++k) {
-                    if (ACT == PN_ACT_RELU) v[k] = v[k] > 0.f ? v[k] : 0.f;
-                    else if (ACT == PN_ACT_LEAKY) v[k] = v[k] > 0.f ? v[k] : v[k] * 0.1f;
-                    else if (ACT != PN_ACT_NONE) v[k] = pn_activate(v[k], act, cw + k, P.yolo_naf);
-                }
-                // bf16x3: two planes [hi | lo] `split` channels apart, hi = bf16(v), lo = bf16(v - hi)
-                for (int pl = 0; pl < (split ? 2 : 1); ++pl) {
-                    T ov[LC];
-#pragma unroll
-                    for (int k = 0; k < LC; ++k) {
-                        const T hi = (T)v[k];
-                        ov[k] = pl == 1 ? (T)(v[k] - (float)hi) : hi;
-                    }
-                    if (slot < npix) {
-                        PN_GLOBAL u32x4 *op = reinterpret_cast<PN_GLOBAL u32x4 *>(ob + (opix * (unsigned)out_cs + (unsigned)(pl * split)));
-                        op[0] = reinterpret_cast<u32x4 *>(ov)[0];
-                        op[1] = reinterpret_cast<u32x4 *>(ov)[1];
-                    }
-                }
-            }
-        };
-        if (P.res) {
-            if (act == PN_ACT_RELU) finish(std::integral_constant<int, PN_ACT_RELU>{}, std::true_type{});
-            else if (act == PN_ACT_LEAKY) finish(std::integral_constant<int, PN_ACT_LEAKY>{}, std::true_type{});
-            else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{}, std::true_type{});
-            else finish(std::integral_constant<int, -1>{}, std::true_type{});
-        } else {
-            if (act == PN_ACT_RELU) finish(std::integral_constant<int, PN_ACT_RELU>{}, std::false_type{});
-            else if (act == PN_ACT_LEAKY) finish(std::integral_constant<int, PN_ACT_LEAKY>{}, std::false_type{});
-            else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{}, std::false_type{});
-            else finish(std::integral_constant<int, -1>{}, std::false_type{});
-        }
+    const int pix0 = (b * Ho + oy0) * Wo + ox0;
+    if (wave_c0 + 64 <= cout && P.out && !P.out_nchw) {      // wave-uniform: the fast epilogue, pixel = (baddr - plane base) / 32 B
+        const int plane0 = PN4_ARING + wp * PN4_BSTRIP + (q >> 1) * PN4_BQUART;
+        pn_with_act<true>(act, P.res != nullptr, [&](auto actc, auto resc) {
+            pn_conv_epilogue_fast<decltype(actc)::value, decltype(resc)::value, false, T, CT, PT>(
+                acc, bias, baddr, [plane0](int a) { return (unsigned)(a - plane0) >> 5; }, c, npix, (unsigned)pix0, (unsigned)Wo,
+                (PN_GLOBAL T *)P.out + P.out_coff + wave_c0, (const PN_GLOBAL T *)P.res + P.res_coff + wave_c0, (unsigned)(LC * q),
+                (unsigned)res_cs, res_split, (unsigned)out_cs, split, act, cw, naf);
+        });
         return;
     }
-    // general path (ragged cout, NCHW f32 export): element-wise, same arithmetic
-    {
-        const PN_GLOBAL T *res_base = P.res ? (const PN_GLOBAL T *)P.res + P.res_coff + cw : nullptr;
-        PN_GLOBAL T *out_base = P.out ? (PN_GLOBAL T *)P.out + P.out_coff + cw : nullptr;
-        PN_GLOBAL float *nchw = (PN_GLOBAL float *)P.out_nchw;
-#pragma clang loop unroll(full)
-        for (int pt = 0; pt < PT; ++pt) {
-            const int slot = pt * 16 + c;
-            if (slot >= npix || cw >= cout) continue;
-            const int ry = (int)(((float)slot + 0.5f) * inv_wc);
-            const int rx = slot - ry * Wc;
-            const unsigned opix = pix0 + (unsigned)(ry * Wo + rx);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int k = 4 * ct + i;
-                    if (cw + k >= cout) continue;
-                    float v = acc[ct][pt][i] + bias[k];
-                    if (res_base) v += (float)res_base[opix * (unsigned)res_cs + k];
-                    if (res_base && res_split) v += (float)res_base[opix * (unsigned)res_cs + res_split + k];
-                    v = pn_activate(v, act, cw + k, P.yolo_naf);
-                    if (out_base) {
-                        const T hi = (T)v;
-                        out_base[opix * (unsigned)out_cs + k] = hi;
-                        if (split) {
-                            out_base[opix * (unsigned)out_cs + split + k] = (T)(v - (float)hi);
-                        }
-                    }
-                    if (nchw) nchw[((size_t)b * cout + cw + k) * ((size_t)Ho * Wo) + (size_t)(oy0 + ry) * Wo + (ox0 + rx)] = v;
-                }
-        }
-    }
+    // ragged cout, NCHW f32 export
+    const PN_GLOBAL T *res_base = P.res ? (const PN_GLOBAL T *)P.res + P.res_coff + cw : nullptr;
+    PN_GLOBAL T *out_base = P.out ? (PN_GLOBAL T *)P.out + P.out_coff + cw : nullptr;
+    pn_with_act<true>(act, [&](auto actc) {
+        pn_conv_epilogue<decltype(actc)::value, T, CT, PT>(acc, bias, c, npix, inv_wc, Wc, cw, cout, act, naf, res_base, res_cs, res_split, out_base,
+                                                           out_cs, split, (PN_GLOBAL float *)P.out_nchw, b, Ho, Wo, oy0, ox0, pix0);
+    });
 }
 
 __global__ __launch_bounds__(256, 2) void conv4_kernel(const ConvProblem *__restrict__ probs) {

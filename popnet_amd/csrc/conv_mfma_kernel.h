@@ -24,36 +24,8 @@
 //   * Epilogue fuses folded-BN bias, residual add, ReLU / LeakyReLU(0.1) / sigmoid casts, and
 //     can emit NHWC (next layer) and/or NCHW f32 (API boundary) in the same pass.
 #pragma once
-#include <type_traits>
-#include "pn_internal.h"
+#include "conv_common.h"
 #include "conv_inst_table.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-// Pointers read out of the ConvProblem record are "generic" to the compiler, which then emits flat_*
-// memory ops (they tick vmcnt AND lgkmcnt and can only be waited for with 0/0, serialising against
-// the LDS pipeline).  Everything that touches HBM goes through explicit global-address-space pointers.
-#define PN_GLOBAL __attribute__((address_space(1)))
-typedef const PN_GLOBAL char *gcptr;
-typedef PN_GLOBAL char *gptr;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // native vector: loadable through address-space pointers
-
-template <int PREC> struct Elem;
-template <> struct Elem<PN_PREC_BF16> {
-    typedef __bf16 T;
-    static constexpr int PIXB = 128;   // LDS bytes per halo pixel (64 channels)
-    static constexpr int FRAGB = 1024; // bytes of one packed A fragment (16 couts x 32 k)
-    static constexpr int SUBX = 64;    // address XOR selecting the second 32-channel half
-    struct Frag { bf16x8 v; };
-};
-template <> struct Elem<PN_PREC_F32> {
-    typedef float T;
-    static constexpr int PIXB = 256;
-    static constexpr int FRAGB = 2048;
-    static constexpr int SUBX = 128;
-    struct Frag { f32x4 lo, hi; };
-};
 
 template <int CFG> struct TileCfg;
 template <> struct TileCfg<PN_CFG_C128> { static constexpr int WC = 4, WP = 1, CT = 2, PT = 7; };
@@ -61,26 +33,6 @@ template <> struct TileCfg<PN_CFG_C64>  { static constexpr int WC = 2, WP = 2, C
 template <> struct TileCfg<PN_CFG_C32>  { static constexpr int WC = 1, WP = 4, CT = 2, PT = 2; };
 template <> struct TileCfg<PN_CFG_C16>  { static constexpr int WC = 1, WP = 4, CT = 1, PT = 2; };
 template <> struct TileCfg<PN_CFG_C64W> { static constexpr int WC = 2, WP = 2, CT = 2, PT = 7; };
-
-__device__ __forceinline__ float pn_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float pn_activate(float v, int act, int co, int naf) {
-    switch (act) {
-        case PN_ACT_RELU: return v > 0.f ? v : 0.f;
-        case PN_ACT_LEAKY: return v > 0.f ? v : v * 0.1f;
-        case PN_ACT_SIG_PM2: return (pn_sigmoid(v) - 0.5f) * 4.f;
-        case PN_ACT_SIG: return pn_sigmoid(v);
-        case PN_ACT_YOLO: {
-            int f = co % naf;
-            float s = pn_sigmoid(v);
-            if (f < 2) return (s - 0.5f) * 2.f;
-            if (f < 4) return s * 2.f;
-            if (f == 4) return s;
-            return (s - 0.5f) * 4.f;
-        }
-        default: return v;
-    }
-}
 
 template <int PREC> __device__ __forceinline__ typename Elem<PREC>::Frag load_a_frag(gcptr p);
 template <> __device__ __forceinline__ Elem<PN_PREC_BF16>::Frag load_a_frag<PN_PREC_BF16>(gcptr p) {
@@ -93,45 +45,6 @@ template <> __device__ __forceinline__ Elem<PN_PREC_F32>::Frag load_a_frag<PN_PR
     f.lo = *reinterpret_cast<const PN_GLOBAL f32x4 *>(p);
     f.hi = *reinterpret_cast<const PN_GLOBAL f32x4 *>(p + 1024);
     return f;
-}
-
-template <int PREC> __device__ __forceinline__ typename Elem<PREC>::Frag read_b_frag(const char *smem, int addr);
-template <> __device__ __forceinline__ Elem<PN_PREC_BF16>::Frag read_b_frag<PN_PREC_BF16>(const char *smem, int addr) {
-    Elem<PN_PREC_BF16>::Frag f;
-    f.v = *reinterpret_cast<const bf16x8 *>(smem + addr);
-    return f;
-}
-template <> __device__ __forceinline__ Elem<PN_PREC_F32>::Frag read_b_frag<PN_PREC_F32>(const char *smem, int addr) {
-    Elem<PN_PREC_F32>::Frag f;
-    f.lo = *reinterpret_cast<const f32x4 *>(smem + addr);
-    f.hi = *reinterpret_cast<const f32x4 *>(smem + addr + 16);
-    return f;
-}
-
-__device__ __forceinline__ f32x4 mma(const Elem<PN_PREC_BF16>::Frag &a, const Elem<PN_PREC_BF16>::Frag &b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mma(const Elem<PN_PREC_F32>::Frag &a, const Elem<PN_PREC_F32>::Frag &b, f32x4 c) {
-    // k-slot s of lane-quarter q is channel 8q+s for BOTH operands (any consistent k order is valid)
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo[0], b.lo[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo[1], b.lo[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo[2], b.lo[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.lo[3], b.lo[3], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.hi[0], b.hi[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.hi[1], b.hi[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.hi[2], b.hi[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.hi[3], b.hi[3], c, 0, 0, 0);
-    return c;
-}
-
-__device__ __forceinline__ void store4(PN_GLOBAL __bf16 *p, const float v[4]) {
-    bf16x4 o;
-    o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-    *reinterpret_cast<PN_GLOBAL bf16x4 *>(p) = o;
-}
-__device__ __forceinline__ void store4(PN_GLOBAL float *p, const float v[4]) {
-    f32x4 o = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<PN_GLOBAL f32x4 *>(p) = o;
 }
 
 // Register-prefetched halo staging: MAXST = 16-B pieces per thread needed to hold the largest halo
@@ -198,15 +111,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
 
     const ConvProblem &P = probs[blockIdx.y];
     if ((int)blockIdx.x >= P.nblocks) return;
-    // XCD-aware remap (speed only): hardware deals consecutive block ids round-robin over the 8
-    // XCDs; give each XCD a contiguous range of logical blocks so that blocks sharing an input
-    // halo / a weight slice hit the same L2.  Bijective for any nblocks.
-    int bx;
-    {
-        const int nb = P.nblocks, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int qq = nb >> 3, rr = nb & 7;
-        bx = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-    }
+    const int bx = pn_xcd_block(blockIdx.x, P.nblocks);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -215,19 +120,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     const int c = lane & 15, q = lane >> 4;
 
     const int cb = bx % P.cout_blocks;
-    const int tt = bx / P.cout_blocks;
-    const int tile = tt % P.tiles_per_img;
-    const int b = tt / P.tiles_per_img;
-    const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-    const int oy0 = ty * P.R, ox0 = tx * P.Wt;
-    const int R = min(P.R, P.Ho - oy0);
     const int Wo = P.Wo;
-    const int Wc = min(P.Wt, Wo - ox0);          // output columns of this tile
-    const int npix = R * Wc;
+    const PnTile tl = pn_tile_decode(bx / P.cout_blocks, P.tiles_per_img, P.tiles_x, P.R, P.Wt, P.Ho, Wo);
+    const int b = tl.b, oy0 = tl.oy0, ox0 = tl.ox0, R = tl.R, Wc = tl.Wc, npix = tl.npix;
     const int HRa = (R - 1) * STRIDE + KSD;      // halo rows actually needed
     const int HC = (Wc - 1) * STRIDE + KSD;      // halo columns
     const int iy0 = oy0 * STRIDE - PAD, ix0 = ox0 * STRIDE - PAD;
-    const float inv_wc = 1.0f / (float)Wc;
+    const float inv_wc = tl.inv_wc;
 
     // ---- per-lane LDS addresses of tap (ky=0,kx) for each pixel tile, current 32-channel half ----
     int baddr[PT][KS];
@@ -235,8 +134,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
     for (int pt = 0; pt < PT; ++pt) {
         int slot = (wp * PT + pt) * 16 + c;
         int s = slot < npix ? slot : 0;
-        int ry = (int)(((float)s + 0.5f) * inv_wc);
-        int rx = s - ry * Wc;
+        int ry, rx;
+        pn_slot_pixel(s, inv_wc, Wc, ry, rx);
         int hp0 = ry * STRIDE * PITCH + rx * STRIDE;
 #pragma unroll
         for (int kx = 0; kx < KS; ++kx) {
@@ -272,13 +171,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
 
     // weight stream: scalar base per cout tile + lane offset
     const int ctile0 = (cb * WC + wc) * CT;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(P.wpack), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = pn_weight_rsrc(P.wpack);
     unsigned wbase[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) wbase[ct] = (unsigned)__builtin_amdgcn_readfirstlane((ctile0 + ct) * P.ksteps * FRAGB);
+    pn_weight_bases<CT>(ctile0, P.ksteps, FRAGB, wbase);
     const unsigned wlane = (unsigned)lane * 16u;
     // bf16: buffer loads (fewer VGPRs); fp32 parity mode: the flat form measured 2 % faster (two loads per fragment)
-#define PN_LOAD_W(off) load_w(off)
     auto load_w = [&](unsigned off) {
         if constexpr (PREC == PN_PREC_F32) return load_a_frag2<PREC>((gcptr)P.wpack + off, wlane);
         else return load_a_frag_buf<PREC>(wrsrc, wlane, off);
@@ -350,12 +247,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
 
     char *buf0 = smem, *buf1 = P.lds_two ? smem + P.lds_buf_bytes : smem;
     Frag aq[NA][CT];
-#pragma unroll
-    for (int d = 0; d < NA - 1; ++d)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) aq[d][ct] = PN_LOAD_W(wbase[ct] + d * FRAGB);
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) wbase[ct] += (NA - 1) * FRAGB;
+    pn_weight_prime<CT, NA>(FRAGB, wbase, aq, load_w);
     if (MAXST > 0) { stage_load(0); stage_store(buf0); }
     else stage_direct(0, buf0);
     __syncthreads();
@@ -385,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
                 if (pt == 0) {
 #pragma unroll
                     for (int ct = 0; ct < CT; ++ct) {    // wpack ends with NA-1 spare fragments
-                        aq[(s + NA - 1) % NA][ct] = PN_LOAD_W(wbase[ct]);
+                        aq[(s + NA - 1) % NA][ct] = load_w(wbase[ct]);
                         wbase[ct] += FRAGB;
                     }
                 }
@@ -436,110 +328,22 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvProblem *__
         }
     }
 
-    // ---- epilogue ------------------------------------------------------------------------------
-    // The MFMA C layout gives a lane 4 consecutive rows (couts) of one pixel per accumulator.  The
-    // packed weight rows are permuted on the host (net.hip::prepare_conv, pn_conv_row_channel) so
-    // that the CT accumulators of a lane together are LC = 4*CT CONSECUTIVE output channels: each
-    // lane adds the folded bias, the residual (one 16-B load), applies the activation and writes
-    // one 16-B (bf16, CT = 2) NHWC piece per pixel tile straight from registers -- no LDS transpose,
-    // no barrier; the four lane quarters of a wave cover 64 contiguous bytes of a pixel's line.
-    constexpr int BC = WC * CT * 16;
+    // ---- epilogue (conv_common.h) ----------------------------------------------------------------
     constexpr int LC = CT * 4;
     const int cw = (cb * WC + wc) * (CT * 16) + LC * q;          // first output channel of this lane
     const int cout = P.cout, act = P.act;
     float bias[LC];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const f32x4 b4 = *reinterpret_cast<const PN_GLOBAL f32x4 *>((const PN_GLOBAL float *)P.bias + cw + 4 * ct);
-        bias[4 * ct + 0] = b4[0]; bias[4 * ct + 1] = b4[1]; bias[4 * ct + 2] = b4[2]; bias[4 * ct + 3] = b4[3];
-    }
-    (void)BC;
-    const bool full = cw + LC <= cout;
+    pn_load_bias<LC>(P.bias, cw, bias);
     const PN_GLOBAL T *res_base = P.res ? (const PN_GLOBAL T *)P.res + P.res_coff + cw : nullptr;
     PN_GLOBAL T *out_base = P.out ? (PN_GLOBAL T *)P.out + P.out_coff + cw : nullptr;
     PN_GLOBAL float *nchw = (PN_GLOBAL float *)P.out_nchw;
     const int res_cs = P.res_cs, out_cs = P.out_cs, Ho = P.Ho, naf = P.yolo_naf;
     const int split = P.split, res_split = P.res_split;
     const int pix0 = (b * Ho + oy0) * Wo + ox0;
-    auto finish = [&](auto actc) {
-        constexpr int ACT = decltype(actc)::value;            // -1: dispatch at run time (sigmoid casts: last layers only)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt) {
-            const int slot = (wp * PT + pt) * 16 + c;
-            if (slot >= npix || cw >= cout) continue;
-            const int ry = (int)(((float)slot + 0.5f) * inv_wc);
-            const int rx = slot - ry * Wc;
-            const int opix = pix0 + ry * Wo + rx;
-            float v[LC];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[4 * ct + i] = acc[ct][pt][i] + bias[4 * ct + i];
-            for (int pl = 0; pl < (res_base ? (res_split ? 2 : 1) : 0); ++pl) {      // bf16x3: residual = hi plane + lo plane
-                const PN_GLOBAL T *rp = res_base + (unsigned)(opix * res_cs + pl * res_split);
-                if (full) {
-                    T rv[LC];
-                    if (LC * sizeof(T) == 16) {
-                        *reinterpret_cast<u32x4 *>(rv) = *reinterpret_cast<const PN_GLOBAL u32x4 *>(rp);
-                    } else if (LC * sizeof(T) == 32) {
-                        reinterpret_cast<u32x4 *>(rv)[0] = reinterpret_cast<const PN_GLOBAL u32x4 *>(rp)[0];
-                        reinterpret_cast<u32x4 *>(rv)[1] = reinterpret_cast<const PN_GLOBAL u32x4 *>(rp)[1];
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < LC; ++k) rv[k] = rp[k];
-                    }
-#pragma unroll
-                    for (int k = 0; k < LC; ++k) v[k] += (float)rv[k];
-                } else {
-                    for (int k = 0; k < LC; ++k)
-                        if (cw + k < cout) v[k] += (float)rp[k];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < LC; ++k) {
-                if (ACT == PN_ACT_NONE) {}
-                else if (ACT == PN_ACT_RELU) v[k] = v[k] > 0.f ? v[k] : 0.f;
-                else if (ACT == PN_ACT_LEAKY) v[k] = v[k] > 0.f ? v[k] : v[k] * 0.1f;
-                else v[k] = pn_activate(v[k], act, cw + k, naf);
-            }
-            if (out_base) {
-                // bf16x3: two planes [hi | lo] `split` channels apart, hi = bf16(v), lo = bf16(v - hi)
-                for (int pl = 0; pl < (split ? 2 : 1); ++pl) {
-                    PN_GLOBAL T *op = out_base + (unsigned)(opix * out_cs + pl * split);
-                    T ov[LC];
-#pragma unroll
-                    for (int k = 0; k < LC; ++k) {
-                        const T hi = (T)v[k];
-                        ov[k] = pl == 1 ? (T)(v[k] - (float)hi) : hi;
-                    }
-                    if (full) {
-                        if (LC * sizeof(T) == 16) {
-                            *reinterpret_cast<PN_GLOBAL u32x4 *>(op) = *reinterpret_cast<u32x4 *>(ov);
-                        } else if (LC * sizeof(T) == 32) {
-                            reinterpret_cast<PN_GLOBAL u32x4 *>(op)[0] = reinterpret_cast<u32x4 *>(ov)[0];
-                            reinterpret_cast<PN_GLOBAL u32x4 *>(op)[1] = reinterpret_cast<u32x4 *>(ov)[1];
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < LC; ++k) op[k] = ov[k];
-                        }
-                    } else {
-                        for (int k = 0; k < LC; ++k)
-                            if (cw + k < cout) op[k] = ov[k];
-                    }
-                }
-            }
-            if (nchw) {                                       // API-boundary layout: 16 lanes = 16 consecutive pixels of a plane
-                const size_t hw = (size_t)Ho * Wo;
-                PN_GLOBAL float *np = nchw + ((size_t)b * cout + cw) * hw + (size_t)(oy0 + ry) * Wo + (ox0 + rx);
-                for (int k = 0; k < LC; ++k)
-                    if (cw + k < cout) np[(size_t)k * hw] = v[k];
-            }
-        }
-    };
-    if (act == PN_ACT_RELU) finish(std::integral_constant<int, PN_ACT_RELU>{});
-    else if (act == PN_ACT_LEAKY) finish(std::integral_constant<int, PN_ACT_LEAKY>{});
-    else if (act == PN_ACT_NONE) finish(std::integral_constant<int, PN_ACT_NONE>{});
-    else finish(std::integral_constant<int, -1>{});
+    pn_with_act<true>(act, [&](auto actc) {                   // -1: dispatch at run time (sigmoid casts: last layers only)
+        pn_conv_epilogue<decltype(actc)::value, T, CT, PT>(acc, bias, wp * PT * 16 + c, npix, inv_wc, Wc, cw, cout, act, naf, res_base, res_cs, res_split,
+                                                           out_base, out_cs, split, nchw, b, Ho, Wo, oy0, ox0, pix0);
+    });
 }
 
 

@@ -4,7 +4,7 @@
 // every weight pack -- per kind one element-count function and one element function, called by the per-call pack kernels, by
 // pn_train_pack_refresh's wpack_all_kernel and by every launch that sizes a pack.
 #pragma once
-#include "pn_internal.h"
+#include "conv_common.h"      // pn_xcd_block: the one copy of the remap
 
 typedef float t_f32x4 __attribute__((ext_vector_type(4)));
 typedef float t_f32x2 __attribute__((ext_vector_type(2)));
@@ -18,15 +18,14 @@ typedef unsigned t_u32x4 __attribute__((ext_vector_type(4)));
 // that read the SAME operand tile -- the cout blocks of one input tile in the forward / data-gradient kernels, the (ci, cout) blocks of
 // one pixel slice in the weight gradient -- sat on different XCDs or ran a whole grid apart in time: every operand tile crossed the
 // fabric once per sharer (a 256 -> 256 weight gradient staged 444 MB for 51 MB of tensors).  t_logical_block() maps the hardware id to
-// a LOGICAL id such that each XCD owns one contiguous range of logical ids (a bijection, the conv kernels' remap of net.hip); the
+// a LOGICAL id such that each XCD owns one contiguous range of logical ids (a bijection: pn_xcd_block, the inference kernels' remap); the
 // kernels decode the logical id with the sharing dimension fastest, so sharers run at the same time behind the same L2.  Which block
 // computes which tile changes, nothing else: results are bit-identical.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int t_logical_block() {
     const int nb = (int)(gridDim.x * gridDim.y * gridDim.z);
     const int L = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-    const int xcd = L & 7, idx = L >> 3, qq = nb >> 3, rr = nb & 7;
-    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+    return pn_xcd_block(L, nb);
 }
 // forward-type grids (tiles, cout blocks): the cout blocks of a tile are neighbours in logical order
 #define T_DECODE_TILE_CB(tile, cb) const int _lg = t_logical_block(), cb = _lg % (int)gridDim.y, tile = _lg / (int)gridDim.y

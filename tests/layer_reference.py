@@ -9,7 +9,7 @@ result by far more than the allowance.  How the kernels define their operands (r
   the K loop reads [x_hi | x_lo | x_hi] against [W_hi | W_hi | W_lo]: x_hi W_hi + x_lo W_hi + x_hi W_lo, with NO
   x_lo W_lo term.  fp32 packs w_f.  The bias is float32((b - mean) * s + beta) (b = 0 without a conv bias); a conv
   without BatchNorm uses float32(b).
-* Epilogue (conv_mfma_kernel.h / conv3_kernel.h / conv4_kernel.h / bb64*_kernel.h): acc + bias, then + residual
+* Epilogue (conv_common.h for conv_mfma_kernel / conv3_kernel / conv4_kernel; bb64*_kernel.h): acc + bias, then + residual
   (bf16x3: + hi, then + lo), then the activation: ReLU, LeakyReLU v * 0.1f (the float32 constant), sigmoid
   1 / (1 + expf(-v)) and its casts (rtpose heads: (s - 0.5) * 4 and s; YOLO head: by channel within an anchor of
   5 + 3J channels, (s - 0.5) * 2, s * 2, s, (s - 0.5) * 4).  Then the store: bf16 RNE, or the two planes
