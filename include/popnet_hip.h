@@ -135,7 +135,11 @@ int pn_net_read_activation(pn_net *net, const char *name, int B, float *host_out
  * how the Python module materialises forward()'s `saved_for_loss` stage-1 entries
  * (tpm/lib/network/rtpose_light3d.py:340-342).                                                   */
 int pn_net_copy_activation(pn_net *net, const char *name, int B, float *dev_out, void *hip_stream);
-/* Test/diagnostic (per-layer checks).  Every activation buffer is also readable by number through
+/* Test/diagnostic, read-only: copies the 2048 bytes that follow activation buffer `buf` (the zero page the kernels' halo padding
+ * reads; zero-filled once by pn_net_finalize and never written) to host_out.  Synchronises on the null stream.  PN_ERR_INVALID for a
+ * buffer index outside the net's buffers or cap < 2048.                                                                            */
+int pn_net_read_zero_page(pn_net *net, int buf, void *host_out, size_t cap);
+/* Test/diagnostic (per-layer checks). Every activation buffer is also readable by number through
  * pn_net_read_activation / pn_net_copy_activation as "buf<i>" (all channels, f32 NCHW; a bf16x3 buffer
  * reads as hi + lo) and, in a bf16x3 net, "buf<i>.hi" / "buf<i>.lo" (one stored plane).
  * pn_net_forward_partial runs steps [0, nsteps) of the compiled step list and stops: the same forward,

@@ -131,6 +131,7 @@ _SIGNATURES = {
     "pn_yolo_forward_frames": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "pn_net_read_activation": (_i, [_vp, C.c_char_p, _i, _vp, _sz, _vp]),
     "pn_net_copy_activation": (_i, [_vp, C.c_char_p, _i, _vp, _vp]),
+    "pn_net_read_zero_page": (_i, [_vp, _i, _vp, _sz]),
     "pn_net_forward_partial": (_i, [_vp, _vp, _i, _i, _vp]),
     "pn_net_forward_frames_partial": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _vp]),
     "pn_net_num_steps": (_i, [_vp]),

@@ -218,6 +218,18 @@ int pn_net_read_activation(pn_net *n, const char *name, int B, float *host_out, 
     return rc;
 }
 
+int pn_net_read_zero_page(pn_net *n, int buf, void *host_out, size_t cap) {
+    if (!n || !host_out) return PN_ERR_INVALID;
+    pn_ctx *ctx = n->ctx;
+    if (ctx->device < 0) return pn_set_error(ctx, PN_ERR_STATE, "context has no device");
+    if (!n->finalized) return pn_set_error(ctx, PN_ERR_STATE, "net not finalized");
+    if (buf < 0 || buf >= (int)n->bufs.size()) return pn_set_error(ctx, PN_ERR_INVALID, "buffer %d outside [0, %zu)", buf, n->bufs.size());
+    if (cap < 2048) return pn_set_error(ctx, PN_ERR_INVALID, "host buffer too small: %zu < 2048", cap);
+    const Buf &b = n->bufs[buf];
+    PN_HIP_CHECK(ctx, hipMemcpy(host_out, (const char *)b.p + b.bytes, 2048, hipMemcpyDeviceToHost));      // the null stream: after every earlier launch of a blocking stream
+    return PN_OK;
+}
+
 int pn_net_forward_partial(pn_net *n, const float *x_dev, int B, int nsteps, void *hip_stream) {
     if (!n) return PN_ERR_INVALID;
     if (!x_dev) return pn_set_error(n->ctx, PN_ERR_INVALID, "null device pointer");

@@ -215,3 +215,22 @@ def vs_oracle(recs, refs):
             dc.append(float(np.abs(r["part_conf"][:n] - np.array(ref["conf"]))[vis].max()) if vis.any() else 0.0)
     return {"frames": len(refs), "same_assignment": same, "differing": differing, "fragile": sum(bool(f["fragile"]) for f in refs),
             "differing_all_fragile": all(refs[i]["fragile"] for i in differing), "d3_m_max": max(d3), "conf_max": max(dc)}
+
+
+G = 64          # sentinel floats in front of and behind every output
+SENT = 12345.0
+
+
+class _Out:
+    """An output tensor inside a larger sentinel-filled buffer."""
+    def __init__(self, shape, gpu, fill):
+        n = int(np.prod(shape))
+        self.buf = torch.full((n + 2 * G,), SENT, device=gpu)
+        self.t = self.buf[G:G + n].view(shape)
+        if isinstance(fill, torch.Tensor):
+            self.t.copy_(fill)
+        else:
+            self.t.fill_(fill)
+
+    def guards_intact(self):
+        return bool((self.buf[:G] == SENT).all()) and bool((self.buf[-G:] == SENT).all())

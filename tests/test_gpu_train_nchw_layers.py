@@ -28,7 +28,7 @@ import torch
 
 import nchw_layer_reference as NR
 import yolo_reference as yr
-from helpers import state_dict_from_keys, train_case_inputs
+from helpers import G, SENT, _Out, state_dict_from_keys, train_case_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -377,25 +377,6 @@ def test_every_launch_of_the_nchw_step_within_fp64_allowance(gpu, golden, cfg):
 
 
 # ---- (b) the primitive table ----------------------------------------------------------------------------------------------------
-G = 64          # sentinel floats in front of and behind every output
-SENT = 12345.0
-
-
-class _Out:
-    """An output tensor inside a larger sentinel-filled buffer."""
-    def __init__(self, shape, gpu, fill):
-        n = int(np.prod(shape))
-        self.buf = torch.full((n + 2 * G,), SENT, device=gpu)
-        self.t = self.buf[G:G + n].view(shape)
-        if isinstance(fill, torch.Tensor):
-            self.t.copy_(fill)
-        else:
-            self.t.fill_(fill)
-
-    def guards_intact(self):
-        return bool((self.buf[:G] == SENT).all()) and bool((self.buf[-G:] == SENT).all())
-
-
 # N, Cin, H, W, Cout, ks, stride, pad | env | expected labels: fp32 (forward, dgrad, wgrad), bf16x3 (forward, dgrad, wgrad) | ops
 T, X, XW, WT, W3, WPP, WV = ("tconv3_tile_kernel", "tconv3_tile_x3_kernel", "tconv3_tile_x3w_kernel", "tconv3_wgrad_tile_kernel", "tconv3_wgrad_x3_kernel",
                             "tconv3_wgrad_x3pp_kernel", "tconv3_wgrad_x3v_kernel")
