@@ -40,8 +40,58 @@
 #define BX_KS 54                              // k-steps per convolution: 3 plane pairs x 2 halves x 9 taps
 #define BX_KBAR asm volatile("s_barrier" ::: "memory")
 
+// the hi / lo split of a value: hi = bf16(v), lo = bf16(v - hi)
+__device__ __forceinline__ void bx_split(float v, __bf16 &hi, __bf16 &lo) {
+    hi = (__bf16)v;
+    lo = (__bf16)(v - (float)hi);
+}
+
+// ---------------- the MFMA loop of one convolution: 54 k-steps (plane pair, 32-channel half, tap), PT pixel tiles per wave, B fragments at ba[] in an
+// image of PLANE bytes per quarter and PITCH pixels per row ----------------
+// Zeroes the accumulators; the B-fragment queue runs BQ - 1 items ahead of the MFMAs.  aq[0] holds k-step 0's weight fragments (read in the prologue /
+// prefetched by the convolution before); slot = the ring slot of the NEXT k-step's fragments, advanced here.
+template <int PT, int PLANE, int PITCH, int CT, int APT, int BQ>
+__device__ __forceinline__ void bx_kloop(char *smem, int aaddr, int &slot, const int (&ba)[PT], f32x4 (&acc)[CT][APT], bf16x8 (&aq)[2][CT], bf16x8 (&bq)[BQ]) {
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#define BX_KOFF(ks, quarter, tapoff) ((((ks) / 18) == 1 ? 4 * (quarter) : 0) + ((((ks) % 18) / 9) * 2 * (quarter)) + (tapoff))
+#define BX_TAP(tap) ((((tap) / 3) * PITCH + ((tap) % 3)) * 32)
+#define BX_OFF(j) BX_KOFF((j) / PT, PLANE, BX_TAP(((j) / PT) % 9))
+#pragma unroll
+    for (int j = 0; j < BQ - 1; ++j) bq[j] = *reinterpret_cast<const bf16x8 *>(smem + ba[j % PT] + BX_OFF(j));
+#pragma clang loop unroll(full)
+    for (int ph = 0; ph < BX_KS; ++ph) {
+        const int an = aaddr + slot * BX_ASLOT;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma clang loop unroll(full)
+        for (int pt = 0; pt < PT; ++pt) {
+            const int j = ph * PT + pt, jr = j + BQ - 1;
+            // the next step's four A fragments in the first two MFMA groups: the last one is >= 10 MFMAs old when its first MFMA issues
+            if (pt < 2) {
+                aq[(ph + 1) & 1][2 * pt] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt) * 1024);
+                aq[(ph + 1) & 1][2 * pt + 1] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt + 1) * 1024);
+            }
+            if (jr < BX_KS * PT) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba[jr % PT] + BX_OFF(jr));
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+                acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
+            if (pt < 2 && jr < BX_KS * PT) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            else if (pt < 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            else if (jr < BX_KS * PT) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        slot = slot == BX_NSLOT - 1 ? 0 : slot + 1;
+        BX_KBAR;     // bare: the fragment reads of the next step stay in flight across it
+    }
+#undef BX_KOFF
+#undef BX_TAP
+#undef BX_OFF
+}
+
 __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
-    typedef __bf16 T;
     constexpr int CT = 4, PT1 = 4, PT2 = 3, BQ = 6;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -163,43 +213,8 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
             ba2[pt] = BX_OFF_MID + (q >> 1) * BX_MIDQ + (q & 1) * 16 + (r * BX_MIDP + x) * 32;
         }
         f32x4 acc[CT][PT1];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int pt = 0; pt < PT1; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // ---------------- conv1: 54 k-steps on the input image (plane pair, half, tap) ----------------
-#define BX_KOFF(ks, quarter, tapoff) ((((ks) / 18) == 1 ? 4 * (quarter) : 0) + ((((ks) % 18) / 9) * 2 * (quarter)) + (tapoff))
-#define BX_TAP1(tap) ((((tap) / 3) * 32 + ((tap) % 3)) * 32)
-#define BX_TAP2(tap) ((((tap) / 3) * BX_MIDP + ((tap) % 3)) * 32)
-#define BX_OFF1(j) BX_KOFF((j) / PT1, BX_INQ, BX_TAP1(((j) / PT1) % 9))
-#define BX_OFF2(j) BX_KOFF((j) / PT2, BX_MIDQ, BX_TAP2(((j) / PT2) % 9))
-#pragma unroll
-        for (int j = 0; j < BQ - 1; ++j) bq[j] = *reinterpret_cast<const bf16x8 *>(smem + ba1[j % PT1] + BX_OFF1(j));
-#pragma clang loop unroll(full)
-        for (int ph = 0; ph < BX_KS; ++ph) {
-            const int an = aaddr + slot * BX_ASLOT;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT1; ++pt) {
-                const int j = ph * PT1 + pt, jr = j + BQ - 1;
-                // the next step's four A fragments in the first two MFMA groups: the last one is >= 10 MFMAs old when its first MFMA issues
-                if (pt < 2) {
-                    aq[(ph + 1) & 1][2 * pt] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt) * 1024);
-                    aq[(ph + 1) & 1][2 * pt + 1] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt + 1) * 1024);
-                }
-                if (jr < BX_KS * PT1) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba1[jr % PT1] + BX_OFF1(jr));
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
-                if (pt < 2 && jr < BX_KS * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                else if (pt < 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                else if (jr < BX_KS * PT1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            slot = slot == BX_NSLOT - 1 ? 0 : slot + 1;
-            BX_KBAR;     // bare: the fragment reads of the next step stay in flight across it
-        }
+        bx_kloop<PT1, BX_INQ, 32>(smem, aaddr, slot, ba1, acc, aq, bq);
         // ---------------- residual: the centre of the input image, both planes, into registers (the image is refilled under conv2) ----------------
         u32x4 rres[PT2][4];
 #pragma clang loop unroll(full)
@@ -219,7 +234,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
             const int r = (int)(((float)s + 0.5f) * inv_mc), x = s - r * MC;
             const int my = oy0 - 1 + r, mx = ox0 - 1 + x;
             const bool inside = (unsigned)my < (unsigned)H && (unsigned)mx < (unsigned)W;
-            alignas(16) T hi[16]; alignas(16) T lo[16];
+            alignas(16) __bf16 hi[16]; alignas(16) __bf16 lo[16];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -227,8 +242,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
                     float v = acc[ct][pt][i] + b1[4 * ct + i];
                     v = v > 0.f ? v : 0.f;
                     if (!inside) v = 0.f;                      // conv2's zero padding
-                    hi[4 * ct + i] = (T)v;
-                    lo[4 * ct + i] = (T)(v - (float)hi[4 * ct + i]);
+                    bx_split(v, hi[4 * ct + i], lo[4 * ct + i]);
                 }
             if (s < nmid) {
                 char *dst = smem + BX_OFF_MID + q * BX_MIDQ + (r * BX_MIDP + x) * 32;
@@ -240,36 +254,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // intermediate image published; the input image is free
         // ---------------- conv2: 54 k-steps on the intermediate image ----------------
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int pt = 0; pt < PT2; ++pt) acc[ct][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < BQ - 1; ++j) bq[j] = *reinterpret_cast<const bf16x8 *>(smem + ba2[j % PT2] + BX_OFF2(j));
-#pragma clang loop unroll(full)
-        for (int ph = 0; ph < BX_KS; ++ph) {
-            const int an = aaddr + slot * BX_ASLOT;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma clang loop unroll(full)
-            for (int pt = 0; pt < PT2; ++pt) {
-                const int j = ph * PT2 + pt, jr = j + BQ - 1;
-                if (pt < 2) {
-                    aq[(ph + 1) & 1][2 * pt] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt) * 1024);
-                    aq[(ph + 1) & 1][2 * pt + 1] = *reinterpret_cast<const bf16x8 *>(smem + an + (2 * pt + 1) * 1024);
-                }
-                if (jr < BX_KS * PT2) bq[jr % BQ] = *reinterpret_cast<const bf16x8 *>(smem + ba2[jr % PT2] + BX_OFF2(jr));
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ph & 1][ct], bq[j % BQ], acc[ct][pt], 0, 0, 0);
-                if (pt < 2 && jr < BX_KS * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                else if (pt < 2) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                else if (jr < BX_KS * PT2) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, CT, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            slot = slot == BX_NSLOT - 1 ? 0 : slot + 1;
-            BX_KBAR;
-        }
+        bx_kloop<PT2, BX_MIDQ, BX_MIDP>(smem, aaddr, slot, ba2, acc, aq, bq);
         // ---------------- output: (acc + b2) + x_hi + x_lo, ReLU, hi / lo split, two planes of 2 x 16-B stores per pixel ----------------
         {
             const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -279,7 +264,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
                 const int s = (wave * PT2 + pt) * 16 + c;
                 const int r = (int)(((float)s + 0.5f) * inv_wc), x = s - r * Wc;
                 const bool valid = s < nout;
-                alignas(16) T hi[16]; alignas(16) T lo[16];
+                alignas(16) __bf16 hi[16]; alignas(16) __bf16 lo[16];
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -290,9 +275,7 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
                         float v = acc[ct][pt][i] + b2[k];
                         v += __builtin_bit_cast(float, (k & 1) ? (wh & 0xffff0000u) : (wh << 16));
                         v += __builtin_bit_cast(float, (k & 1) ? (wl & 0xffff0000u) : (wl << 16));
-                        v = v > 0.f ? v : 0.f;
-                        hi[k] = (T)v;
-                        lo[k] = (T)(v - (float)hi[k]);
+                        bx_split(v > 0.f ? v : 0.f, hi[k], lo[k]);
                     }
                 // out-of-range offset for the unused slots: the store is issued unconditionally and dropped by the hardware
                 const unsigned voff = valid ? (unsigned)(((oy0 + r) * W + ox0 + x) * P.out_cs * 2 + 32 * q) : 0x80000000u;
@@ -305,11 +288,6 @@ __global__ __launch_bounds__(512, 1) void bb64x3_kernel(const BBProblem P) {
         }
         asm volatile("s_barrier" ::: "memory");         // end of tile: the next input image has landed (the image loaders waited for it)
     }
-#undef BX_KOFF
-#undef BX_TAP1
-#undef BX_TAP2
-#undef BX_OFF1
-#undef BX_OFF2
 }
 
 static int bb64x3_launch(pn_ctx *ctx, const BBProblem &P, int num_cus, hipStream_t stream) {

@@ -92,6 +92,98 @@ typedef __attribute__((ext_vector_type(4))) unsigned int stem_u32x4;
 // SRC: 0 = x is the pre-processed [B, 1, H, W] f32 input; 1 / 2 = the kernel reads the RAW depth frames (f16 / f32) and computes
 // every pixel of its input tile with pn_preproc_pixel -- pn_preprocess's own arithmetic, so the tile holds the same floats:
 // the pre-processing launch and the 6.4 MB it writes and the stem reads back (B = 32) disappear (pn_*_forward_frames).
+//
+// The pieces stem7x7_mfma_kernel and stem7x7_pool_kernel share: the input tile (ROWS x 38 bf16 values at STEM_PITCH, hi and -- LO -- lo part; its
+// last row, tap row 7 of the last output row, is zero: its weights are zero, the data must be finite), the register-resident weights, one output
+// row's MFMAs and the epilogue arithmetic.
+template <bool LO>
+__device__ __forceinline__ void stem_put(__bf16 *tile, __bf16 *tile_lo, int idx, float v) {
+    const __bf16 vh = (__bf16)v;
+    tile[idx] = vh;
+    if (LO) tile_lo[idx] = (__bf16)(v - (float)vh);
+}
+// the tile from the pre-processed f32 frame xb, one value at a time
+template <int ROWS, bool LO>
+__device__ __forceinline__ void stem_fill_f32(__bf16 *tile, __bf16 *tile_lo, const float *xb, int iy0, int ix0, int H, int W, int tid) {
+    for (int i = tid; i < ROWS * 38; i += 256) {
+        const int r = i / 38, cc = i - r * 38;
+        const int iy = iy0 + r, ix = ix0 + cc;
+        float v = 0.f;
+        if (r < ROWS - 1 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = xb[(size_t)iy * W + ix];
+        stem_put<LO>(tile, tile_lo, r * STEM_PITCH + cc, v);
+    }
+}
+// the tile from the RAW depth frames (SRC 1 = f16, 2 = f32) of image b: coordinate terms once per tile column / row (threads 0..37 / 64..), then 4 taps
+// + the interpolation per pixel
+template <int SRC, int ROWS, bool LO>
+__device__ __forceinline__ void stem_fill_frames(__bf16 *tile, __bf16 *tile_lo, const PnFrameSrc &src, int b, int iy0, int ix0, int H, int W, int tid) {
+    __shared__ PnAxisX axs[38];
+    __shared__ PnAxisY ays[ROWS];
+    if (tid < 38) axs[tid] = pn_preproc_axis_x(ix0 + tid, src.scale_x, src.W);
+    else if (tid >= 64 && tid < 64 + ROWS) ays[tid - 64] = pn_preproc_axis_y(iy0 + tid - 64, src.scale_y, src.H);
+    __syncthreads();
+    for (int i = tid; i < ROWS * 38; i += 256) {
+        const int r = i / 38, cc = i - r * 38;
+        const int iy = iy0 + r, ix = ix0 + cc;
+        float v = 0.f;
+        if (r < ROWS - 1 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
+            if (SRC == 1) v = pn_preproc_combine((const _Float16 *)src.frames + (size_t)b * src.H * src.W, src.W, axs[cc], ays[r], src.dmax, src.mean, src.stdv);
+            else v = pn_preproc_combine((const float *)src.frames + (size_t)b * src.H * src.W, src.W, axs[cc], ays[r], src.dmax, src.mean, src.stdv);
+        }
+        stem_put<LO>(tile, tile_lo, r * STEM_PITCH + cc, v);
+    }
+}
+// a lane's weight fragments (X3: hi and lo) and the 16 biases of its channels 16 q .. 16 q + 15
+template <bool X3> struct StemW { stem_bf16x8 aw[4][2], awl[X3 ? 4 : 1][2]; float bs[16]; };
+template <bool X3>
+__device__ __forceinline__ void stem_load_w(StemW<X3> &w, const __bf16 *__restrict__ wfrag, const float *__restrict__ bias, int lane, int q) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            w.aw[t][s] = *reinterpret_cast<const stem_bf16x8 *>(wfrag + ((t * 2 + s) * 64 + lane) * 8);
+            if (X3) w.awl[t][s] = *reinterpret_cast<const stem_bf16x8 *>(wfrag + ((8 + t * 2 + s) * 64 + lane) * 8);
+        }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w.bs[i] = bias[16 * q + i];
+}
+// output row ry of the tile, 16 pixels: two k-steps, each B fragment four ds_read_b32 of the lane's 8-tap row segment (X3: the product triple)
+template <bool X3>
+__device__ __forceinline__ void stem_row(const StemW<X3> &w, const __bf16 *tile, const __bf16 *tile_lo, int ry, int q, int c, f32x4 (&acc)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const unsigned *src = reinterpret_cast<const unsigned *>(&tile[(2 * ry + 4 * s + q) * STEM_PITCH + 2 * c]);
+        stem_u32x4 raw = {src[0], src[1], src[2], src[3]};
+        stem_bf16x8 bf = *reinterpret_cast<stem_bf16x8 *>(&raw);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.aw[t][s], bf, acc[t], 0, 0, 0);
+        if (X3) {
+            const unsigned *srl = reinterpret_cast<const unsigned *>(&tile_lo[(2 * ry + 4 * s + q) * STEM_PITCH + 2 * c]);
+            stem_u32x4 rawl = {srl[0], srl[1], srl[2], srl[3]};
+            stem_bf16x8 bl = *reinterpret_cast<stem_bf16x8 *>(&rawl);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.aw[t][s], bl, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.awl[t][s], bf, acc[t], 0, 0, 0);
+            }
+        }
+    }
+}
+// bias + ReLU + bf16 rounding of a lane's 16 channels: o = hi = bf16(v), or -- lo -- bf16(v - hi)
+__device__ __forceinline__ void stem_out16(const f32x4 (&acc)[4], const float (&bs)[16], bool lo, __bf16 (&o)[16]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = acc[t][r] + bs[4 * t + r];
+            v = v > 0.f ? v : 0.f;
+            const __bf16 hi = (__bf16)v;
+            o[4 * t + r] = lo ? (__bf16)(v - (float)hi) : hi;
+        }
+}
+
 template <bool X3, int SRC = 0>
 __global__ __launch_bounds__(256) void stem7x7_mfma_kernel(const float *__restrict__ x, const __bf16 *__restrict__ wfrag,
                                                             const float *__restrict__ bias, __bf16 *__restrict__ out,
@@ -104,24 +196,7 @@ __global__ __launch_bounds__(256) void stem7x7_mfma_kernel(const float *__restri
     const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 4;
     const float *xb = x + (size_t)b * H * W;
     if (SRC != 0) {
-        // coordinate terms once per tile column / row (threads 0..37 / 64..101), then 4 taps + the interpolation per pixel
-        __shared__ PnAxisX axs[38];
-        __shared__ PnAxisY ays[38];
-        if (tid < 38) axs[tid] = pn_preproc_axis_x(ix0 + tid, src.scale_x, src.W);
-        else if (tid >= 64 && tid < 64 + 38) ays[tid - 64] = pn_preproc_axis_y(iy0 + tid - 64, src.scale_y, src.H);
-        __syncthreads();
-        for (int i = tid; i < 38 * 38; i += 256) {
-            const int r = i / 38, cc = i - r * 38;
-            const int iy = iy0 + r, ix = ix0 + cc;
-            float v = 0.f;
-            if (r < 37 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                if (SRC == 1) v = pn_preproc_combine((const _Float16 *)src.frames + (size_t)b * src.H * src.W, src.W, axs[cc], ays[r], src.dmax, src.mean, src.stdv);
-                else v = pn_preproc_combine((const float *)src.frames + (size_t)b * src.H * src.W, src.W, axs[cc], ays[r], src.dmax, src.mean, src.stdv);
-            }
-            const __bf16 vh = (__bf16)v;
-            tile[r * STEM_PITCH + cc] = vh;
-            if (X3) tile_lo[r * STEM_PITCH + cc] = (__bf16)(v - (float)vh);
-        }
+        stem_fill_frames<SRC, 38, X3>(tile, tile_lo, src, b, iy0, ix0, H, W, tid);
     } else if ((W & 3) == 0) {
         // 16-byte loads: ix0 = 32 k - 4 and W are multiples of 4, so a group of four columns is entirely inside or entirely
         // outside the frame; 380 vector loads per block instead of 1 444 scalar ones (round 3: the stem was 25 us of a 0.49 ms
@@ -135,72 +210,28 @@ __global__ __launch_bounds__(256) void stem7x7_mfma_kernel(const float *__restri
             __bf16 h4[4], l4[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                h4[k] = (__bf16)vv[k];                   // row 37 (tap row 7) is zero: its weights are zero, the data must be finite
+                h4[k] = (__bf16)vv[k];
                 l4[k] = (__bf16)(vv[k] - (float)h4[k]);
             }
             *reinterpret_cast<uint2 *>(&tile[r * STEM_PITCH + 4 * g]) = *reinterpret_cast<uint2 *>(h4);
             if (X3) *reinterpret_cast<uint2 *>(&tile_lo[r * STEM_PITCH + 4 * g]) = *reinterpret_cast<uint2 *>(l4);
         }
     } else
-    for (int i = tid; i < 38 * 38; i += 256) {
-        const int r = i / 38, cc = i - r * 38;
-        const int iy = iy0 + r, ix = ix0 + cc;
-        float v = 0.f;
-        if (r < 37 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = xb[(size_t)iy * W + ix];
-        const __bf16 vh = (__bf16)v;
-        tile[r * STEM_PITCH + cc] = vh;                 // row 37 (tap row 7) is zero: its weights are zero, the data must be finite
-        if (X3) tile_lo[r * STEM_PITCH + cc] = (__bf16)(v - (float)vh);
-    }
-    stem_bf16x8 aw[4][2], awl[X3 ? 4 : 1][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            aw[t][s] = *reinterpret_cast<const stem_bf16x8 *>(wfrag + ((t * 2 + s) * 64 + lane) * 8);
-            if (X3) awl[t][s] = *reinterpret_cast<const stem_bf16x8 *>(wfrag + ((8 + t * 2 + s) * 64 + lane) * 8);
-        }
-    float bs[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) bs[i] = bias[16 * q + i];
+        stem_fill_f32<38, X3>(tile, tile_lo, xb, iy0, ix0, H, W, tid);
+    StemW<X3> w;
+    stem_load_w(w, wfrag, bias, lane, q);
     __syncthreads();
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
         const int ry = wave * 4 + rr;                    // output row of this pixel tile (16 pixels: ox0 .. ox0+15)
         f32x4 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const unsigned *src = reinterpret_cast<const unsigned *>(&tile[(2 * ry + 4 * s + q) * STEM_PITCH + 2 * c]);
-            stem_u32x4 raw = {src[0], src[1], src[2], src[3]};
-            stem_bf16x8 bf = *reinterpret_cast<stem_bf16x8 *>(&raw);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[t][s], bf, acc[t], 0, 0, 0);
-            if (X3) {
-                const unsigned *srl = reinterpret_cast<const unsigned *>(&tile_lo[(2 * ry + 4 * s + q) * STEM_PITCH + 2 * c]);
-                stem_u32x4 rawl = {srl[0], srl[1], srl[2], srl[3]};
-                stem_bf16x8 bl = *reinterpret_cast<stem_bf16x8 *>(&rawl);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[t][s], bl, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(awl[t][s], bf, acc[t], 0, 0, 0);
-                }
-            }
-        }
+        stem_row(w, tile, tile_lo, ry, q, c, acc);
         const int oy = oy0 + ry, ox = ox0 + c;
         if (oy < Ho && ox < Wo) {
             // bf16x3: two planes [hi | lo] `split` channels apart (pn_internal.h, ConvProblem::split)
             for (int pl = 0; pl < (split ? 2 : 1); ++pl) {
                 __bf16 o[16];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float v = acc[t][r] + bs[4 * t + r];
-                        v = v > 0.f ? v : 0.f;
-                        const __bf16 hi = (__bf16)v;
-                        o[4 * t + r] = pl == 1 ? (__bf16)(v - (float)hi) : hi;
-                    }
+                stem_out16(acc, w.bs, pl == 1, o);
                 __bf16 *op = out + ((size_t)(b * Ho + oy) * Wo + ox) * out_cs + 16 * q + pl * split;
                 reinterpret_cast<stem_u32x4 *>(op)[0] = reinterpret_cast<stem_u32x4 *>(o)[0];
                 reinterpret_cast<stem_u32x4 *>(op)[1] = reinterpret_cast<stem_u32x4 *>(o)[1];
@@ -213,9 +244,10 @@ __global__ __launch_bounds__(256) void stem7x7_mfma_kernel(const float *__restri
 // Stem + MaxPool2d(3, 2, 1) in one launch (YoloPoseNet: conv1 - bn1 - relu - maxpool, resnet.py:134-148 / yolo_posenet.py:101-108;
 // net.hip::build_yolo, POPNET_NO_STEMPOOL=1 keeps the two launches).  A block owns 8 x 7 pooled pixels: it computes the 17 x 15
 // stem outputs their windows cover (one row and one column shared with the neighbouring blocks are recomputed), parks them as
-// bf16 in LDS and takes the window maxima there -- max is exact, so the result equals pool_kernel's on the stored map bit for
-// bit, and the 112 x 112 x 64 map (51 MB written and read back at B = 32) is never stored.  Same MFMA formulation as
-// stem7x7_mfma_kernel (20 output rows per block instead of 16: wave w owns rows 5w .. 5w + 4, rows 17..19 are skipped).
+// bf16 in LDS and takes the window maxima there -- max is exact, and the parked values come from the functions stem7x7_mfma_kernel
+// computes the stored map with (stem_row, stem_out16), so the result equals pool_kernel's on that map bit for bit, and the
+// 112 x 112 x 64 map (51 MB written and read back at B = 32) is never stored.  20 output rows per block instead of 16: wave w owns
+// rows 5w .. 5w + 4, rows 17..19 are skipped; the tile has 40 rows.
 // ---------------------------------------------------------------------------------------------
 template <int SRC>
 __global__ __launch_bounds__(256) void stem7x7_pool_kernel(const float *__restrict__ x, const __bf16 *__restrict__ wfrag,
@@ -228,63 +260,18 @@ __global__ __launch_bounds__(256) void stem7x7_pool_kernel(const float *__restri
     const int b = blockIdx.z, py0 = blockIdx.y * 8, px0 = blockIdx.x * 7;
     const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1;                  // first stem output row / column of the block (may be -1)
     const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 4;
-    if (SRC != 0) {
-        __shared__ PnAxisX axs[38];
-        __shared__ PnAxisY ays[40];
-        if (tid < 38) axs[tid] = pn_preproc_axis_x(ix0 + tid, src.scale_x, src.W);
-        else if (tid >= 64 && tid < 64 + 40) ays[tid - 64] = pn_preproc_axis_y(iy0 + tid - 64, src.scale_y, src.H);
-        __syncthreads();
-        for (int i = tid; i < 40 * 38; i += 256) {
-            const int r = i / 38, cc = i - r * 38;
-            const int iy = iy0 + r, ix = ix0 + cc;
-            float v = 0.f;
-            if (r < 39 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-                if (SRC == 1) v = pn_preproc_combine((const _Float16 *)src.frames + (size_t)b * src.H * src.W, src.W, axs[cc], ays[r], src.dmax, src.mean, src.stdv);
-                else v = pn_preproc_combine((const float *)src.frames + (size_t)b * src.H * src.W, src.W, axs[cc], ays[r], src.dmax, src.mean, src.stdv);
-            }
-            tile[r * STEM_PITCH + cc] = (__bf16)v;
-        }
-    } else {
-        const float *xb = x + (size_t)b * H * W;
-        for (int i = tid; i < 40 * 38; i += 256) {
-            const int r = i / 38, cc = i - r * 38;
-            const int iy = iy0 + r, ix = ix0 + cc;
-            float v = 0.f;
-            if (r < 39 && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = xb[(size_t)iy * W + ix];
-            tile[r * STEM_PITCH + cc] = (__bf16)v;             // row 39 (tap row 7 of output row 16) is zero: its weights are zero
-        }
-    }
-    stem_bf16x8 aw[4][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) aw[t][s2] = *reinterpret_cast<const stem_bf16x8 *>(wfrag + ((t * 2 + s2) * 64 + lane) * 8);
-    float bs[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) bs[i] = bias[16 * q + i];
+    if (SRC != 0) stem_fill_frames<SRC, 40, false>(tile, nullptr, src, b, iy0, ix0, H, W, tid);
+    else stem_fill_f32<40, false>(tile, nullptr, x + (size_t)b * H * W, iy0, ix0, H, W, tid);
+    StemW<false> w;
+    stem_load_w(w, wfrag, bias, lane, q);
     __syncthreads();
     for (int rr = 0; rr < 5; ++rr) {
         const int ry = wave * 5 + rr;                           // wave-uniform
         if (ry >= 17) break;
         f32x4 acc[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const unsigned *sp = reinterpret_cast<const unsigned *>(&tile[(2 * ry + 4 * s2 + q) * STEM_PITCH + 2 * c]);
-            stem_u32x4 raw = {sp[0], sp[1], sp[2], sp[3]};
-            stem_bf16x8 bf = *reinterpret_cast<stem_bf16x8 *>(&raw);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[t][s2], bf, acc[t], 0, 0, 0);
-        }
+        stem_row(w, tile, nullptr, ry, q, c, acc);
         __bf16 o[16];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = acc[t][r] + bs[4 * t + r];
-                o[4 * t + r] = (__bf16)(v > 0.f ? v : 0.f);       // the same bias + ReLU + rounding as stem7x7_mfma_kernel's epilogue
-            }
+        stem_out16(acc, w.bs, false, o);
         stem_u32x4 *dst = reinterpret_cast<stem_u32x4 *>(&otile[(ry * 16 + c) * 64 + 16 * q]);
         dst[0] = reinterpret_cast<stem_u32x4 *>(o)[0];
         dst[1] = reinterpret_cast<stem_u32x4 *>(o)[1];

@@ -207,7 +207,7 @@ inline int pn_cfg_ct(int cfg) { return cfg == PN_CFG_C16 ? 1 : 2; }
 // form a group of 16*CT channels; lane quarter q = row >> 2 of every tile in the group holds channels
 // [4*CT*q, 4*CT*(q+1)) of it, so a lane's CT accumulators are 4*CT consecutive channels (one 16-B
 // bf16 store for CT = 2).  CT = 1 is the natural order.
-inline int pn_conv_row_channel(int tile, int row, int CT) {
+__host__ __device__ inline int pn_conv_row_channel(int tile, int row, int CT) {
     return (tile / CT) * CT * 16 + 4 * CT * (row >> 2) + 4 * (tile % CT) + (row & 3);
 }
 int pn_cfg_pixels(int cfg);

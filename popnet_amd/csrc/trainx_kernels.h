@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pn_internal.h"
 
 namespace tx {
 
@@ -482,7 +483,6 @@ struct PackDesc {
     unsigned first_group, ngroups;      // 16-byte groups of this pack in the launch (pack_kernel)
     unsigned first_unit, nunits;        // (row, 8 k-channels) units of this pack in the launch (pack_rows_kernel)
 };
-__device__ __forceinline__ int row_channel(int tile, int row, int CT) { return (tile / CT) * CT * 16 + 4 * CT * (row >> 2) + 4 * (tile % CT) + (row & 3); }
 
 __global__ __launch_bounds__(256) void pack_kernel(const PackDesc *__restrict__ tab, int n, unsigned total_groups) {
     const unsigned gid = blockIdx.x * 256u + threadIdx.x;
@@ -502,11 +502,11 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackDesc *__restrict__ 
         kstep = (int)(rest % (unsigned)(d.ksteps + 3));
         const int cbk = (int)(rest / (unsigned)(d.ksteps + 3));
         if (kstep >= d.ksteps) return;              // spare k-steps stay zero
-        row = cbk * 128 + row_channel((int)t, lane & 15, 4);
+        row = cbk * 128 + pn_conv_row_channel((int)t, lane & 15, 4);
     } else {
         const unsigned frag = g >> 6;
         kstep = (int)(frag % (unsigned)d.ksteps);
-        row = row_channel((int)(frag / (unsigned)d.ksteps), lane & 15, d.CT);
+        row = pn_conv_row_channel((int)(frag / (unsigned)d.ksteps), lane & 15, d.CT);
     }
     const int tap = kstep % KK, hs = kstep / KK;
     const int k0 = hs * 32 + 8 * (lane >> 4);
@@ -553,11 +553,11 @@ __device__ __forceinline__ void pack_rows_body(const PackDesc &d, unsigned u) {
     size_t gbase, gstride;
     if (d.conv4) {
         const int cbk = tile >> 3, t = tile & 7;
-        row = cbk * 128 + row_channel(t, r, 4);
+        row = cbk * 128 + pn_conv_row_channel(t, r, 4);
         gbase = ((size_t)cbk * (d.ksteps + 3) * 8 + t) * 64 + lane;
         gstride = 512;
     } else {
-        row = row_channel(tile, r, d.CT);
+        row = pn_conv_row_channel(tile, r, d.CT);
         gbase = (size_t)tile * d.ksteps * 64 + lane;
         gstride = 64;
     }

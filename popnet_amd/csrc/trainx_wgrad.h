@@ -19,7 +19,7 @@
 #pragma once
 #include <functional>
 #include <vector>
-#include "pn_internal.h"
+#include "conv_common.h"
 #include "trainx_kernels.h"
 
 namespace tx {
@@ -27,78 +27,52 @@ namespace tx {
 typedef __attribute__((ext_vector_type(4))) __bf16 bf4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
-__device__ __forceinline__ void glds16(const void *sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-// ---- the kernel: a block walks a column strip row by row ---------------------------------------------------------------------------------------
+// ---- what the two kernels share: a block walks a column strip row by row -------------------------------------------------------------------------
 // A first form fetched a 3-row strip (5 halo rows of x, 3 rows of dy: 64 KB), waited, computed, and -- alone on its CU since the split-K went to one
 // block per CU -- exposed that round trip once per strip (36 % of wave cycles waiting).  Here a block walks a COLUMN STRIP top-down: rings of KS + D x rows
 // and 1 + D dy rows (D = 2: the same 64 KB), per row ONE group of four LDS-DMA instructions per wave for the row D ahead, ONE barrier, a counted
 // `s_waitcnt vmcnt` (the D - 1 newer groups stay in flight) -- and no halo row is ever fetched twice.  A block owns `rows_per_block` consecutive rows of
 // the flattened (image, column strip, row) space; where its range crosses into the next column strip the rings are re-primed.
-struct WgsArgs {
-    const bf *x; int x_cs, x_split; unsigned x_zero;
-    const bf *dy; int dy_cs, dy_split; unsigned dy_zero;
+// Each kernel keeps what is its own -- fragment addresses, DMA lane set-up, the two fetch bodies and the row body -- and reaches wg_walk through
+// lambdas that capture its locals by reference (bb64_common.h's header note); everything here takes its arguments by value.
+struct WgArgs {
+    const void *x; int x_cs, x_split; unsigned x_zero;      // x_split / dy_split: plane distance in elements ([hi | lo] bf16 planes), 0 for fp32 tensors
+    const void *dy; int dy_cs, dy_split; unsigned dy_zero;
     int B, H, W;
     int Wt, tiles_x, rows_total, rows_per_block;
     int ncit, co_pad, ci_pad;
     float *partial;
 };
+constexpr int WG_RING = 5;                      // both rings hold WG_RING rows: ring positions are compile-time in a body unrolled WG_RING rows deep
+constexpr int WG_ROWB = 8192;                   // one ring row: 32 pixel slots x 64 channels x 4 B (fp32) or x 2 planes x 2 B
+constexpr int WG_XRING = WG_RING * WG_ROWB;     // LDS is [x ring][dy ring]
+// rows [ya, yb) of one column strip: columns ox0 .. ox0 + Wc - 1; bx0 / by0 = byte offset of the strip's image row 0 (row offsets are added modulo 2^32)
+struct WgSeg { int ya, yb, ox0, Wc; unsigned bx0, by0; };
 
-template <int KS, int D>
-__global__ __launch_bounds__(256, 2) void wgrad_stream_kernel(WgsArgs a) {
-    typedef __attribute__((address_space(3))) bf4 lds4;
-    constexpr int KK = KS * KS, PAD = KS / 2, RING = 5;       // both rings hold RING rows: ring positions are compile-time in a body unrolled RING rows deep
-    static_assert(KS + D <= RING && 1 + D <= RING, "ring too small for the prefetch distance");
-    constexpr int ROWB = 2 * 32 * 128;
-    constexpr int XRING = RING * ROWB;
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // [x ring][dy ring]
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
+// zeroes the accumulators and both rings, and decodes the block's (cout, cin) tile pair.  Every LDS byte a fragment read can touch holds finite data
+// from the start: a tap-shifted read of the surplus pixel slots runs a few pixels past its row (multiplied by dy = 0 there -- but 0 x NaN is NaN, and
+// LDS starts as whatever the previous kernel left)
+template <int KK>
+__device__ __forceinline__ void wg_begin(const WgArgs a, char *smem, f4 (&acc)[2][2][KK], int &co0, int &ci0) {
     const int cot = blockIdx.y / a.ncit, cit = blockIdx.y - cot * a.ncit;
-    const int co0 = cot * 64, ci0 = cit * 64;
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int pxl = 4 * g + q;
-    // transposed-read addresses (bytes): lane 4q + p of group g supplies row (= pixel) q, channels 4p .. 4p + 3 of the 16-channel window
-    int addrA[2], addrB[KS][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int win = wm * 2 + mt, swz = (pxl >> 1) & 3;
-        addrA[mt] = XRING + pxl * 128 + ((((win ^ swz) << 1) | (p >> 1)) << 4) + ((p & 1) << 3);
-    }
-#pragma unroll
-    for (int kx = 0; kx < KS; ++kx)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int win = wn * 2 + nt, hp = pxl + kx, swz = (hp >> 1) & 3;
-            addrB[kx][nt] = hp * 128 + ((((win ^ swz) << 1) | (p >> 1)) << 4) + ((p & 1) << 3);
-        }
-    f4 acc[2][2][KK];
+    co0 = cot * 64; ci0 = cit * 64;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int tp = 0; tp < KK; ++tp) acc[mt][nt][tp] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int o = threadIdx.x * 16; o < 2 * WG_XRING; o += 256 * 16) *reinterpret_cast<u32x4_t *>(smem + o) = u32x4_t{0u, 0u, 0u, 0u};
+}
 
-    // every LDS byte a fragment read can touch holds finite data from the start: a tap-shifted read of the surplus pixel slots runs a few pixels past its row
-    // (multiplied by dy = 0 there -- but 0 x NaN is NaN, and LDS starts as whatever the previous kernel left)
-    for (int o = threadIdx.x * 16; o < 2 * XRING; o += 256 * 16) *reinterpret_cast<u32x4_t *>(smem + o) = u32x4_t{0u, 0u, 0u, 0u};
-
-    const int dpx = lane >> 3, dsp = lane & 7;
-    const int dma_px = wave * 8 + dpx;
-    const int dma_slot = (((dsp >> 1) ^ ((dma_px >> 1) & 3)) << 1) | (dsp & 1);
-    const unsigned lane_x = (unsigned)(((dma_px - PAD) * a.x_cs + ci0 + dma_slot * 8) * 2);
-    const unsigned lane_y = (unsigned)((dma_px * a.dy_cs + co0 + dma_slot * 8) * 2);
-    const unsigned rowx = (unsigned)(a.W * a.x_cs * 2), rowy = (unsigned)(a.W * a.dy_cs * 2);
-    const unsigned planex = (unsigned)(a.x_split * 2), planey = (unsigned)(a.dy_split * 2);
-    const unsigned dma_lds = (unsigned)__builtin_amdgcn_readfirstlane(wave * 1024);
-
+// The walk over the block's rows.  segment(sg): the kernel takes note of the next segment; fetch_x(n, slot) / fetch_y(n, slot): one group half each (two
+// LDS-DMA instructions per wave) -- x row number n of the segment = image row ya - PAD + n, dy row number n = image row ya + n (rows past the segment are
+// fetched as zeros: their group is issued only to keep the vmcnt arithmetic uniform) -- into ring slot n % WG_RING; row_body(u): the MFMAs of the row in
+// dy slot u.  ES = bytes per stored element.
+template <int KS, int D, int ES, class Segment, class FetchX, class FetchY, class RowBody>
+__device__ __forceinline__ void wg_walk(const WgArgs a, Segment segment, FetchX fetch_x, FetchY fetch_y, RowBody row_body) {
+    constexpr int RING = WG_RING;
+    static_assert(KS + D <= RING && 1 + D <= RING, "ring too small for the prefetch distance");
     int row = blockIdx.x * a.rows_per_block;
     const int row_end = min(row + a.rows_per_block, a.rows_total);
     while (row < row_end) {
@@ -108,29 +82,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_kernel(WgsArgs a) {
         const int nrows = yb - ya;
         const int b = cs / a.tiles_x, tx_ = cs - b * a.tiles_x;
         const int ox0 = tx_ * a.Wt, Wc = min(a.Wt, a.W - ox0);
-        const unsigned bx0 = (unsigned)(((long)b * a.H * a.W + ox0) * (long)a.x_cs * 2);      // image row 0 of the strip (row offsets added below, modulo 2^32)
-        const unsigned by0 = (unsigned)(((long)b * a.H * a.W + ox0) * (long)a.dy_cs * 2);
-        const bool okx = dma_px < Wc + 2 * PAD && (unsigned)(ox0 - PAD + dma_px) < (unsigned)a.W;
-        const bool oky = dma_px < Wc;
-        // x row number n of the segment = image row ya - PAD + n -> ring slot n % RING; dy row number n = image row ya + n -> slot n % RING
-        auto fetch_x = [&](int n, int slot) {
-            const int Y = ya - PAD + n;
-            const bool rowok = (unsigned)Y < (unsigned)a.H;
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                const unsigned off = (okx && rowok) ? bx0 + (unsigned)Y * rowx + (unsigned)pl * planex + lane_x : a.x_zero;
-                glds16(a.x, off, (unsigned)(slot * ROWB + pl * 4096) + dma_lds);
-            }
-        };
-        auto fetch_y = [&](int n, int slot) {
-            const int Y = ya + n;
-            const bool rowok = Y < yb;            // rows past the segment: zeros (their group is issued only to keep the vmcnt arithmetic uniform)
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                const unsigned off = (oky && rowok) ? by0 + (unsigned)Y * rowy + (unsigned)pl * planey + lane_y : a.dy_zero;
-                glds16(a.dy, off, (unsigned)(XRING + slot * ROWB + pl * 4096) + dma_lds);
-            }
-        };
+        segment(WgSeg{ya, yb, ox0, Wc, (unsigned)(((long)b * a.H * a.W + ox0) * (long)a.x_cs * ES), (unsigned)(((long)b * a.H * a.W + ox0) * (long)a.dy_cs * ES)});
         __syncthreads();                          // the previous segment's fragment reads are done: the rings may be overwritten
 #pragma unroll
         for (int n = 0; n < KS - 1; ++n) fetch_x(n, n % RING);
@@ -148,57 +100,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_kernel(WgsArgs a) {
                 __syncthreads();                  // ... for every wave's pieces; and every wave has finished row k - 1, whose slots group k + D overwrites
                 fetch_x(KS - 1 + k + D, (KS - 1 + u + D) % RING);
                 fetch_y(k + D, (u + D) % RING);
-                auto load_a = [&](bf8 (&A)[2][2]) {
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int pl = 0; pl < 2; ++pl) {
-                            const bf4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrA[mt] + u * ROWB + pl * 4096));
-                            const bf4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrA[mt] + u * ROWB + pl * 4096 + 2048));
-                            A[mt][pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                        }
-                };
-                auto load_b = [&](int tp, bf8 (&Bf)[2][2]) {
-                    const int ky = tp / KS, kx = tp - ky * KS;
-                    const int xs = ((u + ky) % RING) * ROWB;
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                        for (int pl = 0; pl < 2; ++pl) {
-                            const bf4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrB[kx][nt] + xs + pl * 4096));
-                            const bf4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrB[kx][nt] + xs + pl * 4096 + 2048));
-                            Bf[nt][pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                        }
-                };
-                bf8 A[2][2], Bq[2][2][2];
-                load_a(A);
-                load_b(0, Bq[0]);
-#pragma unroll
-                for (int tp = 0; tp < KK; ++tp) {
-                    const int cur = tp & 1, nxt = cur ^ 1;
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (tp + 1 < KK) load_b(tp + 1, Bq[nxt]);
-#pragma unroll
-                    for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                            for (int nt = 0; nt < 2; ++nt)
-                                acc[mt][nt][tp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[mt][pr == 1 ? 1 : 0], Bq[cur][nt][pr == 2 ? 1 : 0], acc[mt][nt][tp], 0, 0, 0);
-                    if (tp + 1 < KK) {
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) {
-                            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-                        }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                row_body(u);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the D surplus groups of the segment's tail
         row += nrows;
     }
+}
+
+// the block's partial tile: wave (wm, wn) holds 32 couts x 32 cins x KK taps
+template <int KK>
+__device__ __forceinline__ void wg_store(const WgArgs a, const f4 (&acc)[2][2][KK], int co0, int ci0, int wm, int wn, int lane) {
+    const int g = lane >> 4;
     float *part = a.partial + (size_t)blockIdx.x * KK * a.co_pad * a.ci_pad;
 #pragma unroll
     for (int tp = 0; tp < KK; ++tp)
@@ -213,33 +126,136 @@ __global__ __launch_bounds__(256, 2) void wgrad_stream_kernel(WgsArgs a) {
                 }
 }
 
-// ---- fp32 form (precision "fp32": exact fp32 FMA chains on v_mfma_f32_16x16x4_f32) -------------------------------------------------------------------
-// K = 4 pixels per MFMA and ONE value per lane and operand: lane (m, kg) multiplies dy[pixel 4 s + kg][co m] with x[pixel 4 s + kg + tap][ci n] -- a channel-minor
-// tensor needs no transpose at all here (16 lanes read 16 consecutive channels).  Same row-streaming rings (five rows of x, five of dy, 256 B per pixel: 80 KB),
-// 16-byte slots XOR-swizzled by the pixel's parity so that the two pixels a half-wave's ds_read_b32 touches fall on different banks.
-struct WgfArgs {
-    const float *x; int x_cs; unsigned x_zero;
-    const float *dy; int dy_cs; unsigned dy_zero;
-    int B, H, W;
-    int Wt, tiles_x, rows_total, rows_per_block;
-    int ncit, co_pad, ci_pad;
-    float *partial;
-};
-
+// ---- [hi | lo] bf16 planes -------------------------------------------------------------------------------------------------------------------------
 template <int KS, int D>
-__global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(WgfArgs a) {
-    typedef __attribute__((address_space(3))) float ldsf;
-    constexpr int KK = KS * KS, PAD = KS / 2, RING = 5;
-    static_assert(KS + D <= RING && 1 + D <= RING, "ring too small for the prefetch distance");
-    constexpr int ROWB = 32 * 256;                          // one row: 32 pixel slots x 64 channels x 4 B
-    constexpr int XRING = RING * ROWB;
+__global__ __launch_bounds__(256, 2) void wgrad_stream_kernel(WgArgs a) {
+    typedef __attribute__((address_space(3))) bf4 lds4;
+    constexpr int KK = KS * KS, PAD = KS / 2, RING = WG_RING, ROWB = WG_ROWB, XRING = WG_XRING;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int cot = blockIdx.y / a.ncit, cit = blockIdx.y - cot * a.ncit;
-    const int co0 = cot * 64, ci0 = cit * 64;
+    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    const int pxl = 4 * g + q;
+    // transposed-read addresses (bytes): lane 4q + p of group g supplies row (= pixel) q, channels 4p .. 4p + 3 of the 16-channel window
+    int addrA[2], addrB[KS][2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        const int win = wm * 2 + mt, swz = (pxl >> 1) & 3;
+        addrA[mt] = XRING + pxl * 128 + ((((win ^ swz) << 1) | (p >> 1)) << 4) + ((p & 1) << 3);
+    }
+#pragma unroll
+    for (int kx = 0; kx < KS; ++kx)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int win = wn * 2 + nt, hp = pxl + kx, swz = (hp >> 1) & 3;
+            addrB[kx][nt] = hp * 128 + ((((win ^ swz) << 1) | (p >> 1)) << 4) + ((p & 1) << 3);
+        }
+    f4 acc[2][2][KK];
+    int co0, ci0;
+    wg_begin(a, smem, acc, co0, ci0);
+
+    const int dpx = lane >> 3, dsp = lane & 7;
+    const int dma_px = wave * 8 + dpx;
+    const int dma_slot = (((dsp >> 1) ^ ((dma_px >> 1) & 3)) << 1) | (dsp & 1);
+    const unsigned lane_x = (unsigned)(((dma_px - PAD) * a.x_cs + ci0 + dma_slot * 8) * 2);
+    const unsigned lane_y = (unsigned)((dma_px * a.dy_cs + co0 + dma_slot * 8) * 2);
+    const unsigned rowx = (unsigned)(a.W * a.x_cs * 2), rowy = (unsigned)(a.W * a.dy_cs * 2);
+    const unsigned planex = (unsigned)(a.x_split * 2), planey = (unsigned)(a.dy_split * 2);
+    const unsigned dma_lds = (unsigned)__builtin_amdgcn_readfirstlane(wave * 1024);
+
+    WgSeg sg;
+    bool okx, oky;
+    auto segment = [&](const WgSeg s_) {
+        sg = s_;
+        okx = dma_px < sg.Wc + 2 * PAD && (unsigned)(sg.ox0 - PAD + dma_px) < (unsigned)a.W;
+        oky = dma_px < sg.Wc;
+    };
+    auto fetch_x = [&](int n, int slot) {
+        const int Y = sg.ya - PAD + n;
+        const bool rowok = (unsigned)Y < (unsigned)a.H;
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            const unsigned off = (okx && rowok) ? sg.bx0 + (unsigned)Y * rowx + (unsigned)pl * planex + lane_x : a.x_zero;
+            pn_glds16_s<0>(a.x, off, (unsigned)(slot * ROWB + pl * 4096) + dma_lds);
+        }
+    };
+    auto fetch_y = [&](int n, int slot) {
+        const int Y = sg.ya + n;
+        const bool rowok = Y < sg.yb;
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            const unsigned off = (oky && rowok) ? sg.by0 + (unsigned)Y * rowy + (unsigned)pl * planey + lane_y : a.dy_zero;
+            pn_glds16_s<0>(a.dy, off, (unsigned)(XRING + slot * ROWB + pl * 4096) + dma_lds);
+        }
+    };
+    // the dy fragment of the row is read once and multiplied, product-major, with the KK shifted x fragments (the next tap's are requested before this tap's MFMAs)
+    auto row_body = [&](int u) {
+        auto load_a = [&](bf8 (&A)[2][2]) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const bf4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrA[mt] + u * ROWB + pl * 4096));
+                    const bf4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrA[mt] + u * ROWB + pl * 4096 + 2048));
+                    A[mt][pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                }
+        };
+        auto load_b = [&](int tp, bf8 (&Bf)[2][2]) {
+            const int ky = tp / KS, kx = tp - ky * KS;
+            const int xs = ((u + ky) % RING) * ROWB;
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const bf4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrB[kx][nt] + xs + pl * 4096));
+                    const bf4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4 *)(smem + addrB[kx][nt] + xs + pl * 4096 + 2048));
+                    Bf[nt][pl] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+                }
+        };
+        bf8 A[2][2], Bq[2][2][2];
+        load_a(A);
+        load_b(0, Bq[0]);
+#pragma unroll
+        for (int tp = 0; tp < KK; ++tp) {
+            const int cur = tp & 1, nxt = cur ^ 1;
+            __builtin_amdgcn_sched_barrier(0);
+            if (tp + 1 < KK) load_b(tp + 1, Bq[nxt]);
+#pragma unroll
+            for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt)
+                        acc[mt][nt][tp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[mt][pr == 1 ? 1 : 0], Bq[cur][nt][pr == 2 ? 1 : 0], acc[mt][nt][tp], 0, 0, 0);
+            if (tp + 1 < KK) {
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    wg_walk<KS, D, 2>(a, segment, fetch_x, fetch_y, row_body);
+    wg_store(a, acc, co0, ci0, wm, wn, lane);
+}
+
+// ---- fp32 form (precision "fp32": exact fp32 FMA chains on v_mfma_f32_16x16x4_f32) -------------------------------------------------------------------
+// K = 4 pixels per MFMA and ONE value per lane and operand: lane (m, kg) multiplies dy[pixel 4 s + kg][co m] with x[pixel 4 s + kg + tap][ci n] -- a channel-minor
+// tensor needs no transpose at all here (16 lanes read 16 consecutive channels).  Same row-streaming rings (five rows of x, five of dy, 256 B per pixel: 80 KB),
+// 16-byte slots XOR-swizzled by the pixel's parity so that the two pixels a half-wave's ds_read_b32 touches fall on different banks.
+template <int KS, int D>
+__global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(WgArgs a) {
+    typedef __attribute__((address_space(3))) float ldsf;
+    constexpr int KK = KS * KS, PAD = KS / 2, RING = WG_RING, ROWB = WG_ROWB, XRING = WG_XRING;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
     const int m = lane & 15, kg = lane >> 4;
     // fragment addresses: pixel 4 s + kg (+ kx), channel window of 16; the channel is XORed with 16 on odd pixels
     int addrA[2], addrB[KS][2];
@@ -250,13 +266,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(WgfArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) addrB[kx][nt] = (kg + kx) * 256 + ((((wn * 2 + nt) * 16 + m) ^ (((kg + kx) & 1) << 4)) << 2);
     f4 acc[2][2][KK];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int tp = 0; tp < KK; ++tp) acc[mt][nt][tp] = f4{0.f, 0.f, 0.f, 0.f};
-    for (int o = threadIdx.x * 16; o < 2 * XRING; o += 256 * 16) *reinterpret_cast<u32x4_t *>(smem + o) = u32x4_t{0u, 0u, 0u, 0u};
+    int co0, ci0;
+    wg_begin(a, smem, acc, co0, ci0);
 
     // DMA: one instruction = 4 pixels x 16 slots of 16 B; wave w fetches pixel groups w and w + 4 of every row
     const int dq = lane >> 4, dsp = lane & 15;
@@ -272,102 +283,66 @@ __global__ __launch_bounds__(256, 2) void wgrad_f32_kernel(WgfArgs a) {
     const unsigned rowx = (unsigned)(a.W * a.x_cs * 4), rowy = (unsigned)(a.W * a.dy_cs * 4);
     const unsigned dma_lds0 = (unsigned)__builtin_amdgcn_readfirstlane(wave * 1024);
 
-    int row = blockIdx.x * a.rows_per_block;
-    const int row_end = min(row + a.rows_per_block, a.rows_total);
-    while (row < row_end) {
-        const int cs = row / a.H, ya = row - cs * a.H;
-        const int yb = min(a.H, ya + (row_end - row));
-        const int nrows = yb - ya;
-        const int b = cs / a.tiles_x, tx_ = cs - b * a.tiles_x;
-        const int ox0 = tx_ * a.Wt, Wc = min(a.Wt, a.W - ox0);
-        const unsigned bx0 = (unsigned)(((long)b * a.H * a.W + ox0) * (long)a.x_cs * 4);
-        const unsigned by0 = (unsigned)(((long)b * a.H * a.W + ox0) * (long)a.dy_cs * 4);
-        bool okx[2], oky[2];
+    WgSeg sg;
+    bool okx[2], oky[2];
+    auto segment = [&](const WgSeg s_) {
+        sg = s_;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            okx[h] = dpx[h] < Wc + 2 * PAD && (unsigned)(ox0 - PAD + dpx[h]) < (unsigned)a.W;
-            oky[h] = dpx[h] < Wc;
+            okx[h] = dpx[h] < sg.Wc + 2 * PAD && (unsigned)(sg.ox0 - PAD + dpx[h]) < (unsigned)a.W;
+            oky[h] = dpx[h] < sg.Wc;
         }
-        auto fetch_x = [&](int n, int slot) {
-            const int Y = ya - PAD + n;
-            const bool rowok = (unsigned)Y < (unsigned)a.H;
+    };
+    auto fetch_x = [&](int n, int slot) {
+        const int Y = sg.ya - PAD + n;
+        const bool rowok = (unsigned)Y < (unsigned)a.H;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned off = (okx[h] && rowok) ? bx0 + (unsigned)Y * rowx + lane_x[h] : a.x_zero;
-                glds16(a.x, off, (unsigned)(slot * ROWB + h * 4096) + dma_lds0);
-            }
+        for (int h = 0; h < 2; ++h) {
+            const unsigned off = (okx[h] && rowok) ? sg.bx0 + (unsigned)Y * rowx + lane_x[h] : a.x_zero;
+            pn_glds16_s<0>(a.x, off, (unsigned)(slot * ROWB + h * 4096) + dma_lds0);
+        }
+    };
+    auto fetch_y = [&](int n, int slot) {
+        const int Y = sg.ya + n;
+        const bool rowok = Y < sg.yb;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned off = (oky[h] && rowok) ? sg.by0 + (unsigned)Y * rowy + lane_y[h] : a.dy_zero;
+            pn_glds16_s<0>(a.dy, off, (unsigned)(XRING + slot * ROWB + h * 4096) + dma_lds0);
+        }
+    };
+    // items (k-step s, tap): the two x values of item i + 1 are requested before the four MFMAs of item i
+    auto row_body = [&](int u) {
+        auto ld_a = [&](int s_, float (&A)[2]) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) A[mt] = *(const ldsf *)(smem + addrA[mt] + u * ROWB + s_ * 1024);
         };
-        auto fetch_y = [&](int n, int slot) {
-            const int Y = ya + n;
-            const bool rowok = Y < yb;
+        auto ld_b = [&](int s_, int tp, float (&Bv)[2]) {
+            const int ky = tp / KS, kx = tp - ky * KS;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned off = (oky[h] && rowok) ? by0 + (unsigned)Y * rowy + lane_y[h] : a.dy_zero;
-                glds16(a.dy, off, (unsigned)(XRING + slot * ROWB + h * 4096) + dma_lds0);
-            }
+            for (int nt = 0; nt < 2; ++nt) Bv[nt] = *(const ldsf *)(smem + addrB[kx][nt] + ((u + ky) % RING) * ROWB + s_ * 1024);
         };
-        __syncthreads();
+        float A[2][2], Bq[2][2];
+        ld_a(0, A[0]);
+        ld_b(0, 0, Bq[0]);
 #pragma unroll
-        for (int n = 0; n < KS - 1; ++n) fetch_x(n, n % RING);
+        for (int s_ = 0; s_ < 8; ++s_)
 #pragma unroll
-        for (int j = 0; j < D; ++j) { fetch_x(KS - 1 + j, (KS - 1 + j) % RING); fetch_y(j, j % RING); }
-        for (int k0 = 0; k0 < nrows; k0 += RING) {
-#pragma unroll
-            for (int u = 0; u < RING; ++u) {
-                const int k = k0 + u;
-                if (k >= nrows) break;
-                if (D == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (D == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                __syncthreads();
-                fetch_x(KS - 1 + k + D, (KS - 1 + u + D) % RING);
-                fetch_y(k + D, (u + D) % RING);
-                // items (k-step s, tap): the two x values of item i + 1 are requested before the four MFMAs of item i
-                auto ld_a = [&](int s_, float (&A)[2]) {
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) A[mt] = *(const ldsf *)(smem + addrA[mt] + u * ROWB + s_ * 1024);
-                };
-                auto ld_b = [&](int s_, int tp, float (&Bv)[2]) {
-                    const int ky = tp / KS, kx = tp - ky * KS;
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) Bv[nt] = *(const ldsf *)(smem + addrB[kx][nt] + ((u + ky) % RING) * ROWB + s_ * 1024);
-                };
-                float A[2][2], Bq[2][2];
-                ld_a(0, A[0]);
-                ld_b(0, 0, Bq[0]);
-#pragma unroll
-                for (int s_ = 0; s_ < 8; ++s_)
-#pragma unroll
-                    for (int tp = 0; tp < KK; ++tp) {
-                        const int it = s_ * KK + tp, cur = it & 1, nxt = cur ^ 1, ac = s_ & 1;
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (tp + 1 < KK) ld_b(s_, tp + 1, Bq[nxt]);
-                        else if (s_ + 1 < 8) { ld_b(s_ + 1, 0, Bq[nxt]); ld_a(s_ + 1, A[ac ^ 1]); }
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                            for (int nt = 0; nt < 2; ++nt)
-                                acc[mt][nt][tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[ac][mt], Bq[cur][nt], acc[mt][nt][tp], 0, 0, 0);
-                    }
+            for (int tp = 0; tp < KK; ++tp) {
+                const int it = s_ * KK + tp, cur = it & 1, nxt = cur ^ 1, ac = s_ & 1;
                 __builtin_amdgcn_sched_barrier(0);
+                if (tp + 1 < KK) ld_b(s_, tp + 1, Bq[nxt]);
+                else if (s_ + 1 < 8) { ld_b(s_ + 1, 0, Bq[nxt]); ld_a(s_ + 1, A[ac ^ 1]); }
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt)
+                        acc[mt][nt][tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[ac][mt], Bq[cur][nt], acc[mt][nt][tp], 0, 0, 0);
             }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        row += nrows;
-    }
-    const int g = lane >> 4;
-    float *part = a.partial + (size_t)blockIdx.x * KK * a.co_pad * a.ci_pad;
-#pragma unroll
-    for (int tp = 0; tp < KK; ++tp)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int co = co0 + wm * 32 + mt * 16 + 4 * g + i, ci = ci0 + wn * 32 + nt * 16 + (lane & 15);
-                    part[((size_t)tp * a.co_pad + co) * a.ci_pad + ci] = acc[mt][nt][tp][i];
-                }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    wg_walk<KS, D, 4>(a, segment, fetch_x, fetch_y, row_body);
+    wg_store(a, acc, co0, ci0, wm, wn, lane);
 }
 
 // dw[co][ref ci][tap] = sum over the split slices, in a fixed order; k_map: this engine's input channel -> the reference's (nullptr = identity).
@@ -407,27 +382,23 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 // What a plan decided (diagnostics: the length of the fp32 summation chains of one output element is rows_per_block rows of <= Wt pixels in a block, then Sr slices)
 struct WgPlan { int tiles_x = 0, Wt = 0, rows_per_block = 0, Sr = 0; };
 
-// What differs between the two forms: the argument struct, the kernel, the stored planes per tensor and the wording of the errors.
+// What differs between the two forms: the kernel, the stored planes per tensor and the wording of the errors.
 template <class T> struct Wg;
 template <> struct Wg<bf> {
-    typedef WgsArgs Args;
     static constexpr int planes = 2;
     static constexpr const char *name = "weight gradient on planes", *operands = "planes";
-    static void set_split(Args &w, int x_plane, int dy_plane) { w.x_split = x_plane; w.dy_split = dy_plane; }
-    template <int KS> static void (*kernel())(Args) { return wgrad_stream_kernel<KS, 2>; }
+    template <int KS> static void (*kernel())(WgArgs) { return wgrad_stream_kernel<KS, 2>; }
 };
 template <> struct Wg<float> {
-    typedef WgfArgs Args;
     static constexpr int planes = 1;
     static constexpr const char *name = "fp32 weight gradient", *operands = "tensors";
-    static void set_split(Args &, int, int) {}
-    template <int KS> static void (*kernel())(Args) { return wgrad_f32_kernel<KS, 2>; }
+    template <int KS> static void (*kernel())(WgArgs) { return wgrad_f32_kernel<KS, 2>; }
 };
 
 template <class T, int KS>
-int launch_wgrad(pn_ctx *ctx, dim3 grid, size_t lds, hipStream_t s, const typename Wg<T>::Args &w) {
+int launch_wgrad(pn_ctx *ctx, dim3 grid, size_t lds, hipStream_t s, const WgArgs &w) {
     static PnLdsAttr attr;                                  // one per kernel instantiation
-    void (*const kern)(typename Wg<T>::Args) = Wg<T>::template kernel<KS>();
+    void (*const kern)(WgArgs) = Wg<T>::template kernel<KS>();
     if (int rc = pn_lds_attr(ctx, attr, reinterpret_cast<const void *>(kern), lds)) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, w);
     return PN_OK;
@@ -442,11 +413,11 @@ int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const T *x, int x_plane, const 
     if (ks != 1 && ks != 3) return pn_set_error(ctx, PN_ERR_UNSUPPORTED, "%s: kernel size %d not built", Wg<T>::name, ks);
     const int KK = ks * ks, pad = ks / 2;
     const int seg_max = 32 - 2 * pad;                      // a halo row holds 32 pixels
-    typename Wg<T>::Args w;
+    WgArgs w;
     memset(&w, 0, sizeof w);
     w.x = x; w.x_cs = Wg<T>::planes * x_plane; w.x_zero = (unsigned)((size_t)B * H * W * w.x_cs * sizeof(T));
     w.dy = dy; w.dy_cs = Wg<T>::planes * dy_plane; w.dy_zero = (unsigned)((size_t)B * H * W * w.dy_cs * sizeof(T));
-    Wg<T>::set_split(w, x_plane, dy_plane);
+    if (Wg<T>::planes == 2) { w.x_split = x_plane; w.dy_split = dy_plane; }
     w.B = B; w.H = H; w.W = W;
     w.tiles_x = (W + seg_max - 1) / seg_max;
     w.Wt = (W + w.tiles_x - 1) / w.tiles_x;
@@ -464,9 +435,9 @@ int plan_wgrad(pn_ctx *ctx, int B, int H, int W, const T *x, int x_plane, const 
     Sr = (w.rows_total + w.rows_per_block - 1) / w.rows_per_block;
     *partial_floats = std::max(*partial_floats, (size_t)Sr * KK * w.co_pad * w.ci_pad);
     if (plan) { plan->tiles_x = w.tiles_x; plan->Wt = w.Wt; plan->rows_per_block = w.rows_per_block; plan->Sr = Sr; }
-    const size_t ldss = (size_t)(5 + 5) * 8192;            // two rings of five rows
+    const size_t ldss = (size_t)2 * WG_XRING;              // two rings of five rows
     ops.push_back([=](hipStream_t s) {
-        typename Wg<T>::Args ww = w;
+        WgArgs ww = w;
         ww.partial = *partial;                             // the host reads the pointer when the step launches (the buffer exists by then)
         if (int rc = ks == 3 ? launch_wgrad<T, 3>(ctx, dim3(Sr, pairs), ldss, s, ww) : launch_wgrad<T, 1>(ctx, dim3(Sr, pairs), ldss, s, ww)) return rc;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((size_t)KK * ww.co_pad * ww.ci_pad + 15) / 16)), dim3(256), 0, s, (const float *)ww.partial, Sr, KK, ww.co_pad, ww.ci_pad, Cout, Cin, k_map, dw);
