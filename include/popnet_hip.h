@@ -753,8 +753,13 @@ size_t pn_sizeof_a2j_record(void);
  *   image of int(y1 - y0) x int(x1 - x0) whose paste loop tests start < i < end strictly (the first pasted row and column stay zero); then
  *   cv2.resize(INTER_NEAREST) (source index min(floor(d * (1 / (dsize / ssize))), ssize - 1) in double) and (v - mean) / std in fp32, no clamp.
  *   Where the reference raises -- the image handed to cv2.resize is empty: a clipped region without rows or columns that is not pasted, or a
- *   paste image without rows or columns -- the crop is zeros and flags_dev[row] (may be NULL) is 1, else 0.  A box whose clipped END is negative
- *   (Python's slice would count it from the far edge) is treated as empty as well. */
+ *   paste image without rows or columns -- the crop is zeros and flags_dev[row] (may be NULL) is 1, else 0.  A clipped END that is negative
+ *   counts from the far edge, as Python's slice does (depth[2:-3]), which is also what popnet_amd.a2j_crops.box_items uploads.
+ *   The rows are device data: nothing in them is trusted.  A row above conf_min whose x0, y0, x1, y1, x1 - x0 or y1 - y0 is NaN, infinite or
+ *   past what an int holds (|v| > 2^31 - 128) is such a raise as well (int(nan), int(inf), a zero image of an absurd size): zeros, flag 1; at
+ *   or below conf_min (a NaN confidence included) the coordinates are never read: zeros, flag 0.  A frame index outside [0, F), NaN included,
+ *   names no frame the reference could load, which it does before it looks at the confidence: zeros, flag 1, whatever the confidence.
+ *   pn_a2j_vote's record of such a row carries the frame index as it is, or -1 where it is NaN or past an int. */
 int pn_a2j_crop(pn_ctx *ctx, const void *frames_dev, int depth_dtype, int F, int H, int W, const float *rows_dev, int n,
                 const pn_a2j_cfg *cfg, float *out_dev, int32_t *flags_dev, void *hip_stream);
 /* A2J_model.forward (model.py:179-186) on crops_dev [B, 1, in_h, in_w] f32.  The head maps stay on the device as the last convolutions

@@ -29,20 +29,35 @@ struct CropGeom {
     float start1, start2, end1, end2;
 };
 
+// A float that int() takes without overflow: finite and within [-(2^31 - 128), 2^31 - 128], the largest float below 2^31.  False for a NaN.
+__device__ __forceinline__ bool fits_int(float v) { return v >= -2147483520.f && v <= 2147483520.f; }
+
+// The rows are device data nobody has inspected (a decode's exp of a logit), so nothing is cast to int before plain comparisons have shown
+// that it fits:
+//   frame index not in [0, F) (a NaN included): the reference has no such frame to load and raises whatever the confidence: zeros, flag 1;
+//   conf <= conf_min or NaN: zeros, flag 0, whatever the coordinates hold -- the script never reads them;
+//   otherwise a coordinate, x1 - x0 or y1 - y0 that is NaN, infinite or past an int: the reference raises (int(nan), int(inf), a zero image
+//   of an absurd size): zeros, flag 1.
+// Why every address is then bounded: every value cast below lies in [-(2^31 - 128), 2^31 - 128], so each int() is the truncation it says.
+// cy0 >= 0 and ih <= H - min(cy0, H) by the slice rule, so ih > 0 implies cy0 + ih <= H, and the same in x.  The kernel reads the frame only
+// at (cy0 + py, cx0 + px) with 0 <= py < ih and 0 <= px < iw -- unpadded because sy <= sh - 1 = ih - 1, padded because the paste test
+// demands start < i (so i - start > 0 truncates to py >= 0) and py < ih -- and fi is in [0, F).
 __device__ CropGeom crop_geom(const float *r, const CropArgs &a) {
     CropGeom g;
     g.valid = 0; g.raise = 0; g.padded = 0; g.cy0 = g.cx0 = g.ih = g.iw = g.sh = g.sw = 0;
     g.start1 = g.start2 = g.end1 = g.end2 = 0.f;
-    const int fi = (int)r[0];
     const float x0 = r[1], y0 = r[2], x1 = r[3], y1 = r[4], conf = r[5];
-    if (!(conf > a.conf_min) || fi < 0 || fi >= a.F) return g;
+    if (!(r[0] >= 0.f && r[0] < (float)a.F) || (int)r[0] >= a.F) { g.raise = 1; return g; }      // (float)F may round up: the int test decides
+    if (!(conf > a.conf_min)) return g;
+    if (!(fits_int(x0) && fits_int(y0) && fits_int(x1) && fits_int(y1) && fits_int(__fsub_rn(x1, x0)) && fits_int(__fsub_rn(y1, y0)))) { g.raise = 1; return g; }
     const float nx0 = fmaxf(x0, 0.f), ny0 = fmaxf(y0, 0.f);
     const float nx1 = fminf(x1, (float)(a.W - 1)), ny1 = fminf(y1, (float)(a.H - 1));
     const int cx0 = (int)nx0, cy0 = (int)ny0, cx1 = (int)nx1, cy1 = (int)ny1;      // int(): truncation
-    // depth[cy0:cy1, cx0:cx1]: a start past the frame or an end before the start is an empty slice; a NEGATIVE end is treated as empty too
+    // depth[cy0:cy1, cx0:cx1] by Python's slice rules: a start past the frame or an end before the start is empty, a NEGATIVE end counts from
+    // the far edge (cy1 >= -(2^31 - 128) and H > 0: the sum cannot overflow)
     g.cy0 = cy0; g.cx0 = cx0;
-    g.ih = (cy1 < 0 || cy0 >= a.H) ? 0 : max(min(cy1, a.H) - cy0, 0);
-    g.iw = (cx1 < 0 || cx0 >= a.W) ? 0 : max(min(cx1, a.W) - cx0, 0);
+    g.ih = max((cy1 < 0 ? max(cy1 + a.H, 0) : min(cy1, a.H)) - min(cy0, a.H), 0);
+    g.iw = max((cx1 < 0 ? max(cx1 + a.W, 0) : min(cx1, a.W)) - min(cx0, a.W), 0);
     g.padded = (x0 < 0.f || y0 < 0.f || x1 > (float)a.img_w || y1 > (float)a.img_h) ? 1 : 0;
     if (g.padded) {
         g.sh = (int)__fsub_rn(y1, y0); g.sw = (int)__fsub_rn(x1, x0);
@@ -121,7 +136,7 @@ __device__ __forceinline__ void vote_finish(const VoteArgs &a, int b, int p, con
         R.joint[p][2] = __fdiv_rn(__fmul_rn(__fsub_rn(x, a.cx), vz), a.fx);
         R.joint[p][3] = __fdiv_rn(__fmul_rn(__fsub_rn(y, a.cy), vz), a.fy);
         R.joint[p][4] = vz;
-        if (p == 0) { R.conf = r[5]; R.frame = (int32_t)r[0]; }
+        if (p == 0) { R.conf = r[5]; R.frame = fits_int(r[0]) ? (int32_t)r[0] : -1; }      // no cast of a NaN or of a value past an int
     }
 }
 

@@ -25,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import a2j_cases as AC  # noqa: E402
 import a2j_layer_reference as ALR  # noqa: E402
 import a2j_plan_cases as APC  # noqa: E402
+from a2j_vote_reference import vote_reference as _vote_reference  # noqa: E402
 import layer_reference as LR  # noqa: E402
 from popnet_amd import _lib  # noqa: E402
 
@@ -304,21 +305,6 @@ def test_vote_one_hot_probe_is_exact(gpu):
 
 
 # ---- 5. vote: the net's own heads against fp64 --------------------------------------------------------------
-def _vote_reference(cls, reg, dep, anchors):
-    """fp64 r = N / Z per (crop, joint) and the allowance 2 (n + rho + 2) 2^-24 sum e_i |v_i| / Z: any fp32 summation order of n terms
-    in numerator and denominator, plus expf and the rounding of its argument (rho = 3 + max |c_i - max c|)."""
-    c = cls.astype(np.float64)
-    d = c - c.max(1, keepdims=True)
-    e = np.exp(d)
-    Z = e.sum(1)
-    v = np.concatenate([anchors[None, :, None, :].astype(np.float64) + reg.astype(np.float64), dep.astype(np.float64)[..., None]], -1)      # [B, K, P, 3]
-    r = (e[..., None] * v).sum(1) / Z[..., None]
-    n = c.shape[1]
-    rho = 3 + np.abs(d).max(1)
-    allow = 2 * (n + rho + 2)[..., None] * U * (e[..., None] * np.abs(v)).sum(1) / Z[..., None]
-    return r, allow
-
-
 def _check_vote(net, name, rows=(137,)):
     """rows: the anchor rows whose loss, and whose doubling, the allowance must reject."""
     cls, reg, dep = (t.cpu().numpy() for t in net.heads)
